@@ -9,22 +9,28 @@ rounded to bf16, one MFMA per product, fp32 accumulate; cell state, gates, CTC l
 AdamW in fp32 on fp32 master weights: the precision the contract names (the reference's own GPU runs
 use fp16 autocast, ha/loop.py:125) at BASELINE.md's bf16-MFMA parity gate (loss rel <= 2e-2; tested at
 this very configuration, dropout on, against the CPU oracle with the same masks:
-tests/test_gpu_lstm_b64.py).  The same step in the fp32-grade split-bf16 arithmetic (`bf16x3_mode`:
-three MFMAs per product, meets the fp32 tolerances) and on the exact-f32 MFMA (`f32_mode`) is
-reported beside it, as are larger per-GPU batches (`b_sweep`).
+tests/test_gpu_lstm_b64.py).  With --full, the same step in the fp32-grade split-bf16 arithmetic
+(`bf16x3_mode`: three MFMAs per product, meets the fp32 tolerances) and on the exact-f32 MFMA (`f32_mode`)
+is reported beside it, as are larger per-GPU batches (`b_sweep`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no torch.distributed environment, this process starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD (before anything here has
 touched the GPU) and forwards its JSON line and exit code; under torchrun it is one of the N ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+A plain run sets up, warms up, picks the launch mode (N = 1), times K steps, writes the outputs of the last
+timed step if --dump-outputs is given (dump_outputs) and prints ONE JSON line on rank 0: the headline
+(`metric`, `value`, `unit`, `ms_per_step`, `dtype`, ...), `config` and `step_roofline` (arithmetic on
+ms_per_step, nothing more is run).  --full adds, after the timed region (each leg can still be dropped
+with --no-extras / --no-cpu-baseline / --no-configs):
   roofline     -- the dominant kernel (the recurrent chain of the backward: in bf16 mode ONE persistent launch
                   for both layers, otherwise one per layer, or T' step launches on the fallback path)
                   against the HBM roof; bytes follow SURVEY.md 8d (parameters once per pass + per-step
                   activations), duration measured here with HIP events recorded by the library on the
                   launch stream;
+  inference, inference_bf16x3, bf16x3_mode / f32_mode / bf16_mode, stock3, H1536, b_sweep -- the other
+                  legs above (--no-extras drops them and the run's own PMC traffic passes);
   gpt2_small, asr_transformer32 -- BASELINE configs 3 and 5 (tools/bench_gpt.py, tools/bench_asr.py run as
                   child processes after the timed region, bounded);
   cpu_baseline -- the CPU restatement of the reference path (oracle/, kind "port") timed on this
@@ -53,13 +59,18 @@ def parse_args():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32): loss, params, grads_sample')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run the roofline, the other legs, the CPU baseline and BASELINE configs 3 / 5 '
+                         '(a plain run times the headline alone)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-graph', action='store_true', help='launch the step eagerly')
     ap.add_argument('--graph', action='store_true',
                     help='replay the step from its HIP graph.  Neither flag (one process): both ways are timed over 40 steps after the warm-up and the '
                          'faster one runs the timed region -- at 13 launches per step the host keeps ahead of the GPU and eager launches save the '
                          '~15 us a graph replay costs on ROCm 7.2; a slow or busy host reverses that')
-    ap.add_argument('--no-extras', action='store_true', help='skip the inference / bf16_mode / f32_mode legs')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the inference / bf16_mode / f32_mode legs')
     ap.add_argument('--dp-rehearsal', action='store_true',
                     help='N=1 only, a measurement aid: run the data-parallel code path (three graphs, RCCL all-reduces between them, '
                          'step-launch chain under the first bucket) on a one-rank RCCL group; the line says so in config.parallelism')
@@ -71,7 +82,7 @@ def parse_args():
     ap.add_argument('--math', choices=['f32', 'bf16x3', 'bf16'], default='bf16',
                     help="arithmetic of the dense products: 'bf16' rounds the operands to bf16 (one MFMA per product); 'f32' and "
                          "'bf16x3' meet the fp32 parity tolerances")
-    ap.add_argument('--no-configs', action='store_true', help='skip the GPT-2 small / attention-ASR legs (BASELINE configs 3 and 5)')
+    ap.add_argument('--no-configs', action='store_true', help='with --full: skip the GPT-2 small / attention-ASR legs (BASELINE configs 3 and 5)')
     ap.add_argument('--dp-algo', choices=['allreduce', 'rs_ag', 'rs_ag_flat', 'direct'], default='rs_ag',
                     help='N > 1: allreduce = every rank averages the whole gradient and updates every parameter (DistributedDataParallel); '
                          'rs_ag = the span-sharded step: the top LSTM layer\'s matrix gradients reduce-scattered from the middle of the backward, the '
@@ -414,6 +425,33 @@ def measure_traffic(math):
     return res
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+GRAD_SAMPLE = 1 << 20
+
+
+def dump_outputs(path, trainer):
+    """--dump-outputs: what the last timed step left for its caller, as float32 .npy files under `path`:
+      loss         -- that step's loss, shape [1];
+      params       -- every parameter after its update (13.2 M values for LC-2x1024): the modules' named_parameters() order
+                      (encoder, then recognizer), flattened and concatenated -- independent of the trainer's flat-buffer layout;
+      grads_sample -- the gradients of that step in the same order, at a fixed seeded sample of 2^20 positions (ascending).
+    Inputs, parameters and dropout masks are seeded, so the same arguments give the same files on every run of one build."""
+    import numpy as np
+    import torch
+    named = [(pfx + n, p) for pfx, m in (('encoder.', trainer.encoder), ('recognizer.', trainer.recognizer)) for n, p in m.named_parameters()]
+    params = torch.cat([p.detach().reshape(-1) for _, p in named])
+    grads = torch.cat([trainer.flat.grad_views[n].reshape(-1) for n, _ in named])
+    idx = np.sort(np.random.default_rng(0).choice(grads.numel(), size=min(GRAD_SAMPLE, grads.numel()), replace=False))
+    arrays = {'loss': trainer.loss.detach().reshape(1), 'params': params, 'grads_sample': grads[torch.from_numpy(idx).to(grads.device)]}
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES} byte budget')
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -517,6 +555,11 @@ def main():
         n_ranks_seen = int(ones.item())
     loss = trainer.loss.item()
     trainer.check_status()        # a persistent recurrence that gave up a wait during the run: fail the bench, loudly
+    if args.dump_outputs:
+        if trainer.masters_stale:
+            trainer.gather_master_weights()         # after a bf16 all-gather: the fp32 masters (a collective, every rank)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, trainer)
     dp_components = None
     if (world > 1 or args.dp_rehearsal) and trainer.sharded is not None:
         # after the timed region: the same step launched eagerly with a HIP event behind every collective and optimizer piece (rank 0's
@@ -556,7 +599,7 @@ def main():
                               'frac_of_hbm_peak': round(step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                               'note': 'whole training step against SURVEY.md 8d bytes(B) = 10*4*P + 2.12e6*B'},
         }
-        if world == 1:
+        if world == 1 and args.full:
             # dominant kernel: the backward recurrent chain (bf16 mode: ONE launch for both layers, otherwise one per layer); the
             # forward twin beside it
             two = bool(_lib.lib().halo_lstm_persistent2_eligible(T_SUB, B_PER_GPU, H, L))
@@ -602,7 +645,7 @@ def main():
                                  'frac': round(kf_s / (us_f * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
                                  'frac_10h': round(kf / (us_f * 1e-6) / 1e9 / HBM_PEAK_GBS, 4), 'traffic': traffic(name_f),
                                  'share_of_step': round(chains * us_f * 1e-3 / ms_per_step, 3)}}
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             out['inference'] = time_inference(enc, rec, x, max(20, args.steps // 2))
             out['inference']['dtype'] = MATH_DTYPE[args.math]
             fwd_bytes = 4 * param_count() + 28_300 * B_PER_GPU          # SURVEY.md 8d, forward only: 4P + 28.3e3 B = 54.6 MB at B = 64
@@ -637,9 +680,9 @@ def main():
                                                'step_frac_of_hbm_peak': out['step_roofline']['frac_of_hbm_peak'],
                                                'recurrence': out.get('roofline', {}).get('kernel')}
             _lib.set_math_mode(args.math)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(params)
-        if world == 1 and not args.no_extras and not args.no_configs:
+        if world == 1 and args.full and not args.no_extras and not args.no_configs:
             # BASELINE configs 3 and 5, each in its own process after everything of this one is timed
             torch.cuda.synchronize()
             out['gpt2_small'] = run_config_leg('bench_gpt.py', 'bf16', 240)

@@ -1,5 +1,5 @@
-"""The bench.py output contract, checked on the newest committed line (profiles/rNN_bench_n1.json, produced by `python bench.py` on an
-MI355X box) and on bench.py's own argument surface -- no GPU needed: the keys the driver reads are there, typed, and consistent with each other."""
+"""The bench.py output contract, checked on the newest committed line (profiles/rNN_bench_n1.json, produced by `python bench.py --full`
+on an MI355X) and on bench.py's own argument surface -- no GPU needed: the keys the driver reads are there, typed, and consistent with each other."""
 import glob
 import json
 import os
@@ -49,5 +49,5 @@ def test_committed_bench_line_meets_the_contract():
 def test_bench_argument_surface():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0
-    for flag in ('--gpus', '--steps', '--warmup', '--no-graph', '--graph', '--math', '--dp-algo', '--grad-dtype', 'rs_ag_flat'):
+    for flag in ('--gpus', '--steps', '--warmup', '--no-graph', '--graph', '--math', '--dp-algo', '--grad-dtype', 'rs_ag_flat', '--full', '--dump-outputs'):
         assert flag in out.stdout, flag
