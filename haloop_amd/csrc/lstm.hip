@@ -549,9 +549,17 @@ struct Prologue2Args {
     const float *h0[2]; void *hp0[2]; float *h_rm[2]; const float *c0[2]; float *c_rm[2]; long s_units;   // per layer (forward only)
     unsigned *zero; long zero_units;
     unsigned *zero2; long zero2_units;
+    // the exchanged images the forward launch will produce, ARMED for its data-flag hand-off (halo_lstm_persist2_fwd_armed): narm regions of
+    // arm_units 16-byte units, the first KiB (hi half) of each 2-KiB block from arm[m] on set to 0xFF bytes
+    char *arm[3]; int narm; long arm_units;
     int H, B;
     ImageJobs img;          // the first img.blocks workgroups of persist2_prologue_kernel (pack_pair: behind its tile blocks)
 };
+__device__ __forceinline__ void arm_unit(const Prologue2Args &a, long v) {
+    const int m = (int)(v / a.arm_units);
+    const long w = v - m * a.arm_units;
+    *reinterpret_cast<uint4 *>(a.arm[m] + (w >> 6) * 2048 + (w & 63) * 16) = make_uint4(~0u, ~0u, ~0u, ~0u);
+}
 template <int WMODE>
 __global__ __launch_bounds__(256) void persist2_prologue_kernel(const Prologue2Args a) {
     if ((int)blockIdx.x < a.img.blocks) {
@@ -559,10 +567,12 @@ __global__ __launch_bounds__(256) void persist2_prologue_kernel(const Prologue2A
         image_jobs_block(a.img, blockIdx.x, tile);
         return;
     }
-    const long nw = 3 * a.w_units, ns = 2 * a.s_units;
-    const long total = nw + ns + a.zero_units + a.zero2_units;
+    const long nw = 3 * a.w_units, ns = 2 * a.s_units, na = (long)a.narm * a.arm_units;
+    const long total = nw + ns + a.zero_units + a.zero2_units + na;
     for (long u = (blockIdx.x - a.img.blocks) * 256L + threadIdx.x; u < total; u += (long)(gridDim.x - a.img.blocks) * 256) {
-        if (u < nw) {
+        if (u >= total - na) {
+            arm_unit(a, u - (total - na));
+        } else if (u < nw) {
             const int m = (int)(u / a.w_units);
             pack_unit<true, WMODE, true>(u - m * a.w_units, a.w[m], a.wdst[m], a.H, a.B, a.wK, nullptr, nullptr, nullptr);
         } else if (u < nw + ns) {
@@ -602,10 +612,13 @@ __global__ __launch_bounds__(256) void persist2_pack_pair_kernel(const PackPairA
     }
     if ((int)blockIdx.x >= a.tile_blocks) {
         const Prologue2Args &r = a.rest;
-        const long ns = 2 * r.s_units, nz = 2L * a.zcount * a.zunits, total = ns + r.zero_units + r.zero2_units + nz;
+        const long ns = 2 * r.s_units, nz = 2L * a.zcount * a.zunits, na = (long)r.narm * r.arm_units;
+        const long total = ns + r.zero_units + r.zero2_units + nz + na;
         const int first = a.tile_blocks + a.rest.img.blocks;
         for (long u = (blockIdx.x - first) * 256L + threadIdx.x; u < total; u += (long)(gridDim.x - first) * 256) {
-            if (u >= ns + r.zero_units + r.zero2_units) {
+            if (u >= total - na) {
+                arm_unit(r, u - (total - na));
+            } else if (u >= ns + r.zero_units + r.zero2_units) {
                 const long v = u - (ns + r.zero_units + r.zero2_units);
                 const long per = (long)a.zcount * a.zunits;
                 const int which = (int)(v / per);
@@ -1352,6 +1365,17 @@ int lstm_fwd_persist2(const float *in, int in_dim, int lo, const float *const *w
     pa.s_units = (long)((B + 15) / 16) * (H / 32) * 64;
     pa.zero = flags; pa.zero_units = (long)(PERSIST_FLAG_BYTES / 16);
     pa.zero2 = nullptr; pa.zero2_units = 0;
+    char *xp = p_drop > 0.f ? (char *)fused_yp(extra, lo, T, B, H, L) : nullptr;
+    pa.narm = 0; pa.arm_units = 0;
+    if (halo_lstm_persist2_fwd_armed(T, B, H)) {
+        // the forward's data-flag hand-off reads images 1 .. T of h0 (image 0: the initial state, packed above) and of h1, and images
+        // 0 .. T-1 of dropout(h0): T images each, armed here, ahead of their only writer
+        const size_t image = (size_t)((B + 15) / 16) * (H / 32) * 2048;
+        pa.arm[pa.narm++] = (char *)l0.hp + image;
+        pa.arm[pa.narm++] = (char *)l1.hp + image;
+        if (xp) pa.arm[pa.narm++] = xp;
+        pa.arm_units = (long)T * (long)(image / 2048) * 64;
+    }
     pa.H = H; pa.B = B;
     ctx.packT_reserve = nullptr;
     ctx.emitT_reserve = nullptr;
@@ -1389,7 +1413,8 @@ int lstm_fwd_persist2(const float *in, int in_dim, int lo, const float *const *w
                 ctx.fwdT_reserve = reserve; ctx.fwdT_src[0] = in; ctx.fwdT_src[1] = w_ih[0];
             }
         }
-        const unsigned rest_blocks = pack_grid((size_t)(2 * pa.s_units + pa.zero_units + pp.rest.zero2_units + 2L * pp.zcount * pp.zunits));
+        const unsigned rest_blocks = pack_grid((size_t)(2 * pa.s_units + pa.zero_units + pp.rest.zero2_units + 2L * pp.zcount * pp.zunits +
+                                                        (long)pa.narm * pa.arm_units));
         hipLaunchKernelGGL(persist2_pack_pair_kernel, dim3((unsigned)(pp.tile_blocks + pp.rest.img.blocks) + rest_blocks), dim3(256), 0, st, pp);
         HALO_TRY(halo_launch_status());
         if (images_by_pack)
@@ -1409,7 +1434,8 @@ int lstm_fwd_persist2(const float *in, int in_dim, int lo, const float *const *w
             image_jobs_add(pa.img, in, T * B, in_dim, in_dim, 0, img_in);
             image_jobs_add(pa.img, w_ih[0], 4 * H, in_dim, in_dim, 0, img_w);
         }
-        hipLaunchKernelGGL(persist2_prologue_kernel<0>, dim3((unsigned)pa.img.blocks + pack_grid((size_t)(3 * pa.w_units + 2 * pa.s_units + pa.zero_units))),
+        hipLaunchKernelGGL(persist2_prologue_kernel<0>, dim3((unsigned)pa.img.blocks + pack_grid((size_t)(3 * pa.w_units + 2 * pa.s_units + pa.zero_units +
+                                                                                                      (long)pa.narm * pa.arm_units))),
                            dim3(256), 0, st, pa);
         HALO_TRY(halo_launch_status());
         if (images_by_pack)
@@ -1422,7 +1448,7 @@ int lstm_fwd_persist2(const float *in, int in_dim, int lo, const float *const *w
     Persist2Fwd a;
     a.wp0 = (const char *)wp0; a.wp1 = (const char *)wp1; a.wpi = (const char *)wpi;
     a.hp0 = (char *)l0.hp; a.hp1 = (char *)l1.hp;
-    a.xp = p_drop > 0.f ? (char *)fused_yp(extra, lo, T, B, H, L) : nullptr;
+    a.xp = xp;
     a.gates0 = l0.gates; a.h0 = l0.h; a.c0 = l0.c;
     a.gates1 = l1.gates; a.h1 = l1.h; a.c1 = l1.c;
     a.b_ih1 = b_ih[1]; a.b_hh1 = b_hh[1];
@@ -1755,6 +1781,7 @@ int halo_lstm_bwd(const float *x, const float *const *w_ih, const float *const *
         pa.s_units = 0;
         pa.zero = (unsigned *)flag_base; pa.zero_units = (long)(PERSIST_FLAG_BYTES / 16);
         pa.zero2 = nullptr; pa.zero2_units = 0;
+        pa.narm = 0; pa.arm_units = 0;
         if (emit0 && need_din && (T * B) % 128 != 0) {   // the padded last row tile of the lower layer's dG row image
             const long tile_bytes = (long)(4 * H / 32) * 16384;
             pa.zero2 = (unsigned *)(img_g + (long)((T * B) / 128) * tile_bytes); pa.zero2_units = tile_bytes / 16;

@@ -138,6 +138,11 @@ struct Persist2Bwd {
 };
 
 bool halo_lstm_persist2_ok(int T, int B, int H, int L);   // shape, arithmetic mode (bf16), CU count, switch
+// the two-layer forward hands h off by the data (HALO_PERSIST_DATAFLAG, default on; =0: epoch words): the images it produces must then be
+// ARMED (every bf16 0xFFFF) by a launch ahead of it -- for this shape when halo_lstm_persist2_fwd_armed says so (not for the interleaved
+// launches, which keep the epoch words)
+bool halo_lstm_persist2_dataflag();
+bool halo_lstm_persist2_fwd_armed(int T, int B, int H);
 void halo_lstm_persist2_enable(int on);
 void halo_lstm_interleave_enable(int on);
 int halo_lstm_persist2_fwd(const Persist2Fwd &a, hipStream_t st);

@@ -16,7 +16,12 @@
 // at layer 0 (times W_ih1): waves 4-7 multiply the SAME fragments by both matrices (W_hh1^T in registers, W_ih1^T in LDS), so
 // the batched input-gradient GEMM between the chains and its operand images disappear too.
 //
-// Hand-off protocol, epoch words, block placement: lstm_persist.hip / lstm_persist_dev.h, unchanged.
+// Hand-off protocol.  Forward (default, HALO_PERSIST_DATAFLAG unset or 1): the data IS the flag.  The packing launch ahead ARMS every
+// piece of the images this launch produces (bf16 0xFFFF, a NaN); a consumer wave issues its fragment loads at the top of the step with no
+// poll, checks the first bf16 of every 16-byte fragment, and repeats the whole pass (loads outside conditionals) until no lane of the wave
+// sees the sentinel, bounded by SPIN_TIMEOUT_TICKS; a producer's 16-byte sc1 store of a piece is its publication: no drain, no epoch
+// word.  Precondition and its standing: the helpers below.  HALO_PERSIST_DATAFLAG=0, the backward, and the interleaved launches of
+// lstm_persist2x.hip: epoch words, block placement as lstm_persist.hip / lstm_persist_dev.h.
 #include <stdlib.h>
 #include "halo_common.h"
 #include "halo_internal.h"
@@ -24,6 +29,43 @@
 #include "lstm_persist_dev.h"
 
 namespace {
+
+// ---- data flags (HALO_PERSIST_DATAFLAG, default on; forward) ----
+// Every 16-byte piece of an exchanged image that a consumer loads starts ARMED: its bf16s are 0xFFFF, a NaN that no finite h has
+// (lstm.hip writes the pattern into the images the launch will produce, in the packing launch ahead of it).  A producer stores a piece
+// with one 16-byte sc1 store of one lane and a consumer loads it with one 16-byte sc1 load of one lane (fragment lane l of k-block i
+// is packed piece ((jt & 1) * 2 + kg) * 16 + row == l of the workgroup jt with jt / 2 == i), so the piece's first bf16 tells whether
+// the whole piece has arrived.  That relies on the 16-byte sc1 store being observed whole by the 16-byte sc1 load: the assumption the
+// epoch words' hand-off makes too (the loads behind a matched poll see whole pieces), observed untorn on gfx950 but NOT among the
+// measured forms of MI355X_MICROARCH.md's "Valid forms" table.  A piece whose first bf16 is 0xFFFF (a NaN h) goes out as 0xFFFE,
+// another NaN: only a NaN's payload changes.
+__device__ __forceinline__ bf16x8 unarm(bf16x8 v) {
+    u32x4 w = __builtin_bit_cast(u32x4, v);
+    if ((w.x & 0xffffu) == 0xffffu) w.x -= 1u;
+    return __builtin_bit_cast(bf16x8, w);
+}
+// this lane saw an armed fragment
+template <int N>
+__device__ __forceinline__ bool armed_lane(const bf16x8 (&f)[N]) {
+    bool a = false;
+#pragma unroll
+    for (int i = 0; i < N; ++i) a |= (__builtin_bit_cast(u32x4, f[i]).x & 0xffffu) == 0xffffu;
+    return a;
+}
+// a pass saw an armed fragment: wait a little before the next one; false once SPIN_TIMEOUT_TICKS have passed since the first repeat
+__device__ __forceinline__ bool rearm_wait(unsigned long long &t0, int pass, int nap) {
+    const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+    if (pass == 0) t0 = now;
+    else if (now - t0 > SPIN_TIMEOUT_TICKS) return false;
+    if (nap == 1) __builtin_amdgcn_s_sleep(1);
+    else if (nap == 2) __builtin_amdgcn_s_sleep(4);
+    else if (nap == 3) __builtin_amdgcn_s_sleep(16);
+    return true;
+}
+// diagnostic: a count in a stamp slot (the passes a consumer needed)
+__device__ __forceinline__ void stamp_value(unsigned long long *stamps, int T, int step, int point, int lane, unsigned v) {
+    if (stamps && lane == 0) stamps[((long)blockIdx.x * T + step) * 16 + point] = v;
+}
 
 // ================================================================================================================
 // forward
@@ -45,7 +87,7 @@ struct Fwd2Shared {
     unsigned *s_published;
 };
 
-template <int KBQ>
+template <int KBQ, bool DF>
 __device__ __forceinline__ void fwd2_layer0_waves(const Persist2Fwd &p, const Fwd2Shared sh, int jt, int bt, int wave, int lane, int u) {
     const int wq = wave & 3;
     const int H = p.H, B = p.B, T = p.T;
@@ -78,11 +120,13 @@ __device__ __forceinline__ void fwd2_layer0_waves(const Persist2Fwd &p, const Fw
         if (wave == 0) stamp(p.stamps, T + 2, s, 0, lane);
         const bool act0 = s < T, act1 = s >= 2;
         // ---- epoch s: every workgroup of the batch group has published h0_{s-1}, dropout(h0_{s-1}) and h1_{s-3} ----
-        bool ok = true;
-        if (s > 0 && wave == 1) ok = poll_group(grp_flags, 0, NJ, p.epoch0 + (unsigned)s, lane, p.nap);
-        if (!ok && lane == 0) {
-            *sh.s_abort = 1;
-            raise_abort(p.flags, p.status);
+        if (!DF) {
+            bool ok = true;
+            if (s > 0 && wave == 1) ok = poll_group(grp_flags, 0, NJ, p.epoch0 + (unsigned)s, lane, p.nap);
+            if (!ok && lane == 0) {
+                *sh.s_abort = 1;
+                raise_abort(p.flags, p.status);
+            }
         }
         lds_barrier();                                                             // (A)
         if (*sh.s_abort) return;
@@ -90,16 +134,30 @@ __device__ __forceinline__ void fwd2_layer0_waves(const Persist2Fwd &p, const Fw
         if (act0) {
             const int img = ((s * NBT + bt) * nkb + wq * KBQ) * 2048;              // image s = h0_{s-1}; wave-uniform: the loads' scalar offset
             bf16x8 ah[KBQ];
-#pragma unroll
-            for (int i = 0; i < KBQ; ++i) ah[i] = load_sc1_u(hp0_rsrc, lane * 16, img + i * 2048);
-            __builtin_amdgcn_sched_barrier(0);
             f32x4 acc[4];
+            // data flags: the loads ARE the poll.  The products of a pass that saw an armed fragment are dropped and the pass is
+            // repeated (acc starts from zero every pass, so a repeated pass gives the same bits)
+            unsigned long long t0 = 0;
+            for (int pass = 0;; ++pass) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int i = 0; i < KBQ; ++i) ah[i] = load_sc1_u(hp0_rsrc, lane * 16, img + i * 2048);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < KBQ; ++i)
+                for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], wr[g][i], acc[g], 0, 0, 0);
+                for (int i = 0; i < KBQ; ++i)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], wr[g][i], acc[g], 0, 0, 0);
+                if (!DF) break;
+                if (!__any(armed_lane<KBQ>(ah))) {
+                    if (wave == 0) { stamp(p.stamps, T + 2, s, 10, lane); stamp_value(p.stamps, T + 2, s, 11, lane, (unsigned)pass); }
+                    break;
+                }
+                if (!rearm_wait(t0, pass, p.nap)) {
+                    if (lane == 0) { *sh.s_abort = 1; raise_abort(p.flags, p.status); }
+                    break;
+                }
+            }
             const int r = lane & 15, q = lane >> 4;      // D layout: col = lane & 15 (hidden unit), row = 4 (lane >> 4) + reg (batch row)
 #pragma unroll
             for (int g = 0; g < 4; ++g)
@@ -107,6 +165,7 @@ __device__ __forceinline__ void fwd2_layer0_waves(const Persist2Fwd &p, const Fw
                 for (int e = 0; e < 4; ++e) sh.red[0][wq][g][(4 * q + e) * 16 + r] = acc[g][e];
         }
         lds_barrier();                                                             // (B)
+        if (DF && *sh.s_abort) return;                                             // a wave's fragments never arrived
         if (wave == 0) stamp(p.stamps, T + 2, s, 2, lane);
         float ig = 0.f, fg = 0.f, gg = 0.f, og = 0.f, h = 0.f, xv = 0.f;
         if (act0) {
@@ -136,23 +195,29 @@ __device__ __forceinline__ void fwd2_layer0_waves(const Persist2Fwd &p, const Fw
             bf16x8 hi;
 #pragma unroll
             for (int e = 0; e < 8; ++e) hi[e] = (__bf16)src[row][kg * 8 + e];
+            if (DF) hi = unarm(hi);
             const int within = (jt >> 1) * 2048 + (((jt & 1) * 2 + kg) * 16 + row) * 16;
+            const bool store = !DF || (int)blockIdx.x != p.mute;                  // (data flags: a mute workgroup publishes nothing)
             if (wave == 3) {
-                if (sel == 0) store_sc1(hp0_rsrc, (((s + 1) * NBT + bt) * nkb) * 2048 + within, hi);
-                else if (p.xp) store_sc1(x_rsrc, ((s * NBT + bt) * nkb) * 2048 + within, hi);
-            } else if (sel == 0) {
+                if (sel == 0 && store) store_sc1(hp0_rsrc, (((s + 1) * NBT + bt) * nkb) * 2048 + within, hi);
+                else if (sel == 1 && p.xp && store) store_sc1(x_rsrc, ((s * NBT + bt) * nkb) * 2048 + within, hi);
+            } else if (sel == 0 && store) {
                 store_sc1(hp1_rsrc, (((s - 1) * NBT + bt) * nkb) * 2048 + within, hi);
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      // the write-through stores have left
-            // the last storing wave of the step to get here signals for the workgroup (counter in LDS: Guideline 16); through
-            // combined step s layer 0 has stored min(s + 1, T) times, layer 1 max(s - 1, 0) times
-            unsigned old = 0;
-            if (lane == 0) old = atomicAdd(sh.s_published, 1u);
-            old = __builtin_amdgcn_readfirstlane(old);
-            const unsigned target = (unsigned)((s + 1 < T ? s + 1 : T) + (s >= 2 ? s - 1 : 0));
-            if (old + 1u == target && (int)blockIdx.x != p.mute) publish_epoch(p.flags, btl * NJ + jt, p.epoch0 + (unsigned)(s + 1), lane);
-            stamp(p.stamps, T + 2, s, wave == 3 ? 4 : 5, lane);
-        } else if (wave == 3 && !act0 && !act1) {
+            if (DF) {
+                stamp(p.stamps, T + 2, s, wave == 3 ? 4 : 5, lane);               // the stores are the publication: no drain, no epoch word
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      // the write-through stores have left
+                // the last storing wave of the step to get here signals for the workgroup (counter in LDS: Guideline 16); through
+                // combined step s layer 0 has stored min(s + 1, T) times, layer 1 max(s - 1, 0) times
+                unsigned old = 0;
+                if (lane == 0) old = atomicAdd(sh.s_published, 1u);
+                old = __builtin_amdgcn_readfirstlane(old);
+                const unsigned target = (unsigned)((s + 1 < T ? s + 1 : T) + (s >= 2 ? s - 1 : 0));
+                if (old + 1u == target && (int)blockIdx.x != p.mute) publish_epoch(p.flags, btl * NJ + jt, p.epoch0 + (unsigned)(s + 1), lane);
+                stamp(p.stamps, T + 2, s, wave == 3 ? 4 : 5, lane);
+            }
+        } else if (!DF && wave == 3 && !act0 && !act1) {
             publish_epoch(p.flags, btl * NJ + jt, p.epoch0 + (unsigned)(s + 1), lane);       // T = 1: neither layer has a step here, the epoch still moves
         }
         if (p.img_hT0 && ((wave == 3 && act0) || (wave == 2 && act1))) {
@@ -190,7 +255,7 @@ __device__ __forceinline__ void fwd2_layer0_waves(const Persist2Fwd &p, const Fw
     }
 }
 
-template <int KBQ>
+template <int KBQ, bool DF>
 __device__ __forceinline__ void fwd2_layer1_waves(const Persist2Fwd &p, const Fwd2Shared sh, char *wi_lds, int jt, int bt, int wave, int lane,
                                                   int u) {
     // W_ih1's K-quarter is 4 KBQ fragments of 1 KiB per layer-1 wave, kept in LDS; at KBQ = 8 the four quarters (128 KiB) and the
@@ -244,28 +309,65 @@ __device__ __forceinline__ void fwd2_layer1_waves(const Persist2Fwd &p, const Fw
         // step's poll matched, are requested with the step's own: nothing of them is left for the hand-off window, where loads
         // would sit in front of the epoch stores and polls in the CU's memory queue
         bf16x8 ax[KBQ];
-        if (xin) {
-            const int ximg = (((p.xp ? s - 1 : s) * NBT + bt) * nkb + wq * KBQ) * 2048;
-#pragma unroll
-            for (int i = 0; i < KBQ; ++i) ax[i] = load_sc1_u(x_rsrc, lane * 16, ximg + i * 2048);
-        }
-        if (act1) {
-            const int img = ((t * NBT + bt) * nkb + wq * KBQ) * 2048;              // image t = h1_{t-1}
+        if constexpr (DF) {
+            // data flags: both sets of fragments in every pass, from images clamped into range (a set the step does not use is not
+            // checked), loads outside conditionals; the products follow the check, for xacc already holds the
+            // input half of this step and cannot be recomputed
+            const int ximg = ((min(max(p.xp ? s - 1 : s, 0), p.xp ? T - 1 : T) * NBT + bt) * nkb + wq * KBQ) * 2048;
+            const int img = ((max(t, 0) * NBT + bt) * nkb + wq * KBQ) * 2048;    // t <= T - 1
             bf16x8 ah[KBQ];
+            unsigned long long t0 = 0;
+            for (int pass = 0;; ++pass) {
 #pragma unroll
-            for (int i = 0; i < KBQ; ++i) ah[i] = load_sc1_u(hp1_rsrc, lane * 16, img + i * 2048);
-            __builtin_amdgcn_sched_barrier(0);
+                for (int i = 0; i < KBQ; ++i) ax[i] = load_sc1_u(x_rsrc, lane * 16, ximg + i * 2048);
 #pragma unroll
-            for (int i = 0; i < KBQ; ++i)
+                for (int i = 0; i < KBQ; ++i) ah[i] = load_sc1_u(hp1_rsrc, lane * 16, img + i * 2048);
+                const bool bx = armed_lane<KBQ>(ax), bh = armed_lane<KBQ>(ah);
+                if (!__any((xin && bx) || (act1 && bh))) {
+                    if (wave == 4) { stamp(p.stamps, T + 2, s, 12, lane); stamp_value(p.stamps, T + 2, s, 13, lane, (unsigned)pass); }
+                    break;
+                }
+                if (!rearm_wait(t0, pass, p.nap)) {
+                    if (lane == 0) { *sh.s_abort = 1; raise_abort(p.flags, p.status); }
+                    break;
+                }
+            }
+            if (act1) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) xacc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], wr[g][i], xacc[g], 0, 0, 0);
-            const int r = lane & 15, q = lane >> 4;
+                for (int i = 0; i < KBQ; ++i)
 #pragma unroll
-            for (int g = 0; g < 4; ++g)
+                    for (int g = 0; g < 4; ++g) xacc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], wr[g][i], xacc[g], 0, 0, 0);
+                const int r = lane & 15, q = lane >> 4;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) sh.red[1][wq][g][(4 * q + e) * 16 + r] = xacc[g][e];
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sh.red[1][wq][g][(4 * q + e) * 16 + r] = xacc[g][e];
+            }
+        } else {
+            if (xin) {
+                const int ximg = (((p.xp ? s - 1 : s) * NBT + bt) * nkb + wq * KBQ) * 2048;
+#pragma unroll
+                for (int i = 0; i < KBQ; ++i) ax[i] = load_sc1_u(x_rsrc, lane * 16, ximg + i * 2048);
+            }
+            if (act1) {
+                const int img = ((t * NBT + bt) * nkb + wq * KBQ) * 2048;              // image t = h1_{t-1}
+                bf16x8 ah[KBQ];
+#pragma unroll
+                for (int i = 0; i < KBQ; ++i) ah[i] = load_sc1_u(hp1_rsrc, lane * 16, img + i * 2048);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < KBQ; ++i)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) xacc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], wr[g][i], xacc[g], 0, 0, 0);
+                const int r = lane & 15, q = lane >> 4;
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sh.red[1][wq][g][(4 * q + e) * 16 + r] = xacc[g][e];
+            }
         }
         lds_barrier();                                                             // (B)
+        if (DF && *sh.s_abort) return;
         float ig = 0.f, fg = 0.f, gg = 0.f, og = 0.f, h = 0.f;
         if (act1) {
             if (cell) {
@@ -310,7 +412,7 @@ __device__ __forceinline__ void fwd2_layer1_waves(const Persist2Fwd &p, const Fw
     }
 }
 
-template <int KBQ>
+template <int KBQ, bool DF>
 __global__ __launch_bounds__(512, 2) void lstm_persist2_fwd_kernel(const Persist2Fwd p) {
     __shared__ float red[2][4][4][256];
     __shared__ __attribute__((aligned(16))) float hbuf[3][16][16];
@@ -326,8 +428,8 @@ __global__ __launch_bounds__(512, 2) void lstm_persist2_fwd_kernel(const Persist
     if (wave == 0) stamp(p.stamps, p.T + 2, 0, 14, lane);            // (diagnostic: launch entry / exit of this workgroup)
     const Fwd2Shared sh = {red, hbuf, &s_abort, &s_published};
     // (the first barrier of either loop orders the two initialisations above before any use)
-    if (wave < 4) fwd2_layer0_waves<KBQ>(p, sh, jt, bt, wave, lane, tid & 255);
-    else fwd2_layer1_waves<KBQ>(p, sh, wi_lds, jt, bt, wave, lane, tid & 255);
+    if (wave < 4) fwd2_layer0_waves<KBQ, DF>(p, sh, jt, bt, wave, lane, tid & 255);
+    else fwd2_layer1_waves<KBQ, DF>(p, sh, wi_lds, jt, bt, wave, lane, tid & 255);
     if (wave == 0) stamp(p.stamps, p.T + 2, 0, 15, lane);
 }
 
@@ -717,12 +819,22 @@ inline bool interleave_on() {
     static const bool env_off = getenv("HALO_LSTM_INTERLEAVE") && atoi(getenv("HALO_LSTM_INTERLEAVE")) == 0;
     return !env_off && halo_ctx_cur().lstm_interleave != 0;
 }
+// the interleaved launches (two tiles per workgroup) take this batch
+inline bool pairs_for(int T, int B, int H) {
+    return (B + 15) / 16 > tiles_per_launch(H) && interleave_on() && (long)(T + 1) * B * 4 * H * (long)sizeof(float) < (1L << 31);
+}
+
+bool halo_lstm_persist2_dataflag() {
+    static const bool on = !(getenv("HALO_PERSIST_DATAFLAG") && atoi(getenv("HALO_PERSIST_DATAFLAG")) == 0);
+    return on;
+}
+bool halo_lstm_persist2_fwd_armed(int T, int B, int H) { return halo_lstm_persist2_dataflag() && !pairs_for(T, B, H); }
 
 template <typename A, typename F, typename FX>
 int launch_groups(const A &a0, int steps, F launch_one, FX launch_pairs) {
     const int nbt = (a0.B + 15) / 16, per = tiles_per_launch(a0.H);
     // (the interleaved kernels address the saved activations through 2 GiB buffer resources: a longer array keeps the consecutive launches)
-    const bool pairs = nbt > per && interleave_on() && (long)(a0.T + 1) * a0.B * 4 * a0.H * (long)sizeof(float) < (1L << 31);
+    const bool pairs = pairs_for(a0.T, a0.B, a0.H);
     for (int bt0 = 0, g = 0; bt0 < nbt; ++g) {
         A a = a0;
         const int left = nbt - bt0;
@@ -747,12 +859,17 @@ int launch_groups(const A &a0, int steps, F launch_one, FX launch_pairs) {
 int halo_lstm_persist2_fwd(const Persist2Fwd &a0, hipStream_t st) {
     const int kbq = a0.H / 128;
     const size_t dyn = (size_t)4 * 1024 * (4 * kbq - (kbq >= 8 ? 2 : 0));      // 4 quarters x NWLDS fragments of 1 KiB
+    const bool df = halo_lstm_persist2_fwd_armed(a0.T, a0.B, a0.H);       // the launch ahead armed the images exactly then (lstm.hip)
     return launch_groups(a0, a0.T + 2, [&](const Persist2Fwd &a, int blocks) {
-        switch (kbq) {
-            case 2: return launch2(lstm_persist2_fwd_kernel<2>, a, blocks, dyn, st);
-            case 4: return launch2(lstm_persist2_fwd_kernel<4>, a, blocks, dyn, st);
-            case 6: return launch2(lstm_persist2_fwd_kernel<6>, a, blocks, dyn, st);
-            case 8: return launch2(lstm_persist2_fwd_kernel<8>, a, blocks, dyn, st);
+        switch (kbq * 2 + (df ? 1 : 0)) {
+            case 4: return launch2(lstm_persist2_fwd_kernel<2, false>, a, blocks, dyn, st);
+            case 5: return launch2(lstm_persist2_fwd_kernel<2, true>, a, blocks, dyn, st);
+            case 8: return launch2(lstm_persist2_fwd_kernel<4, false>, a, blocks, dyn, st);
+            case 9: return launch2(lstm_persist2_fwd_kernel<4, true>, a, blocks, dyn, st);
+            case 12: return launch2(lstm_persist2_fwd_kernel<6, false>, a, blocks, dyn, st);
+            case 13: return launch2(lstm_persist2_fwd_kernel<6, true>, a, blocks, dyn, st);
+            case 16: return launch2(lstm_persist2_fwd_kernel<8, false>, a, blocks, dyn, st);
+            case 17: return launch2(lstm_persist2_fwd_kernel<8, true>, a, blocks, dyn, st);
             default: return (int)HALO_ENOTSUP;
         }
     }, [&](const Persist2Fwd &a) { return halo_lstm_persist2x_fwd(a, st); });
