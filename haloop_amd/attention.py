@@ -507,9 +507,11 @@ class GPT(nn.Module):
             x, sv = fwd(self._images, blk, x, B, T, cfg, sites)
             blocks.append(sv)
         targets = target_ids.reshape(-1)
-        if fwd is block_forward_train_rm and rows_ok(B * T, C) and cfg.vocab_size % 8 == 0:
+        V = cfg.vocab_size
+        if fwd is block_forward_train_rm and rows_ok(B * T, C) and ops.gemm_rows_supported(B * T, V, C) and ops.gemm_rows_supported(B * T, C, V):
             # round 5: ln_f's rows as row-major bf16, the lm_head product on halo_gemm_rows with the cross-entropy statistics in its
-            # epilogue (from the fp32 accumulators) and the logits KEPT AS bf16 (1.65 GB of fp32 at B = 8, T = 1024 no longer written)
+            # epilogue (from the fp32 accumulators) and the logits KEPT AS bf16 (1.65 GB of fp32 at B = 8, T = 1024 no longer written).
+            # Only when the backward's input-gradient product (K = V) runs on halo_gemm_rows too: V % 32 == 0.
             xf = ops.layernorm_bf16(x, tr.ln_f.weight, tr.ln_f.bias)
             loss, row_lse, logits = ops.gemm_rows_ce(xf, self._images.split((self.lm_head.weight,)), B * T, cfg.vocab_size, C, targets,
                                                      ignore_index=0, want_logits=True, want_lse=True)

@@ -153,8 +153,9 @@ __global__ __launch_bounds__(256) void dec_linear_kernel(const DecLinearArgs p) 
 #pragma unroll
         for (int i = 0; i < NK; ++i) product(xv[i], wh[i], wl[i]);
     } else {
-        // K % 512 == 0: every wave walks its K quarter U k steps at a time (8 while that divides it: K = 1024 is then one round of
-        // loads, K = 2048 two), all loads of a group issued before its first MFMA
+        // K % 512 == 0: every wave walks its ksw k steps U at a time (8 while that divides it: K = 1024 is then one round of loads,
+        // K = 2048 two; else 4, and a last group of 2 when ksw % 4 == 2 -- two K-slices at K = 1536 or 512), all loads of a group issued
+        // before its first MFMA.  ksw = K / (128 * nsl) is even for every K the host accepts.
         auto group = [&](int i0, auto uc) {
             constexpr int U = decltype(uc)::value;
             float xv[U][8];
@@ -174,8 +175,13 @@ __global__ __launch_bounds__(256) void dec_linear_kernel(const DecLinearArgs p) 
 #pragma unroll
             for (int u = 0; u < U; ++u) product(xv[u], wh[u], wl[u]);
         };
-        if (ksw % 8 == 0) for (int i0 = 0; i0 < ksw; i0 += 8) group(i0, std::integral_constant<int, 8>{});
-        else for (int i0 = 0; i0 < ksw; i0 += 4) group(i0, std::integral_constant<int, 4>{});
+        if (ksw % 8 == 0) {
+            for (int i0 = 0; i0 < ksw; i0 += 8) group(i0, std::integral_constant<int, 8>{});
+        } else {
+            int i0 = 0;
+            for (; i0 + 4 <= ksw; i0 += 4) group(i0, std::integral_constant<int, 4>{});
+            if (i0 < ksw) group(i0, std::integral_constant<int, 2>{});
+        }
     }
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
@@ -525,9 +531,10 @@ int halo_decode_linear(const float *x, long ldx, int rows, int k, const float *l
 int halo_decode_linear_pair(const float *x, const float *x_side, long ldx, int rows, int k, const float *ln_weight, float eps, const void *w_image,
                             int n_out, float *out, const float *side_in, float *side_out, long ldo, int flags, halo_stream_t stream) {
     HALO_CHECK_ARG(x && w_image && out && rows > 0 && n_out > 0 && ldx >= k && ldo >= n_out);
-    // the side of the input rows: LayerNorm variants only; the K-sliced accumulate: no LayerNorm, ACCUM alone, whole k-steps per wave and slice
+    // the side of the input rows: LayerNorm variants only; the K-sliced accumulate: no LayerNorm, ACCUM alone, an even count of k-steps per
+    // wave and slice (K % 512 == 0, as halo_decode_linear_supported asks of every product without LayerNorm)
     HALO_CHECK_ARG(!x_side || ln_weight);
-    HALO_CHECK_ARG(!side_out || (!ln_weight && flags == HALO_GEMM_ACCUM && k % 256 == 0 && side_out != out && side_out != side_in));
+    HALO_CHECK_ARG(!side_out || (!ln_weight && flags == HALO_GEMM_ACCUM && k % 512 == 0 && side_out != out && side_out != side_in));
     HALO_CHECK_ARG(!side_in || side_out);
     HALO_CHECK_ARG(((uintptr_t)x_side) % 16 == 0);
     HALO_CHECK_ARG(halo_decode_linear_supported(k, ln_weight != nullptr));

@@ -1144,7 +1144,7 @@ def decode_image(weight):
 def decode_linear(x, image, n_out, out, ln_weight=None, eps=1e-5, accumulate=False, gelu=False, x_side=None, side_in=None, side_out=None):
     """out (+)= act(layer_norm?(x) W^T) with W given by its decode image; x [rows, k] and out [rows, >= n_out] fp32 (row strides kept).
     The residual stream as a pair (halo_decode_linear_pair): ``x_side`` (LayerNorm variants) is added to the input rows; ``side_out``
-    (accumulating, no LayerNorm, k % 256 == 0) runs the product as two K-slices: out = (out + side_in) + the first half, side_out = the
+    (accumulating, no LayerNorm, k % 512 == 0) runs the product as two K-slices: out = (out + side_in) + the first half, side_out = the
     second -- the next launch reads out + side_out."""
     rows, k = x.shape
     flags = (_lib.HALO_GEMM_ACCUM if accumulate else 0) | (_lib.HALO_GEMM_GELU_ERF if gelu else 0)

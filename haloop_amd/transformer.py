@@ -610,7 +610,7 @@ class Decoder(nn.Module):
         # its rows over the whole K) run as two K-slices on twice the workgroups: the residual stream is the pair (y, side) -- slice 0
         # writes y = (y + side) + its half, slice 1 its half to the OTHER side buffer; the LayerNorm launches read y + side.  Every sum in
         # a fixed order (HALO_DECODE_KSPLIT=0: one slice, the round-4 launches).
-        ksplit = os.environ.get('HALO_DECODE_KSPLIT', '1') != '0' and (2 * C) % 256 == 0
+        ksplit = os.environ.get('HALO_DECODE_KSPLIT', '1') != '0' and (2 * C) % 512 == 0
         sa, sb = (torch.empty(N, C, device=dev, dtype=torch.float32) for _ in range(2)) if ksplit else (None, None)
         for t in range(T):
             side = None                                                      # (y alone: the embedding of the step's token)

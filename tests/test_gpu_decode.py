@@ -6,9 +6,9 @@
         <= 2e-6 abs (another summation order of the dot products), the fp16 caches BITWISE;
     halo_decode_token against halo_logprob_max + halo_greedy_update + halo_embed_fwd: tokens, alive flags, lengths and the next
         embedding BITWISE, the log-prob / entropy accumulators to 2e-5 + 2e-6 relative (another fixed summation order over the vocabulary);
-    Decoder.decode on the fused launches against the operator-per-launch path on a random 3-layer 8x64 model: token ids and lengths
-        EXACT, log-probs / entropies <= 2e-3 (the reference-generated `transformer:32` fixture is checked in test_gpu_asr.py, which
-        runs the fused path in bf16x3 mode).
+    Decoder.decode on the fused launches against the operator-per-launch path on random 3-layer 8x64 and 12x64 models: token ids and
+        lengths EXACT, log-probs / entropies <= 2e-3 (the reference-generated `transformer:32` fixture is checked in test_gpu_asr.py, which
+        runs the fused path in bf16x3 mode); at C = 12 x 64 = 768 also against oracle.transformer_ref.decoder_decode.
 """
 import numpy as np
 import pytest
@@ -54,23 +54,42 @@ def test_decode_linear(hal, rows, K, n_out, ln, accumulate, gelu):
     assert torch.equal(got[:, n_out:], out0[:, n_out:])                             # nothing written past the features
 
 
-@pytest.mark.parametrize('rows,K,n_out', [(64, 1024, 512), (64, 2048, 512), (21, 1024, 100), (128, 2048, 1024)])
+def _nan_guarded_x(x, guard_floats=4 * 32):
+    """x [rows, K] at the head of a NaN-filled buffer with `guard_floats` after its last row: a read past the operand lands in the
+    test's own allocation and turns the result into NaN, it cannot fault."""
+    buf = torch.full((x.numel() + guard_floats,), float('nan'), device=DEV)
+    buf[:x.numel()] = x.reshape(-1).to(DEV)
+    return buf[:x.numel()].view(x.shape)
+
+
+def _nan_guarded_image(img, guard_bytes=8192):
+    """A copy of a decode image followed by `guard_bytes` of 0xff (a bf16 NaN in every fragment element)."""
+    buf = torch.full((img.numel() + guard_bytes,), 255, device=DEV, dtype=torch.uint8)
+    buf[:img.numel()] = img
+    return buf[:img.numel()]
+
+
+@pytest.mark.parametrize('rows,K,n_out', [(64, 1024, 512), (64, 2048, 512), (21, 1024, 100), (128, 2048, 1024),
+                                          (64, 1536, 768), (64, 512, 256), (21, 1536, 100)])
 def test_decode_linear_with_the_residual_stream_as_a_pair(hal, rows, K, n_out):
     """halo_decode_linear_pair: an accumulating product as two K-slices -- out = (out + side_in) + the first half, side_out = the second
     half -- against the fp64 product; out + side_out is the accumulated stream; the same bits on every run; a LayerNorm launch given the
-    pair reads exactly what it reads from the summed rows."""
+    pair reads exactly what it reads from the summed rows.  K = 1536 (2C at C = 768) and 512 give each wave 6 and 2 k-steps, not a
+    multiple of 4: x and the weight image sit in front of NaN guard bands, so a wave that walks past its own k-steps (past the operands)
+    shows up as NaN or as a wrong sum, never as a fault."""
     ops, lib = hal['ops'], hal['lib']
     g = torch.Generator().manual_seed(rows + K + n_out)
     x = torch.randn(rows, K, generator=g) * 1.5 + 0.3
     w = torch.randn(n_out, K, generator=g) / K ** 0.5
+    xg = _nan_guarded_x(x)
+    img = _nan_guarded_image(ops.decode_image(w.to(DEV)))
     main0 = torch.randn(rows, n_out + 8, generator=g)
     side0 = torch.randn(rows, n_out + 8, generator=g)
-    img = ops.decode_image(w.to(DEV))
     ref = x.double() @ w.double().t() + main0[:, :n_out].double() + side0[:, :n_out].double()
     runs = []
     for _ in range(2):
         main, side_in, side_out = main0.to(DEV), side0.to(DEV), torch.full((rows, n_out + 8), 7.0, device=DEV)
-        ops.decode_linear(x.to(DEV), img, n_out, main, accumulate=True, side_in=side_in, side_out=side_out)
+        ops.decode_linear(xg, img, n_out, main, accumulate=True, side_in=side_in, side_out=side_out)
         runs.append((main.cpu(), side_out.cpu()))
     (main, side), (main_b, side_b) = runs
     assert torch.equal(main, main_b) and torch.equal(side, side_b)
@@ -79,7 +98,7 @@ def test_decode_linear_with_the_residual_stream_as_a_pair(hal, rows, K, n_out):
     assert torch.equal(main[:, n_out:], main0[:, n_out:]) and bool((side[:, n_out:] == 7.0).all())       # nothing written past the features
     # without a side coming in
     main = main0.to(DEV); side_out = torch.zeros(rows, n_out + 8, device=DEV)
-    ops.decode_linear(x.to(DEV), img, n_out, main, accumulate=True, side_out=side_out)
+    ops.decode_linear(xg, img, n_out, main, accumulate=True, side_out=side_out)
     got = (main[:, :n_out].double() + side_out[:, :n_out].double()).cpu()
     np.testing.assert_allclose(got.numpy(), (ref - side0[:, :n_out].double()).numpy(), rtol=0, atol=3e-5 * float(ref.abs().max()))
     # a LayerNorm launch reading the pair == the same launch on the summed rows
@@ -94,9 +113,9 @@ def test_decode_linear_with_the_residual_stream_as_a_pair(hal, rows, K, n_out):
         assert torch.equal(o1, o2)
     # refusals: the sliced form needs ACCUM alone and distinct buffers
     with pytest.raises(lib.HaloError):
-        ops.decode_linear(x.to(DEV), img, n_out, main, accumulate=False, side_out=side_out)
+        ops.decode_linear(xg, img, n_out, main, accumulate=False, side_out=side_out)
     with pytest.raises(lib.HaloError):
-        ops.decode_linear(x.to(DEV), img, n_out, main, accumulate=True, side_in=side_out, side_out=side_out)
+        ops.decode_linear(xg, img, n_out, main, accumulate=True, side_in=side_out, side_out=side_out)
 
 
 def test_decode_linear_refusals(hal):
@@ -106,6 +125,13 @@ def test_decode_linear_refusals(hal):
     img = ops.decode_image(torch.zeros(16, 640, device=DEV))
     with pytest.raises(lib.HaloError):
         ops.decode_linear(x, img, 16, torch.zeros(4, 16, device=DEV))
+    # the K-sliced form: every wave of both slices walks whole pairs of k-steps, so K % 512 == 0 (768 = 3 x 256 would leave a wave an odd
+    # count of k-steps)
+    assert not ops.decode_linear_supported(768, False)
+    x = torch.zeros(4, 768, device=DEV)
+    img = ops.decode_image(torch.zeros(16, 768, device=DEV))
+    with pytest.raises(lib.HaloError):
+        ops.decode_linear(x, img, 16, torch.zeros(4, 16, device=DEV), accumulate=True, side_out=torch.zeros(4, 16, device=DEV))
 
 
 @pytest.mark.parametrize('N,heads,hd,S,T,t', [(5, 8, 64, 10, 9, 0), (5, 8, 64, 10, 9, 4), (3, 2, 32, 70, 80, 71), (64, 8, 64, 10, 9, 8)])
@@ -170,31 +196,62 @@ def test_decode_token_equals_three_launches(hal, N, V, C, t, plen):
         np.testing.assert_allclose(u.cpu().numpy(), v.cpu().numpy(), rtol=2e-6, atol=2e-5)
 
 
-@pytest.mark.parametrize('prompt', [False, True])
-def test_fused_decode_matches_operator_path(hal, monkeypatch, prompt):
+class _SlicedProducts:
+    """Counts the halo_decode_linear_pair launches that run as two K-slices (side_out given), by K: the end-to-end cases below must
+    reach the sliced K = 2C product."""
+
+    def __init__(self, lib):
+        self.lib, self.by_k = lib, {}
+
+    def __enter__(self):
+        L = self.lib.lib()
+        self.fn = L.halo_decode_linear_pair
+
+        def wrap(*a):
+            if a[11] is not None:                                        # side_out
+                self.by_k[a[4]] = self.by_k.get(a[4], 0) + 1
+            return self.fn(*a)
+        L.halo_decode_linear_pair = wrap
+        return self
+
+    def __exit__(self, *exc):
+        self.lib.lib().halo_decode_linear_pair = self.fn
+
+
+def _decoder(tr, V, hd, heads, L, seed):
     from oracle import transformer_ref
+    pd = transformer_ref.make_decoder_params(V, hd, heads, L, seed, sharp=4.0)
+    dec = tr.Decoder(vocab=V, head_dim=hd, heads=heads, p_drop=0.2, layers=L)
+    dec.load_state_dict({k[len('decoder.'):]: v for k, v in pd.items() if k.startswith('decoder.')}, strict=True)
+    return pd, dec.to(DEV).eval()
+
+
+@pytest.mark.parametrize('prompt,hd,heads,N', [pytest.param(p, 64, 8, 21, id=str(p)) for p in (False, True)]
+                         + [pytest.param(p, 64, 12, n, id=f'c768-n{n}-{p}') for n in (21, 64) for p in (False, True)])
+def test_fused_decode_matches_operator_path(hal, monkeypatch, prompt, hd, heads, N):
+    """heads = 12 is C = 768, the reference's default width: the K-sliced products run at K = 2C = 1536 (6 k-steps per wave)."""
     tr, lib = hal['tr'], hal['lib']
     prev = lib.get_math_mode()
     lib.set_math_mode('bf16x3')
     try:
-        V, hd, heads, L, N, S = 32, 64, 8, 3, 21, 10
-        pd = transformer_ref.make_decoder_params(V, hd, heads, L, 11)
-        dec = tr.Decoder(vocab=V, head_dim=hd, heads=heads, p_drop=0.2, layers=L)
-        dec.load_state_dict({k[len('decoder.'):]: v for k, v in pd.items() if k.startswith('decoder.')}, strict=True)
-        dec = dec.to(DEV).eval()
+        V, L, S = 32, 3, 10
+        C = heads * hd
+        _, dec = _decoder(tr, V, hd, heads, L, 11)
         g = torch.Generator().manual_seed(5)
-        feats = torch.randn(N, S, heads * hd, generator=g).to(DEV)
+        feats = torch.randn(N, S, C, generator=g).to(DEV)
         flen = torch.randint(3, S + 1, (N,), generator=g).to(DEV)
         tl = torch.randint(4, 9, (N,), generator=g).to(DEV)
         pr = torch.tensor([[7, 9]] * N) if prompt else None
-        assert dec._fused_decode_ok(heads * hd)
+        assert dec._fused_decode_ok(C)
         res = {}
         for fused in ('1', '0'):
             monkeypatch.setenv('HALO_DECODE_FUSED', fused)
             for graph in ('1', '0'):
                 monkeypatch.setenv('HALO_DECODE_GRAPH', graph)
-                with torch.no_grad():
+                with torch.no_grad(), _SlicedProducts(lib) as sliced:
                     outs, olen, _, lps, ents = dec.decode(feats, flen, tl, prompt=pr)
+                if fused == '1':
+                    assert sliced.by_k.get(2 * C, 0) >= L and sliced.by_k.get(4 * C, 0) >= L, (graph, sliced.by_k)
                 res[fused, graph] = ([o.tolist() for o in outs.unbind()], olen.cpu(), lps.cpu(), ents.cpu())
         base = res['0', '0']
         for key, (toks, olen, lps, ents) in res.items():
@@ -202,5 +259,34 @@ def test_fused_decode_matches_operator_path(hal, monkeypatch, prompt):
             np.testing.assert_allclose(lps.numpy(), base[2].numpy(), rtol=0, atol=2e-3, err_msg=str(key))
             np.testing.assert_allclose(ents.numpy(), base[3].numpy(), rtol=1e-4, atol=2e-3, err_msg=str(key))
         assert torch.equal(res['1', '1'][2], res['1', '0'][2])                       # graph replay = eager launches, bitwise
+    finally:
+        lib.set_math_mode(prev)
+
+
+@pytest.mark.parametrize('N', [21, 64])
+def test_fused_decode_at_width_768_matches_the_oracle(hal, N):
+    """Decoder.decode at C = 12 x 64 = 768 (ha/transformer.py's default width) on the fused launches with K-sliced products, graph
+    replay, against oracle.transformer_ref.decoder_decode: token ids and lengths EXACT, accumulated log-probs <= 2e-3 abs."""
+    from oracle import transformer_ref
+    tr, lib = hal['tr'], hal['lib']
+    prev = lib.get_math_mode()
+    lib.set_math_mode('bf16x3')
+    try:
+        V, hd, heads, L, S = 32, 64, 12, 2, 12
+        C = heads * hd
+        pd, dec = _decoder(tr, V, hd, heads, L, 13)
+        g = torch.Generator().manual_seed(N)
+        feats = torch.randn(N, S, C, generator=g)
+        flen = torch.randint(3, S + 1, (N,), generator=g)
+        tl = torch.randint(4, 9, (N,), generator=g)
+        assert dec._fused_decode_ok(C)
+        with torch.no_grad(), _SlicedProducts(lib) as sliced:
+            outs, olen, _, lps, ents = dec.decode(feats.to(DEV), flen.to(DEV), tl.to(DEV))
+            o_outs, o_len, o_lps, o_ents, _ = transformer_ref.decoder_decode(pd, feats, flen, tl, heads, pre='decoder.')
+        assert sliced.by_k.get(2 * C, 0) >= L and sliced.by_k.get(4 * C, 0) >= L, sliced.by_k
+        assert olen.cpu().tolist() == o_len.tolist()
+        assert [o.tolist() for o in outs.unbind()] == [o.tolist() for o in o_outs]
+        np.testing.assert_allclose(lps.cpu().numpy(), o_lps.numpy(), rtol=0, atol=2e-3)
+        np.testing.assert_allclose(ents.cpu().numpy(), o_ents.numpy(), rtol=1e-4, atol=2e-3)
     finally:
         lib.set_math_mode(prev)

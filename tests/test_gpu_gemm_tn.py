@@ -207,23 +207,48 @@ def test_tn_rows_refusals(bf16_mode):
 
 
 def test_gpt_step_with_the_256_row_weight_gradients(bf16_mode, monkeypatch):
-    """The GPT training step's gradients with the weight gradients on the 256-row tiles against the 128 x 128 tiles (same operands, another
-    summation order): every gradient within fp32 accumulation noise."""
-    from haloop_amd import attention
+    """The GPT training step's gradients with the weight gradients on the 256-row tiles (halo_gemm_tn_rows_group) against the 128 x 128
+    tiles (halo_gemm_tn_bf16_group): same operands, another summation order, so every gradient within fp32 accumulation noise.  At
+    M = 8192 token rows and C = 512, where the row-major training path (and with it gemm_tn_group) runs; the launches are counted."""
+    import contextlib
+    from haloop_amd import _lib, attention
     torch.manual_seed(3)
-    cfg = attention.GPTConfig(block_size=256, vocab_size=1024, n_layer=2, n_head=4, n_embd=256)
+    cfg = attention.GPTConfig(block_size=1024, vocab_size=1024, n_layer=1, n_head=8, n_embd=512)
     model = attention.GPT(cfg).cuda().train()
-    ids = torch.randint(1, 1024, (4, 256), device='cuda')
+    ids = torch.randint(1, 1024, (8, 1024), device='cuda')
     tg = torch.roll(ids, -1, 1)
+    assert attention.rowmajor_train_ok(cfg, model.transformer.h, 8 * 1024, True) and attention.rows_ok(8 * 1024, 512)
+
+    @contextlib.contextmanager
+    def counted():
+        L = _lib.lib()
+        calls = {}
+        orig = {n: getattr(L, n) for n in ('halo_gemm_tn_rows_group', 'halo_gemm_tn_bf16_group')}
+
+        def wrap(n, fn):
+            def f(*a):
+                calls[n] = calls.get(n, 0) + 1
+                return fn(*a)
+            return f
+        for n, fn in orig.items():
+            setattr(L, n, wrap(n, fn))
+        try:
+            yield calls
+        finally:
+            for n, fn in orig.items():
+                setattr(L, n, fn)
 
     def grads():
         for p in model.parameters():
             p.grad = None
-        model.forward_all(ids, tg).backward()
-        return [p.grad.clone() for p in model.parameters()]
+        with counted() as calls:
+            model.forward_all(ids, tg).backward()
+        return [p.grad.clone() for p in model.parameters()], calls
     monkeypatch.setenv('HALO_GEMM_TN_ROWS', '1')
-    new = grads()
+    new, calls = grads()
+    assert calls.get('halo_gemm_tn_rows_group', 0) >= 2 and 'halo_gemm_tn_bf16_group' not in calls, calls     # the block's four, the lm_head
     monkeypatch.setenv('HALO_GEMM_TN_ROWS', '0')
-    old = grads()
+    old, calls = grads()
+    assert calls.get('halo_gemm_tn_bf16_group', 0) >= 2 and 'halo_gemm_tn_rows_group' not in calls, calls
     for a, b in zip(new, old):
         assert (a - b).abs().max().item() <= 1e-5 + 1e-4 * b.abs().max().item()
