@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'csrc', 'libhalo.so')
 
-HALO_ABI_VERSION = 19
+HALO_ABI_VERSION = 20
 HALO_GEMM_RELU = 1
 HALO_GEMM_GELU = 2
 HALO_GEMM_ACCUM = 4
@@ -67,6 +67,13 @@ SIGNATURES = {
     'halo_gemm_rows_ce_workspace_bytes': (_sz, [_i, _i]),
     'halo_gemm_rows_ce': (_i, [_vp, _vp, _l, _vp, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _vp, _l, _vp]),
     'halo_cross_entropy_bwd_bf16': (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _l, _l, _vp]),
+    'halo_lora_supported': (_i, [_i, _i, _i, _i]),
+    'halo_lora_pack_bytes': (_sz, [_i, _i]),
+    'halo_lora_pack': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    'halo_lora_down': (_i, [_vp, _l, _vp, _i, _i, _f, _vp, _f, _u64, _u32, _u32, _vp, _vp]),
+    'halo_lora_up': (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _l, _f, _u64, _u32, _u32, _vp, _vp]),
+    'halo_lora_tn_workspace_bytes': (_sz, [_i, _i]),
+    'halo_lora_tn': (_i, [_vp, _vp, _l, _i, _i, _i, _f, _i, _vp, _vp, _f, _u64, _u32, _u32, _vp, _vp]),
     'halo_gemm_split_ce_workspace_bytes': (_sz, [_i, _i]),
     'halo_gemm_split_ce': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _l, _vp, _vp, _vp, _vp]),
     'halo_image_pair': (_i, [_vp, _vp, _i, _i, _l, _l, _i, _vp, _vp, _vp]),

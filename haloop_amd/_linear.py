@@ -167,12 +167,13 @@ def forward_images(x2d, n_out, op=ops.PAIR_COPY):
     return None, None
 
 
-def grad_images(dy2d, n_in, op=ops.PAIR_COPY, x2=None):
+def grad_images(dy2d, n_in, op=ops.PAIR_COPY, x2=None, want_dx=True, want_dw=True):
     """(image of dy, image of dy^T) from ONE read of dy [M, out] -- what linear_dx and linear_dw of the same Linear (n_in inputs)
-    each want -- or (None, None) when the split GEMM would not run for it (the callers then pass the fp32 tensor as before)."""
+    each want -- or (None, None) when the split GEMM would not run for it (the callers then pass the fp32 tensor as before).
+    ``want_dx`` / ``want_dw`` False: that product will not run (a frozen weight, nothing trainable below), its image is not built."""
     M, K = dy2d.shape
-    if use_split(M, n_in, K) and use_split(K, n_in, M):
-        return ops.image_pair(dy2d, op, x2)
+    if (want_dx or want_dw) and use_split(M, n_in, K) and use_split(K, n_in, M):
+        return ops.image_pair(dy2d, op, x2, rows_image=want_dx, cols_image=want_dw)
     return None, None
 
 
@@ -180,13 +181,23 @@ class DropSites:
     """Dropout of one training forward: (p, seed, offset) from the module's DropoutStream plus a running stream id, one per
     dropout site in forward order (the backward replays the same ids).  p == 0 hands out NO_DROPOUT."""
     BASE = 64
+    LORA_BASE = 4096          # the adapter-input dropout of block i (haloop_amd/lora.py): id 4096 + i, clear of the ids above
 
-    def __init__(self, drop):
-        self.drop, self.n = drop, 0
+    def __init__(self, drop, lora=None):
+        """lora: (seed, offset, counter) of this forward for the adapter sites, or None (no adapter dropout: eval, or no adapters)."""
+        self.drop, self.n, self.lora, self.layer = drop, 0, lora, 0
 
     def next(self):
         self.n += 1
         return self.drop, self.BASE + self.n - 1
+
+    def next_lora(self, p):
+        """The adapter site of the next block (every block takes one, adapter or not, so that the id is 4096 + layer); its own p."""
+        self.layer += 1
+        sid = self.LORA_BASE + self.layer - 1
+        if self.lora is None or p <= 0.0:
+            return ops.NO_DROPOUT, sid
+        return ops.Dropout(p, *self.lora), sid
 
 
 NO_SITES = DropSites(ops.NO_DROPOUT)

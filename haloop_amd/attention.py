@@ -20,17 +20,22 @@ probabilities inside the attention kernels, c_proj and MLP outputs as GEMM epilo
 
 ``stable_embedding`` (ha/attention.py:30-61: each embedding followed by its own LayerNorm) is built, forward and backward.
 
+LoRA (haloop_amd/lora.py, ``hala --lora``): a ``c_attn`` that is a lora.Linear with an unmerged adapter adds its low-rank term at every
+c_attn site below, and the backward computes a weight gradient only for parameters that require one (a frozen base pays for no
+weight-gradient product).
+
 Not built (raises NotImplementedError): rotary (flash_attn) blocks -- the reference itself cannot construct them without
 flash_attn.
 """
 import math
 import os
+from collections import namedtuple
 from dataclasses import dataclass, asdict
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, lora, ops
 from ._linear import (SMALL_M, DropSites, training_images, WeightImages, drop_rows, forward_images, grad_images, linear, linear_dw, linear_dx, rowmajor_ok,
                       ln_linear, use_split)
 from .rnn import DropoutStream
@@ -112,11 +117,40 @@ class Block(nn.Module):
         self.mlp = MLP(config)
 
 
+# What a block's training forward keeps for its backward: which of the two paths ran (``rowmajor``: block_forward_train_rm), that path's
+# tensors, and the adapter's record (u, dropout site) when an unmerged LoRA adapter sat on c_attn, else None.
+BlockSaved = namedtuple('BlockSaved', 'rowmajor core lora')
+
+
+def adapter_dropout(blocks):
+    """The largest lora_dropout of the unmerged adapters on ``blocks`` (0.0: none would draw a mask in a training forward)."""
+    return max([blk.attn.c_attn.lora_dropout_p for blk in blocks if lora.is_active(blk.attn.c_attn)], default=0.0)
+
+
+def train_sites(stream, p, training, blocks):
+    """DropSites of one training forward over ``blocks``: the module's stream hands out one (seed, offset) per forward, shared by the
+    existing sites (probability p) and the adapter sites (each adapter's own lora_dropout); the offset advances once per forward if
+    either probability is positive."""
+    p_lora = adapter_dropout(blocks) if training else 0.0
+    if p_lora > 0.0 and stream.counter is not None:
+        raise NotImplementedError('adapter dropout under a device-side step counter (captured graph steps) is not built')
+    state = (stream.seed, stream.offset, stream.counter)
+    drop = stream.next(p, training)
+    if p_lora <= 0.0:
+        return DropSites(drop)
+    if drop is ops.NO_DROPOUT:
+        stream.offset += 1
+    return DropSites(drop, state)
+
+
 # ---- one pre-LN GPT block (ha/attention.py:147-180), shared by GPT and haloop_amd.attention_audio.AudioEncoder ----------------
 def block_forward(images, blk, x, B, T, cfg):
     """Inference: the residual stream x [B*T, C] is updated in place."""
     C, H = cfg.n_embd, cfg.n_head
-    qkv, _ = ln_linear(images, x, blk.ln_1.weight, blk.ln_1.bias, blk.attn.c_attn.weight, bias=blk.attn.c_attn.bias)
+    lo = lora.is_active(blk.attn.c_attn)
+    qkv, h1 = ln_linear(images, x, blk.ln_1.weight, blk.ln_1.bias, blk.attn.c_attn.weight, bias=blk.attn.c_attn.bias, want_normed=lo)
+    if lo:
+        lora.lora_forward(blk.attn.c_attn, h1, qkv)
     y, _, _ = ops.attention_fwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal)
     linear(images, y, blk.attn.c_proj.weight, bias=blk.attn.c_proj.bias, out=x, accumulate=True)           # x += c_proj(y)
     if rowmajor_ok(B * T, 4 * C, C) and C % 32 == 0:
@@ -147,6 +181,9 @@ def block_forward_train(images, blk, x0, B, T, cfg, sites):
     C, H = cfg.n_embd, cfg.n_head
     qkv, h1 = ln_linear(images, x0, blk.ln_1.weight, blk.ln_1.bias, blk.attn.c_attn.weight, bias=blk.attn.c_attn.bias, want_normed=True)
     s_att, s_res, s_mlp = sites.next(), sites.next(), sites.next()
+    lo = lora.is_active(blk.attn.c_attn)
+    s_lo = sites.next_lora(blk.attn.c_attn.lora_dropout_p if lo else 0.0)
+    lo_saved = (lora.lora_forward(blk.attn.c_attn, h1, qkv, s_lo), s_lo) if lo else None
     y, lse, _ = ops.attention_fwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal, want_lse=True,
                                   drop=s_att[0], stream_id=s_att[1])
     # y and gelu(a) each feed one Linear now and its weight gradient later: both operand images come out of one read, and
@@ -159,48 +196,56 @@ def block_forward_train(images, blk, x0, B, T, cfg, sites):
     g = ops.gelu_fwd(a) if g_img is None else None
     x = linear(images, g, blk.mlp.c_proj.weight, bias=blk.mlp.c_proj.bias, residual=x1, drop=s_mlp[0],
                stream_id=s_mlp[1], a_image=g_img, shape=a.shape)
-    return x, (x0, h1, qkv, y, y_img_t, lse, x1, h2, a, g, g_img_t, s_att, s_res, s_mlp)
+    return x, BlockSaved(False, (x0, h1, qkv, y, y_img_t, lse, x1, h2, a, g, g_img_t, s_att, s_res, s_mlp), lo_saved)
 
 
-def block_backward(images, blk, saved, dx, B, T, cfg, put):
-    """dx: gradient w.r.t. the block's output [B*T, C]; returns the gradient w.r.t. its input; parameter gradients go to put(p, g)."""
+def block_backward(images, blk, saved, dx, B, T, cfg, put, need_dx=True):
+    """dx: gradient w.r.t. the block's output [B*T, C]; returns the gradient w.r.t. its input; parameter gradients go to put(p, g).
+    A weight-gradient product runs only for a parameter that requires a gradient; ``need_dx`` False (nothing trainable below the block's
+    c_attn): the block stops after c_attn's own gradients and returns None."""
     C, H = cfg.n_embd, cfg.n_head
     M = B * T
     img = images
-    x0, h1, qkv, y, y_img_t, lse, x1, h2, a, g, g_img_t, s_att, s_res, s_mlp = saved
+    x0, h1, qkv, y, y_img_t, lse, x1, h2, a, g, g_img_t, s_att, s_res, s_mlp = saved.core
+    want = lambda p: p is not None and p.requires_grad
     # x = x1 + drop(c_proj(gelu(c_fc(ln_2(x1)))))
     dm = drop_rows(dx, s_mlp)
-    dm_img, dm_img_t = grad_images(dm, 4 * C)
-    put(blk.mlp.c_proj.weight, linear_dw(dm, g, dy_image_t=dm_img_t, x_image_t=g_img_t, shapes=(dm.shape, a.shape)))
-    if blk.mlp.c_proj.bias is not None: put(blk.mlp.c_proj.bias, ops.colsum(dm))
+    dm_img, dm_img_t = grad_images(dm, 4 * C, want_dw=want(blk.mlp.c_proj.weight))
+    if want(blk.mlp.c_proj.weight): put(blk.mlp.c_proj.weight, linear_dw(dm, g, dy_image_t=dm_img_t, x_image_t=g_img_t, shapes=(dm.shape, a.shape)))
+    if want(blk.mlp.c_proj.bias): put(blk.mlp.c_proj.bias, ops.colsum(dm))
     dg = linear_dx(img, dm, blk.mlp.c_proj.weight, dy_image=dm_img)
     if blk.mlp.c_fc.bias is None and use_split(M, C, 4 * C) and use_split(4 * C, C, M):
         # da = dg * gelu'(a) is only ever a GEMM operand: write its two images, not the fp32 matrix
-        da_img, da_img_t = ops.image_pair(dg, ops.PAIR_GELU_BWD, a)
-        put(blk.mlp.c_fc.weight, linear_dw(None, h2, dy_image_t=da_img_t, shapes=(a.shape, h2.shape)))
+        da_img, da_img_t = ops.image_pair(dg, ops.PAIR_GELU_BWD, a, cols_image=want(blk.mlp.c_fc.weight))
+        if want(blk.mlp.c_fc.weight): put(blk.mlp.c_fc.weight, linear_dw(None, h2, dy_image_t=da_img_t, shapes=(a.shape, h2.shape)))
         d_ln2 = linear_dx(img, None, blk.mlp.c_fc.weight, dy_image=da_img, shape=a.shape)
         del da_img, da_img_t
     else:
         da = ops.gelu_bwd(dg, a)
-        put(blk.mlp.c_fc.weight, linear_dw(da, h2))
-        if blk.mlp.c_fc.bias is not None: put(blk.mlp.c_fc.bias, ops.colsum(da))
+        if want(blk.mlp.c_fc.weight): put(blk.mlp.c_fc.weight, linear_dw(da, h2))
+        if want(blk.mlp.c_fc.bias): put(blk.mlp.c_fc.bias, ops.colsum(da))
         d_ln2 = linear_dx(img, da, blk.mlp.c_fc.weight)
     dx1, dw, db = ops.layernorm_bwd(d_ln2, x1, blk.ln_2.weight, dx, blk.ln_2.bias is not None)
     put(blk.ln_2.weight, dw); put(blk.ln_2.bias, db)
     # x1 = x0 + drop(c_proj(attention(c_attn(ln_1(x0)))))
     dr = drop_rows(dx1, s_res)
-    dr_img, dr_img_t = grad_images(dr, C)
-    put(blk.attn.c_proj.weight, linear_dw(dr, y, dy_image_t=dr_img_t, x_image_t=y_img_t))
-    if blk.attn.c_proj.bias is not None: put(blk.attn.c_proj.bias, ops.colsum(dr))
+    dr_img, dr_img_t = grad_images(dr, C, want_dw=want(blk.attn.c_proj.weight))
+    if want(blk.attn.c_proj.weight): put(blk.attn.c_proj.weight, linear_dw(dr, y, dy_image_t=dr_img_t, x_image_t=y_img_t))
+    if want(blk.attn.c_proj.bias): put(blk.attn.c_proj.bias, ops.colsum(dr))
     dy = linear_dx(img, dr, blk.attn.c_proj.weight, dy_image=dr_img)
     dqkv = torch.empty_like(qkv)
     ops.attention_bwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], y, dy, lse, dqkv[:, :C], dqkv[:, C:2 * C], dqkv[:, 2 * C:],
                       B, H, C // H, T, T, causal=cfg.causal, drop=s_att[0], stream_id=s_att[1])
-    dq_img, dq_img_t = grad_images(dqkv, C)
-    put(blk.attn.c_attn.weight, linear_dw(dqkv, h1, dy_image_t=dq_img_t))
-    if blk.attn.c_attn.bias is not None: put(blk.attn.c_attn.bias, ops.colsum(dqkv))
-    dx0, dw, db = ops.layernorm_bwd(linear_dx(img, dqkv, blk.attn.c_attn.weight, dy_image=dq_img), x0, blk.ln_1.weight, dx1,
-                                    blk.ln_1.bias is not None)
+    dq_img, dq_img_t = grad_images(dqkv, C, want_dx=need_dx, want_dw=want(blk.attn.c_attn.weight))
+    if want(blk.attn.c_attn.weight): put(blk.attn.c_attn.weight, linear_dw(dqkv, h1, dy_image_t=dq_img_t))
+    if want(blk.attn.c_attn.bias): put(blk.attn.c_attn.bias, ops.colsum(dqkv))
+    d_ln1 = linear_dx(img, dqkv, blk.attn.c_attn.weight, dy_image=dq_img) if need_dx else None
+    if saved.lora is not None:                               # the adapter: its gradients, and its share of d ln_1(x0)
+        u, s_lo = saved.lora
+        lora.lora_backward(blk.attn.c_attn, h1, u, dqkv, d_ln1, put, s_lo)
+    if not need_dx:
+        return None
+    dx0, dw, db = ops.layernorm_bwd(d_ln1, x0, blk.ln_1.weight, dx1, blk.ln_1.bias is not None)
     put(blk.ln_1.weight, dw); put(blk.ln_1.bias, db)
     return dx0
 
@@ -221,7 +266,17 @@ def rowmajor_train_ok(cfg, blocks, M, training):
         return False
     if C // cfg.n_head not in (32, 64):               # the matrix-core attention kernels write the bf16 outputs
         return False
-    return all(blk.attn.c_attn.bias is None and blk.mlp.c_fc.bias is None for blk in blocks)
+    # (an unmerged adapter on c_attn rides along on the halo_lora_* kernels up to rank 16; a larger one takes the model to the general path)
+    return all(blk.attn.c_attn.bias is None and blk.mlp.c_fc.bias is None
+               and (not lora.is_active(blk.attn.c_attn) or lora.fast_ok(blk.attn.c_attn, M)) for blk in blocks)
+
+
+def lora_rows_forward(images, lin, h1b, qkv, site=(ops.NO_DROPOUT, 0)):
+    """qkv [M, 3C] (bf16 or fp32 rows) += scaling * ((mask * h1b) A^T) B^T on the halo_lora_* kernels -> u [M, 16] bf16 for the backward."""
+    A16, _, B16, _ = lora.packed(images, lin)
+    u = ops.lora_down(h1b, A16, 1.0, site[0], site[1])
+    ops.lora_up_(qkv, u, B16, lin.scaling)
+    return u
 
 
 def rows_ok(M, C):
@@ -234,6 +289,9 @@ def block_forward_train_rm(images, blk, x0, B, T, cfg, sites):
     w = lambda lin: images.split((lin.weight,))
     rows = rows_ok(M, C)
     s_att, s_res, s_mlp = sites.next(), sites.next(), sites.next()
+    lo = lora.is_active(blk.attn.c_attn)
+    s_lo = sites.next_lora(blk.attn.c_attn.lora_dropout_p if lo else 0.0)
+    adapt = lambda h1b, qkv: (lora_rows_forward(images, blk.attn.c_attn, h1b, qkv, s_lo), s_lo) if lo else None
     if rows:
         _lib.lend_scratch(128 << 20, device=x0.device)      # K-slice slabs of the lm_head's input gradient and of the weight gradients' tails
         # round 5: every activation-by-weight product on halo_gemm_rows (256-row tiles cut to whole rounds of the CUs, A staged from the
@@ -244,9 +302,11 @@ def block_forward_train_rm(images, blk, x0, B, T, cfg, sites):
             # q | k | v stay bf16 between the c_attn product and the attention launches (forward and backward stage the rows as they are, two
             # tiles in flight: csrc/attn_b16.hip); the attention output is kept as bf16 only
             qkv = ops.gemm_rows(h1b, w(blk.attn.c_attn), M, 3 * C, C, out_bf16=True)
+            lo_saved = adapt(h1b, qkv)
             y, lse, yb = ops.attention_fwd_b16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal, want_lse=True)
         else:
             qkv = ops.gemm_rows(h1b, w(blk.attn.c_attn), M, 3 * C, C)
+            lo_saved = adapt(h1b, qkv)
             y, lse, yb = ops.attention_fwd_bf16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal,
                                                 drop=s_att[0], stream_id=s_att[1])
         x1 = ops.gemm_rows(yb, w(blk.attn.c_proj), M, C, C, residual=x0)
@@ -258,12 +318,13 @@ def block_forward_train_rm(images, blk, x0, B, T, cfg, sites):
             a = ops.gemm_rows(h2b, w(blk.mlp.c_fc), M, 4 * C, C, out_bf16=True)
             gb = ops.gelu_b16(a)
         x = ops.gemm_rows(gb, w(blk.mlp.c_proj), M, C, 4 * C, residual=x1)
-        return x, (x0, h1b, qkv, y, yb, lse, x1, h2b, a, gb, s_att)
+        return x, BlockSaved(True, (x0, h1b, qkv, y, yb, lse, x1, h2b, a, gb, s_att), lo_saved)
     # (the normalised rows twice from one launch: the tiled image for the forward product, which stages an image 10-15 % faster than
     # rows from cold caches, and the row-major rows for the weight-gradient product)
     h1b, h1i = ops.layernorm_bf16(x0, blk.ln_1.weight, blk.ln_1.bias, want_image=True)
     qkv = ops.gemm_split(h1i, w(blk.attn.c_attn), M, 3 * C, C)
     del h1i
+    lo_saved = adapt(h1b, qkv)
     y, lse, yb = ops.attention_fwd_bf16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal,
                                         drop=s_att[0], stream_id=s_att[1])
     x1 = ops.gemm_split_io((yb, None), w(blk.attn.c_proj), M, C, C, residual=x0)
@@ -272,14 +333,15 @@ def block_forward_train_rm(images, blk, x0, B, T, cfg, sites):
     del h2i
     gb = ops.gelu_bf16(a)
     x = ops.gemm_split_io((gb, None), w(blk.mlp.c_proj), M, C, 4 * C, residual=x1)
-    return x, (x0, h1b, qkv, y, yb, lse, x1, h2b, a, gb, s_att)
+    return x, BlockSaved(True, (x0, h1b, qkv, y, yb, lse, x1, h2b, a, gb, s_att), lo_saved)
 
 
-def block_backward_rm(images, blk, saved, dx, dxb, B, T, cfg, put):
-    """dx / dxb: the gradient w.r.t. the block's output as fp32 and as row-major bf16 -> the same pair for its input."""
+def block_backward_rm(images, blk, saved, dx, dxb, B, T, cfg, put, need_dx=True):
+    """dx / dxb: the gradient w.r.t. the block's output as fp32 and as row-major bf16 -> the same pair for its input ((None, None) with
+    ``need_dx`` False: nothing trainable below the block's c_attn).  Weight-gradient products only for parameters that require one."""
     C, H, M = cfg.n_embd, cfg.n_head, B * T
     wt = lambda lin: images.split_t((lin.weight,))
-    x0, h1b, qkv, y, yb, lse, x1, h2b, a, gb, s_att = saved
+    x0, h1b, qkv, y, yb, lse, x1, h2b, a, gb, s_att = saved.core
     rows = a.dtype == torch.bfloat16                     # the forward ran on halo_gemm_rows
     # the four weight gradients contract over the same M token rows: collected here, ONE grouped launch at the end of the block
     # (whole-K tiles, no K-slices or reduce launches); HALO_GPT_DW_GROUP=0: one launch each, as round 4
@@ -290,6 +352,8 @@ def block_backward_rm(images, blk, saved, dx, dxb, B, T, cfg, put):
     todo = []
 
     def dweight(p, dy_b, x_b):
+        if not p.requires_grad:
+            return
         if grouped:
             todo.append((p, dy_b, x_b))
         else:
@@ -316,9 +380,25 @@ def block_backward_rm(images, blk, saved, dx, dxb, B, T, cfg, put):
         ops.attention_bwd_bf16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], y, dy, lse, dqkvb[:, :C], dqkvb[:, C:2 * C], dqkvb[:, 2 * C:],
                                B, H, C // H, T, T, causal=cfg.causal, drop=s_att[0], stream_id=s_att[1])
     dweight(blk.attn.c_attn.weight, dqkvb, h1b)
-    d_ln1 = ops.gemm_rows(dqkvb, wt(blk.attn.c_attn), M, C, 3 * C, out_bf16=b16_ln) if rows else ops.gemm_split_io((dqkvb, None), wt(blk.attn.c_attn), M, C, 3 * C)
-    dx0, dw, db, dx0b = ops.layernorm_bwd(d_ln1, x0, blk.ln_1.weight, dx1, blk.ln_1.bias is not None, want_bf16=True)
-    put(blk.ln_1.weight, dw); put(blk.ln_1.bias, db)
+    d_ln1 = None
+    if need_dx:
+        d_ln1 = ops.gemm_rows(dqkvb, wt(blk.attn.c_attn), M, C, 3 * C, out_bf16=b16_ln) if rows else ops.gemm_split_io((dqkvb, None), wt(blk.attn.c_attn), M, C, 3 * C)
+    if saved.lora is not None:
+        # the adapter (csrc/lora.hip): du = s dqkv B, dB = s dqkv^T u, dA = du^T (m * h1), d_ln1 += m * (du A)
+        lin = blk.attn.c_attn
+        u, s_lo = saved.lora
+        _, At16, _, Bt16 = lora.packed(images, lin)
+        du = ops.lora_down(dqkvb, Bt16, lin.scaling)
+        if lin.lora_B.weight.requires_grad:
+            put(lin.lora_B.weight, ops.lora_tn(u, dqkvb, lin.r, lin.scaling, transpose_out=True))
+        if lin.lora_A.weight.requires_grad:
+            put(lin.lora_A.weight, ops.lora_tn(du, h1b, lin.r, 1.0, drop=s_lo[0], stream_id=s_lo[1]))
+        if need_dx:
+            ops.lora_up_(d_ln1, du, At16, 1.0, s_lo[0], s_lo[1])
+    dx0 = dx0b = None
+    if need_dx:
+        dx0, dw, db, dx0b = ops.layernorm_bwd(d_ln1, x0, blk.ln_1.weight, dx1, blk.ln_1.bias is not None, want_bf16=True)
+        put(blk.ln_1.weight, dw); put(blk.ln_1.bias, db)
     if todo:
         for (p, _, _), g in zip(todo, ops.gemm_tn_group([(d, x_) for _, d, x_ in todo])):
             put(p, g)
@@ -398,7 +478,10 @@ class GPT(nn.Module):
             if t0:
                 present[..., :t0, :] = past
         for i, blk in enumerate(tr.h):
-            qkv, _ = ln_linear(self._images, x, blk.ln_1.weight, blk.ln_1.bias, blk.attn.c_attn.weight, bias=blk.attn.c_attn.bias)
+            lo = lora.is_active(blk.attn.c_attn)
+            qkv, h1 = ln_linear(self._images, x, blk.ln_1.weight, blk.ln_1.bias, blk.attn.c_attn.weight, bias=blk.attn.c_attn.bias, want_normed=lo)
+            if lo:
+                lora.lora_forward(blk.attn.c_attn, h1, qkv)
             if present is not None:
                 ops.kv_cache_store(qkv[:, C:], C, present[i, 0], present[i, 1], B, T, H, C // H, t0)
                 y = ops.attention_cached_fwd(qkv, present[i, 0], present[i, 1], T, t0 + T, causal=cfg.causal)
@@ -431,9 +514,13 @@ class GPT(nn.Module):
             if C // H == 64 and os.environ.get('HALO_GPT_ATTN_B16', '1') != '0':
                 # q | k | v stay bf16 between the c_attn product and the attention launch, which stages them as they are
                 qkv = ops.gemm_rows(h1b, w(blk.attn.c_attn), M, 3 * C, C, out_bf16=True)
+                if lora.is_active(blk.attn.c_attn):
+                    lora_rows_forward(self._images, blk.attn.c_attn, h1b, qkv)
                 _, _, yb = ops.attention_fwd_b16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal)
             else:
                 qkv = ops.gemm_rows(h1b, w(blk.attn.c_attn), M, 3 * C, C)
+                if lora.is_active(blk.attn.c_attn):
+                    lora_rows_forward(self._images, blk.attn.c_attn, h1b, qkv)
                 _, _, yb = ops.attention_fwd_bf16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal)
             ops.gemm_rows(yb, w(blk.attn.c_proj), M, C, C, out=x, residual=x)                   # x += c_proj(y)
             h2b = ops.layernorm_bf16(x, blk.ln_2.weight, blk.ln_2.bias)
@@ -455,7 +542,7 @@ class GPT(nn.Module):
             params = [p for p in self.parameters() if p.requires_grad]
             loss = _GPTLoss.apply(self, input_ids, target_ids, *params)          # per-token NLL with a grad_fn
             return self._reduce(loss, target_ids.reshape(-1), reduction)
-        if self.training and self.config.dropout > 0:
+        if self.training and (self.config.dropout > 0 or adapter_dropout(self.transformer.h) > 0):
             raise NotImplementedError('training-mode dropout is built into the autograd path only: enable grad, or call .eval()')
         targets = target_ids.reshape(-1)
         C = self.config.n_embd
@@ -496,7 +583,7 @@ class GPT(nn.Module):
         tr = self.transformer
         # dropout sites in forward order (ha/attention.py:224,90,127,141): embeddings, then per block the attention
         # probabilities, the c_proj output and the MLP output; output dropouts are GEMM epilogues
-        sites = DropSites(self.dropout_stream.next(cfg.dropout, self.training))
+        sites = train_sites(self.dropout_stream, cfg.dropout, self.training, tr.h)
         s_emb = sites.next()
         x, emb_saved = self._embed(input_ids, 0, keep=True)
         x = drop_rows(x, s_emb)
@@ -540,31 +627,47 @@ class GPT(nn.Module):
                 grads[id(p)] = g if id(p) not in grads else grads[id(p)] + g
 
         M, V = logits.shape
+        # what is trainable at and below each point of the backward: a frozen parameter gets no weight-gradient product, and the sweep
+        # stops at the lowest block whose c_attn adapters are the last trainable thing
+        live = lambda mod: any(p.requires_grad for p in mod.parameters())
+        head, emb = self.lm_head.weight.requires_grad, live(tr.wte) or live(tr.wpe)
+        below = [emb]
+        for blk in tr.h:
+            below.append(below[-1] or live(blk))
         if logits.dtype == torch.bfloat16:
             # the stored bf16 logits become d loss / d logits IN PLACE: the row-major bf16 operand of both gradient products
             dl = ops.cross_entropy_bwd_bf16_(logits, targets, row_lse, grad_per_tok, ignore_index=0)
-            dw_head = ops.gemm_tn_group([(dl, xf)])[0]                                       # [V, C]; the tied wte gradient lands here too
+            dw_head = ops.gemm_tn_group([(dl, xf)])[0] if head else None                     # [V, C]; the tied wte gradient lands here too
             dxf = ops.gemm_rows(dl, img.split_t((self.lm_head.weight,)), M, C, V)
             del dl, logits
         elif use_split(M, C, V) and use_split(V, C, M):
             # d loss / d logits goes straight into the two operand images of the lm_head's backward products
             dl_img, dl_img_t = ops.cross_entropy_bwd_images(logits, targets, row_lse, grad_per_tok, ignore_index=0)
-            dw_head = linear_dw(None, xf, dy_image_t=dl_img_t, shapes=((M, V), xf.shape))    # [V, C]; the tied wte gradient lands here too
+            dw_head = linear_dw(None, xf, dy_image_t=dl_img_t, shapes=((M, V), xf.shape)) if head else None    # [V, C]; the tied wte gradient lands here too
             dxf = linear_dx(img, None, self.lm_head.weight, dy_image=dl_img, shape=(M, V))
             del dl_img, dl_img_t
         else:
             dlogits = ops.cross_entropy_bwd_(logits, targets, row_lse, grad_per_tok, ignore_index=0)
-            dw_head = linear_dw(dlogits, xf)
+            dw_head = linear_dw(dlogits, xf) if head else None
             dxf = linear_dx(img, dlogits, self.lm_head.weight)
-        rm = len(blocks) > 0 and len(blocks[0]) == 11           # block_forward_train_rm's record
+        rm = len(blocks) > 0 and blocks[0].rowmajor             # block_forward_train_rm's records
         dx, dw, db, *dxb = ops.layernorm_bwd(dxf, x_last, tr.ln_f.weight, None, tr.ln_f.bias is not None, want_bf16=rm)
         put(tr.ln_f.weight, dw); put(tr.ln_f.bias, db)
-        for blk, sv in zip(reversed(tr.h), reversed(blocks)):
+        for i in reversed(range(len(blocks))):
+            blk, sv = tr.h[i], blocks[i]
+            need_dx = below[i] or live(blk.ln_1)
+            if not (need_dx or live(blk)):
+                break
             if rm:
-                dx, dxb[0] = block_backward_rm(img, blk, sv, dx, dxb[0], B, T, cfg, put)
+                dx, dxb[0] = block_backward_rm(img, blk, sv, dx, dxb[0], B, T, cfg, put, need_dx)
             else:
-                dx = block_backward(img, blk, sv, dx, B, T, cfg, put)
-        dwpe = torch.zeros_like(tr.wpe.weight)
+                dx = block_backward(img, blk, sv, dx, B, T, cfg, put, need_dx)
+            if not need_dx:
+                break
+        if not emb:
+            return grads
+        # (a frozen lm_head / wte or wpe takes no scatter: dw_head is None then, and the embedding kernels skip a NULL target)
+        dwpe = torch.zeros_like(tr.wpe.weight) if tr.wpe.weight.requires_grad else None
         dx = drop_rows(dx, s_emb)
         if emb_saved is not None:                                                # StableEmbedding: through the two LayerNorms first
             et, ep = emb_saved
@@ -574,12 +677,14 @@ class GPT(nn.Module):
             put(tr.wte.norm.weight, dw); put(tr.wte.norm.bias, db)
             dep, dw, db = ops.layernorm_bwd(dpos, ep, tr.wpe.norm.weight, None, True)
             put(tr.wpe.norm.weight, dw); put(tr.wpe.norm.bias, db)
-            dwpe[:T] = dep
-            ops.embed_bwd(input_ids, dx, dw_head, None, 0)                       # tied: token rows add into the lm_head gradient
-        else:
+            if dwpe is not None:
+                dwpe[:T] = dep
+            if dw_head is not None:
+                ops.embed_bwd(input_ids, dx, dw_head, None, 0)                   # tied: token rows add into the lm_head gradient
+        elif dw_head is not None or dwpe is not None:
             ops.embed_bwd(input_ids, dx, dw_head, dwpe, 0)
-        put(self.lm_head.weight, dw_head)
-        put(tr.wpe.weight, dwpe)
+        if dw_head is not None: put(self.lm_head.weight, dw_head)
+        if dwpe is not None: put(tr.wpe.weight, dwpe)
         return grads
 
     def forward_context(self, input_ids):

@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._linear import DropSites, WeightImages, drop_rows, linear, linear_dw, linear_dx, training_images
-from .attention import Block, LayerNorm, block_backward, block_forward, block_forward_train, prefetch_block_weights
+from .attention import Block, LayerNorm, block_backward, block_forward, block_forward_train, adapter_dropout, prefetch_block_weights, train_sites
 from .rnn import DropoutStream
 
 
@@ -100,7 +100,7 @@ class AudioEncoder(nn.Module):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             out = _EncoderFn.apply(self, x, *[p for p in self.parameters() if p.requires_grad])
             return out, self.subsampled_lengths(input_lengths), {}
-        if self.training and self.config.dropout > 0:
+        if self.training and (self.config.dropout > 0 or adapter_dropout(self.transformer.h) > 0):
             raise NotImplementedError('training-mode dropout is built into the autograd path only: enable grad, or call .eval()')
         return self._forward_infer(x), self.subsampled_lengths(input_lengths), {}
 
@@ -136,7 +136,7 @@ class AudioEncoder(nn.Module):
         assert T <= cfg.block_size, f'Cannot forward sequence of length {T}, block size is only {cfg.block_size}'
         ops.add_rows_bcast_(y, self.transformer.wpe.weight.detach()[:T].contiguous(), T)
         # dropout sites in forward order: the embedding dropout (ha/attention_audio.py:110), then three per block
-        sites = DropSites(self.dropout_stream.next(cfg.dropout, self.training))
+        sites = train_sites(self.dropout_stream, cfg.dropout, self.training, self.transformer.h)
         s_emb = sites.next()
         y = drop_rows(y, s_emb)
         blocks = []

@@ -369,6 +369,75 @@ def gelu_bwd_b16(dy, a, exact=False):
     return y
 
 
+# ---- LoRA adapters on row-major bf16 rows (csrc/lora.hip) -------------------------------------------------------------------------
+LORA_RANK_PAD = 16
+
+
+def lora_supported(M, n_in, n_out, r):
+    """The halo_lora_* kernels take an adapter of rank r on a Linear [n_in -> n_out] at M rows."""
+    return bool(lib().halo_lora_supported(M, n_in, n_out, r))
+
+
+def lora_pack(A, B):
+    """A [r, n_in], B [n_out, r] fp32 -> (A16 [16, n_in], At16 [n_in, 16], B16 [n_out, 16], Bt16 [16, n_out]): the rank-padded bf16
+    operands of the three kernels, views of one buffer written by one launch."""
+    _f32c(A, 'A'); _f32c(B, 'B')
+    r, n_in = A.shape
+    n_out = B.shape[0]
+    if B.shape[1] != r:
+        raise ValueError('lora_pack: A [r, n_in] and B [n_out, r]')
+    R = LORA_RANK_PAD
+    buf = torch.empty(lib().halo_lora_pack_bytes(n_in, n_out) // 2, device=A.device, dtype=torch.bfloat16)
+    check(lib().halo_lora_pack(ptr(A), ptr(B), r, n_in, n_out, ptr(buf), _stream()), 'halo_lora_pack')
+    na, nb = R * n_in, R * n_out
+    return (buf[:na].view(R, n_in), buf[na:2 * na].view(n_in, R), buf[2 * na:2 * na + nb].view(n_out, R), buf[2 * na + nb:].view(R, n_out))
+
+
+def _bf16_rows(t, name, cols=None):
+    if t.dtype != torch.bfloat16 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or (cols is not None and t.shape[1] != cols):
+        raise ValueError(f'{name}: expected row-major bf16 rows on the HIP device')
+    return t
+
+
+def lora_down(x, p16, scale=1.0, drop=NO_DROPOUT, stream_id=0):
+    """U [M, 16] = scale * (mask * x [M, K]) p16 [16, K]^T as bf16; the mask of ``drop`` at the flat index row * K + col."""
+    _bf16_rows(x, 'x'); _bf16_rows(p16, 'p16')
+    M, K = x.shape
+    if p16.shape != (LORA_RANK_PAD, K) or not p16.is_contiguous():
+        raise ValueError('lora_down: p16 [16, K]')
+    u = torch.empty(M, LORA_RANK_PAD, device=x.device, dtype=torch.bfloat16)
+    check(lib().halo_lora_down(ptr(x), x.stride(0), ptr(p16), M, K, float(scale), ptr(u), drop.p, drop.seed, stream_id, drop.offset,
+                               drop.counter_ptr, _stream()), 'halo_lora_down')
+    return u
+
+
+def lora_up_(y, u, p16, scale=1.0, drop=NO_DROPOUT, stream_id=0):
+    """y [M, N] += scale * mask * (u [M, 16] p16 [N, 16]^T) in place; y row-major bf16 or fp32; the mask at the flat index row * N + col."""
+    _bf16_rows(u, 'u', LORA_RANK_PAD); _bf16_rows(p16, 'p16', LORA_RANK_PAD)
+    M, N = y.shape
+    if y.dtype not in (torch.bfloat16, torch.float32) or y.stride(1) != 1 or u.shape[0] != M or p16.shape[0] != N \
+            or not u.is_contiguous() or not p16.is_contiguous():
+        raise ValueError('lora_up_: y [M, N] bf16 / fp32 rows, u [M, 16], p16 [N, 16]')
+    b16 = y.dtype == torch.bfloat16
+    check(lib().halo_lora_up(ptr(u), ptr(p16), M, N, float(scale), ptr(y) if b16 else None, None if b16 else ptr(y), y.stride(0), drop.p,
+                             drop.seed, stream_id, drop.offset, drop.counter_ptr, _stream()), 'halo_lora_up')
+    return y
+
+
+def lora_tn(u, x, r, scale=1.0, transpose_out=False, drop=NO_DROPOUT, stream_id=0):
+    """scale * u [M, 16]^T (mask * x [M, K]), rows 0 .. r-1: fp32 [r, K], or [K, r] with ``transpose_out``.  Slabs of M summed in a fixed
+    order: bitwise reproducible."""
+    _bf16_rows(u, 'u', LORA_RANK_PAD); _bf16_rows(x, 'x')
+    M, K = x.shape
+    if u.shape[0] != M or not u.is_contiguous():
+        raise ValueError('lora_tn: u [M, 16] contiguous')
+    g = torch.empty((K, r) if transpose_out else (r, K), device=x.device, dtype=torch.float32)
+    ws = torch.empty(lib().halo_lora_tn_workspace_bytes(M, K), device=x.device, dtype=torch.uint8)
+    check(lib().halo_lora_tn(ptr(u), ptr(x), x.stride(0), M, K, r, float(scale), int(transpose_out), ptr(g), ptr(ws), drop.p, drop.seed,
+                             stream_id, drop.offset, drop.counter_ptr, _stream()), 'halo_lora_tn')
+    return g
+
+
 def dropout_fwd(x, drop, stream_id):
     _f32c(x, 'x')
     y = torch.empty_like(x)

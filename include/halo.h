@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define HALO_ABI_VERSION 19
+#define HALO_ABI_VERSION 20
 
 #define HALO_OK 0
 #define HALO_EINVAL (-22)    /* bad argument (null pointer, non-positive size, unsupported shape) */
@@ -265,6 +265,32 @@ int halo_gemm_rows_ce(const void *a_image, const void *a_bf16, long lda, const v
                       long ignore_index, void *workspace, float *loss, float *lse, void *logits_bf16, long ldo, halo_stream_t stream);
 int halo_cross_entropy_bwd_bf16(void *logits_bf16, const int64_t *targets, const float *lse, const float *grad, long grad_stride, int rows,
                                 int V, long ld, long ignore_index, halo_stream_t stream);
+
+/* LoRA adapters of the c_attn Linear on the row-major bf16 rows of the GPT `bf16` path (csrc/lora.hip), rank r <= 16 padded to 16 so that
+ * one 16x16x32 bf16 MFMA spans it, fp32 accumulation.  With h = ln_1(x) [M][C], A [r][C], B [3C][r], s = lora_alpha / r and m the dropout
+ * mask of the adapter's input:  u = (m*h) A^T,  qkv += s u B^T;  du = s dqkv B,  dB = s dqkv^T u,  dA = du^T (m*h),  d_ln1 += m * (du A).
+ *   halo_lora_pack   A, B (fp32) -> the four padded bf16 operands in one buffer of halo_lora_pack_bytes(n_in, n_out):
+ *                    A16 [16][n_in] | At16 [n_in][16] | B16 [n_out][16] | Bt16 [16][n_out]
+ *   halo_lora_down   U [M][16] = scale * (mask * X [M][K]) P [16][K]^T, bf16 out (M % 16 == 0, K % 32 == 0, ldx % 8 == 0)
+ *   halo_lora_up     Y [M][N] += scale * mask * (U [M][16] P [N][16]^T) onto bf16 rows (y_bf16) or fp32 rows (y_f32), exactly one (N % 32 == 0)
+ *   halo_lora_tn     G = scale * U [M][16]^T (mask * X [M][K]): rows 0 .. r-1 as fp32 g [r][K], or [K][r] with transpose_out; M is cut into
+ *                    slabs whose partial tiles go to workspace (halo_lora_tn_workspace_bytes(M, K)) and are summed in a fixed order (no
+ *                    atomics: two runs give the same bits).  M % 32 == 0, K % 16 == 0.
+ * The mask is recomputed inside each kernel from the dropout stream (above) at the flat index row * K + col (row * N + col for
+ * halo_lora_up), i.e. what halo_dropout_fwd draws for the [M][K] rows; p_drop == 0: no mask.  The row width of that index is K (N), not the
+ * leading dimension: X (Y) is taken to be the whole [M][K] matrix the mask belongs to, also when ldx (ldy) is larger.
+ * replaces: lora_B(lora_A(lora_dropout(x))) * scaling in Linear.forward (ha/lora.py:84-91) and its autograd backward. */
+int halo_lora_supported(int M, int n_in, int n_out, int r);
+size_t halo_lora_pack_bytes(int n_in, int n_out);
+int halo_lora_pack(const float *A, const float *B, int r, int n_in, int n_out, void *packed, halo_stream_t stream);
+int halo_lora_down(const void *x_bf16, long ldx, const void *p16, int M, int K, float scale, void *u_bf16, float p_drop, uint64_t seed,
+                   uint32_t stream_id, uint32_t offset, const uint32_t *offset_dev, halo_stream_t stream);
+int halo_lora_up(const void *u_bf16, const void *p16, int M, int N, float scale, void *y_bf16, float *y_f32, long ldy, float p_drop,
+                 uint64_t seed, uint32_t stream_id, uint32_t offset, const uint32_t *offset_dev, halo_stream_t stream);
+size_t halo_lora_tn_workspace_bytes(int M, int K);
+int halo_lora_tn(const void *u_bf16, const void *x_bf16, long ldx, int M, int K, int r, float scale, int transpose_out, float *g,
+                 void *workspace, float p_drop, uint64_t seed, uint32_t stream_id, uint32_t offset, const uint32_t *offset_dev,
+                 halo_stream_t stream);
 
 /* lm_head + cross-entropy without materialising the logits (ha/attention.py:228-231): the split GEMM
  * logits[M,N] = A B^T (+ bias[N]) whose epilogue reduces each 64-column strip of a row to (max, sum exp) and picks out the
