@@ -6,7 +6,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'csrc', 'libhalo.so')
 
-HALO_ABI_VERSION = 20
+HALO_ABI_VERSION = 21
+HALO_GPT_SAMPLE_STREAM = 0x47505453
 HALO_GEMM_RELU = 1
 HALO_GEMM_GELU = 2
 HALO_GEMM_ACCUM = 4
@@ -169,6 +170,10 @@ SIGNATURES = {
     'halo_decode_attention_pair': (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _l, _vp]),
     'halo_decode_memory_caches': (_i, [_vp, _l, _i, _vp, _i, _i, _i, _i, _vp]),
     'halo_decode_token': (_i, [_vp, _l, _i, _i, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    'halo_gpt_decode_linear_supported': (_i, [_i, _i]),
+    'halo_gpt_decode_linear': (_i, [_vp, _l, _i, _i, _vp, _f, _vp, _i, _vp, _l, _i, _vp]),
+    'halo_gpt_decode_attention': (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _l, _vp]),
+    'halo_gpt_sample': (_i, [_vp, _l, _i, _i, _vp, _vp, _l, _vp, _l, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     'halo_attention_bwd': (_i, [_vp, _l, _l, _vp, _vp, _l, _l, _vp, _vp, _l, _l, _vp, _vp, _vp, _l, _l, _vp, _vp, _l, _l,
                                 _i, _i, _i, _i, _i, _i, _vp, _f, _u64, _u32, _u32, _vp, _vp]),
     'halo_attention_masked': (_i, [_vp, _vp, _vp, _vp, _l, _l, _l, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

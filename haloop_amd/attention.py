@@ -462,18 +462,21 @@ class GPT(nn.Module):
         return x, ((et, ep) if keep else None)
 
     @torch.no_grad()
-    def _trunk(self, input_ids, past=None, want_present=False):
+    def _trunk(self, input_ids, past=None, want_present=False, cache=None, t0=0):
         """Embedding + blocks + ln_f.  With ``past`` [L, 2, B, nh, T0, hs] (or want_present) keys/values go through a
-        fp32 cache in the reference's layout (attend_cached, ha/attention.py:64-93) and ``present`` is returned."""
+        fp32 cache in the reference's layout (attend_cached, ha/attention.py:64-93) and ``present`` is returned.
+        ``cache`` [L, 2, B, nh, Tc, hs] (haloop_amd.generation): a preallocated cache that already holds positions [0, t0); the T new
+        positions are stored behind them in place, nothing is allocated or copied, and ``cache`` itself is returned as ``present``."""
         cfg = self.config
         B, T = input_ids.shape
-        t0 = 0 if past is None else past.size(-2)
+        if cache is None:
+            t0 = 0 if past is None else past.size(-2)
         assert t0 + T <= cfg.block_size, f'Cannot forward sequence of length {t0 + T}, block size is only {cfg.block_size}'
         C, H = cfg.n_embd, cfg.n_head
         tr = self.transformer
         x, _ = self._embed(input_ids, t0)                                                # [B*T, C], the residual stream
-        present = None
-        if past is not None or want_present:
+        present = cache
+        if cache is None and (past is not None or want_present):
             present = torch.empty(cfg.n_layer, 2, B, H, t0 + T, C // H, device=x.device, dtype=torch.float32)
             if t0:
                 present[..., :t0, :] = past

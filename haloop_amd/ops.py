@@ -1258,6 +1258,52 @@ def decode_token(logits, tokens, t, plen, etx, alive, out_len, log_probs, sum_en
                                   wte.shape[1] if wte is not None else 0, ptr(y_next), _stream()), 'halo_decode_token')
 
 
+# ---- fused launches of a GPT sampling step (csrc/gpt_decode.hip); none of these allocates: they run inside a captured step ----------
+def gpt_decode_linear_supported(k, layernorm):
+    return bool(lib().halo_gpt_decode_linear_supported(k, int(layernorm)))
+
+
+def gpt_decode_linear(x, image, n_out, out, ln_weight=None, eps=1e-5, accumulate=False, gelu=False):
+    """out (+)= act(layer_norm?(x) W^T) with W given by its decode image, in the library's math mode (tanh-GELU)."""
+    rows, k = x.shape
+    flags = (_lib.HALO_GEMM_ACCUM if accumulate else 0) | (_lib.HALO_GEMM_GELU if gelu else 0)
+    check(lib().halo_gpt_decode_linear(ptr(x), x.stride(0), rows, k, ptr(ln_weight), eps, ptr(image), n_out, ptr(out), out.stride(0), flags,
+                                       _stream()), 'halo_gpt_decode_linear')
+    return out
+
+
+def gpt_decode_attention(qkv, cache_k, cache_v, pos, out):
+    """qkv [B, 3C] -> out [B, C]; row b's k / v are stored at position pos[b] (device int32) of cache_{k,v} [B, heads, Tc, 64] fp32."""
+    B, heads, Tc, hd = cache_k.shape
+    check(lib().halo_gpt_decode_attention(ptr(qkv), qkv.stride(0), B, heads, hd, ptr(cache_k), ptr(cache_v), Tc, ptr(pos), ptr(out),
+                                          out.stride(0), _stream()), 'halo_gpt_decode_attention')
+    return out
+
+
+def gpt_sample_cfg(temperature, top_k, stop_token, seed, device):
+    """The draw's settings as the device words halo_gpt_sample reads (include/halo.h)."""
+    import struct
+    if not temperature > 0.0:
+        raise ValueError('temperature must be positive')
+    inv = struct.unpack('<i', struct.pack('<f', 1.0 / float(temperature)))[0]
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    s32 = lambda u: u - (1 << 32) if u >= (1 << 31) else u
+    stop = int(stop_token)
+    if not -(1 << 31) <= stop < (1 << 31):
+        stop = -1
+    words = [inv, int(top_k) if top_k is not None else 0, stop, s32(seed & 0xFFFFFFFF), s32(seed >> 32), 0, 0, 0]
+    return torch.tensor(words, dtype=torch.int32).to(device, non_blocking=True)
+
+
+def gpt_sample(logits, cfg, state, tokens, next_ids, wte=None, wpe=None, x_next=None):
+    """One draw per row of logits [B, V] and the step's bookkeeping (include/halo.h): state int32 [4, >= B] = pos | step | length |
+    alive; tokens int64 [B, n_slots] receives slot ``step``; next_ids int64 [B]; x_next [B, C] <- wte[token] + wpe[pos + 1]."""
+    B, V = logits.shape
+    check(lib().halo_gpt_sample(ptr(logits), logits.stride(0), B, V, ptr(cfg), ptr(state), state.stride(0), ptr(tokens), tokens.stride(0),
+                                tokens.shape[1], ptr(next_ids), ptr(wte), ptr(wpe), wpe.shape[0] if wpe is not None else 0,
+                                wte.shape[1] if wte is not None else 0, ptr(x_next), _stream()), 'halo_gpt_sample')
+
+
 # ---- channels-last conv front-end (ha/conv.py) -------------------------------------------------------------
 def conv_out_length(T, ks, stride, pad):
     return (T + 2 * pad - ks) // stride + 1

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define HALO_ABI_VERSION 20
+#define HALO_ABI_VERSION 21
 
 #define HALO_OK 0
 #define HALO_EINVAL (-22)    /* bad argument (null pointer, non-positive size, unsupported shape) */
@@ -759,6 +759,47 @@ int halo_decode_attention_pair(const float *a, long a_row_stride, int N, int hea
 int halo_decode_token(const float *logits, long ld, int N, int V, int64_t *tokens, long tokens_ld, int t, int plen, int etx,
                       uint8_t *alive, int *output_lengths, float *log_probs, float *sum_entropies, const float *wte,
                       int vocab, int C, float *y_next, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fused launches of one batched GPT sampling step (haloop_amd/generation.py; the T == 1 case of ha/attention.py:253-321 under a KV
+ * cache): 5 launches per layer (LayerNorm + c_attn | cache store + attention | c_proj, accumulate | LayerNorm + c_fc + tanh-GELU |
+ * mlp.c_proj, accumulate) and 2 per token (LayerNorm + lm_head | the draw), over the decode images of halo_decode_image.  Every per-step
+ * scalar (position, draw counter, alive flags, seed, temperature, top_k, stop token) is read from device memory, so the launch arguments
+ * of a step never change and one captured step serves every position.
+ *   halo_gpt_decode_linear   out (+)= act(layer_norm?(x) W^T) as halo_decode_linear, with flags HALO_GEMM_ACCUM and / or HALO_GEMM_GELU (the
+ *                            tanh form).  With LayerNorm (no bias) k in {512, 768, 1024}; without, k % 256 == 0
+ *                            (halo_gpt_decode_linear_supported).  Arithmetic by the math mode: bf16x3 the three-MFMA split product, bf16 the
+ *                            activations rounded to bf16 against the hi fragments alone (one MFMA, half the image read); HALO_ENOTSUP in f32.
+ *   halo_gpt_decode_attention  one layer's attention of a step from the packed rows qkv [B][>= 3C] = q | k | v: row b's k and v are stored at
+ *                            position p = clamp(pos[b], 0, cache_len - 1) of the fp32 cache planes [B][heads][cache_len][64] (the reference's
+ *                            `present` layout, ha/attention.py:64-69), the query attends over keys 0 .. p, y [B][C].  pos: device int32 [B];
+ *                            the host checks the largest position it will reach before launching.  head_dim 64, cache_len <= 8192.
+ *   halo_gpt_sample          the draw and the bookkeeping of a step, one workgroup per row of logits [B][V].  cfg: device int32 [8] =
+ *                            { bits of float 1 / temperature, top_k (<= 0: none), stop_token, lo32(seed), hi32(seed), 0, 0, 0 };
+ *                            state: device int32 [4][state_ld] = pos | step | length | alive, one word of each per row (a row's words are
+ *                            read and written by that row's workgroup alone, so nothing races within the launch; the launches that read
+ *                            pos are ordered against this one by the stream).  A row:
+ *                              l_v = logits[v] / temperature as fl(logits[v] * (1 / temperature)); with top_k the kept set is
+ *                              { v : logits[v] >= the min(top_k, V)-th largest logit } (ties at the threshold stay), else every v;
+ *                              e_v = expf(l_v - max l) over the kept set; chunk sums in vocabulary order (chunk = 4 ceil(V / 1024) consecutive
+ *                              indices, summed left to right), the chunk sums accumulated left to right: total;
+ *                              r = philox4x32_10(ctr = (row, 0, HALO_GPT_SAMPLE_STREAM, step[row]), key = seed)[0], u = (r >> 8) * 2^-24;
+ *                              token = the smallest kept v whose cumulative mass (the chunk prefix plus the running sum inside its chunk)
+ *                              exceeds u * total; top_k == 1: the arg max, lowest index on ties.
+ *                            Then, for an alive row: token == stop_token turns the row dead (the token is not counted), else length += 1;
+ *                            a dead row's token is stop_token.  tokens[row][step] = token while step < n_slots; next_ids[row] = token;
+ *                            step += 1; pos += 1; x_next[row] = wte[clamp(token)] + wpe[min(pos, n_pos - 1)] when x_next is given (the
+ *                            next step's input row).  Same (logits, cfg, state) -> same tokens.
+ * HALO_GPT_SAMPLE_STREAM is outside the dropout sites' ids (small integers) and the LoRA sites' (4096 + layer). */
+#define HALO_GPT_SAMPLE_STREAM 0x47505453u   /* 'GPTS' */
+int halo_gpt_decode_linear_supported(int k, int layernorm);
+int halo_gpt_decode_linear(const float *x, long ldx, int rows, int k, const float *ln_weight, float eps, const void *w_image,
+                           int n_out, float *out, long ldo, int flags, halo_stream_t stream);
+int halo_gpt_decode_attention(const float *qkv, long row_stride, int B, int heads, int head_dim, float *cache_k, float *cache_v,
+                              int cache_len, const int *pos, float *y, long y_row_stride, halo_stream_t stream);
+int halo_gpt_sample(const float *logits, long ld, int B, int V, const int *cfg, int *state, long state_ld, int64_t *tokens,
+                    long tokens_ld, int n_slots, int64_t *next_ids, const float *wte, const float *wpe, int n_pos, int C,
+                    float *x_next, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Backward operators of the GPT / transformer training step (the autograd graph of ha/attention.py:205-232 as
