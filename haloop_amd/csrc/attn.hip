@@ -758,15 +758,11 @@ int halo_attention_masked(const float *q, const float *k, const float *v, const 
     HALO_CHECK_ARG(q && k && v && y && N > 0 && heads > 0 && T > 0 && S > 0 && head_dim > 0);
     const size_t lds = (size_t)4 * (head_dim + S) * sizeof(float);
     if (lds > 160 * 1024 - 256 || (long)N * heads * T >= (1L << 31)) return HALO_ENOTSUP;
-    static size_t opted = 0;
-    if (lds > opted) {
-        if (hipFuncSetAttribute((const void *)attention_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return HALO_ELAUNCH;
-        opted = lds;
-    }
     const int rows = N * heads * T;
-    hipLaunchKernelGGL(attention_generic_kernel, dim3((rows + 3) / 4), dim3(256), lds, (hipStream_t)stream, q, k, v, mask, mask_stride_n,
-                       mask_stride_h, mask_stride_t, y, entropy, rows, heads, T, S, head_dim, 1.0f / sqrtf((float)head_dim));
+    if (halo_launch_lds<attention_generic_kernel>(dim3((rows + 3) / 4), dim3(256), (int)lds, (hipStream_t)stream, q, k, v, mask, mask_stride_n,
+                                                  mask_stride_h, mask_stride_t, y, entropy, rows, heads, T, S, head_dim,
+                                                  1.0f / sqrtf((float)head_dim)) != HALO_OK)
+        return HALO_ELAUNCH;
     return halo_launch_status();
 }
 

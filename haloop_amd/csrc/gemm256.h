@@ -234,12 +234,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const Args a) {
 
 template <int LAB = 0>
 static inline hipError_t launch(const Args &a, int nwg, hipStream_t st) {
-    if (!halo_func_attr_done(1 + (LAB != 0))) {         // per device (halo_internal.h)
-        const hipError_t e = hipFuncSetAttribute((const void *)gemm256_kernel<LAB>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return e;
-        halo_func_attr_set(1 + (LAB != 0));
-    }
-    hipLaunchKernelGGL(gemm256_kernel<LAB>, dim3((unsigned)nwg), dim3(512), LDS_BYTES, st, a);
+    if (halo_launch_lds<gemm256_kernel<LAB>>(dim3((unsigned)nwg), dim3(512), LDS_BYTES, st, a) != HALO_OK) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

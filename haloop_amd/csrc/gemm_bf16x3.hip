@@ -858,26 +858,9 @@ static int gemm_bf16x3_tiled_impl(const void *Aimg, const void *Bimg, int M, int
                                   hipStream_t st, const float *resid, int ldr) {
     static int nstage = -1, nstage1 = 0;     // nstage: -1 not read yet, 0 chosen per call by tile count, else forced by HALO_GEMM_STAGES
     if (nstage < 0) {
-        // three-pass ring depth: 1 slot = 32 KiB (three workgroups per CU), 2 = 64 KiB (two), 4 = 128 KiB (one); opt in to the LDS size once
+        // three-pass ring depth: 1 slot = 32 KiB (three workgroups per CU), 2 = 64 KiB (two), 4 = 128 KiB (one)
         const char *e = getenv("HALO_GEMM_STAGES");
         const int want = e ? atoi(e) : 2;
-        if (hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                2 * STAGE_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                4 * STAGE_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                2 * STAGE_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                4 * STAGE_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<2, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                2 * STAGE_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<2, 3, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                2 * STAGE_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<2, 3, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                2 * STAGE_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<2, 3, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                2 * STAGE_BYTES) != hipSuccess)
-            return HALO_ELAUNCH;
         nstage = e ? (want == 4 ? 4 : (want == 1 ? 1 : 2)) : 0;      // 0: by tile count (below)
         // single pass, half-size slots: 3 = 48 KiB, THREE workgroups per CU (default: [8192 x 3072 x 768] 90 -> 69 us and the lm_head
         // product 1365 -> 1020 us against 4 slots on the same box); 4 = 64 KiB (two per CU), 8 = 128 KiB (one), 2 = 32 KiB
@@ -906,6 +889,7 @@ static int gemm_bf16x3_tiled_impl(const void *Aimg, const void *Bimg, int M, int
     const bool slice = p.ksplit > 1;                                                     // raw sums: the reduce kernel applies the epilogue
     const bool lean_any = p.ksplit == 1 && !p.use_drop && (relu & ~HALO_GEMM_ACCUM) == 0;
     const bool lean = lean_any && !(relu & HALO_GEMM_ACCUM), lean_add = lean_any && (relu & HALO_GEMM_ACCUM);   // bias only / bias + C += result
+    int rc = HALO_OK;       // of the dynamic-LDS opt-in, for the launches that ask for more than 64 KiB (halo_launch_lds)
     if (one_pass && nstage1 == 3 && !ce && (lean || lean_add) && half_tiles_wanted(M, p.ntiles, p.ksplit)) {
         p.ntiles = ((M + 63) / 64) * p.tiles_n;
         const dim3 gh((unsigned)p.ntiles);
@@ -917,15 +901,15 @@ static int gemm_bf16x3_tiled_impl(const void *Aimg, const void *Bimg, int M, int
                                     // epilogue code cost every product 6-17 % and the LSTM-CTC step 2.6 %, same-box A/B)
         if (one_pass) hipLaunchKernelGGL((gemm_bf16x3_kernel<3, 1, true>), grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
         else if ((long)p.ntiles * p.ksplit >= 768) hipLaunchKernelGGL((gemm_bf16x3_kernel<1, 3, true>), grid, dim3(256), STAGE_BYTES, st, p);
-        else hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 3, true>), grid, dim3(256), 2 * STAGE_BYTES, st, p);
+        else rc = halo_launch_lds<gemm_bf16x3_kernel<2, 3, true>>(grid, dim3(256), 2 * STAGE_BYTES, st, p);
     } else
     if (one_pass && nstage1 == 3 && lean) hipLaunchKernelGGL((gemm_bf16x3_kernel<3, 1, false, 1>), grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
     else if (one_pass && nstage1 == 3 && lean_add) hipLaunchKernelGGL((gemm_bf16x3_kernel<3, 1, false, 3>), grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
     else if (one_pass && nstage1 == 3 && slice) hipLaunchKernelGGL((gemm_bf16x3_kernel<3, 1, false, 2>), grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
     else if (one_pass && nstage1 == 3) hipLaunchKernelGGL((gemm_bf16x3_kernel<3, 1>), grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
     else if (one_pass && nstage1 == 2) hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 1>), grid, dim3(256), STAGE_BYTES, st, p);
-    else if (one_pass && nstage1 == 8) hipLaunchKernelGGL((gemm_bf16x3_kernel<8, 1>), grid, dim3(256), 4 * STAGE_BYTES, st, p);
-    else if (one_pass) hipLaunchKernelGGL((gemm_bf16x3_kernel<4, 1>), grid, dim3(256), 2 * STAGE_BYTES, st, p);
+    else if (one_pass && nstage1 == 8) rc = halo_launch_lds<gemm_bf16x3_kernel<8, 1>>(grid, dim3(256), 4 * STAGE_BYTES, st, p);
+    else if (one_pass) rc = halo_launch_lds<gemm_bf16x3_kernel<4, 1>>(grid, dim3(256), 2 * STAGE_BYTES, st, p);
     // three passes: ONE 32 KiB slot (refilled under the MFMAs once every wave holds its fragments) lets three workgroups share a CU
     // and wins where there are that many (>= 768 tiles: [8192 x 3072 x 768] 153 -> 136 us, lm_head 2172 -> 1928 us); with fewer the
     // two-slot ring at two per CU is faster ([4096 x 1024 x 1344], the LSTM weight gradient: 54 vs 63 us)
@@ -933,12 +917,12 @@ static int gemm_bf16x3_tiled_impl(const void *Aimg, const void *Bimg, int M, int
         if (lean) hipLaunchKernelGGL((gemm_bf16x3_kernel<1, 3, false, 1>), grid, dim3(256), STAGE_BYTES, st, p);
         else if (lean_add) hipLaunchKernelGGL((gemm_bf16x3_kernel<1, 3, false, 3>), grid, dim3(256), STAGE_BYTES, st, p);
         else hipLaunchKernelGGL((gemm_bf16x3_kernel<1, 3>), grid, dim3(256), STAGE_BYTES, st, p);
-    } else if (nstage == 4) hipLaunchKernelGGL((gemm_bf16x3_kernel<4, 3>), grid, dim3(256), 4 * STAGE_BYTES, st, p);
-    else if (lean) hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 3, false, 1>), grid, dim3(256), 2 * STAGE_BYTES, st, p);
-    else if (lean_add) hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 3, false, 3>), grid, dim3(256), 2 * STAGE_BYTES, st, p);
-    else if (slice) hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 3, false, 2>), grid, dim3(256), 2 * STAGE_BYTES, st, p);
-    else hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 3>), grid, dim3(256), 2 * STAGE_BYTES, st, p);
-    int rc = halo_launch_status();
+    } else if (nstage == 4) rc = halo_launch_lds<gemm_bf16x3_kernel<4, 3>>(grid, dim3(256), 4 * STAGE_BYTES, st, p);
+    else if (lean) rc = halo_launch_lds<gemm_bf16x3_kernel<2, 3, false, 1>>(grid, dim3(256), 2 * STAGE_BYTES, st, p);
+    else if (lean_add) rc = halo_launch_lds<gemm_bf16x3_kernel<2, 3, false, 3>>(grid, dim3(256), 2 * STAGE_BYTES, st, p);
+    else if (slice) rc = halo_launch_lds<gemm_bf16x3_kernel<2, 3, false, 2>>(grid, dim3(256), 2 * STAGE_BYTES, st, p);
+    else rc = halo_launch_lds<gemm_bf16x3_kernel<2, 3>>(grid, dim3(256), 2 * STAGE_BYTES, st, p);
+    if (rc == HALO_OK) rc = halo_launch_status();
     if (rc != HALO_OK || p.ksplit == 1) return rc;
     // the reduce adds into C: an addend held elsewhere is copied there first
     if ((relu & HALO_GEMM_ACCUM) && resid != C &&
@@ -954,12 +938,6 @@ static int gemm_bf16x3_tiled_impl(const void *Aimg, const void *Bimg, int M, int
 // the reduce launch between them, 8 us for 2.7 MB, is pure latency).  *slices = how many were written (<= want).
 int halo_gemm_bf16x3_tiled_slices(const void *Aimg, const void *Bimg, int M, int N, int K, float *slab, int want, int *slices, hipStream_t st) {
     if (!Aimg || !Bimg || !slab || !slices || M <= 0 || N <= 0 || K <= 0 || want < 1) return HALO_EINVAL;
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<2, 3, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES) != hipSuccess)
-            return HALO_ELAUNCH;
-        attr = true;
-    }
     TiledGemmArgs p = {};
     p.A = (const char *)Aimg; p.B = (const char *)Bimg;
     p.M = M; p.N = N; p.KT = (K + TK - 1) / TK; p.ldc = N;
@@ -972,7 +950,7 @@ int halo_gemm_bf16x3_tiled_slices(const void *Aimg, const void *Bimg, int M, int
     *slices = p.ksplit;
     const dim3 grid((unsigned)(p.ntiles * p.ksplit));
     if (halo_math_mode() == HALO_MATH_BF16) hipLaunchKernelGGL((gemm_bf16x3_kernel<3, 1, false, 2>), grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
-    else hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 3, false, 2>), grid, dim3(256), 2 * STAGE_BYTES, st, p);
+    else if (halo_launch_lds<gemm_bf16x3_kernel<2, 3, false, 2>>(grid, dim3(256), 2 * STAGE_BYTES, st, p) != HALO_OK) return HALO_ELAUNCH;
     return halo_launch_status();
 }
 
@@ -991,14 +969,6 @@ int halo_gemm_bf16x3_tiled_nsplit_carry(const void *Aimg, const void *Bimg, int 
                                         float *sumsq_part, int *sumsq_parts, hipStream_t st) {
     if (slices) *slices = 0;
     if (n_split % TR != 0 || n_split <= 0 || n_split >= N) return HALO_EINVAL;
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<2, 3, false, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<1, 3, false, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, STAGE_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<3, 1, false, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * STAGE_BYTES / 2) != hipSuccess)
-            return HALO_ELAUNCH;
-        attr = true;
-    }
     TiledGemmArgs p = {};
     p.A = (const char *)Aimg; p.B = (const char *)Bimg; p.C = C; p.C2 = C2; p.n_split = n_split; p.ldc2 = ldc2;
     p.M = M; p.N = N; p.KT = (K + TK - 1) / TK; p.ldc = ldc;
@@ -1027,10 +997,11 @@ int halo_gemm_bf16x3_tiled_nsplit_carry(const void *Aimg, const void *Bimg, int 
         return halo_launch_status();
     }
     if (sumsq_parts) *sumsq_parts = p.ntiles;       // (the carried product's workgroups write none)
-    if (halo_math_mode() == HALO_MATH_BF16) hipLaunchKernelGGL((gemm_bf16x3_kernel<3, 1, false, 1, 4>), grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
-    else if (p.ntiles >= 768) hipLaunchKernelGGL((gemm_bf16x3_kernel<1, 3, false, 1, 4>), grid, dim3(256), STAGE_BYTES, st, p);
-    else hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 3, false, 1, 4>), grid, dim3(256), 2 * STAGE_BYTES, st, p);
-    return halo_launch_status();
+    int rc;
+    if (halo_math_mode() == HALO_MATH_BF16) rc = halo_launch_lds<gemm_bf16x3_kernel<3, 1, false, 1, 4>>(grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
+    else if (p.ntiles >= 768) rc = halo_launch_lds<gemm_bf16x3_kernel<1, 3, false, 1, 4>>(grid, dim3(256), STAGE_BYTES, st, p);
+    else rc = halo_launch_lds<gemm_bf16x3_kernel<2, 3, false, 1, 4>>(grid, dim3(256), 2 * STAGE_BYTES, st, p);
+    return rc == HALO_OK ? halo_launch_status() : rc;
 }
 
 // The tiled product with row-major bf16 on either side (IO instantiations of the kernel): A from a row-major bf16 matrix (a_hi [, a_lo])
@@ -1048,16 +1019,7 @@ static int launch_io(const TiledGemmArgs &p0, bool one_pass, hipStream_t st) {
     const dim3 grid((unsigned)p.ntiles);
     if (one_pass) hipLaunchKernelGGL((gemm_bf16x3_kernel<3, 1, false, EPI, IO>), grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
     else if (p.ntiles >= 768) hipLaunchKernelGGL((gemm_bf16x3_kernel<1, 3, false, EPI, IO>), grid, dim3(256), STAGE_BYTES, st, p);
-    else {
-        static bool attr = false;
-        if (!attr) {
-            if (hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<2, 3, false, EPI, IO>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    2 * STAGE_BYTES) != hipSuccess)
-                return HALO_ELAUNCH;
-            attr = true;
-        }
-        hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 3, false, EPI, IO>), grid, dim3(256), 2 * STAGE_BYTES, st, p);
-    }
+    else if (halo_launch_lds<gemm_bf16x3_kernel<2, 3, false, EPI, IO>>(grid, dim3(256), 2 * STAGE_BYTES, st, p) != HALO_OK) return HALO_ELAUNCH;
     return halo_launch_status();
 }
 
@@ -1086,14 +1048,6 @@ static int gemm_bf16x3_io(const void *Aimg, const void *a_hi, const void *a_lo, 
 
 // C [M][N] (+)= A^T B with A [K][M], B [K][N] row-major bf16 (IO & 8).  Split-K by the same rule as the image products.
 static int gemm_tn_bf16(const void *a, long lda, const void *b, long ldb, int M, int N, int K, float *C, int ldc, int flags, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<3, 1, false, 1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * STAGE_BYTES / 2) != hipSuccess ||
-            hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<3, 1, false, 2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * STAGE_BYTES / 2) != hipSuccess ||
-            hipFuncSetAttribute((const void *)gemm_bf16x3_kernel<3, 1, false, 3, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * STAGE_BYTES / 2) != hipSuccess)
-            return HALO_ELAUNCH;
-        attr = true;
-    }
     TiledGemmArgs p = {};
     p.Arm_hi = (const __bf16 *)a; p.lda = lda; p.Brm = (const __bf16 *)b; p.ldb = ldb;
     p.C = C; p.R = C; p.ldr = ldc; p.ldc = ldc;
@@ -1108,23 +1062,17 @@ static int gemm_tn_bf16(const void *a, long lda, const void *b, long ldb, int M,
     halo_get_scratch(&scratch, &bytes);
     p.slab = (float *)scratch;
     const dim3 grid((unsigned)(p.ntiles * p.ksplit));
-    if (p.ksplit > 1) hipLaunchKernelGGL((gemm_bf16x3_kernel<3, 1, false, 2, 8>), grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
-    else if (flags & HALO_GEMM_ACCUM) hipLaunchKernelGGL((gemm_bf16x3_kernel<3, 1, false, 3, 8>), grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
-    else hipLaunchKernelGGL((gemm_bf16x3_kernel<3, 1, false, 1, 8>), grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
-    const int rc = halo_launch_status();
+    int rc;
+    if (p.ksplit > 1) rc = halo_launch_lds<gemm_bf16x3_kernel<3, 1, false, 2, 8>>(grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
+    else if (flags & HALO_GEMM_ACCUM) rc = halo_launch_lds<gemm_bf16x3_kernel<3, 1, false, 3, 8>>(grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
+    else rc = halo_launch_lds<gemm_bf16x3_kernel<3, 1, false, 1, 8>>(grid, dim3(256), 3 * STAGE_BYTES / 2, st, p);
+    if (rc == HALO_OK) rc = halo_launch_status();
     if (rc != HALO_OK || p.ksplit == 1) return rc;
     return halo_splitk_reduce(p.slab, p.ksplit, M, N, C, ldc, nullptr, nullptr, flags, p.drop, 0, st);
 }
 
 static int gemm_tn_bf16_group(int n, const void *const *a, const long *lda, const void *const *b, const long *ldb, const int *M, const int *N, int K,
                               float *const *C, const int *ldc, int flags, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void *)gemm_tn_group_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * STAGE_BYTES / 2) != hipSuccess ||
-            hipFuncSetAttribute((const void *)gemm_tn_group_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * STAGE_BYTES / 2) != hipSuccess)
-            return HALO_ELAUNCH;
-        attr = true;
-    }
     TnGroup g = {};
     g.n = n; g.KT = K / TK; g.accumulate = (flags & HALO_GEMM_ACCUM) ? 1 : 0;
     int total = 0;
@@ -1133,9 +1081,9 @@ static int gemm_tn_bf16_group(int n, const void *const *a, const long *lda, cons
         g.c[i] = C[i]; g.ldc[i] = ldc[i]; g.M[i] = M[i]; g.N[i] = N[i]; g.first[i] = total;
         total += ((M[i] + TR - 1) / TR) * ((N[i] + TR - 1) / TR);
     }
-    if (g.accumulate) hipLaunchKernelGGL(gemm_tn_group_kernel<3>, dim3((unsigned)total), dim3(256), 3 * STAGE_BYTES / 2, st, g);
-    else hipLaunchKernelGGL(gemm_tn_group_kernel<1>, dim3((unsigned)total), dim3(256), 3 * STAGE_BYTES / 2, st, g);
-    return halo_launch_status();
+    const int rc = g.accumulate ? halo_launch_lds<gemm_tn_group_kernel<3>>(dim3((unsigned)total), dim3(256), 3 * STAGE_BYTES / 2, st, g)
+                                : halo_launch_lds<gemm_tn_group_kernel<1>>(dim3((unsigned)total), dim3(256), 3 * STAGE_BYTES / 2, st, g);
+    return rc == HALO_OK ? halo_launch_status() : rc;
 }
 
 // Diagnostic (halo_debug_mfma_clock): the clock the chip holds under a bare bf16 MFMA loop on random operands -- fragments in

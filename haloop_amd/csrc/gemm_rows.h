@@ -326,14 +326,9 @@ __global__ __launch_bounds__(512) void gemm_rows_kernel(const Args a) {
 
 template <int TN, int EPI, bool AIMG, int LAB = 0>
 static inline hipError_t launch(const Args &a, hipStream_t st) {
-    constexpr int slot = 8 + (TN / 3 - 1) * 8 + EPI * 2 + (AIMG ? 1 : 0);
-    if (LAB || !halo_func_attr_done(slot)) {         // per device (halo_internal.h)
-        const hipError_t e = hipFuncSetAttribute((const void *)gemm_rows_kernel<TN, EPI, AIMG, LAB>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg<TN>::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        if (!LAB) halo_func_attr_set(slot);
-    }
     const int ks = EPI == EPI_F32 && a.kslices > 1 ? a.kslices : 1;
-    hipLaunchKernelGGL((gemm_rows_kernel<TN, EPI, AIMG, LAB>), dim3((unsigned)(a.tiles_m * a.tiles_n * ks)), dim3(512), Cfg<TN>::LDS_BYTES, st, a);
+    if (halo_launch_lds<gemm_rows_kernel<TN, EPI, AIMG, LAB>>(dim3((unsigned)(a.tiles_m * a.tiles_n * ks)), dim3(512), Cfg<TN>::LDS_BYTES, st, a) != HALO_OK)
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -292,18 +292,14 @@ void plan_slices(int nitems, int KT, int BN, int &n_full, int &S) {
 }
 
 template <int TN>
-hipError_t launch(TnrArgs &g, hipStream_t st, int slot_id) {
-    if (!halo_func_attr_done(slot_id)) {
-        const hipError_t e = hipFuncSetAttribute((const void *)gemm_tn_rows_kernel<TN>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg<TN>::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        halo_func_attr_set(slot_id);
-    }
+hipError_t launch(TnrArgs &g, hipStream_t st) {
     g.n_full = g.nitems; g.slices = 1; g.ktper = g.KT; g.slab = nullptr;
     int n_full, S;
     plan_slices(g.nitems, g.KT, Cfg<TN>::BN, n_full, S);
     if (S > 1) { g.n_full = n_full; g.slices = S; g.ktper = (g.KT + S - 1) / S; g.slab = (float *)halo_scratch_ptr(); }
     const int split_wgs = (g.nitems - g.n_full) * g.slices;
-    hipLaunchKernelGGL((gemm_tn_rows_kernel<TN>), dim3((unsigned)(g.n_full + split_wgs)), dim3(512), Cfg<TN>::LDS_BYTES, st, g);
+    if (halo_launch_lds<gemm_tn_rows_kernel<TN>>(dim3((unsigned)(g.n_full + split_wgs)), dim3(512), Cfg<TN>::LDS_BYTES, st, g) != HALO_OK)
+        return hipErrorInvalidValue;
     if (split_wgs) hipLaunchKernelGGL((tn_rows_slab_sum_kernel<TN>), dim3((unsigned)(g.nitems - g.n_full), 16), dim3(256), 0, st, g);
     return hipGetLastError();
 }
@@ -368,7 +364,7 @@ int halo_gemm_tn_rows_group(int n, const void *const *a, const long *lda, const 
         items += ((M[i] + 255) / 256) * g.tiles_n[i];
     }
     g.nitems = items;
-    const hipError_t e = tn == 8 ? launch<8>(g, (hipStream_t)stream, 38) : launch<4>(g, (hipStream_t)stream, 39);
+    const hipError_t e = tn == 8 ? launch<8>(g, (hipStream_t)stream) : launch<4>(g, (hipStream_t)stream);
     return e == hipSuccess ? HALO_OK : HALO_ELAUNCH;
 }
 

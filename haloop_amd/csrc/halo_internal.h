@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include "halo_common.h"
+#include "dyn_lds.h"
 #include "small_jobs.h"
 
 int halo_transpose(const float *in, float *out, int rows, int cols, hipStream_t st);
@@ -70,12 +71,9 @@ struct HaloCtx {
     int mute_block = -1;                 // test hook (halo_debug_mute_workgroup): this workgroup of a persistent forward never publishes
 };
 HaloCtx &halo_ctx_cur();
-// CUs of the current device (hipDeviceProp_t::multiProcessorCount, cached per device; <= 0: the query failed)
+// CUs of the current device (the device property, cached per device; <= 0: the query failed)
 int halo_cu_count();
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per DEVICE: one flag per (kernel slot, device) instead of a process-wide bool.
-// Slots: 0 ctc_head_train_kernel, 1 / 2 gemm256_kernel (product / lab variants), 8 .. 31 the gemm_rows_kernel instantiations
-bool halo_func_attr_done(int slot);
-void halo_func_attr_set(int slot);
+// (the dynamic-LDS opt-in of the large-LDS kernels is per device too: halo_allow_dyn_lds / halo_launch_lds, dyn_lds.h)
 // C | C2 = A x (B stacked on B2)^T in one launch (columns [n_split, N) of the result go to C2); plain sums
 int halo_gemm_bf16x3_tiled_nsplit(const void *Aimg, const void *Bimg, int M, int N, int K, float *C, int ldc, int n_split, float *C2, int ldc2,
                                   hipStream_t st);

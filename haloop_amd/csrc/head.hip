@@ -947,12 +947,6 @@ int halo_ctc_head_fwd(const float *features, const float *weight, const float *b
                    grad_out && loss && ticket && B > 0);
     if (!halo_ctc_head_supported(T, H, V, S)) return HALO_ENOTSUP;
     HALO_CHECK_ARG(((uintptr_t)features % 16 == 0) && ((uintptr_t)weight % 16 == 0));
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void *)ctc_head_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAD_FWD_LDS) != hipSuccess)
-            return HALO_ELAUNCH;
-        attr = true;
-    }
     HeadFwdArgs a;
     a.feats = features; a.w = weight; a.bias = bias;
     a.drop = make_dropout(p_drop, seed, stream_id, offset, offset_dev);
@@ -960,7 +954,7 @@ int halo_ctc_head_fwd(const float *features, const float *weight, const float *b
     a.lp = lp; a.alpha = alpha; a.nll = nll; a.grad_out = grad_out; a.loss = loss; a.flen = feature_lengths; a.ticket = ticket;
     a.B = B; a.T = T; a.H = H; a.V = V; a.S = S; a.ks = ks; a.stride = stride; a.pad = pad;
     a.ali = a.hyp = a.hyp_len = nullptr; a.scores = nullptr;
-    hipLaunchKernelGGL(ctc_head_fwd_kernel<false>, dim3(B), dim3(1024), HEAD_FWD_LDS, (hipStream_t)stream, a);
+    if (halo_launch_lds<ctc_head_fwd_kernel<false>>(dim3(B), dim3(1024), (int)HEAD_FWD_LDS, (hipStream_t)stream, a) != HALO_OK) return HALO_ELAUNCH;
     return halo_launch_status();
 }
 
@@ -969,12 +963,6 @@ int halo_ctc_head_greedy(const float *features, const float *weight, const float
     HALO_CHECK_ARG(features && weight && bias && alignments && scores && hyp && hyp_len && B > 0);
     if (!halo_ctc_head_supported(T, H, V, 0)) return HALO_ENOTSUP;
     HALO_CHECK_ARG(((uintptr_t)features % 16 == 0) && ((uintptr_t)weight % 16 == 0));
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void *)ctc_head_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAD_FWD_LDS) != hipSuccess)
-            return HALO_ELAUNCH;
-        attr = true;
-    }
     HeadFwdArgs a = {};
     a.feats = features; a.w = weight; a.bias = bias;
     a.drop = make_dropout(0.f, 0, 0, 0, nullptr);
@@ -984,7 +972,7 @@ int halo_ctc_head_greedy(const float *features, const float *weight, const float
         hipLaunchKernelGGL(ctc_head_greedy2_kernel, dim3(B), dim3(TNT), (size_t)TNW * 1024 * sizeof(float), (hipStream_t)stream, a);
         return halo_launch_status();
     }
-    hipLaunchKernelGGL(ctc_head_fwd_kernel<true>, dim3(B), dim3(1024), HEAD_FWD_LDS, (hipStream_t)stream, a);
+    if (halo_launch_lds<ctc_head_fwd_kernel<true>>(dim3(B), dim3(1024), (int)HEAD_FWD_LDS, (hipStream_t)stream, a) != HALO_OK) return HALO_ELAUNCH;
     return halo_launch_status();
 }
 
@@ -1007,14 +995,8 @@ int halo_ctc_head_bwd(const float *features, const float *weight, float p_drop, 
     int slices = 1;
     while (slices < 8 && (H / 32) % (2 * slices) == 0 && (long)B * 2 * slices <= 256) slices *= 2;
     const size_t mask_bytes = p_drop > 0.f ? (size_t)T * (H / slices) * sizeof(float) : 0;       // <= 128 KiB at T = 32, H = 1024
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void *)ctc_head_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 1024 * 4) != hipSuccess)
-            return HALO_ELAUNCH;
-        attr = true;
-    }
     if (mask_bytes > 32 * 1024 * 4) return HALO_ENOTSUP;
-    hipLaunchKernelGGL(ctc_head_bwd_kernel, dim3(B, slices), dim3(512), mask_bytes, (hipStream_t)stream, a);
+    if (halo_launch_lds<ctc_head_bwd_kernel>(dim3(B, slices), dim3(512), (int)mask_bytes, (hipStream_t)stream, a) != HALO_OK) return HALO_ELAUNCH;
     int rc = halo_launch_status();
     if (rc != HALO_OK) return rc;
     const long VH = (long)V * H;
@@ -1058,11 +1040,6 @@ int halo_ctc_head_train(const float *features, const float *weight, const float 
     HALO_CHECK_ARG(((uintptr_t)features % 16 == 0) && ((uintptr_t)weight % 16 == 0));
     const int slices = head_train_slices(B, H);
     const size_t lds = (size_t)TNW * 1024 * sizeof(float) + (p_drop > 0.f ? (size_t)32 * (H / slices) : 0);
-    if (!halo_func_attr_done(0)) {         // (the attribute is per device: one flag per device and kernel, halo_internal.h)
-        if (hipFuncSetAttribute((const void *)ctc_head_train_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(TNW * 1024 * sizeof(float) + 32 * 2048)) != hipSuccess)
-            return HALO_ELAUNCH;
-        halo_func_attr_set(0);
-    }
     if (H / slices > 2048) return HALO_ENOTSUP;
     HeadTrainArgs a;
     a.feats = features; a.w = weight; a.bias = bias;
@@ -1073,7 +1050,7 @@ int halo_ctc_head_train(const float *features, const float *weight, const float 
     a.mute = halo_ctx_cur().mute_block;
     a.dfeats = dfeatures; a.dw_part = (float *)workspace; a.db_part = a.dw_part + (size_t)B * V * H;
     a.B = B; a.T = T; a.H = H; a.V = V; a.S = S; a.ks = ks; a.stride = stride; a.pad = pad;
-    hipLaunchKernelGGL(ctc_head_train_kernel, dim3(B, slices), dim3(TNT), lds, (hipStream_t)stream, a);
+    if (halo_launch_lds<ctc_head_train_kernel>(dim3(B, slices), dim3(TNT), (int)lds, (hipStream_t)stream, a) != HALO_OK) return HALO_ELAUNCH;
     int rc = halo_launch_status();
     if (rc != HALO_OK) return rc;
     HaloSmallJob j = {};

@@ -953,14 +953,8 @@ int launch_step_fwd_ks(const StepFwdArgs &a, hipStream_t st) {
     static const bool want_alds = !(getenv("HALO_LSTM_ALDS") && atoi(getenv("HALO_LSTM_ALDS")) == 0);
     const bool alds = want_alds && ((nkb / KS) % (2 * WCH) == 0) && red_bytes + tile_bytes <= 128 * 1024;
     if (alds) {
-        static bool attr = false;
-        if (!attr) {
-            if (hipFuncSetAttribute((const void *)lstm_step_fwd_kernel<KS, X3, true, ONE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    128 * 1024) != hipSuccess)
-                return HALO_ELAUNCH;
-            attr = true;
-        }
-        hipLaunchKernelGGL((lstm_step_fwd_kernel<KS, X3, true, ONE>), grid, dim3(256 * KS), red_bytes + tile_bytes, st, a);
+        if (halo_launch_lds<lstm_step_fwd_kernel<KS, X3, true, ONE>>(grid, dim3(256 * KS), (int)(red_bytes + tile_bytes), st, a) != HALO_OK)
+            return HALO_ELAUNCH;
     } else {
         hipLaunchKernelGGL((lstm_step_fwd_kernel<KS, X3, false, ONE>), grid, dim3(256 * KS), red_bytes, st, a);
     }
@@ -1088,12 +1082,6 @@ int lstm_fwd_fused(const float *x, const float *const *w_ih, const float *const 
     }
     const bool alds = (nkb / 2) % (2 * WCH) == 0;
     const size_t lds_bytes = (size_t)8 * 256 * sizeof(float) + (alds ? (size_t)nkb * 2048 : 0);
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void *)lstm_diag_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-            return HALO_ELAUNCH;
-        attr = true;
-    }
     for (int d = 0; d < T + L - 1; ++d) {
         DiagFwdArgs a;
         a.B = B; a.H = H;
@@ -1128,7 +1116,7 @@ int lstm_fwd_fused(const float *x, const float *const *w_ih, const float *const 
                 q.yp_out = fused_yp(extra, l, T, B, H, L) + (size_t)t * PH;
             }
         }
-        hipLaunchKernelGGL(lstm_diag_fwd_kernel, dim3(H / 16, (B + 15) / 16, L), dim3(512), lds_bytes, st, a);
+        HALO_TRY(halo_launch_lds<lstm_diag_fwd_kernel>(dim3(H / 16, (B + 15) / 16, L), dim3(512), (int)lds_bytes, st, a));
         HALO_TRY(halo_launch_status());
     }
     for (int l = 0; l < L; ++l) {

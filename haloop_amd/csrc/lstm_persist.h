@@ -1,7 +1,10 @@
 // Host-side interface of the weight-resident persistent LSTM recurrence (lstm_persist.hip); not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
+#include <type_traits>
 #include "halo_common.h"
+#include "halo_internal.h"
 
 constexpr int PERSIST_FLAG_HEADER = 16;                  // words: [0] abort / timeout word (replica 0), rest reserved
 constexpr int PERSIST_MAX_BLOCKS = 256;                  // one epoch word per workgroup
@@ -150,3 +153,33 @@ int halo_lstm_persist2_bwd(const Persist2Bwd &a, hipStream_t st);
 // the same launches with TWO batch tiles per workgroup, interleaved (lstm_persist2x.hip): tiles [a.bt0, a.bt0 + a.nbt), a.epoch0 set by the caller
 int halo_lstm_persist2x_fwd(const Persist2Fwd &a, hipStream_t st);
 int halo_lstm_persist2x_bwd(const Persist2Bwd &a, hipStream_t st);
+
+// ---- the host launcher of all four persistent translation units (lstm_persist.hip, lstm_persist32.hip, lstm_persist2.hip, lstm_persist2x.hip) ----
+// A dynamic LDS request that, with a kernel's static arrays, comes to more than half a CU's LDS: one workgroup per CU.  The 32-row kernels'
+// static arrays take up to 66 KiB, so they ask for less.
+constexpr int PERSIST_ONE_PER_CU_LDS = 64 * 1024, PERSIST32_ONE_PER_CU_LDS = 48 * 1024;
+
+// the hand-off switches of the environment, read on first use
+struct PersistEnv {
+    int poll_mode, replica_shift, nap;
+};
+inline const PersistEnv &halo_persist_env() {
+    const auto num = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
+    static const PersistEnv env = {num("HALO_PERSIST_POLL", 0), num("HALO_PERSIST_REPLICA_SHIFT", 3), num("HALO_PERSIST_NAP", 2)};
+    return env;
+}
+
+// One launch of `blocks` workgroups of 512 threads with `dyn_lds` bytes of dynamic LDS (opted in per device, dyn_lds.h) on a copy of the
+// arguments that carries what the launcher owns: the hand-off switches, the caller's status word and, in the forward structs, the muted
+// workgroup of the test hook.  Only the per-layer 16-row launches pass a poll_mode (HALO_PERSIST_POLL).  a.flags is zeroed by the caller's
+// prologue launch (lstm.hip).
+template <auto Kernel, typename A>
+int halo_persist_launch(const A &a0, int blocks, int dyn_lds, hipStream_t st, int poll_mode = 0) {
+    static_assert(sizeof(A) <= 4096, "kernel arguments");
+    A a = a0;
+    a.poll_mode = poll_mode; a.replica_shift = halo_persist_env().replica_shift; a.nap = halo_persist_env().nap;
+    a.status = halo_ctx_cur().status;
+    if constexpr (std::is_same_v<A, PersistFwd> || std::is_same_v<A, Persist2Fwd>) a.mute = halo_ctx_cur().mute_block;
+    if (halo_launch_lds<Kernel>(dim3((unsigned)blocks), dim3(512), dyn_lds, st, a) != HALO_OK) return HALO_ELAUNCH;
+    return halo_launch_status();
+}

@@ -394,48 +394,6 @@ __global__ __launch_bounds__(512, 2) void lstm_persist_bwd_kernel(const PersistB
     }
 }
 
-int g_cu_count = 0;
-inline int poll_mode() {
-    static const int m = getenv("HALO_PERSIST_POLL") ? atoi(getenv("HALO_PERSIST_POLL")) : 0;
-    return m;
-}
-
-inline int cu_count() {
-    if (!g_cu_count) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) g_cu_count = prop.multiProcessorCount;
-        else g_cu_count = -1;
-    }
-    return g_cu_count;
-}
-
-constexpr size_t FORCE_ONE_PER_CU_LDS = 64 * 1024;    // dynamic LDS request on top of the static arrays: one workgroup per CU
-
-inline void set_mute(PersistFwd &a) { a.mute = halo_ctx_cur().mute_block; }
-inline void set_mute(PersistBwd &) {}
-
-template <typename K, typename A>
-int launch_persist(K kernel, const A &a0, int blocks, hipStream_t st) {
-    static_assert(sizeof(A) <= 4096, "kernel arguments");
-    A a = a0;
-    a.poll_mode = poll_mode();
-    static const int shift = getenv("HALO_PERSIST_REPLICA_SHIFT") ? atoi(getenv("HALO_PERSIST_REPLICA_SHIFT")) : 3;
-    static const int nap = getenv("HALO_PERSIST_NAP") ? atoi(getenv("HALO_PERSIST_NAP")) : 2;
-    a.replica_shift = shift; a.nap = nap;
-    a.status = halo_ctx_cur().status;
-    set_mute(a);
-    // a.flags is zeroed by the caller's prologue launch (lstm.hip, persist_prologue_kernel)
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(512), FORCE_ONE_PER_CU_LDS, st, a);
-    return halo_launch_status();
-}
-
-template <typename K>
-int allow_lds(K kernel) {
-    return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FORCE_ONE_PER_CU_LDS) == hipSuccess
-               ? HALO_OK : HALO_ELAUNCH;
-}
-
 }  // namespace
 
 void halo_lstm_persist_enable(int on) { halo_ctx_cur().lstm_persistent = on ? 1 : 0; }
@@ -468,41 +426,27 @@ bool halo_lstm_persist_ok(int B, int H) {
     // (the reference's wider variant, ha/init.py:171) still leave room
     if (H % 256 != 0 || B <= 0 || H > (halo_math_mode() == HALO_MATH_BF16 ? 1536 : 1024)) return false;
     const int blocks = (H / 16) * ((B + 15) / 16);
-    if (blocks <= cu_count()) return true;
+    if (blocks <= halo_cu_count()) return true;
     // 32 batch rows per workgroup (lstm_persist32.hip): single-pass bf16 only -- the split-bf16 kernels have no registers for a second sub-tile
-    return halo_math_mode() == HALO_MATH_BF16 && wide_enabled() && (H / 16) * ((B + 31) / 32) <= cu_count();
+    return halo_math_mode() == HALO_MATH_BF16 && wide_enabled() && (H / 16) * ((B + 31) / 32) <= halo_cu_count();
 }
 
 int halo_lstm_persist_fwd(const PersistFwd &a, hipStream_t st) {
     const int blocks = (a.H / 16) * ((a.B + 15) / 16);
     const bool one = halo_math_mode() == HALO_MATH_BF16;
-    if (blocks > cu_count()) return one ? halo_lstm_persist_fwd32(a, st) : HALO_ENOTSUP;
-    static bool attr = false;
-    if (!attr) {
-        int rc = allow_lds(lstm_persist_fwd_kernel<1, false>);
-        if (!rc) rc = allow_lds(lstm_persist_fwd_kernel<2, false>);
-        if (!rc) rc = allow_lds(lstm_persist_fwd_kernel<3, false>);
-        if (!rc) rc = allow_lds(lstm_persist_fwd_kernel<4, false>);
-        if (!rc) rc = allow_lds(lstm_persist_fwd_kernel<1, true>);
-        if (!rc) rc = allow_lds(lstm_persist_fwd_kernel<2, true>);
-        if (!rc) rc = allow_lds(lstm_persist_fwd_kernel<3, true>);
-        if (!rc) rc = allow_lds(lstm_persist_fwd_kernel<4, true>);
-        if (!rc) rc = allow_lds(lstm_persist_fwd_kernel<5, true>);
-        if (!rc) rc = allow_lds(lstm_persist_fwd_kernel<6, true>);
-        if (rc) return rc;
-        attr = true;
-    }
+    if (blocks > halo_cu_count()) return one ? halo_lstm_persist_fwd32(a, st) : HALO_ENOTSUP;
+    const int poll = halo_persist_env().poll_mode;
     switch ((a.H / 256) * 2 + (one ? 1 : 0)) {
-        case 2: return launch_persist(lstm_persist_fwd_kernel<1, false>, a, blocks, st);
-        case 3: return launch_persist(lstm_persist_fwd_kernel<1, true>, a, blocks, st);
-        case 4: return launch_persist(lstm_persist_fwd_kernel<2, false>, a, blocks, st);
-        case 5: return launch_persist(lstm_persist_fwd_kernel<2, true>, a, blocks, st);
-        case 6: return launch_persist(lstm_persist_fwd_kernel<3, false>, a, blocks, st);
-        case 7: return launch_persist(lstm_persist_fwd_kernel<3, true>, a, blocks, st);
-        case 8: return launch_persist(lstm_persist_fwd_kernel<4, false>, a, blocks, st);
-        case 9: return launch_persist(lstm_persist_fwd_kernel<4, true>, a, blocks, st);
-        case 11: return launch_persist(lstm_persist_fwd_kernel<5, true>, a, blocks, st);
-        case 13: return launch_persist(lstm_persist_fwd_kernel<6, true>, a, blocks, st);
+        case 2: return halo_persist_launch<lstm_persist_fwd_kernel<1, false>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 3: return halo_persist_launch<lstm_persist_fwd_kernel<1, true>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 4: return halo_persist_launch<lstm_persist_fwd_kernel<2, false>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 5: return halo_persist_launch<lstm_persist_fwd_kernel<2, true>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 6: return halo_persist_launch<lstm_persist_fwd_kernel<3, false>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 7: return halo_persist_launch<lstm_persist_fwd_kernel<3, true>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 8: return halo_persist_launch<lstm_persist_fwd_kernel<4, false>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 9: return halo_persist_launch<lstm_persist_fwd_kernel<4, true>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 11: return halo_persist_launch<lstm_persist_fwd_kernel<5, true>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 13: return halo_persist_launch<lstm_persist_fwd_kernel<6, true>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
         default: return HALO_ENOTSUP;
     }
 }
@@ -510,33 +454,19 @@ int halo_lstm_persist_fwd(const PersistFwd &a, hipStream_t st) {
 int halo_lstm_persist_bwd(const PersistBwd &a, hipStream_t st) {
     const int blocks = (a.H / 16) * ((a.B + 15) / 16);
     const bool one = halo_math_mode() == HALO_MATH_BF16;
-    if (blocks > cu_count()) return one ? halo_lstm_persist_bwd32(a, st) : HALO_ENOTSUP;
-    static bool attr = false;
-    if (!attr) {
-        int rc = allow_lds(lstm_persist_bwd_kernel<1, false>);
-        if (!rc) rc = allow_lds(lstm_persist_bwd_kernel<2, false>);
-        if (!rc) rc = allow_lds(lstm_persist_bwd_kernel<3, false>);
-        if (!rc) rc = allow_lds(lstm_persist_bwd_kernel<4, false>);
-        if (!rc) rc = allow_lds(lstm_persist_bwd_kernel<1, true>);
-        if (!rc) rc = allow_lds(lstm_persist_bwd_kernel<2, true>);
-        if (!rc) rc = allow_lds(lstm_persist_bwd_kernel<3, true>);
-        if (!rc) rc = allow_lds(lstm_persist_bwd_kernel<4, true>);
-        if (!rc) rc = allow_lds(lstm_persist_bwd_kernel<5, true>);
-        if (!rc) rc = allow_lds(lstm_persist_bwd_kernel<6, true>);
-        if (rc) return rc;
-        attr = true;
-    }
+    if (blocks > halo_cu_count()) return one ? halo_lstm_persist_bwd32(a, st) : HALO_ENOTSUP;
+    const int poll = halo_persist_env().poll_mode;
     switch ((a.H / 256) * 2 + (one ? 1 : 0)) {
-        case 2: return launch_persist(lstm_persist_bwd_kernel<1, false>, a, blocks, st);
-        case 3: return launch_persist(lstm_persist_bwd_kernel<1, true>, a, blocks, st);
-        case 4: return launch_persist(lstm_persist_bwd_kernel<2, false>, a, blocks, st);
-        case 5: return launch_persist(lstm_persist_bwd_kernel<2, true>, a, blocks, st);
-        case 6: return launch_persist(lstm_persist_bwd_kernel<3, false>, a, blocks, st);
-        case 7: return launch_persist(lstm_persist_bwd_kernel<3, true>, a, blocks, st);
-        case 8: return launch_persist(lstm_persist_bwd_kernel<4, false>, a, blocks, st);
-        case 9: return launch_persist(lstm_persist_bwd_kernel<4, true>, a, blocks, st);
-        case 11: return launch_persist(lstm_persist_bwd_kernel<5, true>, a, blocks, st);
-        case 13: return launch_persist(lstm_persist_bwd_kernel<6, true>, a, blocks, st);
+        case 2: return halo_persist_launch<lstm_persist_bwd_kernel<1, false>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 3: return halo_persist_launch<lstm_persist_bwd_kernel<1, true>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 4: return halo_persist_launch<lstm_persist_bwd_kernel<2, false>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 5: return halo_persist_launch<lstm_persist_bwd_kernel<2, true>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 6: return halo_persist_launch<lstm_persist_bwd_kernel<3, false>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 7: return halo_persist_launch<lstm_persist_bwd_kernel<3, true>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 8: return halo_persist_launch<lstm_persist_bwd_kernel<4, false>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 9: return halo_persist_launch<lstm_persist_bwd_kernel<4, true>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 11: return halo_persist_launch<lstm_persist_bwd_kernel<5, true>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
+        case 13: return halo_persist_launch<lstm_persist_bwd_kernel<6, true>>(a, blocks, PERSIST_ONE_PER_CU_LDS, st, poll);
         default: return HALO_ENOTSUP;
     }
 }

@@ -756,39 +756,8 @@ __global__ __launch_bounds__(512, 2) void lstm_persist2_bwd_kernel(const Persist
     if (wave == 0) stamp(p.stamps, p.T + 1, 0, 15, lane);
 }
 
-int g_cu_count2 = 0;
-inline int cu_count2() {
-    if (!g_cu_count2) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) g_cu_count2 = prop.multiProcessorCount;
-        else g_cu_count2 = -1;
-    }
-    return g_cu_count2;
-}
-
 // batch tiles a launch can hold: every workgroup of a launch must be resident (one per CU)
-inline int tiles_per_launch(int H) { return max(1, cu_count2() / (H / 16)); }
-
-constexpr size_t MIN_DYN_LDS = 64 * 1024;             // with the static arrays: more than half a CU's LDS -> one workgroup per CU
-
-inline void set_mute(Persist2Fwd &a) { a.mute = halo_ctx_cur().mute_block; }
-inline void set_mute(Persist2Bwd &) {}
-
-template <typename K, typename A>
-int launch2(K kernel, const A &a0, int blocks, size_t dyn, hipStream_t st) {
-    static_assert(sizeof(A) <= 4096, "kernel arguments");
-    A a = a0;
-    static const int shift = getenv("HALO_PERSIST_REPLICA_SHIFT") ? atoi(getenv("HALO_PERSIST_REPLICA_SHIFT")) : 3;
-    static const int nap = getenv("HALO_PERSIST_NAP") ? atoi(getenv("HALO_PERSIST_NAP")) : 2;
-    a.poll_mode = 0; a.replica_shift = shift; a.nap = nap;
-    a.status = halo_ctx_cur().status;
-    set_mute(a);
-    if (dyn < MIN_DYN_LDS) dyn = MIN_DYN_LDS;
-    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) return HALO_ELAUNCH;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(512), dyn, st, a);
-    return halo_launch_status();
-}
+inline int tiles_per_launch(int H) { return max(1, halo_cu_count() / (H / 16)); }
 
 }  // namespace
 
@@ -807,7 +776,7 @@ bool halo_lstm_persist2_ok(int T, int B, int H, int L) {
     if ((long)(T + 2) * nbt * (4 * H / 32) * 2048 >= (1L << 31)) return false;
     if ((long)(T + 1) * B * 4 * H >= (1L << 31)) return false;             // 32-bit element indices inside the kernels
     // the epoch words of a launch's tiles (local index) fit a replica
-    return H / 16 <= cu_count2() && PERSIST_FLAG_HEADER + 2L * tiles_per_launch(H) * (H / 16) <= PERSIST_REPLICA_WORDS;      // (two tiles per workgroup: lstm_persist2x.hip)
+    return H / 16 <= halo_cu_count() && PERSIST_FLAG_HEADER + 2L * tiles_per_launch(H) * (H / 16) <= PERSIST_REPLICA_WORDS;      // (two tiles per workgroup: lstm_persist2x.hip)
 }
 
 // The batch rows are independent chains: a batch of more 16-row tiles than the chip holds workgroups for runs as consecutive launches over
@@ -858,18 +827,19 @@ int launch_groups(const A &a0, int steps, F launch_one, FX launch_pairs) {
 
 int halo_lstm_persist2_fwd(const Persist2Fwd &a0, hipStream_t st) {
     const int kbq = a0.H / 128;
-    const size_t dyn = (size_t)4 * 1024 * (4 * kbq - (kbq >= 8 ? 2 : 0));      // 4 quarters x NWLDS fragments of 1 KiB
+    // 4 quarters x NWLDS fragments of 1 KiB, and at least the request that keeps the launch at one workgroup per CU
+    const int dyn = max(4 * 1024 * (4 * kbq - (kbq >= 8 ? 2 : 0)), PERSIST_ONE_PER_CU_LDS);
     const bool df = halo_lstm_persist2_fwd_armed(a0.T, a0.B, a0.H);       // the launch ahead armed the images exactly then (lstm.hip)
     return launch_groups(a0, a0.T + 2, [&](const Persist2Fwd &a, int blocks) {
         switch (kbq * 2 + (df ? 1 : 0)) {
-            case 4: return launch2(lstm_persist2_fwd_kernel<2, false>, a, blocks, dyn, st);
-            case 5: return launch2(lstm_persist2_fwd_kernel<2, true>, a, blocks, dyn, st);
-            case 8: return launch2(lstm_persist2_fwd_kernel<4, false>, a, blocks, dyn, st);
-            case 9: return launch2(lstm_persist2_fwd_kernel<4, true>, a, blocks, dyn, st);
-            case 12: return launch2(lstm_persist2_fwd_kernel<6, false>, a, blocks, dyn, st);
-            case 13: return launch2(lstm_persist2_fwd_kernel<6, true>, a, blocks, dyn, st);
-            case 16: return launch2(lstm_persist2_fwd_kernel<8, false>, a, blocks, dyn, st);
-            case 17: return launch2(lstm_persist2_fwd_kernel<8, true>, a, blocks, dyn, st);
+            case 4: return halo_persist_launch<lstm_persist2_fwd_kernel<2, false>>(a, blocks, dyn, st);
+            case 5: return halo_persist_launch<lstm_persist2_fwd_kernel<2, true>>(a, blocks, dyn, st);
+            case 8: return halo_persist_launch<lstm_persist2_fwd_kernel<4, false>>(a, blocks, dyn, st);
+            case 9: return halo_persist_launch<lstm_persist2_fwd_kernel<4, true>>(a, blocks, dyn, st);
+            case 12: return halo_persist_launch<lstm_persist2_fwd_kernel<6, false>>(a, blocks, dyn, st);
+            case 13: return halo_persist_launch<lstm_persist2_fwd_kernel<6, true>>(a, blocks, dyn, st);
+            case 16: return halo_persist_launch<lstm_persist2_fwd_kernel<8, false>>(a, blocks, dyn, st);
+            case 17: return halo_persist_launch<lstm_persist2_fwd_kernel<8, true>>(a, blocks, dyn, st);
             default: return (int)HALO_ENOTSUP;
         }
     }, [&](const Persist2Fwd &a) { return halo_lstm_persist2x_fwd(a, st); });
@@ -877,13 +847,13 @@ int halo_lstm_persist2_fwd(const Persist2Fwd &a0, hipStream_t st) {
 
 int halo_lstm_persist2_bwd(const Persist2Bwd &a0, hipStream_t st) {
     const int kc = a0.H / 128;
-    const size_t dyn = (size_t)4 * 4 * kc * 1024;     // 4 quarters x KBW fragments of 1 KiB
+    const int dyn = max(4 * 4 * kc * 1024, PERSIST_ONE_PER_CU_LDS);     // 4 quarters x KBW fragments of 1 KiB (at least: one workgroup per CU)
     return launch_groups(a0, a0.T + 1, [&](const Persist2Bwd &a, int blocks) {
         switch (kc) {
-            case 2: return launch2(lstm_persist2_bwd_kernel<2>, a, blocks, dyn, st);
-            case 4: return launch2(lstm_persist2_bwd_kernel<4>, a, blocks, dyn, st);
-            case 6: return launch2(lstm_persist2_bwd_kernel<6>, a, blocks, dyn, st);
-            case 8: return launch2(lstm_persist2_bwd_kernel<8>, a, blocks, dyn, st);
+            case 2: return halo_persist_launch<lstm_persist2_bwd_kernel<2>>(a, blocks, dyn, st);
+            case 4: return halo_persist_launch<lstm_persist2_bwd_kernel<4>>(a, blocks, dyn, st);
+            case 6: return halo_persist_launch<lstm_persist2_bwd_kernel<6>>(a, blocks, dyn, st);
+            case 8: return halo_persist_launch<lstm_persist2_bwd_kernel<8>>(a, blocks, dyn, st);
             default: return (int)HALO_ENOTSUP;
         }
     }, [&](const Persist2Bwd &a) { return halo_lstm_persist2x_bwd(a, st); });

@@ -740,49 +740,29 @@ __global__ __launch_bounds__(512, 2) void lstm_persist2x_bwd_kernel(const Persis
     if (wave == 0) stamp(p.stamps, p.T + 1, 0, 15, lane);
 }
 
-constexpr size_t MIN_DYN_LDS_X = 64 * 1024;           // with the static arrays: more than half a CU's LDS -> one workgroup per CU
-
-inline void set_mute_x(Persist2Fwd &a) { a.mute = halo_ctx_cur().mute_block; }
-inline void set_mute_x(Persist2Bwd &) {}
-
-template <typename K, typename A>
-int launch2x(K kernel, const A &a0, int blocks, size_t dyn, hipStream_t st) {
-    static_assert(sizeof(A) <= 4096, "kernel arguments");
-    A a = a0;
-    static const int shift = getenv("HALO_PERSIST_REPLICA_SHIFT") ? atoi(getenv("HALO_PERSIST_REPLICA_SHIFT")) : 3;
-    static const int nap = getenv("HALO_PERSIST_NAP") ? atoi(getenv("HALO_PERSIST_NAP")) : 2;
-    a.poll_mode = 0; a.replica_shift = shift; a.nap = nap;
-    a.status = halo_ctx_cur().status;
-    set_mute_x(a);
-    if (dyn < MIN_DYN_LDS_X) dyn = MIN_DYN_LDS_X;
-    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) return HALO_ELAUNCH;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(512), dyn, st, a);
-    return halo_launch_status();
-}
-
 }  // namespace
 
 // a.bt0 / a.nbt / a.epoch0 set by the caller (lstm_persist2.hip, launch_groups): the launch takes tiles [bt0, bt0 + nbt), two per workgroup
 int halo_lstm_persist2x_fwd(const Persist2Fwd &a, hipStream_t st) {
     const int kbq = a.H / 128, blocks = (a.H / 16) * ((a.nbt + 1) / 2);
-    const size_t dyn = (size_t)4 * 1024 * (4 * kbq - (kbq >= 8 ? 2 : 0));
+    const int dyn = max(4 * 1024 * (4 * kbq - (kbq >= 8 ? 2 : 0)), PERSIST_ONE_PER_CU_LDS);     // (as lstm_persist2.hip)
     switch (kbq) {
-        case 2: return launch2x(lstm_persist2x_fwd_kernel<2>, a, blocks, dyn, st);
-        case 4: return launch2x(lstm_persist2x_fwd_kernel<4>, a, blocks, dyn, st);
-        case 6: return launch2x(lstm_persist2x_fwd_kernel<6>, a, blocks, dyn, st);
-        case 8: return launch2x(lstm_persist2x_fwd_kernel<8>, a, blocks, dyn, st);
+        case 2: return halo_persist_launch<lstm_persist2x_fwd_kernel<2>>(a, blocks, dyn, st);
+        case 4: return halo_persist_launch<lstm_persist2x_fwd_kernel<4>>(a, blocks, dyn, st);
+        case 6: return halo_persist_launch<lstm_persist2x_fwd_kernel<6>>(a, blocks, dyn, st);
+        case 8: return halo_persist_launch<lstm_persist2x_fwd_kernel<8>>(a, blocks, dyn, st);
         default: return (int)HALO_ENOTSUP;
     }
 }
 
 int halo_lstm_persist2x_bwd(const Persist2Bwd &a, hipStream_t st) {
     const int kc = a.H / 128, blocks = (a.H / 16) * ((a.nbt + 1) / 2);
-    const size_t dyn = (size_t)4 * 4 * kc * 1024;
+    const int dyn = max(4 * 4 * kc * 1024, PERSIST_ONE_PER_CU_LDS);
     switch (kc) {
-        case 2: return launch2x(lstm_persist2x_bwd_kernel<2>, a, blocks, dyn, st);
-        case 4: return launch2x(lstm_persist2x_bwd_kernel<4>, a, blocks, dyn, st);
-        case 6: return launch2x(lstm_persist2x_bwd_kernel<6>, a, blocks, dyn, st);
-        case 8: return launch2x(lstm_persist2x_bwd_kernel<8>, a, blocks, dyn, st);
+        case 2: return halo_persist_launch<lstm_persist2x_bwd_kernel<2>>(a, blocks, dyn, st);
+        case 4: return halo_persist_launch<lstm_persist2x_bwd_kernel<4>>(a, blocks, dyn, st);
+        case 6: return halo_persist_launch<lstm_persist2x_bwd_kernel<6>>(a, blocks, dyn, st);
+        case 8: return halo_persist_launch<lstm_persist2x_bwd_kernel<8>>(a, blocks, dyn, st);
         default: return (int)HALO_ENOTSUP;
     }
 }

@@ -351,33 +351,17 @@ __global__ __launch_bounds__(512, 2) void lstm_persist_bwd32_kernel(const Persis
     }
 }
 
-constexpr size_t FORCE_ONE_PER_CU_LDS32 = 48 * 1024;  // with the static arrays (up to 66 KiB): more than half a CU's LDS
-
-template <typename K, typename A>
-int launch32(K kernel, A a, int blocks, hipStream_t st) {
-    static const int shift = getenv("HALO_PERSIST_REPLICA_SHIFT") ? atoi(getenv("HALO_PERSIST_REPLICA_SHIFT")) : 3;
-    static const int nap = getenv("HALO_PERSIST_NAP") ? atoi(getenv("HALO_PERSIST_NAP")) : 2;
-    a.poll_mode = 0; a.replica_shift = shift; a.nap = nap;
-    a.status = halo_ctx_cur().status;
-    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FORCE_ONE_PER_CU_LDS32) != hipSuccess)
-        return HALO_ELAUNCH;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(512), FORCE_ONE_PER_CU_LDS32, st, a);
-    return halo_launch_status();
-}
-
 }  // namespace
 
-int halo_lstm_persist_fwd32(const PersistFwd &a0, hipStream_t st) {
-    PersistFwd a = a0;
-    a.mute = halo_ctx_cur().mute_block;
+int halo_lstm_persist_fwd32(const PersistFwd &a, hipStream_t st) {
     const int blocks = (a.H / 16) * ((a.B + 31) / 32);
     switch (a.H / 256) {
-        case 1: return launch32(lstm_persist_fwd32_kernel<1>, a, blocks, st);
-        case 2: return launch32(lstm_persist_fwd32_kernel<2>, a, blocks, st);
-        case 3: return launch32(lstm_persist_fwd32_kernel<3>, a, blocks, st);
-        case 4: return launch32(lstm_persist_fwd32_kernel<4>, a, blocks, st);
-        case 5: return launch32(lstm_persist_fwd32_kernel<5>, a, blocks, st);
-        case 6: return launch32(lstm_persist_fwd32_kernel<6>, a, blocks, st);
+        case 1: return halo_persist_launch<lstm_persist_fwd32_kernel<1>>(a, blocks, PERSIST32_ONE_PER_CU_LDS, st);
+        case 2: return halo_persist_launch<lstm_persist_fwd32_kernel<2>>(a, blocks, PERSIST32_ONE_PER_CU_LDS, st);
+        case 3: return halo_persist_launch<lstm_persist_fwd32_kernel<3>>(a, blocks, PERSIST32_ONE_PER_CU_LDS, st);
+        case 4: return halo_persist_launch<lstm_persist_fwd32_kernel<4>>(a, blocks, PERSIST32_ONE_PER_CU_LDS, st);
+        case 5: return halo_persist_launch<lstm_persist_fwd32_kernel<5>>(a, blocks, PERSIST32_ONE_PER_CU_LDS, st);
+        case 6: return halo_persist_launch<lstm_persist_fwd32_kernel<6>>(a, blocks, PERSIST32_ONE_PER_CU_LDS, st);
         default: return HALO_ENOTSUP;
     }
 }
@@ -385,12 +369,12 @@ int halo_lstm_persist_fwd32(const PersistFwd &a0, hipStream_t st) {
 int halo_lstm_persist_bwd32(const PersistBwd &a, hipStream_t st) {
     const int blocks = (a.H / 16) * ((a.B + 31) / 32);
     switch (a.H / 256) {
-        case 1: return launch32(lstm_persist_bwd32_kernel<1>, a, blocks, st);
-        case 2: return launch32(lstm_persist_bwd32_kernel<2>, a, blocks, st);
-        case 3: return launch32(lstm_persist_bwd32_kernel<3>, a, blocks, st);
-        case 4: return launch32(lstm_persist_bwd32_kernel<4>, a, blocks, st);
-        case 5: return launch32(lstm_persist_bwd32_kernel<5>, a, blocks, st);
-        case 6: return launch32(lstm_persist_bwd32_kernel<6>, a, blocks, st);
+        case 1: return halo_persist_launch<lstm_persist_bwd32_kernel<1>>(a, blocks, PERSIST32_ONE_PER_CU_LDS, st);
+        case 2: return halo_persist_launch<lstm_persist_bwd32_kernel<2>>(a, blocks, PERSIST32_ONE_PER_CU_LDS, st);
+        case 3: return halo_persist_launch<lstm_persist_bwd32_kernel<3>>(a, blocks, PERSIST32_ONE_PER_CU_LDS, st);
+        case 4: return halo_persist_launch<lstm_persist_bwd32_kernel<4>>(a, blocks, PERSIST32_ONE_PER_CU_LDS, st);
+        case 5: return halo_persist_launch<lstm_persist_bwd32_kernel<5>>(a, blocks, PERSIST32_ONE_PER_CU_LDS, st);
+        case 6: return halo_persist_launch<lstm_persist_bwd32_kernel<6>>(a, blocks, PERSIST32_ONE_PER_CU_LDS, st);
         default: return HALO_ENOTSUP;
     }
 }

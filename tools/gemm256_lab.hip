@@ -1,5 +1,5 @@
 // Laboratory build of the 256 x 256 workgroup-tile single-pass bf16 product over the tiled operand images (csrc/tiled_image.h):
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I haloop_amd/csrc tools/gemm256_lab.hip -o gpurun_out/gemm256_lab && gpurun_out/gemm256_lab
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I haloop_amd/csrc -I include tools/gemm256_lab.hip -o build/gemm256_lab && build/gemm256_lab
 // One launch over a list of problems (the LSTM's two weight-gradient products + the carried input-gradient slices), verified against a
 // plain device product, timed with HIP events.  The kernel under test is csrc/gemm256.h, the one the library links.
 #include <hip/hip_runtime.h>
@@ -10,11 +10,8 @@
 #include <vector>
 #include "gemm256.h"
 
-// (the library keeps these per device in abi.hip; a one-device lab binary needs no more)
-static bool g_attr_done[8];
+// (the library asks the device, abi.hip; the lab binary runs on an MI355X)
 int halo_cu_count() { return 256; }
-bool halo_func_attr_done(int slot) { return g_attr_done[slot]; }
-void halo_func_attr_set(int slot) { g_attr_done[slot] = true; }
 
 // ==== lab only: the four-wave variant of the 256 x 256 tile (measured equal to the eight-wave kernel the library links: DESIGN.md 3.1e) ====
 namespace halo_g256 {
@@ -182,13 +179,7 @@ __global__ __launch_bounds__(256) void gemm256w4_kernel(const Args a) {
 
 template <int LAB = 0>
 static inline hipError_t launch_w4(const Args &a, int nwg, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        const hipError_t e = hipFuncSetAttribute((const void *)gemm256w4_kernel<LAB>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    hipLaunchKernelGGL(gemm256w4_kernel<LAB>, dim3((unsigned)nwg), dim3(256), LDS_BYTES, st, a);
+    if (halo_launch_lds<gemm256w4_kernel<LAB>>(dim3((unsigned)nwg), dim3(256), LDS_BYTES, st, a) != HALO_OK) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
