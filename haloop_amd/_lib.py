@@ -8,6 +8,7 @@ LIB_PATH = os.path.join(_HERE, 'csrc', 'libhalo.so')
 
 HALO_ABI_VERSION = 21
 HALO_GPT_SAMPLE_STREAM = 0x47505453
+HALO_MLM_STREAM = 0x4D4C4D31
 HALO_GEMM_RELU = 1
 HALO_GEMM_GELU = 2
 HALO_GEMM_ACCUM = 4
@@ -198,6 +199,11 @@ SIGNATURES = {
     'halo_dwconv1d_cl_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'halo_tape_batch': (_i, [_vp, _i, _l, _i, _i, _l, _i, _l, _vp, _vp]),
     'halo_lm_batch_u16': (_i, [_vp, _l, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    'halo_mask_tokens': (_i, [_vp, _vp, _l, _f, _l, _l, _l, _u64, _u32, _vp]),
+    'halo_mlm_batch_u16': (_i, [_vp, _l, _vp, _i, _i, _f, _l, _l, _l, _u64, _u32, _vp, _vp, _vp]),
+    'halo_target_rows': (_i, [_vp, _i, _l, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'halo_gather_rows': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    'halo_scatter_rows': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'halo_scale_add': (_i, [_vp, _vp, _f, _f, _sz, _vp]),
     'halo_cast_f32_bf16': (_i, [_vp, _vp, _sz, _vp]),
     'halo_cast_bf16_f32': (_i, [_vp, _vp, _f, _sz, _vp]),

@@ -442,6 +442,29 @@ class GPT(nn.Module):
         self.transformer.wte.weight = self.lm_head.weight       # weight tying
         self._images = WeightImages()
         self.dropout_stream = DropoutStream()                   # Philox (seed, offset) per training forward
+        self._target_capacity = None                            # set_target_capacity: not part of the state dict
+
+    def set_target_capacity(self, rows):
+        """``rows``: forward_all compacts the first ``rows`` token rows whose target is non-zero, in ascending order, and runs ln_f, the
+        lm_head, the cross-entropy and their backward on those rows only -- the masked objectives ("denoise":
+        symbol_tape.target_capacity(B, T); "cond": B), where F.cross_entropy(ignore_index=0) ignores every other row.  Every shape is set
+        by the capacity, none by the count, and nothing returns to the host.  More targets than ``rows``: every per-token loss of that
+        call is NaN.  None (the default): the dense path.  Ignored with ``past``."""
+        if rows is not None and (int(rows) != rows or rows <= 0):
+            raise ValueError(f'target capacity must be a positive number of rows or None, got {rows!r}')
+        self._target_capacity = None if rows is None else int(rows)
+
+    def _compact_rows(self, M):
+        """(compact rows K, targets allowed for) of a call with M token rows under the set capacity.  K is the capacity rounded up to a
+        multiple of 32 (the weight-gradient products' contraction step) and, where the dense head runs above the small-M gate, to the
+        first such count above it too: at or below SMALL_M rows the head's products would fall to the exact-f32 kernel and a contraction
+        shorter than 64 rows takes its weight gradient there as well, so a small capacity would change the head's arithmetic against
+        the dense path's in the bf16x3 / bf16 modes.  The padding rows cost nothing that matters at that size."""
+        limit = self._target_capacity
+        K = (limit + 31) // 32 * 32
+        if M > SMALL_M:
+            K = max(K, (SMALL_M + 1 + 31) // 32 * 32)
+        return K, limit
 
     # ---- one Linear: y = x W^T + b, with the epilogue fused ------------------------------------
     def _linear(self, x2d, lin, out=None, gelu=False, accumulate=False, site=(ops.NO_DROPOUT, 0), a_image=None, shape=None):
@@ -462,11 +485,12 @@ class GPT(nn.Module):
         return x, ((et, ep) if keep else None)
 
     @torch.no_grad()
-    def _trunk(self, input_ids, past=None, want_present=False, cache=None, t0=0):
+    def _trunk(self, input_ids, past=None, want_present=False, cache=None, t0=0, want_residual=False):
         """Embedding + blocks + ln_f.  With ``past`` [L, 2, B, nh, T0, hs] (or want_present) keys/values go through a
         fp32 cache in the reference's layout (attend_cached, ha/attention.py:64-93) and ``present`` is returned.
         ``cache`` [L, 2, B, nh, Tc, hs] (haloop_amd.generation): a preallocated cache that already holds positions [0, t0); the T new
-        positions are stored behind them in place, nothing is allocated or copied, and ``cache`` itself is returned as ``present``."""
+        positions are stored behind them in place, nothing is allocated or copied, and ``cache`` itself is returned as ``present``.
+        ``want_residual``: the residual stream before ln_f in place of ln_f's output."""
         cfg = self.config
         B, T = input_ids.shape
         if cache is None:
@@ -499,12 +523,15 @@ class GPT(nn.Module):
                 continue
             h, _ = ln_linear(self._images, x, blk.ln_2.weight, blk.ln_2.bias, blk.mlp.c_fc.weight, bias=blk.mlp.c_fc.bias, gelu=True)
             self._linear(h, blk.mlp.c_proj, out=x, accumulate=True)                      # x += mlp(h)
+        if want_residual:
+            return x, present
         return ops.layernorm_fwd(x, tr.ln_f.weight, tr.ln_f.bias), present
 
     @torch.no_grad()
-    def _trunk_rows(self, input_ids):
+    def _trunk_rows(self, input_ids, want_residual=False):
         """Embedding + blocks + ln_f in single-pass bf16 arithmetic on halo_gemm_rows (scoring without a KV cache): the residual stream
-        fp32, updated in place by the products' residual epilogues; every Linear input row-major bf16.  -> ln_f(x) as row-major bf16."""
+        fp32, updated in place by the products' residual epilogues; every Linear input row-major bf16.  -> ln_f(x) as row-major bf16, or
+        with ``want_residual`` the fp32 residual stream before ln_f."""
         cfg = self.config
         B, T = input_ids.shape
         assert T <= cfg.block_size, f'Cannot forward sequence of length {T}, block size is only {cfg.block_size}'
@@ -532,6 +559,8 @@ class GPT(nn.Module):
             else:
                 gb = ops.gelu_b16(ops.gemm_rows(h2b, w(blk.mlp.c_fc), M, 4 * C, C, out_bf16=True))
             ops.gemm_rows(gb, w(blk.mlp.c_proj), M, C, 4 * C, out=x, residual=x)                # x += mlp(x)
+        if want_residual:
+            return x
         return ops.layernorm_bf16(x, tr.ln_f.weight, tr.ln_f.bias)
 
     def forward_all(self, input_ids, target_ids, past=None, reduction='mean'):
@@ -549,22 +578,49 @@ class GPT(nn.Module):
             raise NotImplementedError('training-mode dropout is built into the autograd path only: enable grad, or call .eval()')
         targets = target_ids.reshape(-1)
         C = self.config.n_embd
-        if past is None and B * T > SMALL_M and V % 8 == 0 and rows_ok(B * T, C) and rowmajor_train_ok(self.config, self.transformer.h, B * T, False):
+        rows_trunk = past is None and B * T > SMALL_M and V % 8 == 0 and rows_ok(B * T, C) and rowmajor_train_ok(self.config, self.transformer.h, B * T, False)
+        if past is None and self._target_capacity is not None:
+            return self._reduce(self._score_compact(input_ids, targets, rows_trunk), targets, reduction)
+        if rows_trunk:
             loss, _, _ = ops.gemm_rows_ce(self._trunk_rows(input_ids), self._images.split((self.lm_head.weight,)), B * T, V, C, targets, ignore_index=0)
             return self._reduce(loss, targets, reduction)
         x, _ = self._trunk(input_ids, past)
-        if use_split(B * T, V, C) and B * T > SMALL_M:
+        return self._reduce(self._score_head(x, targets), targets, reduction)
+
+    def _score_head(self, xf, targets):
+        """Per-row NLL of lm_head(xf) for ln_f's fp32 rows xf [R, C] (no grad)."""
+        R, C = xf.shape
+        V = self.config.vocab_size
+        if use_split(R, V, C) and R > SMALL_M:
             # lm_head + cross-entropy in the GEMM's epilogue: the [rows, V] logits are never written (SURVEY.md 8f-1)
-            loss, _, _ = ops.gemm_split_ce(ops.split_image(x), self._images.split((self.lm_head.weight,)), B * T, V, C, targets, ignore_index=0)
-            return self._reduce(loss, targets, reduction)
+            loss, _, _ = ops.gemm_split_ce(ops.split_image(xf), self._images.split((self.lm_head.weight,)), R, V, C, targets, ignore_index=0)
+            return loss
         # otherwise in row chunks so the logits stay bounded (206 MB per 1024 rows at V=50304)
-        loss = torch.empty(B * T, device=x.device, dtype=torch.float32)
-        chunk = max(64, min(B * T, (1 << 28) // (4 * V)))
-        for r0 in range(0, B * T, chunk):
-            r1 = min(B * T, r0 + chunk)
-            logits = self._linear(x[r0:r1], self.lm_head)
+        loss = torch.empty(R, device=xf.device, dtype=torch.float32)
+        chunk = max(64, min(R, (1 << 28) // (4 * V)))
+        for r0 in range(0, R, chunk):
+            r1 = min(R, r0 + chunk)
+            logits = self._linear(xf[r0:r1], self.lm_head)
             loss[r0:r1] = ops.cross_entropy_fwd(logits, targets[r0:r1], ignore_index=0)
-        return self._reduce(loss, targets, reduction)
+        return loss
+
+    @torch.no_grad()
+    def _score_compact(self, input_ids, targets, rows_trunk):
+        """forward_all's scoring path with a target capacity (K compact rows, _compact_rows): the trunk as the dense path runs it, then ln_f, the lm_head and the loss on
+        the K compacted rows, the head's product path chosen from K by the predicates the dense path applies to M.  -> per-token NLL [M]."""
+        tr = self.transformer
+        M = targets.numel()
+        K, limit = self._compact_rows(M)
+        C, V = self.config.n_embd, self.config.vocab_size
+        x = self._trunk_rows(input_ids, want_residual=True) if rows_trunk else self._trunk(input_ids, None, want_residual=True)[0]
+        rec = ops.target_rows(targets, K, ignore_index=0, limit=limit)
+        x_c = ops.gather_rows(x, rec.rows)
+        if rows_trunk and K > SMALL_M and rows_ok(K, C):
+            loss_c, _, _ = ops.gemm_rows_ce(ops.layernorm_bf16(x_c, tr.ln_f.weight, tr.ln_f.bias), self._images.split((self.lm_head.weight,)), K, V, C,
+                                            rec.targets, ignore_index=0)
+        else:
+            loss_c = self._score_head(ops.layernorm_fwd(x_c, tr.ln_f.weight, tr.ln_f.bias), rec.targets)
+        return ops.scatter_rows(loss_c, rec, M)
 
     @staticmethod
     def _reduce(loss, targets, reduction):
@@ -597,28 +653,71 @@ class GPT(nn.Module):
             x, sv = fwd(self._images, blk, x, B, T, cfg, sites)
             blocks.append(sv)
         targets = target_ids.reshape(-1)
+        rm = fwd is block_forward_train_rm
+        if self._target_capacity is not None:
+            # the masked objectives: ln_f, the lm_head and the loss on the compacted target rows; the per-token losses go back to their rows
+            K, limit = self._compact_rows(B * T)
+            rec = ops.target_rows(targets, K, ignore_index=0, limit=limit)
+            x_c = ops.gather_rows(x, rec.rows)
+            loss_c, xf, logits, row_lse = self._head_train(x_c, rec.targets, rm)
+            return ops.scatter_rows(loss_c, rec, B * T), (input_ids, rec.targets, blocks, x_c, xf, logits, row_lse, s_emb, emb_saved, rec)
+        loss, xf, logits, row_lse = self._head_train(x, targets, rm)
+        return loss, (input_ids, targets, blocks, x, xf, logits, row_lse, s_emb, emb_saved)
+
+    def _head_train(self, x, targets, rm):
+        """ln_f, the lm_head and the per-row cross-entropy on the residual rows x [R, C] -> (loss [R], ln_f's rows, logits, row lse), the
+        last three for _head_backward.  ``rm``: the blocks ran block_forward_train_rm."""
+        cfg, tr = self.config, self.transformer
+        R, C = x.shape
         V = cfg.vocab_size
-        if fwd is block_forward_train_rm and rows_ok(B * T, C) and ops.gemm_rows_supported(B * T, V, C) and ops.gemm_rows_supported(B * T, C, V):
+        if rm and rows_ok(R, C) and ops.gemm_rows_supported(R, V, C) and ops.gemm_rows_supported(R, C, V):
             # round 5: ln_f's rows as row-major bf16, the lm_head product on halo_gemm_rows with the cross-entropy statistics in its
             # epilogue (from the fp32 accumulators) and the logits KEPT AS bf16 (1.65 GB of fp32 at B = 8, T = 1024 no longer written).
             # Only when the backward's input-gradient product (K = V) runs on halo_gemm_rows too: V % 32 == 0.
+            _lib.lend_scratch(128 << 20, device=x.device)       # (the blocks lent it already unless only the compacted rows take this path)
             xf = ops.layernorm_bf16(x, tr.ln_f.weight, tr.ln_f.bias)
-            loss, row_lse, logits = ops.gemm_rows_ce(xf, self._images.split((self.lm_head.weight,)), B * T, cfg.vocab_size, C, targets,
+            loss, row_lse, logits = ops.gemm_rows_ce(xf, self._images.split((self.lm_head.weight,)), R, V, C, targets,
                                                      ignore_index=0, want_logits=True, want_lse=True)
-            return loss, (input_ids, targets, blocks, x, xf, logits, row_lse, s_emb, emb_saved)
+            return loss, xf, logits, row_lse
         xf = ops.layernorm_fwd(x, tr.ln_f.weight, tr.ln_f.bias)
-        if use_split(B * T, cfg.vocab_size, C) and B * T > SMALL_M:          # statistics in the GEMM epilogue; the logits are kept for the backward
-            loss, row_lse, logits = ops.gemm_split_ce(ops.split_image(xf), self._images.split((self.lm_head.weight,)), B * T, cfg.vocab_size, C,
+        if use_split(R, V, C) and R > SMALL_M:          # statistics in the GEMM epilogue; the logits are kept for the backward
+            loss, row_lse, logits = ops.gemm_split_ce(ops.split_image(xf), self._images.split((self.lm_head.weight,)), R, V, C,
                                                       targets, ignore_index=0, want_logits=True, want_lse=True)
         else:
             logits = self._linear(xf, self.lm_head)
             loss, row_lse = ops.cross_entropy_fwd_lse(logits, targets, ignore_index=0)
-        return loss, (input_ids, targets, blocks, x, xf, logits, row_lse, s_emb, emb_saved)
+        return loss, xf, logits, row_lse
+
+    def _head_backward(self, x_last, xf, logits, row_lse, targets, grad_rows, head, want_bf16, put):
+        """The backward of _head_train on its R rows: -> (d x_last [R, C], [the same as row-major bf16] with ``want_bf16``, the lm_head's
+        weight gradient [V, C] or None with ``head`` False); ln_f's gradients go to put."""
+        tr, img = self.transformer, self._images
+        M, V = logits.shape
+        C = self.config.n_embd
+        if logits.dtype == torch.bfloat16:
+            # the stored bf16 logits become d loss / d logits IN PLACE: the row-major bf16 operand of both gradient products
+            dl = ops.cross_entropy_bwd_bf16_(logits, targets, row_lse, grad_rows, ignore_index=0)
+            dw_head = ops.gemm_tn_group([(dl, xf)])[0] if head else None                     # [V, C]; the tied wte gradient lands here too
+            dxf = ops.gemm_rows(dl, img.split_t((self.lm_head.weight,)), M, C, V)
+            del dl, logits
+        elif use_split(M, C, V) and use_split(V, C, M):
+            # d loss / d logits goes straight into the two operand images of the lm_head's backward products
+            dl_img, dl_img_t = ops.cross_entropy_bwd_images(logits, targets, row_lse, grad_rows, ignore_index=0)
+            dw_head = linear_dw(None, xf, dy_image_t=dl_img_t, shapes=((M, V), xf.shape)) if head else None    # [V, C]; the tied wte gradient lands here too
+            dxf = linear_dx(img, None, self.lm_head.weight, dy_image=dl_img, shape=(M, V))
+            del dl_img, dl_img_t
+        else:
+            dlogits = ops.cross_entropy_bwd_(logits, targets, row_lse, grad_rows, ignore_index=0)
+            dw_head = linear_dw(dlogits, xf) if head else None
+            dxf = linear_dx(img, dlogits, self.lm_head.weight)
+        dx, dw, db, *dxb = ops.layernorm_bwd(dxf, x_last, tr.ln_f.weight, None, tr.ln_f.bias is not None, want_bf16=want_bf16)
+        put(tr.ln_f.weight, dw); put(tr.ln_f.bias, db)
+        return dx, dxb, dw_head
 
     @torch.no_grad()
     def _backward_train(self, saved, grad_per_tok):
         cfg = self.config
-        input_ids, targets, blocks, x_last, xf, logits, row_lse, s_emb, emb_saved = saved
+        input_ids, targets, blocks, x_last, xf, logits, row_lse, s_emb, emb_saved, *compact = saved
         B, T = input_ids.shape
         C, H = cfg.n_embd, cfg.n_head
         tr = self.transformer
@@ -629,7 +728,6 @@ class GPT(nn.Module):
             if p is not None and p.requires_grad:
                 grads[id(p)] = g if id(p) not in grads else grads[id(p)] + g
 
-        M, V = logits.shape
         # what is trainable at and below each point of the backward: a frozen parameter gets no weight-gradient product, and the sweep
         # stops at the lowest block whose c_attn adapters are the last trainable thing
         live = lambda mod: any(p.requires_grad for p in mod.parameters())
@@ -637,25 +735,14 @@ class GPT(nn.Module):
         below = [emb]
         for blk in tr.h:
             below.append(below[-1] or live(blk))
-        if logits.dtype == torch.bfloat16:
-            # the stored bf16 logits become d loss / d logits IN PLACE: the row-major bf16 operand of both gradient products
-            dl = ops.cross_entropy_bwd_bf16_(logits, targets, row_lse, grad_per_tok, ignore_index=0)
-            dw_head = ops.gemm_tn_group([(dl, xf)])[0] if head else None                     # [V, C]; the tied wte gradient lands here too
-            dxf = ops.gemm_rows(dl, img.split_t((self.lm_head.weight,)), M, C, V)
-            del dl, logits
-        elif use_split(M, C, V) and use_split(V, C, M):
-            # d loss / d logits goes straight into the two operand images of the lm_head's backward products
-            dl_img, dl_img_t = ops.cross_entropy_bwd_images(logits, targets, row_lse, grad_per_tok, ignore_index=0)
-            dw_head = linear_dw(None, xf, dy_image_t=dl_img_t, shapes=((M, V), xf.shape)) if head else None    # [V, C]; the tied wte gradient lands here too
-            dxf = linear_dx(img, None, self.lm_head.weight, dy_image=dl_img, shape=(M, V))
-            del dl_img, dl_img_t
-        else:
-            dlogits = ops.cross_entropy_bwd_(logits, targets, row_lse, grad_per_tok, ignore_index=0)
-            dw_head = linear_dw(dlogits, xf) if head else None
-            dxf = linear_dx(img, dlogits, self.lm_head.weight)
         rm = len(blocks) > 0 and blocks[0].rowmajor             # block_forward_train_rm's records
-        dx, dw, db, *dxb = ops.layernorm_bwd(dxf, x_last, tr.ln_f.weight, None, tr.ln_f.bias is not None, want_bf16=rm)
-        put(tr.ln_f.weight, dw); put(tr.ln_f.bias, db)
+        if compact:
+            # the head ran on the compacted target rows: their share of grad_per_tok in, their d x back to its rows (zero elsewhere)
+            rec = compact[0]
+            dx_c, _, dw_head = self._head_backward(x_last, xf, logits, row_lse, targets, ops.gather_rows(grad_per_tok, rec.rows), head, False, put)
+            dx, *dxb = ops.scatter_rows(dx_c, rec, B * T, want_bf16=True) if rm else (ops.scatter_rows(dx_c, rec, B * T),)
+        else:
+            dx, dxb, dw_head = self._head_backward(x_last, xf, logits, row_lse, targets, grad_per_tok, head, rm, put)
         for i in reversed(range(len(blocks))):
             blk, sv = tr.h[i], blocks[i]
             need_dx = below[i] or live(blk.ln_1)

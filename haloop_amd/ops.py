@@ -2,6 +2,7 @@
 current HIP stream and allocates its outputs/workspaces with torch (device memory plumbing only).
 """
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
@@ -1535,3 +1536,57 @@ def add_rows_bcast_(x2d, p2d, T):
     _f32c(x2d, 'x'); _f32c(p2d, 'p')
     check(lib().halo_add_rows_bcast(ptr(x2d), ptr(p2d), x2d.shape[0], T, x2d.shape[1], _stream()), 'halo_add_rows_bcast')
     return x2d
+
+
+# ---- the masked objectives: token masking, and the compaction of the rows that carry a target (csrc/sparse_head.hip) ----------------
+def mask_tokens_(inputs, mlm_probability, mask_token, endoftext_token, max_token, seed, step=0):
+    """inputs [..] int64, masked in place as include/halo.h defines the draws -> labels (same shape)."""
+    if inputs.dtype != torch.int64 or not inputs.is_cuda or not inputs.is_contiguous():
+        raise ValueError('mask_tokens_: expected a contiguous int64 HIP tensor')
+    labels = torch.empty_like(inputs)
+    check(lib().halo_mask_tokens(ptr(inputs), ptr(labels), inputs.numel(), mlm_probability, mask_token, endoftext_token, max_token,
+                                 seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF, _stream()), 'halo_mask_tokens')
+    return labels
+
+
+TargetRows = namedtuple('TargetRows', 'rows targets slot count capacity limit')
+
+
+def target_rows(targets, capacity, ignore_index=0, limit=None):
+    """targets [M] int64 -> TargetRows: ``rows`` [capacity] int32 (the first ``limit`` rows whose target is not ignore_index, ascending,
+    -1 behind them), ``targets`` [capacity] int64 (theirs, ignore_index behind them), ``slot`` [M] int32 (the inverse map, -1 where
+    a row has no place), ``count`` [1] int32 (every row with a target; more than ``limit``: overflow).  ``limit`` (default: capacity)
+    is the number of targets allowed for, ``capacity`` >= limit the number of compact rows.  Nothing returns to the host."""
+    tg = _i64c(targets.reshape(-1), 'targets')
+    M, dev = tg.numel(), tg.device
+    limit = capacity if limit is None else limit
+    rows = torch.empty(capacity, device=dev, dtype=torch.int32)
+    tc = torch.empty(capacity, device=dev, dtype=torch.int64)
+    slot = torch.empty(M, device=dev, dtype=torch.int32)
+    count = torch.empty(1, device=dev, dtype=torch.int32)
+    check(lib().halo_target_rows(ptr(tg), M, ignore_index, capacity, limit, ptr(rows), ptr(tc), ptr(slot), ptr(count), _stream()),
+          'halo_target_rows')
+    return TargetRows(rows, tc, slot, count, capacity, limit)
+
+
+def gather_rows(src, rows):
+    """src [M, C] (or [M]) fp32 -> [K, C] (or [K]): src[rows[k]], zeros where rows[k] < 0."""
+    _f32c(src, 'src')
+    K = rows.numel()
+    dst = torch.empty((K,) + tuple(src.shape[1:]), device=src.device, dtype=torch.float32)
+    check(lib().halo_gather_rows(ptr(src), ptr(rows), src.shape[0], K, src[0].numel(), ptr(dst), _stream()), 'halo_gather_rows')
+    return dst
+
+
+def scatter_rows(src, tr, M, want_bf16=False, nan_on_overflow=True):
+    """src [capacity, C] (or [capacity]) fp32 -> dst [M, C] (or [M]) with dst[i] = src[tr.slot[i]], zeros where a row has no slot: every
+    row is written.  ``nan_on_overflow``: all NaN when tr.count > tr.limit.  ``want_bf16``: -> (dst, dst as row-major bf16)."""
+    _f32c(src, 'src')
+    if src.shape[0] != tr.capacity or tr.slot.numel() != M:
+        raise ValueError('scatter_rows: src must hold tr.capacity rows and tr.slot M entries')
+    dst = torch.empty((M,) + tuple(src.shape[1:]), device=src.device, dtype=torch.float32)
+    dstb = torch.empty_like(dst, dtype=torch.bfloat16) if want_bf16 else None
+    check(lib().halo_scatter_rows(ptr(src), ptr(tr.slot), ptr(tr.count) if nan_on_overflow else None, tr.capacity, tr.limit, M, src[0].numel(),
+                                  ptr(dst),
+                                  ptr(dstb), _stream()), 'halo_scatter_rows')
+    return (dst, dstb) if want_bf16 else dst

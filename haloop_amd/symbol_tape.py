@@ -53,18 +53,34 @@ class SymbolTapeNoPad:
         return batch
 
 
-def get_batch(data_u16, offsets, block_size, objective='lm'):
+def get_batch(data_u16, offsets, block_size, objective='lm', *, seed=None, step=0, mlm_probability=0.15, mask_token=50254,
+              endoftext_token=50256, max_token=50257):
     """data_u16: flat uint16 tokens on the device (int16 storage, see load_u16); offsets [B] int64 start positions
     -> (x, y) int64 [B, block_size] as ha/attention_loop.py:98-125 builds them ("lm": next-token targets, last column 0;
-    "cond": only the final token of each row is a target)."""
-    if objective not in ('lm', 'cond'):
-        raise NotImplementedError(f'objective {objective!r}: only "lm" and "cond" are built')
+    "cond": only the final token of each row is a target; "denoise": x masked as haloop_amd.mlm.mask_tokens masks it with the
+    draws of (seed, step), y the labels -- gather and masking in one launch; the keywords after ``objective`` are its alone)."""
+    if objective not in ('lm', 'cond', 'denoise'):
+        raise NotImplementedError(f'objective {objective!r}: "lm", "cond" and "denoise" are built')
     if not data_u16.is_cuda or data_u16.element_size() != 2:
         raise ValueError('expected a 2-byte token tape on the HIP device')
+    if objective == 'denoise' and seed is None:
+        raise ValueError('objective "denoise" draws its masks from (seed, step): pass seed=')
     offsets = offsets.to(device=data_u16.device, dtype=torch.int64).contiguous()
     B = offsets.numel()
     x = torch.empty(B, block_size, dtype=torch.int64, device=data_u16.device)
     y = torch.empty_like(x)
+    if objective == 'denoise':
+        check(lib().halo_mlm_batch_u16(ptr(data_u16), data_u16.numel(), ptr(offsets), B, block_size, mlm_probability, mask_token,
+                                       endoftext_token, max_token, seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF, ptr(x), ptr(y), _stream()),
+              'halo_mlm_batch_u16')
+        return x, y
     check(lib().halo_lm_batch_u16(ptr(data_u16), data_u16.numel(), ptr(offsets), B, block_size, int(objective == 'cond'), ptr(x), ptr(y),
                                   _stream()), 'halo_lm_batch_u16')
     return x, y
+
+
+def target_capacity(B, T, p=0.15):
+    """Rows to give GPT.set_target_capacity for a "denoise" batch of B x T positions masked with probability p: the mean count of
+    targets plus eight standard deviations of the binomial, rounded up to a multiple of 256 (1536 at 64 x 128).  For "cond" pass B."""
+    M = B * T
+    return -(-math.ceil(p * M + 8.0 * math.sqrt(M * p * (1.0 - p))) // 256) * 256

@@ -792,6 +792,7 @@ int halo_decode_token(const float *logits, long ld, int N, int V, int64_t *token
  *                            next step's input row).  Same (logits, cfg, state) -> same tokens.
  * HALO_GPT_SAMPLE_STREAM is outside the dropout sites' ids (small integers) and the LoRA sites' (4096 + layer). */
 #define HALO_GPT_SAMPLE_STREAM 0x47505453u   /* 'GPTS' */
+#define HALO_MLM_STREAM 0x4D4C4D31u          /* 'MLM1': the token-masking draws of halo_mask_tokens / halo_mlm_batch_u16 */
 int halo_gpt_decode_linear_supported(int k, int layernorm);
 int halo_gpt_decode_linear(const float *x, long ldx, int rows, int k, const float *ln_weight, float eps, const void *w_image,
                            int n_out, float *out, long ldo, int flags, halo_stream_t stream);
@@ -901,6 +902,46 @@ int halo_tape_batch(const void *data, int elem_bytes, long n_tokens, int batch_s
                     int rows, long pad_value, void *out, halo_stream_t stream);
 int halo_lm_batch_u16(const uint16_t *data, long n_tokens, const int64_t *offsets, int B, int T, int objective_cond,
                       int64_t *x, int64_t *y, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The masked objectives of the GPT trainer (--objective denoise | cond, ha/attention_loop.py:110-120).
+ *
+ * Token masking.  replaces: mask_tokens (ha/mlm.py:11-40) and its call in get_batch (ha/attention_loop.py:113-114).  torch's
+ * generator cannot be reproduced on the device, so the draws come from the library's counter stream (the policy of the dropout
+ * masks).  For the flat position e = b*T + t holding ``token``:
+ *     (r0, r1, r2, r3) = philox4x32_10(ctr = (lo32(e), hi32(e), HALO_MLM_STREAM, step), key = (lo32(seed), hi32(seed)))
+ *     thr(p)   = min(int(float32(p) * 2^32), 0xFFFFFFFF)
+ *     selected = token != endoftext_token and r0 < thr(mlm_probability)
+ *     replaced = selected and r1 < thr(0.8)                         -> mask_token
+ *     random   = selected and not replaced and r2 < thr(0.5)        -> (uint64(r3) * max_token) >> 32
+ *     label    = token where selected, else 0; every other input keeps its token.
+ *   halo_mask_tokens    inputs [n] int64 masked in place, labels [n] int64 written.  0 <= p <= 1, 0 < max_token <= 2^32.
+ *   halo_mlm_batch_u16  the gather of halo_lm_batch_u16 (x[b, t] = data[offsets[b] + t], 0 past the tape) and the masking in one
+ *                       launch: x [B, T] the masked inputs, y [B, T] the labels.  A position past the tape draws like any other.
+ *
+ * Target rows.  replaces: the work F.cross_entropy(..., ignore_index=0) (ha/attention.py:230-231) and the lm_head spend on rows
+ * without a target: the caller runs ln_f, the lm_head and the loss on the compacted rows.  Every shape is set by ``capacity``, none
+ * by the count, and no launch uses atomics: the compact order is the ascending row order.
+ *   halo_target_rows    targets [M] int64 -> rows [capacity] int32 (the first ``limit`` <= capacity rows with targets[row] != ignore_index,
+ *                       ascending; -1 behind them), targets_c [capacity] int64 (their targets; ignore_index behind them), slot [M] int32
+ *                       (the inverse map: rows[slot[i]] == i; -1 for a row without a target or past the limit), count [1] int32 (all
+ *                       rows with a target, which may exceed limit).  capacity sizes the compact rows (a caller rounds it up to what its
+ *                       products need), limit is the number of targets it allowed for.
+ *   halo_gather_rows    dst [K, C] fp32: dst[k] = src[rows[k]], a zero row where rows[k] is outside [0, M).  16-byte accesses along C
+ *                       when C % 4 == 0.
+ *   halo_scatter_rows   dst [M, C] fp32: dst[i] = src[slot[i]] (src [capacity, C]), a zero row where slot[i] is outside [0, capacity):
+ *                       every row of dst is written.  dst_bf16 (optional): the same rows as row-major bf16.  count (optional, device):
+ *                       when *count > limit every element written is NaN (more targets than the caller allowed for). */
+int halo_mask_tokens(int64_t *inputs, int64_t *labels, long n, float mlm_probability, long mask_token, long endoftext_token,
+                     long max_token, uint64_t seed, uint32_t step, halo_stream_t stream);
+int halo_mlm_batch_u16(const uint16_t *data, long n_tokens, const int64_t *offsets, int B, int T, float mlm_probability,
+                       long mask_token, long endoftext_token, long max_token, uint64_t seed, uint32_t step, int64_t *x, int64_t *y,
+                       halo_stream_t stream);
+int halo_target_rows(const int64_t *targets, int M, long ignore_index, int capacity, int limit, int *rows, int64_t *targets_c,
+                     int *slot, int *count, halo_stream_t stream);
+int halo_gather_rows(const float *src, const int *rows, int M, int K, int C, float *dst, halo_stream_t stream);
+int halo_scatter_rows(const float *src, const int *slot, const int *count, int capacity, int limit, int M, int C, float *dst,
+                      void *dst_bf16, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimizer step on flat buffers.
