@@ -26,6 +26,18 @@ weight-gradient product).
 
 Not built (raises NotImplementedError): rotary (flash_attn) blocks -- the reference itself cannot construct them without
 flash_attn.
+
+The pre-LN block (ha/attention.py:147-180) is stated once per form, as a launch sequence:
+
+- ``block_forward``: inference on the 128-tile products, the residual stream updated in place; with ``kv`` the new keys / values go into
+  a cache and attention reads the cache.  GPT._trunk (scoring at few rows or in f32 / bf16x3, generation) and AudioEncoder.
+- ``block_forward_train`` / ``block_backward`` (form IMAGES): training in any mode and shape, operand images of the activations.
+- ``block_forward_train_rm`` / ``block_backward_rm``: training in `bf16` with row-major bf16 activations where ``rowmajor_train_ok``
+  holds -- on ``halo_gemm_rows`` (form ROWS: ``rows_block_forward``, which is also GPT._trunk_rows' scoring block) where ``rows_ok``
+  holds, else on the 128-tile products (form RM128).
+
+Each training forward records its form in the BlockSaved it returns, and the backward reads the record.  The ``HALO_GPT_*`` switches are
+read by the predicates right below the imports and nowhere else.
 """
 import math
 import os
@@ -39,6 +51,21 @@ from . import _lib, lora, ops
 from ._linear import (SMALL_M, DropSites, training_images, WeightImages, drop_rows, forward_images, grad_images, linear, linear_dw, linear_dx, rowmajor_ok,
                       ln_linear, use_split)
 from .rnn import DropoutStream
+
+
+# ---- the HALO_GPT_* switches of the block paths (README): read here and nowhere else, at call time; '0' is off ----------------------
+def _switch(name, default):
+    return os.environ.get(name, default) != '0'
+
+
+def rowmajor_on(): return _switch('HALO_GPT_ROWMAJOR', '1')             # row-major bf16 activations in `bf16` training and scoring
+def rows_on(): return _switch('HALO_GPT_ROWS', '1')                     # ... on the 256-row tiles of halo_gemm_rows
+def attn_b16_on(): return _switch('HALO_GPT_ATTN_B16', '1')             # q | k | v kept as bf16 rows at head_dim 64
+def dw_group_on(): return _switch('HALO_GPT_DW_GROUP', '1')             # a block's four weight gradients in one grouped launch
+# built, measured, off: the epilogue's arithmetic is not covered at one workgroup per CU (13.57 against 13.45 ms per step on one box,
+# DESIGN.md section 8); the bf16 gradient rows gain nothing (12.40 against 12.40 ms)
+def gelu_epilogue_on(): return _switch('HALO_GPT_GELU_EPILOGUE', '0')   # new_gelu in the c_fc product's epilogue
+def dln_b16_on(): return _switch('HALO_GPT_DLN_B16', '0')               # input gradients that only a LayerNorm backward reads as bf16 rows
 
 
 @dataclass
@@ -117,9 +144,20 @@ class Block(nn.Module):
         self.mlp = MLP(config)
 
 
-# What a block's training forward keeps for its backward: which of the two paths ran (``rowmajor``: block_forward_train_rm), that path's
-# tensors, and the adapter's record (u, dropout site) when an unmerged LoRA adapter sat on c_attn, else None.
-BlockSaved = namedtuple('BlockSaved', 'rowmajor core lora')
+# What a block's training forward keeps for its backward: which form ran, whether q | k | v were kept as bf16 rows (form ROWS only), that
+# form's tensors (ImagesCore, or RowMajorCore for ROWS and RM128, which keep the same things) and the adapter's record (u, dropout site)
+# when an unmerged LoRA adapter sat on c_attn, else None.
+IMAGES, RM128, ROWS = 'images', 'rm128', 'rows'
+BlockSaved = namedtuple('BlockSaved', 'form qkv_b16 core lora')
+ImagesCore = namedtuple('ImagesCore', 'x0 h1 qkv y y_img_t lse x1 h2 a g g_img_t s_att s_res s_mlp')
+RowMajorCore = namedtuple('RowMajorCore', 'x0 h1b qkv y yb lse x1 h2b a gb s_att')
+# The head's record (GPT._head_train): which of its forms ran -- ROWS (halo_gemm_rows_ce, bf16 logits), SPLIT_CE (halo_gemm_split_ce) or DENSE
+# -- the residual rows x it read, ln_f's rows, the logits and the rows' lse.  The whole step's holds the head's fields in line, in the
+# order the step's tuple always had (positional readers keep working), then ``rec`` -- None on the dense path, the compaction record
+# with a target capacity (x, xf, logits are then the compacted rows') -- and the head's form.
+SPLIT_CE, DENSE = 'split_ce', 'dense'
+HeadSaved = namedtuple('HeadSaved', 'x xf logits row_lse form')
+StepSaved = namedtuple('StepSaved', 'input_ids targets blocks x xf logits row_lse s_emb emb rec head_form')
 
 
 def adapter_dropout(blocks):
@@ -144,24 +182,30 @@ def train_sites(stream, p, training, blocks):
 
 
 # ---- one pre-LN GPT block (ha/attention.py:147-180), shared by GPT and haloop_amd.attention_audio.AudioEncoder ----------------
-def block_forward(images, blk, x, B, T, cfg):
-    """Inference: the residual stream x [B*T, C] is updated in place."""
+def block_forward(images, blk, x, B, T, cfg, kv=None):
+    """Inference: the residual stream x [B*T, C] is updated in place.  ``kv`` = (cache_k, cache_v, t0), one layer's fp32 cache
+    [B, nh, Tc, hs] that holds positions [0, t0): the T new keys / values are stored behind them and attention runs over t0 + T keys."""
     C, H = cfg.n_embd, cfg.n_head
     lo = lora.is_active(blk.attn.c_attn)
     qkv, h1 = ln_linear(images, x, blk.ln_1.weight, blk.ln_1.bias, blk.attn.c_attn.weight, bias=blk.attn.c_attn.bias, want_normed=lo)
     if lo:
         lora.lora_forward(blk.attn.c_attn, h1, qkv)
-    y, _, _ = ops.attention_fwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal)
+    if kv is not None:
+        cache_k, cache_v, t0 = kv
+        ops.kv_cache_store(qkv[:, C:], C, cache_k, cache_v, B, T, H, C // H, t0)
+        y = ops.attention_cached_fwd(qkv, cache_k, cache_v, T, t0 + T, causal=cfg.causal)
+    else:
+        y, _, _ = ops.attention_fwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal)
     linear(images, y, blk.attn.c_proj.weight, bias=blk.attn.c_proj.bias, out=x, accumulate=True)           # x += c_proj(y)
-    if rowmajor_ok(B * T, 4 * C, C) and C % 32 == 0:
-        # gelu(c_fc(ln_2(x))) leaves its GEMM as row-major bf16 (hi, lo) and the c_proj GEMM stages it from there: neither the fp32
-        # activations nor an operand image of them are written
-        h, _ = ln_linear(images, x, blk.ln_2.weight, blk.ln_2.bias, blk.mlp.c_fc.weight, bias=blk.mlp.c_fc.bias, gelu=True, out_rowmajor=True)
+    # where it can, gelu(c_fc(ln_2(x))) leaves its GEMM as row-major bf16 (hi, lo) and the c_proj GEMM stages it from there: neither the
+    # fp32 activations nor an operand image of them are written
+    rm = rowmajor_ok(B * T, 4 * C, C) and C % 32 == 0
+    h, _ = ln_linear(images, x, blk.ln_2.weight, blk.ln_2.bias, blk.mlp.c_fc.weight, bias=blk.mlp.c_fc.bias, gelu=True, out_rowmajor=rm)
+    if rm:
         linear(images, None, blk.mlp.c_proj.weight, bias=blk.mlp.c_proj.bias, out=x, accumulate=True, a_rowmajor=h, shape=(B * T, 4 * C))
-        return x
-    h, _ = ln_linear(images, x, blk.ln_2.weight, blk.ln_2.bias, blk.mlp.c_fc.weight, bias=blk.mlp.c_fc.bias, gelu=True)
-    linear(images, h, blk.mlp.c_proj.weight, bias=blk.mlp.c_proj.bias, out=x, accumulate=True)              # x += mlp(h)
-    return x
+    else:
+        linear(images, h, blk.mlp.c_proj.weight, bias=blk.mlp.c_proj.bias, out=x, accumulate=True)
+    return x                                                                                              # x += mlp(x)
 
 
 def prefetch_block_weights(images, blocks, M):
@@ -196,7 +240,7 @@ def block_forward_train(images, blk, x0, B, T, cfg, sites):
     g = ops.gelu_fwd(a) if g_img is None else None
     x = linear(images, g, blk.mlp.c_proj.weight, bias=blk.mlp.c_proj.bias, residual=x1, drop=s_mlp[0],
                stream_id=s_mlp[1], a_image=g_img, shape=a.shape)
-    return x, BlockSaved(False, (x0, h1, qkv, y, y_img_t, lse, x1, h2, a, g, g_img_t, s_att, s_res, s_mlp), lo_saved)
+    return x, BlockSaved(IMAGES, False, ImagesCore(x0, h1, qkv, y, y_img_t, lse, x1, h2, a, g, g_img_t, s_att, s_res, s_mlp), lo_saved)
 
 
 def block_backward(images, blk, saved, dx, B, T, cfg, put, need_dx=True):
@@ -206,46 +250,47 @@ def block_backward(images, blk, saved, dx, B, T, cfg, put, need_dx=True):
     C, H = cfg.n_embd, cfg.n_head
     M = B * T
     img = images
-    x0, h1, qkv, y, y_img_t, lse, x1, h2, a, g, g_img_t, s_att, s_res, s_mlp = saved.core
+    k = saved.core                                           # ImagesCore
     want = lambda p: p is not None and p.requires_grad
     # x = x1 + drop(c_proj(gelu(c_fc(ln_2(x1)))))
-    dm = drop_rows(dx, s_mlp)
+    dm = drop_rows(dx, k.s_mlp)
     dm_img, dm_img_t = grad_images(dm, 4 * C, want_dw=want(blk.mlp.c_proj.weight))
-    if want(blk.mlp.c_proj.weight): put(blk.mlp.c_proj.weight, linear_dw(dm, g, dy_image_t=dm_img_t, x_image_t=g_img_t, shapes=(dm.shape, a.shape)))
+    if want(blk.mlp.c_proj.weight): put(blk.mlp.c_proj.weight, linear_dw(dm, k.g, dy_image_t=dm_img_t, x_image_t=k.g_img_t, shapes=(dm.shape, k.a.shape)))
     if want(blk.mlp.c_proj.bias): put(blk.mlp.c_proj.bias, ops.colsum(dm))
     dg = linear_dx(img, dm, blk.mlp.c_proj.weight, dy_image=dm_img)
     if blk.mlp.c_fc.bias is None and use_split(M, C, 4 * C) and use_split(4 * C, C, M):
         # da = dg * gelu'(a) is only ever a GEMM operand: write its two images, not the fp32 matrix
-        da_img, da_img_t = ops.image_pair(dg, ops.PAIR_GELU_BWD, a, cols_image=want(blk.mlp.c_fc.weight))
-        if want(blk.mlp.c_fc.weight): put(blk.mlp.c_fc.weight, linear_dw(None, h2, dy_image_t=da_img_t, shapes=(a.shape, h2.shape)))
-        d_ln2 = linear_dx(img, None, blk.mlp.c_fc.weight, dy_image=da_img, shape=a.shape)
+        da_img, da_img_t = ops.image_pair(dg, ops.PAIR_GELU_BWD, k.a, cols_image=want(blk.mlp.c_fc.weight))
+        if want(blk.mlp.c_fc.weight): put(blk.mlp.c_fc.weight, linear_dw(None, k.h2, dy_image_t=da_img_t, shapes=(k.a.shape, k.h2.shape)))
+        d_ln2 = linear_dx(img, None, blk.mlp.c_fc.weight, dy_image=da_img, shape=k.a.shape)
         del da_img, da_img_t
     else:
-        da = ops.gelu_bwd(dg, a)
-        if want(blk.mlp.c_fc.weight): put(blk.mlp.c_fc.weight, linear_dw(da, h2))
+        da = ops.gelu_bwd(dg, k.a)
+        if want(blk.mlp.c_fc.weight): put(blk.mlp.c_fc.weight, linear_dw(da, k.h2))
         if want(blk.mlp.c_fc.bias): put(blk.mlp.c_fc.bias, ops.colsum(da))
         d_ln2 = linear_dx(img, da, blk.mlp.c_fc.weight)
-    dx1, dw, db = ops.layernorm_bwd(d_ln2, x1, blk.ln_2.weight, dx, blk.ln_2.bias is not None)
+    dx1, dw, db = ops.layernorm_bwd(d_ln2, k.x1, blk.ln_2.weight, dx, blk.ln_2.bias is not None)
     put(blk.ln_2.weight, dw); put(blk.ln_2.bias, db)
     # x1 = x0 + drop(c_proj(attention(c_attn(ln_1(x0)))))
-    dr = drop_rows(dx1, s_res)
+    dr = drop_rows(dx1, k.s_res)
     dr_img, dr_img_t = grad_images(dr, C, want_dw=want(blk.attn.c_proj.weight))
-    if want(blk.attn.c_proj.weight): put(blk.attn.c_proj.weight, linear_dw(dr, y, dy_image_t=dr_img_t, x_image_t=y_img_t))
+    if want(blk.attn.c_proj.weight): put(blk.attn.c_proj.weight, linear_dw(dr, k.y, dy_image_t=dr_img_t, x_image_t=k.y_img_t))
     if want(blk.attn.c_proj.bias): put(blk.attn.c_proj.bias, ops.colsum(dr))
     dy = linear_dx(img, dr, blk.attn.c_proj.weight, dy_image=dr_img)
+    qkv = k.qkv
     dqkv = torch.empty_like(qkv)
-    ops.attention_bwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], y, dy, lse, dqkv[:, :C], dqkv[:, C:2 * C], dqkv[:, 2 * C:],
-                      B, H, C // H, T, T, causal=cfg.causal, drop=s_att[0], stream_id=s_att[1])
+    ops.attention_bwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], k.y, dy, k.lse, dqkv[:, :C], dqkv[:, C:2 * C], dqkv[:, 2 * C:],
+                      B, H, C // H, T, T, causal=cfg.causal, drop=k.s_att[0], stream_id=k.s_att[1])
     dq_img, dq_img_t = grad_images(dqkv, C, want_dx=need_dx, want_dw=want(blk.attn.c_attn.weight))
-    if want(blk.attn.c_attn.weight): put(blk.attn.c_attn.weight, linear_dw(dqkv, h1, dy_image_t=dq_img_t))
+    if want(blk.attn.c_attn.weight): put(blk.attn.c_attn.weight, linear_dw(dqkv, k.h1, dy_image_t=dq_img_t))
     if want(blk.attn.c_attn.bias): put(blk.attn.c_attn.bias, ops.colsum(dqkv))
     d_ln1 = linear_dx(img, dqkv, blk.attn.c_attn.weight, dy_image=dq_img) if need_dx else None
     if saved.lora is not None:                               # the adapter: its gradients, and its share of d ln_1(x0)
         u, s_lo = saved.lora
-        lora.lora_backward(blk.attn.c_attn, h1, u, dqkv, d_ln1, put, s_lo)
+        lora.lora_backward(blk.attn.c_attn, k.h1, u, dqkv, d_ln1, put, s_lo)
     if not need_dx:
         return None
-    dx0, dw, db = ops.layernorm_bwd(d_ln1, x0, blk.ln_1.weight, dx1, blk.ln_1.bias is not None)
+    dx0, dw, db = ops.layernorm_bwd(d_ln1, k.x0, blk.ln_1.weight, dx1, blk.ln_1.bias is not None)
     put(blk.ln_1.weight, dw); put(blk.ln_1.bias, db)
     return dx0
 
@@ -259,7 +304,7 @@ def block_backward(images, blk, saved, dx, B, T, cfg, put, need_dx=True):
 # gelu(a)'s gradient and of the normalised rows.  Same bf16 operand values, same fp32 accumulation.
 def rowmajor_train_ok(cfg, blocks, M, training):
     """bf16 arithmetic, no biases, no output dropout, enough rows that the products without split-K fill the chip."""
-    if os.environ.get('HALO_GPT_ROWMAJOR', '1') == '0' or _lib.get_math_mode() != 'bf16':
+    if not rowmajor_on() or _lib.get_math_mode() != 'bf16':
         return False
     C = cfg.n_embd
     if cfg.bias or (training and cfg.dropout > 0.0) or M % 32 != 0 or C % 32 != 0 or not rowmajor_ok(M, 4 * C, C) or not rowmajor_ok(M, C, C):
@@ -271,60 +316,62 @@ def rowmajor_train_ok(cfg, blocks, M, training):
                and (not lora.is_active(blk.attn.c_attn) or lora.fast_ok(blk.attn.c_attn, M)) for blk in blocks)
 
 
-def lora_rows_forward(images, lin, h1b, qkv, site=(ops.NO_DROPOUT, 0)):
-    """qkv [M, 3C] (bf16 or fp32 rows) += scaling * ((mask * h1b) A^T) B^T on the halo_lora_* kernels -> u [M, 16] bf16 for the backward."""
-    A16, _, B16, _ = lora.packed(images, lin)
-    u = ops.lora_down(h1b, A16, 1.0, site[0], site[1])
-    ops.lora_up_(qkv, u, B16, lin.scaling)
-    return u
-
-
 def rows_ok(M, C):
     """The 256-row-tile products (halo_gemm_rows: single-pass bf16 arithmetic) take every Linear of a block of width C at M rows."""
-    return os.environ.get('HALO_GPT_ROWS', '1') != '0' and ops.gemm_rows_supported(M, C, C) and C % 32 == 0
+    return rows_on() and ops.gemm_rows_supported(M, C, C) and C % 32 == 0
+
+
+def rows_block_forward(images, blk, x, B, T, cfg, train=False, s_att=(ops.NO_DROPOUT, 0), s_lo=(ops.NO_DROPOUT, 0)):
+    """The block with every activation-by-weight product on halo_gemm_rows (round 5: 256-row tiles cut to whole rounds of the CUs, A staged
+    from the row-major bf16 rows the producing launch left); c_fc's result and the MLP's hidden activations stay bf16 (what the reference's
+    autocast path holds there, ha/attention_loop.py:164) -- no fp32 [M, 4C] round trip between c_fc and new_gelu.
+    Scoring (``train`` False): the fp32 residual stream x is updated in place by the products' residual epilogues -> (x, None).
+    Training: x is left as it is, the attention launch also writes the rows' lse and takes the dropout site ``s_att``, the adapter its
+    site ``s_lo`` -> (the block's output, BlockSaved)."""
+    C, H, M = cfg.n_embd, cfg.n_head, B * T
+    w = lambda lin: images.split((lin.weight,))
+    h1b = ops.layernorm_bf16(x, blk.ln_1.weight, blk.ln_1.bias)
+    # q | k | v stay bf16 between the c_attn product and the attention launches (forward and backward stage the rows as they are, two
+    # tiles in flight: csrc/attn_b16.hip); the attention output is kept as bf16 only
+    b16 = C // H == 64 and attn_b16_on()
+    qkv = ops.gemm_rows(h1b, w(blk.attn.c_attn), M, 3 * C, C, out_bf16=b16)
+    u = lora.lora_rows_forward(images, blk.attn.c_attn, h1b, qkv, s_lo) if lora.is_active(blk.attn.c_attn) else None
+    q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+    if b16:
+        y, lse, yb = ops.attention_fwd_b16(q, k, v, B, H, C // H, T, T, causal=cfg.causal, want_lse=train)
+    else:
+        y, lse, yb = ops.attention_fwd_bf16(q, k, v, B, H, C // H, T, T, causal=cfg.causal, drop=s_att[0], stream_id=s_att[1])
+    x1 = ops.gemm_rows(yb, w(blk.attn.c_proj), M, C, C, out=None if train else x, residual=x)               # x + c_proj(y)
+    h2b = ops.layernorm_bf16(x1, blk.ln_2.weight, blk.ln_2.bias)
+    if gelu_epilogue_on():                                                    # new_gelu in the c_fc product's epilogue
+        gb = ops.gemm_rows_gelu(h2b, w(blk.mlp.c_fc), M, 4 * C, C, keep_pre=train)
+        gb, a = gb if train else (gb, None)                                   # (training keeps the pre-activation for gelu's backward)
+    else:
+        a = ops.gemm_rows(h2b, w(blk.mlp.c_fc), M, 4 * C, C, out_bf16=True)
+        gb = ops.gelu_b16(a)
+    x2 = ops.gemm_rows(gb, w(blk.mlp.c_proj), M, C, 4 * C, out=None if train else x1, residual=x1)          # x1 + mlp(x1)
+    if not train:
+        return x2, None
+    return x2, BlockSaved(ROWS, b16, RowMajorCore(x, h1b, qkv, y, yb, lse, x1, h2b, a, gb, s_att), None if u is None else (u, s_lo))
 
 
 def block_forward_train_rm(images, blk, x0, B, T, cfg, sites):
+    """Training forward with row-major bf16 activations: rows_block_forward where rows_ok holds, else the 128-tile products below."""
     C, H, M = cfg.n_embd, cfg.n_head, B * T
     w = lambda lin: images.split((lin.weight,))
     rows = rows_ok(M, C)
-    s_att, s_res, s_mlp = sites.next(), sites.next(), sites.next()
+    s_att, _, _ = sites.next(), sites.next(), sites.next()         # (the two output dropouts keep their ids: this path runs without them)
     lo = lora.is_active(blk.attn.c_attn)
     s_lo = sites.next_lora(blk.attn.c_attn.lora_dropout_p if lo else 0.0)
-    adapt = lambda h1b, qkv: (lora_rows_forward(images, blk.attn.c_attn, h1b, qkv, s_lo), s_lo) if lo else None
     if rows:
         _lib.lend_scratch(128 << 20, device=x0.device)      # K-slice slabs of the lm_head's input gradient and of the weight gradients' tails
-        # round 5: every activation-by-weight product on halo_gemm_rows (256-row tiles cut to whole rounds of the CUs, A staged from the
-        # row-major bf16 rows the producing launch left); c_fc's result and the MLP's hidden activations stay bf16 (what the reference's
-        # autocast path holds there, ha/attention_loop.py:164) -- the fp32 [M, 4C] round trip between c_fc and new_gelu is gone
-        h1b = ops.layernorm_bf16(x0, blk.ln_1.weight, blk.ln_1.bias)
-        if C // H == 64 and os.environ.get('HALO_GPT_ATTN_B16', '1') != '0':
-            # q | k | v stay bf16 between the c_attn product and the attention launches (forward and backward stage the rows as they are, two
-            # tiles in flight: csrc/attn_b16.hip); the attention output is kept as bf16 only
-            qkv = ops.gemm_rows(h1b, w(blk.attn.c_attn), M, 3 * C, C, out_bf16=True)
-            lo_saved = adapt(h1b, qkv)
-            y, lse, yb = ops.attention_fwd_b16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal, want_lse=True)
-        else:
-            qkv = ops.gemm_rows(h1b, w(blk.attn.c_attn), M, 3 * C, C)
-            lo_saved = adapt(h1b, qkv)
-            y, lse, yb = ops.attention_fwd_bf16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal,
-                                                drop=s_att[0], stream_id=s_att[1])
-        x1 = ops.gemm_rows(yb, w(blk.attn.c_proj), M, C, C, residual=x0)
-        h2b = ops.layernorm_bf16(x1, blk.ln_2.weight, blk.ln_2.bias)
-        if os.environ.get('HALO_GPT_GELU_EPILOGUE', '0') != '0':         # new_gelu in the c_fc product's epilogue (built, measured, off: at one
-            # workgroup per CU nothing covers the epilogue's arithmetic -- 13.57 against 13.45 ms per step on one box, DESIGN.md section 8)
-            gb, a = ops.gemm_rows_gelu(h2b, w(blk.mlp.c_fc), M, 4 * C, C, keep_pre=True)
-        else:
-            a = ops.gemm_rows(h2b, w(blk.mlp.c_fc), M, 4 * C, C, out_bf16=True)
-            gb = ops.gelu_b16(a)
-        x = ops.gemm_rows(gb, w(blk.mlp.c_proj), M, C, 4 * C, residual=x1)
-        return x, BlockSaved(True, (x0, h1b, qkv, y, yb, lse, x1, h2b, a, gb, s_att), lo_saved)
+        return rows_block_forward(images, blk, x0, B, T, cfg, True, s_att, s_lo)
     # (the normalised rows twice from one launch: the tiled image for the forward product, which stages an image 10-15 % faster than
     # rows from cold caches, and the row-major rows for the weight-gradient product)
     h1b, h1i = ops.layernorm_bf16(x0, blk.ln_1.weight, blk.ln_1.bias, want_image=True)
     qkv = ops.gemm_split(h1i, w(blk.attn.c_attn), M, 3 * C, C)
     del h1i
-    lo_saved = adapt(h1b, qkv)
+    lo_saved = (lora.lora_rows_forward(images, blk.attn.c_attn, h1b, qkv, s_lo), s_lo) if lo else None
     y, lse, yb = ops.attention_fwd_bf16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal,
                                         drop=s_att[0], stream_id=s_att[1])
     x1 = ops.gemm_split_io((yb, None), w(blk.attn.c_proj), M, C, C, residual=x0)
@@ -333,22 +380,21 @@ def block_forward_train_rm(images, blk, x0, B, T, cfg, sites):
     del h2i
     gb = ops.gelu_bf16(a)
     x = ops.gemm_split_io((gb, None), w(blk.mlp.c_proj), M, C, 4 * C, residual=x1)
-    return x, BlockSaved(True, (x0, h1b, qkv, y, yb, lse, x1, h2b, a, gb, s_att), lo_saved)
+    return x, BlockSaved(RM128, False, RowMajorCore(x0, h1b, qkv, y, yb, lse, x1, h2b, a, gb, s_att), lo_saved)
 
 
 def block_backward_rm(images, blk, saved, dx, dxb, B, T, cfg, put, need_dx=True):
     """dx / dxb: the gradient w.r.t. the block's output as fp32 and as row-major bf16 -> the same pair for its input ((None, None) with
     ``need_dx`` False: nothing trainable below the block's c_attn).  Weight-gradient products only for parameters that require one."""
     C, H, M = cfg.n_embd, cfg.n_head, B * T
-    wt = lambda lin: images.split_t((lin.weight,))
-    x0, h1b, qkv, y, yb, lse, x1, h2b, a, gb, s_att = saved.core
-    rows = a.dtype == torch.bfloat16                     # the forward ran on halo_gemm_rows
+    k = saved.core                                       # RowMajorCore
+    rows = saved.form == ROWS                            # the forward ran on halo_gemm_rows
     # the four weight gradients contract over the same M token rows: collected here, ONE grouped launch at the end of the block
     # (whole-K tiles, no K-slices or reduce launches); HALO_GPT_DW_GROUP=0: one launch each, as round 4
-    grouped = os.environ.get('HALO_GPT_DW_GROUP', '1') != '0' and M % 32 == 0
+    grouped = dw_group_on() and M % 32 == 0
     # the two input gradients that only a LayerNorm backward reads leave their products as bf16 rows (that launch adds the fp32 residual
     # gradient to them in fp32)
-    b16_ln = rows and C % 4 == 0 and C <= 2048 and os.environ.get('HALO_GPT_DLN_B16', '0') != '0'        # (measured: no gain, 12.40 against 12.40 ms; off)
+    b16_ln = rows and C % 4 == 0 and C <= 2048 and dln_b16_on()
     todo = []
 
     def dweight(p, dy_b, x_b):
@@ -358,46 +404,40 @@ def block_backward_rm(images, blk, saved, dx, dxb, B, T, cfg, put, need_dx=True)
             todo.append((p, dy_b, x_b))
         else:
             put(p, ops.gemm_tn(dy_b, x_b))
+
+    def dinput(dy_b, lin, N, K, out_bf16=False):
+        """dy_b [M, K] (bf16 rows) times lin's weight [K, N]: the input gradient [M, N], on the tiles the forward ran on; ``out_bf16``
+        (form ROWS only): as bf16 rows."""
+        if rows:
+            return ops.gemm_rows(dy_b, images.split_t((lin.weight,)), M, N, K, out_bf16=out_bf16)
+        return ops.gemm_split_io((dy_b, None), images.split_t((lin.weight,)), M, N, K)
     # x = x1 + c_proj(gelu(c_fc(ln_2(x1))))
-    dweight(blk.mlp.c_proj.weight, dxb, gb)
-    if rows:
-        dab = ops.gelu_bwd_b16(ops.gemm_rows(dxb, wt(blk.mlp.c_proj), M, 4 * C, C, out_bf16=True), a)    # d a = (dx W) gelu'(a), bf16 throughout
-    else:
-        dab = ops.gelu_bwd_bf16(ops.gemm_split_io((dxb, None), wt(blk.mlp.c_proj), M, 4 * C, C), a)
-    dweight(blk.mlp.c_fc.weight, dab, h2b)
-    d_ln2 = ops.gemm_rows(dab, wt(blk.mlp.c_fc), M, C, 4 * C, out_bf16=b16_ln) if rows else ops.gemm_split_io((dab, None), wt(blk.mlp.c_fc), M, C, 4 * C)
-    dx1, dw, db, dx1b = ops.layernorm_bwd(d_ln2, x1, blk.ln_2.weight, dx, blk.ln_2.bias is not None, want_bf16=True)
+    dweight(blk.mlp.c_proj.weight, dxb, k.gb)
+    # d a = (dx W) gelu'(a); form ROWS: bf16 throughout
+    dab = (ops.gelu_bwd_b16 if rows else ops.gelu_bwd_bf16)(dinput(dxb, blk.mlp.c_proj, 4 * C, C, out_bf16=True), k.a)
+    dweight(blk.mlp.c_fc.weight, dab, k.h2b)
+    d_ln2 = dinput(dab, blk.mlp.c_fc, C, 4 * C, out_bf16=b16_ln)
+    dx1, dw, db, dx1b = ops.layernorm_bwd(d_ln2, k.x1, blk.ln_2.weight, dx, blk.ln_2.bias is not None, want_bf16=True)
     put(blk.ln_2.weight, dw); put(blk.ln_2.bias, db)
     # x1 = x0 + c_proj(attention(c_attn(ln_1(x0))))
-    dweight(blk.attn.c_proj.weight, dx1b, yb)
+    dweight(blk.attn.c_proj.weight, dx1b, k.yb)
+    qkv = k.qkv
     dqkvb = torch.empty(M, 3 * C, device=dx.device, dtype=torch.bfloat16)
-    if qkv.dtype == torch.bfloat16:                      # the forward kept q | k | v as bf16 rows: the output gradient arrives as bf16 rows too
-        dyb = ops.gemm_rows(dx1b, wt(blk.attn.c_proj), M, C, C, out_bf16=True)
-        ops.attention_bwd_b16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], yb, dyb, lse, dqkvb[:, :C], dqkvb[:, C:2 * C], dqkvb[:, 2 * C:],
+    dy = dinput(dx1b, blk.attn.c_proj, C, C, out_bf16=saved.qkv_b16)
+    if saved.qkv_b16:                                    # the forward kept q | k | v as bf16 rows: the output gradient arrives as bf16 rows too
+        ops.attention_bwd_b16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], k.yb, dy, k.lse, dqkvb[:, :C], dqkvb[:, C:2 * C], dqkvb[:, 2 * C:],
                               B, H, C // H, T, T, causal=cfg.causal)
     else:
-        dy = ops.gemm_rows(dx1b, wt(blk.attn.c_proj), M, C, C) if rows else ops.gemm_split_io((dx1b, None), wt(blk.attn.c_proj), M, C, C)
-        ops.attention_bwd_bf16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], y, dy, lse, dqkvb[:, :C], dqkvb[:, C:2 * C], dqkvb[:, 2 * C:],
-                               B, H, C // H, T, T, causal=cfg.causal, drop=s_att[0], stream_id=s_att[1])
-    dweight(blk.attn.c_attn.weight, dqkvb, h1b)
-    d_ln1 = None
-    if need_dx:
-        d_ln1 = ops.gemm_rows(dqkvb, wt(blk.attn.c_attn), M, C, 3 * C, out_bf16=b16_ln) if rows else ops.gemm_split_io((dqkvb, None), wt(blk.attn.c_attn), M, C, 3 * C)
-    if saved.lora is not None:
-        # the adapter (csrc/lora.hip): du = s dqkv B, dB = s dqkv^T u, dA = du^T (m * h1), d_ln1 += m * (du A)
-        lin = blk.attn.c_attn
+        ops.attention_bwd_bf16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], k.y, dy, k.lse, dqkvb[:, :C], dqkvb[:, C:2 * C], dqkvb[:, 2 * C:],
+                               B, H, C // H, T, T, causal=cfg.causal, drop=k.s_att[0], stream_id=k.s_att[1])
+    dweight(blk.attn.c_attn.weight, dqkvb, k.h1b)
+    d_ln1 = dinput(dqkvb, blk.attn.c_attn, C, 3 * C, out_bf16=b16_ln) if need_dx else None
+    if saved.lora is not None:                           # the adapter: its gradients, and its share of d ln_1(x0)
         u, s_lo = saved.lora
-        _, At16, _, Bt16 = lora.packed(images, lin)
-        du = ops.lora_down(dqkvb, Bt16, lin.scaling)
-        if lin.lora_B.weight.requires_grad:
-            put(lin.lora_B.weight, ops.lora_tn(u, dqkvb, lin.r, lin.scaling, transpose_out=True))
-        if lin.lora_A.weight.requires_grad:
-            put(lin.lora_A.weight, ops.lora_tn(du, h1b, lin.r, 1.0, drop=s_lo[0], stream_id=s_lo[1]))
-        if need_dx:
-            ops.lora_up_(d_ln1, du, At16, 1.0, s_lo[0], s_lo[1])
+        lora.lora_rows_backward(images, blk.attn.c_attn, k.h1b, u, dqkvb, d_ln1, put, s_lo)
     dx0 = dx0b = None
     if need_dx:
-        dx0, dw, db, dx0b = ops.layernorm_bwd(d_ln1, x0, blk.ln_1.weight, dx1, blk.ln_1.bias is not None, want_bf16=True)
+        dx0, dw, db, dx0b = ops.layernorm_bwd(d_ln1, k.x0, blk.ln_1.weight, dx1, blk.ln_1.bias is not None, want_bf16=True)
         put(blk.ln_1.weight, dw); put(blk.ln_1.bias, db)
     if todo:
         for (p, _, _), g in zip(todo, ops.gemm_tn_group([(d, x_) for _, d, x_ in todo])):
@@ -505,63 +545,22 @@ class GPT(nn.Module):
             if t0:
                 present[..., :t0, :] = past
         for i, blk in enumerate(tr.h):
-            lo = lora.is_active(blk.attn.c_attn)
-            qkv, h1 = ln_linear(self._images, x, blk.ln_1.weight, blk.ln_1.bias, blk.attn.c_attn.weight, bias=blk.attn.c_attn.bias, want_normed=lo)
-            if lo:
-                lora.lora_forward(blk.attn.c_attn, h1, qkv)
-            if present is not None:
-                ops.kv_cache_store(qkv[:, C:], C, present[i, 0], present[i, 1], B, T, H, C // H, t0)
-                y = ops.attention_cached_fwd(qkv, present[i, 0], present[i, 1], T, t0 + T, causal=cfg.causal)
-            else:
-                y, _, _ = ops.attention_fwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal)
-            self._linear(y, blk.attn.c_proj, out=x, accumulate=True)                     # x += c_proj(y)
-            if rowmajor_ok(B * T, 4 * C, C) and C % 32 == 0:          # as block_forward: the MLP's activations as row-major bf16
-                h, _ = ln_linear(self._images, x, blk.ln_2.weight, blk.ln_2.bias, blk.mlp.c_fc.weight, bias=blk.mlp.c_fc.bias, gelu=True,
-                                 out_rowmajor=True)
-                linear(self._images, None, blk.mlp.c_proj.weight, bias=blk.mlp.c_proj.bias, out=x, accumulate=True, a_rowmajor=h,
-                       shape=(B * T, 4 * C))
-                continue
-            h, _ = ln_linear(self._images, x, blk.ln_2.weight, blk.ln_2.bias, blk.mlp.c_fc.weight, bias=blk.mlp.c_fc.bias, gelu=True)
-            self._linear(h, blk.mlp.c_proj, out=x, accumulate=True)                      # x += mlp(h)
+            block_forward(self._images, blk, x, B, T, cfg, None if present is None else (present[i, 0], present[i, 1], t0))
         if want_residual:
             return x, present
         return ops.layernorm_fwd(x, tr.ln_f.weight, tr.ln_f.bias), present
 
     @torch.no_grad()
-    def _trunk_rows(self, input_ids, want_residual=False):
-        """Embedding + blocks + ln_f in single-pass bf16 arithmetic on halo_gemm_rows (scoring without a KV cache): the residual stream
-        fp32, updated in place by the products' residual epilogues; every Linear input row-major bf16.  -> ln_f(x) as row-major bf16, or
-        with ``want_residual`` the fp32 residual stream before ln_f."""
+    def _trunk_rows(self, input_ids):
+        """Embedding + blocks in single-pass bf16 arithmetic on halo_gemm_rows (scoring without a KV cache): the residual stream fp32,
+        updated in place by the products' residual epilogues; every Linear input row-major bf16.  -> the residual stream before ln_f."""
         cfg = self.config
         B, T = input_ids.shape
         assert T <= cfg.block_size, f'Cannot forward sequence of length {T}, block size is only {cfg.block_size}'
-        C, H, M = cfg.n_embd, cfg.n_head, B * T
-        tr = self.transformer
-        w = lambda lin: self._images.split((lin.weight,))
         x, _ = self._embed(input_ids, 0)
-        for blk in tr.h:
-            h1b = ops.layernorm_bf16(x, blk.ln_1.weight, blk.ln_1.bias)
-            if C // H == 64 and os.environ.get('HALO_GPT_ATTN_B16', '1') != '0':
-                # q | k | v stay bf16 between the c_attn product and the attention launch, which stages them as they are
-                qkv = ops.gemm_rows(h1b, w(blk.attn.c_attn), M, 3 * C, C, out_bf16=True)
-                if lora.is_active(blk.attn.c_attn):
-                    lora_rows_forward(self._images, blk.attn.c_attn, h1b, qkv)
-                _, _, yb = ops.attention_fwd_b16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal)
-            else:
-                qkv = ops.gemm_rows(h1b, w(blk.attn.c_attn), M, 3 * C, C)
-                if lora.is_active(blk.attn.c_attn):
-                    lora_rows_forward(self._images, blk.attn.c_attn, h1b, qkv)
-                _, _, yb = ops.attention_fwd_bf16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal)
-            ops.gemm_rows(yb, w(blk.attn.c_proj), M, C, C, out=x, residual=x)                   # x += c_proj(y)
-            h2b = ops.layernorm_bf16(x, blk.ln_2.weight, blk.ln_2.bias)
-            if os.environ.get('HALO_GPT_GELU_EPILOGUE', '0') != '0':
-                gb = ops.gemm_rows_gelu(h2b, w(blk.mlp.c_fc), M, 4 * C, C)
-            else:
-                gb = ops.gelu_b16(ops.gemm_rows(h2b, w(blk.mlp.c_fc), M, 4 * C, C, out_bf16=True))
-            ops.gemm_rows(gb, w(blk.mlp.c_proj), M, C, 4 * C, out=x, residual=x)                # x += mlp(x)
-        if want_residual:
-            return x
-        return ops.layernorm_bf16(x, tr.ln_f.weight, tr.ln_f.bias)
+        for blk in self.transformer.h:
+            rows_block_forward(self._images, blk, x, B, T, cfg)
+        return x
 
     def forward_all(self, input_ids, target_ids, past=None, reduction='mean'):
         if not input_ids.is_cuda:
@@ -577,22 +576,36 @@ class GPT(nn.Module):
         if self.training and (self.config.dropout > 0 or adapter_dropout(self.transformer.h) > 0):
             raise NotImplementedError('training-mode dropout is built into the autograd path only: enable grad, or call .eval()')
         targets = target_ids.reshape(-1)
-        C = self.config.n_embd
-        rows_trunk = past is None and B * T > SMALL_M and V % 8 == 0 and rows_ok(B * T, C) and rowmajor_train_ok(self.config, self.transformer.h, B * T, False)
+        C, M = self.config.n_embd, B * T
+        rows = past is None and M > SMALL_M and V % 8 == 0 and rows_ok(M, C) and rowmajor_train_ok(self.config, self.transformer.h, M, False)
+        x = self._trunk_rows(input_ids) if rows else self._trunk(input_ids, past, want_residual=True)[0]
         if past is None and self._target_capacity is not None:
-            return self._reduce(self._score_compact(input_ids, targets, rows_trunk), targets, reduction)
-        if rows_trunk:
-            loss, _, _ = ops.gemm_rows_ce(self._trunk_rows(input_ids), self._images.split((self.lm_head.weight,)), B * T, V, C, targets, ignore_index=0)
-            return self._reduce(loss, targets, reduction)
-        x, _ = self._trunk(input_ids, past)
-        return self._reduce(self._score_head(x, targets), targets, reduction)
+            # the masked objectives: ln_f, the lm_head and the loss on the K compacted target rows (_compact_rows), the head's product path
+            # chosen from K by the predicates the dense path applies to M; the per-token losses go back to their rows
+            K, limit = self._compact_rows(M)
+            rec = ops.target_rows(targets, K, ignore_index=0, limit=limit)
+            x_c = ops.gather_rows(x, rec.rows)
+            loss = ops.scatter_rows(self._score_head(x_c, rec.targets, rows and K > SMALL_M and rows_ok(K, C)), rec, M)
+        else:
+            loss = self._score_head(x, targets, rows)
+        return self._reduce(loss, targets, reduction)
 
-    def _score_head(self, xf, targets):
-        """Per-row NLL of lm_head(xf) for ln_f's fp32 rows xf [R, C] (no grad)."""
-        R, C = xf.shape
+    def _split_head(self, R):
+        """The lm_head product of R rows runs on the split GEMM with the cross-entropy statistics in its epilogue."""
+        return use_split(R, self.config.vocab_size, self.config.n_embd) and R > SMALL_M
+
+    def _score_head(self, x, targets, rows):
+        """Per-row NLL of lm_head(ln_f(x)) for the residual rows x [R, C] (no grad); the [R, V] logits are never written where the loss
+        comes out of a GEMM's epilogue.  ``rows``: ln_f's rows as row-major bf16 into halo_gemm_rows_ce."""
+        tr = self.transformer
+        R, C = x.shape
         V = self.config.vocab_size
-        if use_split(R, V, C) and R > SMALL_M:
-            # lm_head + cross-entropy in the GEMM's epilogue: the [rows, V] logits are never written (SURVEY.md 8f-1)
+        if rows:
+            loss, _, _ = ops.gemm_rows_ce(ops.layernorm_bf16(x, tr.ln_f.weight, tr.ln_f.bias), self._images.split((self.lm_head.weight,)), R, V, C,
+                                          targets, ignore_index=0)
+            return loss
+        xf = ops.layernorm_fwd(x, tr.ln_f.weight, tr.ln_f.bias)
+        if self._split_head(R):
             loss, _, _ = ops.gemm_split_ce(ops.split_image(xf), self._images.split((self.lm_head.weight,)), R, V, C, targets, ignore_index=0)
             return loss
         # otherwise in row chunks so the logits stay bounded (206 MB per 1024 rows at V=50304)
@@ -603,24 +616,6 @@ class GPT(nn.Module):
             logits = self._linear(xf[r0:r1], self.lm_head)
             loss[r0:r1] = ops.cross_entropy_fwd(logits, targets[r0:r1], ignore_index=0)
         return loss
-
-    @torch.no_grad()
-    def _score_compact(self, input_ids, targets, rows_trunk):
-        """forward_all's scoring path with a target capacity (K compact rows, _compact_rows): the trunk as the dense path runs it, then ln_f, the lm_head and the loss on
-        the K compacted rows, the head's product path chosen from K by the predicates the dense path applies to M.  -> per-token NLL [M]."""
-        tr = self.transformer
-        M = targets.numel()
-        K, limit = self._compact_rows(M)
-        C, V = self.config.n_embd, self.config.vocab_size
-        x = self._trunk_rows(input_ids, want_residual=True) if rows_trunk else self._trunk(input_ids, None, want_residual=True)[0]
-        rec = ops.target_rows(targets, K, ignore_index=0, limit=limit)
-        x_c = ops.gather_rows(x, rec.rows)
-        if rows_trunk and K > SMALL_M and rows_ok(K, C):
-            loss_c, _, _ = ops.gemm_rows_ce(ops.layernorm_bf16(x_c, tr.ln_f.weight, tr.ln_f.bias), self._images.split((self.lm_head.weight,)), K, V, C,
-                                            rec.targets, ignore_index=0)
-        else:
-            loss_c = self._score_head(ops.layernorm_fwd(x_c, tr.ln_f.weight, tr.ln_f.bias), rec.targets)
-        return ops.scatter_rows(loss_c, rec, M)
 
     @staticmethod
     def _reduce(loss, targets, reduction):
@@ -638,7 +633,6 @@ class GPT(nn.Module):
         cfg = self.config
         B, T = input_ids.shape
         assert T <= cfg.block_size, f'Cannot forward sequence of length {T}, block size is only {cfg.block_size}'
-        C, H = cfg.n_embd, cfg.n_head
         tr = self.transformer
         # dropout sites in forward order (ha/attention.py:224,90,127,141): embeddings, then per block the attention
         # probabilities, the c_proj output and the MLP output; output dropouts are GEMM epilogues
@@ -652,21 +646,20 @@ class GPT(nn.Module):
         for blk in tr.h:
             x, sv = fwd(self._images, blk, x, B, T, cfg, sites)
             blocks.append(sv)
-        targets = target_ids.reshape(-1)
-        rm = fwd is block_forward_train_rm
+        targets, rec = target_ids.reshape(-1), None
         if self._target_capacity is not None:
             # the masked objectives: ln_f, the lm_head and the loss on the compacted target rows; the per-token losses go back to their rows
             K, limit = self._compact_rows(B * T)
             rec = ops.target_rows(targets, K, ignore_index=0, limit=limit)
-            x_c = ops.gather_rows(x, rec.rows)
-            loss_c, xf, logits, row_lse = self._head_train(x_c, rec.targets, rm)
-            return ops.scatter_rows(loss_c, rec, B * T), (input_ids, rec.targets, blocks, x_c, xf, logits, row_lse, s_emb, emb_saved, rec)
-        loss, xf, logits, row_lse = self._head_train(x, targets, rm)
-        return loss, (input_ids, targets, blocks, x, xf, logits, row_lse, s_emb, emb_saved)
+            x, targets = ops.gather_rows(x, rec.rows), rec.targets
+        loss, head = self._head_train(x, targets, fwd is block_forward_train_rm)
+        if rec is not None:
+            loss = ops.scatter_rows(loss, rec, B * T)
+        return loss, StepSaved(input_ids, targets, blocks, head.x, head.xf, head.logits, head.row_lse, s_emb, emb_saved, rec, head.form)
 
     def _head_train(self, x, targets, rm):
-        """ln_f, the lm_head and the per-row cross-entropy on the residual rows x [R, C] -> (loss [R], ln_f's rows, logits, row lse), the
-        last three for _head_backward.  ``rm``: the blocks ran block_forward_train_rm."""
+        """ln_f, the lm_head and the per-row cross-entropy on the residual rows x [R, C] -> (loss [R], HeadSaved for _head_backward).
+        ``rm``: the blocks ran block_forward_train_rm."""
         cfg, tr = self.config, self.transformer
         R, C = x.shape
         V = cfg.vocab_size
@@ -678,23 +671,24 @@ class GPT(nn.Module):
             xf = ops.layernorm_bf16(x, tr.ln_f.weight, tr.ln_f.bias)
             loss, row_lse, logits = ops.gemm_rows_ce(xf, self._images.split((self.lm_head.weight,)), R, V, C, targets,
                                                      ignore_index=0, want_logits=True, want_lse=True)
-            return loss, xf, logits, row_lse
+            return loss, HeadSaved(x, xf, logits, row_lse, ROWS)
         xf = ops.layernorm_fwd(x, tr.ln_f.weight, tr.ln_f.bias)
-        if use_split(R, V, C) and R > SMALL_M:          # statistics in the GEMM epilogue; the logits are kept for the backward
+        if self._split_head(R):                         # statistics in the GEMM epilogue; the logits are kept for the backward
             loss, row_lse, logits = ops.gemm_split_ce(ops.split_image(xf), self._images.split((self.lm_head.weight,)), R, V, C,
                                                       targets, ignore_index=0, want_logits=True, want_lse=True)
-        else:
-            logits = self._linear(xf, self.lm_head)
-            loss, row_lse = ops.cross_entropy_fwd_lse(logits, targets, ignore_index=0)
-        return loss, xf, logits, row_lse
+            return loss, HeadSaved(x, xf, logits, row_lse, SPLIT_CE)
+        logits = self._linear(xf, self.lm_head)
+        loss, row_lse = ops.cross_entropy_fwd_lse(logits, targets, ignore_index=0)
+        return loss, HeadSaved(x, xf, logits, row_lse, DENSE)
 
-    def _head_backward(self, x_last, xf, logits, row_lse, targets, grad_rows, head, want_bf16, put):
-        """The backward of _head_train on its R rows: -> (d x_last [R, C], [the same as row-major bf16] with ``want_bf16``, the lm_head's
-        weight gradient [V, C] or None with ``head`` False); ln_f's gradients go to put."""
+    def _head_backward(self, saved, targets, grad_rows, head, want_bf16, put):
+        """The backward of _head_train (``saved``: its HeadSaved) on its R rows: -> (d x [R, C], [the same as row-major bf16] with
+        ``want_bf16``, the lm_head's weight gradient [V, C] or None with ``head`` False); ln_f's gradients go to put."""
         tr, img = self.transformer, self._images
+        xf, logits, row_lse = saved.xf, saved.logits, saved.row_lse
         M, V = logits.shape
         C = self.config.n_embd
-        if logits.dtype == torch.bfloat16:
+        if saved.form == ROWS:
             # the stored bf16 logits become d loss / d logits IN PLACE: the row-major bf16 operand of both gradient products
             dl = ops.cross_entropy_bwd_bf16_(logits, targets, row_lse, grad_rows, ignore_index=0)
             dw_head = ops.gemm_tn_group([(dl, xf)])[0] if head else None                     # [V, C]; the tied wte gradient lands here too
@@ -710,16 +704,15 @@ class GPT(nn.Module):
             dlogits = ops.cross_entropy_bwd_(logits, targets, row_lse, grad_rows, ignore_index=0)
             dw_head = linear_dw(dlogits, xf) if head else None
             dxf = linear_dx(img, dlogits, self.lm_head.weight)
-        dx, dw, db, *dxb = ops.layernorm_bwd(dxf, x_last, tr.ln_f.weight, None, tr.ln_f.bias is not None, want_bf16=want_bf16)
+        dx, dw, db, *dxb = ops.layernorm_bwd(dxf, saved.x, tr.ln_f.weight, None, tr.ln_f.bias is not None, want_bf16=want_bf16)
         put(tr.ln_f.weight, dw); put(tr.ln_f.bias, db)
         return dx, dxb, dw_head
 
     @torch.no_grad()
     def _backward_train(self, saved, grad_per_tok):
         cfg = self.config
-        input_ids, targets, blocks, x_last, xf, logits, row_lse, s_emb, emb_saved, *compact = saved
+        input_ids, blocks, rec = saved.input_ids, saved.blocks, saved.rec
         B, T = input_ids.shape
-        C, H = cfg.n_embd, cfg.n_head
         tr = self.transformer
         img = self._images
         grads = {}
@@ -735,14 +728,14 @@ class GPT(nn.Module):
         below = [emb]
         for blk in tr.h:
             below.append(below[-1] or live(blk))
-        rm = len(blocks) > 0 and blocks[0].rowmajor             # block_forward_train_rm's records
-        if compact:
+        rm = len(blocks) > 0 and blocks[0].form != IMAGES       # block_forward_train_rm's records
+        head_saved = HeadSaved(saved.x, saved.xf, saved.logits, saved.row_lse, saved.head_form)
+        if rec is not None:
             # the head ran on the compacted target rows: their share of grad_per_tok in, their d x back to its rows (zero elsewhere)
-            rec = compact[0]
-            dx_c, _, dw_head = self._head_backward(x_last, xf, logits, row_lse, targets, ops.gather_rows(grad_per_tok, rec.rows), head, False, put)
+            dx_c, _, dw_head = self._head_backward(head_saved, saved.targets, ops.gather_rows(grad_per_tok, rec.rows), head, False, put)
             dx, *dxb = ops.scatter_rows(dx_c, rec, B * T, want_bf16=True) if rm else (ops.scatter_rows(dx_c, rec, B * T),)
         else:
-            dx, dxb, dw_head = self._head_backward(x_last, xf, logits, row_lse, targets, grad_per_tok, head, rm, put)
+            dx, dxb, dw_head = self._head_backward(head_saved, saved.targets, grad_per_tok, head, rm, put)
         for i in reversed(range(len(blocks))):
             blk, sv = tr.h[i], blocks[i]
             need_dx = below[i] or live(blk.ln_1)
@@ -758,9 +751,9 @@ class GPT(nn.Module):
             return grads
         # (a frozen lm_head / wte or wpe takes no scatter: dw_head is None then, and the embedding kernels skip a NULL target)
         dwpe = torch.zeros_like(tr.wpe.weight) if tr.wpe.weight.requires_grad else None
-        dx = drop_rows(dx, s_emb)
-        if emb_saved is not None:                                                # StableEmbedding: through the two LayerNorms first
-            et, ep = emb_saved
+        dx = drop_rows(dx, saved.s_emb)
+        if saved.emb is not None:                                                # StableEmbedding: through the two LayerNorms first
+            et, ep = saved.emb
             dpos = torch.empty_like(ep)
             ops.embed_bwd(input_ids, dx, None, dpos, 0)                          # dpos[t] = sum_b dx[b, t]
             dx, dw, db = ops.layernorm_bwd(dx, et, tr.wte.norm.weight, None, True)

@@ -9,8 +9,8 @@ the base Linear has one), so a checkpoint written by ``hala --lora`` loads after
 ``Linear.train(False)`` with ``merge_weights`` folds ``scaling * B A`` into the base weight (the adapter Linears' own biases are NOT
 folded: the reference's quirk, kept), ``train(True)`` takes it out again.  The GPT blocks do not call the module: they read ``.weight``
 and, while the adapter is unmerged, add the low-rank term at every c_attn site (haloop_amd/attention.py: ``lora_forward`` /
-``lora_backward`` here on the general path, the ``halo_lora_*`` kernels of csrc/lora.hip on the row-major bf16 path for r <= 16; a larger
-rank runs on the general path).  Dropout of the adapter's input is a Philox site of the model's dropout stream (id 4096 + layer) in
+``lora_backward`` here on the general path, ``lora_rows_forward`` / ``lora_rows_backward`` -- the ``halo_lora_*`` kernels of csrc/lora.hip
+-- on the row-major bf16 path for r <= 16; a larger rank runs on the general path).  Dropout of the adapter's input is a Philox site of the model's dropout stream (id 4096 + layer) in
 training forwards (``forward_all`` with grad enabled).  Without grad, in train() mode: ``GPT.forward_all`` and the audio encoder raise when
 an unmerged adapter has lora_dropout > 0, exactly as they do for config.dropout > 0 (scoring wants eval()); ``GPT.forward`` /
 ``forward_context`` / ``generate`` and ``Linear.forward`` apply the adapter unmerged and draw no dropout of any kind, as they never did
@@ -132,6 +132,28 @@ def lora_backward(lin, h, u, dqkv, d_h, put, site=(ops.NO_DROPOUT, 0)):
         if drop.p > 0:
             t = ops.dropout_fwd(t, drop, sid)
         ops.scale_add_(d_h, t, 1.0, 1.0)
+
+
+# ---- the row-major bf16 path (rank <= 16, fast_ok): the halo_lora_* kernels of csrc/lora.hip on bf16 rows -----------------------------
+def lora_rows_forward(images, lin, h, qkv, site=(ops.NO_DROPOUT, 0)):
+    """qkv [M, out] (bf16 or fp32 rows) += scaling * ((mask * h) A^T) B^T for the bf16 rows h [M, in]; -> u [M, 16] bf16 for the backward."""
+    A16, _, B16, _ = packed(images, lin)
+    u = ops.lora_down(h, A16, 1.0, site[0], site[1])
+    ops.lora_up_(qkv, u, B16, lin.scaling)
+    return u
+
+
+def lora_rows_backward(images, lin, h, u, dqkv, d_h, put, site=(ops.NO_DROPOUT, 0)):
+    """Adapter gradients to put(): du = s dqkv B, dB = s dqkv^T u, dA = du^T (mask * h); d_h [M, in] (or None when nobody reads it)
+    += mask * (du A).  h, u, dqkv: bf16 rows."""
+    _, At16, _, Bt16 = packed(images, lin)
+    du = ops.lora_down(dqkv, Bt16, lin.scaling)
+    if lin.lora_B.weight.requires_grad:
+        put(lin.lora_B.weight, ops.lora_tn(u, dqkv, lin.r, lin.scaling, transpose_out=True))
+    if lin.lora_A.weight.requires_grad:
+        put(lin.lora_A.weight, ops.lora_tn(du, h, lin.r, 1.0, drop=site[0], stream_id=site[1]))
+    if d_h is not None:
+        ops.lora_up_(d_h, du, At16, 1.0, site[0], site[1])
 
 
 # ---- the reference's module surgery -----------------------------------------------------------------------------------------------

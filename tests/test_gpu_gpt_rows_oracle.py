@@ -190,7 +190,7 @@ def gpu_pass(case, train, env=None):
 
             def keep_dtype(ids, tg):
                 loss, saved = fwd(ids, tg)
-                out['logits'] = saved[5].dtype
+                out['logits'] = saved.logits.dtype
                 return loss, saved
             model._forward_train = keep_dtype
             try:

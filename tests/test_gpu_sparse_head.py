@@ -302,7 +302,7 @@ def rows_case(lib):
 
     def keep(i, t):
         loss, saved = fwd(i, t)
-        saved_logits.append((saved[5].dtype, tuple(saved[5].shape), len(saved)))
+        saved_logits.append((saved.logits.dtype, tuple(saved.logits.shape), saved.rec is not None))
         return loss, saved
     L_.halo_gemm_rows_ce, model._forward_train = ce, keep
     res = {}
@@ -360,8 +360,8 @@ def test_row_tile_head_runs_on_the_capacity(rows_case):
     c, res = ROWS, rows_case['res']
     # training then scoring, one halo_gemm_rows_ce each: dense at M rows, compact at the capacity
     assert res['dense']['ce_rows'] == [rows_case['M']] * 2 and res['compact']['ce_rows'] == [c['capacity']] * 2, (res['dense']['ce_rows'], res['compact']['ce_rows'])
-    assert res['dense']['logits'] == (torch.bfloat16, (rows_case['M'], c['V']), 9)                   # the dense record keeps its layout
-    assert res['compact']['logits'] == (torch.bfloat16, (c['capacity'], c['V']), 10)
+    assert res['dense']['logits'] == (torch.bfloat16, (rows_case['M'], c['V']), False)               # the dense record carries no compaction
+    assert res['compact']['logits'] == (torch.bfloat16, (c['capacity'], c['V']), True)
 
 
 @pytest.mark.parametrize('who', ['dense', 'compact'])

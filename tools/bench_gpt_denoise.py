@@ -107,17 +107,17 @@ put = lambda p, g: None
 
 def head_dense():
     with torch.no_grad(), attention.training_images():
-        loss, xf, logits, lse = model._head_train(x, tg, True)
-        return model._head_backward(x, xf, logits, lse, tg, grad, True, True, put)
+        loss, saved = model._head_train(x, tg, True)
+        return model._head_backward(saved, tg, grad, True, True, put)
 
 
 def head_compact():
     with torch.no_grad(), attention.training_images():
         rec = ops.target_rows(tg, K)
         x_c = ops.gather_rows(x, rec.rows)
-        loss_c, xf, logits, lse = model._head_train(x_c, rec.targets, True)
+        loss_c, saved = model._head_train(x_c, rec.targets, True)
         ops.scatter_rows(loss_c, rec, M)
-        dx_c, _, dw = model._head_backward(x_c, xf, logits, lse, rec.targets, ops.gather_rows(grad, rec.rows), True, False, put)
+        dx_c, _, dw = model._head_backward(saved, rec.targets, ops.gather_rows(grad, rec.rows), True, False, put)
         return ops.scatter_rows(dx_c, rec, M, want_bf16=True)
 
 
