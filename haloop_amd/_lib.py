@@ -148,6 +148,7 @@ SIGNATURES = {
     'halo_kv_cache_store_f32': (_i, [_vp, _l, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'halo_rope_table': (_i, [_vp, _vp, _i, _i, _f, _vp]),
     'halo_rope_interleaved': (_i, [_vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
+    'halo_rope_rows': (_i, [_vp, _i, _l, _l, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     'halo_kv_cache_store': (_i, [_vp, _l, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'halo_attention_decode': (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'halo_attention_decode_step': (_i, [_vp, _vp, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -24,8 +24,17 @@ LoRA (haloop_amd/lora.py, ``hala --lora``): a ``c_attn`` that is a lora.Linear w
 c_attn site below, and the backward computes a weight gradient only for parameters that require one (a frozen base pays for no
 weight-gradient product).
 
-Not built (raises NotImplementedError): rotary (flash_attn) blocks -- the reference itself cannot construct them without
-flash_attn.
+Rotary blocks (``config.rotary_emb_dim`` equal to the head dimension: the reference's flash_attn ``MHA(rotary_emb_interleaved=True)``,
+ha/attention.py:155-167, which its tests/test_flash_compat.py pins to ``rotate_interleaved`` on q and k, softmax scale 1/sqrt(head_dim),
+``out_proj``): the attention module carries flash_attn's parameter names (``attn.Wqkv``, ``attn.out_proj``; ``attn.c_attn`` / ``attn.c_proj``
+read the same two Linears, so the block forms below are stated once), the rotation is ONE ``ops.rope_rows_`` launch on the packed q | k | v
+rows between the c_attn product and the attention launch of every form, and one inverse launch on dq | dk | dv in the backward (fp32
+rows: ``HALO_ROPE_ROWS`` chooses between that launch and the scalar operator, one launch per tensor; DESIGN.md 3.3i has the default).  flash MHA
+has no dropout behind ``out_proj``: a rotary block draws the c_proj site (the stream ids of every other site keep their numbering) and does
+not apply it.  They are what haloop_amd.attention_audio's rotary encoders are built from.
+
+Not built (raises NotImplementedError): a ``rotary_emb_dim`` other than the head dimension (no arch rotates part of a head), a rotary block
+with a KV cache, ``GPT`` with rotary blocks (no arch builds one), LoRA on a rotary block.
 
 The pre-LN block (ha/attention.py:147-180) is stated once per form, as a launch sequence:
 
@@ -36,8 +45,8 @@ The pre-LN block (ha/attention.py:147-180) is stated once per form, as a launch 
   holds -- on ``halo_gemm_rows`` (form ROWS: ``rows_block_forward``, which is also GPT._trunk_rows' scoring block) where ``rows_ok``
   holds, else on the 128-tile products (form RM128).
 
-Each training forward records its form in the BlockSaved it returns, and the backward reads the record.  The ``HALO_GPT_*`` switches are
-read by the predicates right below the imports and nowhere else.
+Each training forward records its form in the BlockSaved it returns, and the backward reads the record.  The ``HALO_GPT_*`` switches and
+``HALO_ROPE_ROWS`` are read by the predicates right below the imports and nowhere else.
 """
 import math
 import os
@@ -66,6 +75,9 @@ def dw_group_on(): return _switch('HALO_GPT_DW_GROUP', '1')             # a bloc
 # DESIGN.md section 8); the bf16 gradient rows gain nothing (12.40 against 12.40 ms)
 def gelu_epilogue_on(): return _switch('HALO_GPT_GELU_EPILOGUE', '0')   # new_gelu in the c_fc product's epilogue
 def dln_b16_on(): return _switch('HALO_GPT_DLN_B16', '0')               # input gradients that only a LayerNorm backward reads as bf16 rows
+# rotary blocks: q and k of fp32 rows rotated by ONE halo_rope_rows launch; '0': by the scalar operator, one launch each (bf16 rows have
+# the one kernel).  Built, not yet measured against the two scalar launches on an MI355X: off until it is
+def rope_rows_on(): return _switch('HALO_ROPE_ROWS', '0')
 
 
 @dataclass
@@ -85,6 +97,28 @@ class GPTConfig:
 
     def state_dict(self):
         return asdict(self)
+
+
+@dataclass
+class AudioEncoderConfig(GPTConfig):
+    """ha/init.py:42-48."""
+    block_size: int = 2048
+    vocab_size: int = 128
+    causal: bool = False
+    d_input: int = 80
+    rotary_emb_dim: int = 64
+
+
+@dataclass
+class StridingAudioEncoderConfig(GPTConfig):
+    """ha/init.py:51-59."""
+    block_size: int = 2048
+    vocab_size: int = 16384
+    causal: bool = False
+    d_input: int = 80
+    rotary_emb_dim: int = 64
+    d_conv: int = 256
+    conv_strides: tuple = (2, 2, 2)
 
 
 def new_gelu(x):
@@ -125,6 +159,45 @@ class MonitoredSelfAttention(nn.Module):
         self.n_head, self.n_embd, self.dropout, self.causal = config.n_head, config.n_embd, config.dropout, config.causal
 
 
+def check_rotary(config):
+    """What a rotary config must satisfy to be built: the whole head is rotated."""
+    if config.rotary_emb_dim and config.rotary_emb_dim != config.n_embd // config.n_head:
+        raise NotImplementedError(f'rotary_emb_dim {config.rotary_emb_dim} is not the head dimension {config.n_embd // config.n_head}: partial '
+                                  'rotations are not built (no arch of ha/init.py uses one; flash_attn asserts rotary_dim <= headdim)')
+    if config.rotary_emb_dim % 8:
+        raise NotImplementedError('rotary blocks need a head dimension that is a multiple of 8 (halo_rope_rows)')
+
+
+class RotaryEmbedding(nn.Module):
+    """The ``rotary_emb`` submodule of flash_attn's MHA as far as a state dict sees it: the non-persistent buffer ``inv_freq``.  Nothing
+    here computes with it (the angles are ops.RopeTable's, rotate_interleaved's arithmetic); checkpoints written when the buffer was
+    persistent still load with strict=True."""
+
+    def __init__(self, dim, base=10000.0):
+        super().__init__()
+        self.register_buffer('inv_freq', 1.0 / (base ** (torch.arange(0, dim, 2, dtype=torch.float32) / dim)), persistent=False)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args):
+        state_dict.pop(prefix + 'inv_freq', None)
+        super()._load_from_state_dict(state_dict, prefix, *args)
+
+
+class RotarySelfAttention(nn.Module):
+    """flash_attn.modules.mha.MHA(rotary_emb_dim=head_dim, rotary_emb_interleaved=True) as ha/attention.py:155-167 builds it: its parameter
+    names, and the two Linears under the names the block forms read."""
+
+    def __init__(self, config):
+        super().__init__()
+        assert config.n_embd % config.n_head == 0
+        self.Wqkv = nn.Linear(config.n_embd, 3 * config.n_embd, bias=config.bias)
+        self.out_proj = nn.Linear(config.n_embd, config.n_embd, bias=config.bias)
+        self.rotary_emb = RotaryEmbedding(config.rotary_emb_dim)
+        self.n_head, self.n_embd, self.dropout, self.causal = config.n_head, config.n_embd, config.dropout, config.causal
+
+    c_attn = property(lambda self: self.Wqkv)
+    c_proj = property(lambda self: self.out_proj)
+
+
 class MLP(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -136,10 +209,10 @@ class MLP(nn.Module):
 class Block(nn.Module):
     def __init__(self, config):
         super().__init__()
-        if config.rotary_emb_dim:
-            raise NotImplementedError('rotary blocks need flash_attn in the reference and are not built here')
+        check_rotary(config)
+        self.rotary = bool(config.rotary_emb_dim)
         self.ln_1 = LayerNorm(config.n_embd, bias=config.bias)
-        self.attn = MonitoredSelfAttention(config)
+        self.attn = RotarySelfAttention(config) if self.rotary else MonitoredSelfAttention(config)
         self.ln_2 = LayerNorm(config.n_embd, bias=config.bias)
         self.mlp = MLP(config)
 
@@ -181,15 +254,53 @@ def train_sites(stream, p, training, blocks):
     return DropSites(drop, state)
 
 
-# ---- one pre-LN GPT block (ha/attention.py:147-180), shared by GPT and haloop_amd.attention_audio.AudioEncoder ----------------
+# ---- the rotation of a rotary block's q and k -----------------------------------------------------------------------------------
+_ROPE_TABLES = {}
+
+
+def _rope_table(T, head_dim, device):
+    """The cos / sin tables per (head_dim, device), grown on demand (as transformer._rope_table)."""
+    hit = _ROPE_TABLES.get((head_dim, str(device)))
+    if hit is None or hit.T < T:
+        hit = ops.RopeTable(max(T, 256), head_dim, device)
+        _ROPE_TABLES[(head_dim, str(device))] = hit
+    return hit
+
+
+def rope_qk_(blk, rows, T, cfg, inverse=False):
+    """A rotary block: rotate_interleaved on the q and k column blocks of the packed rows [B*T, 3C] (fp32 or bf16), in place, row r at
+    position r % T; ``inverse``: the backward, on dq | dk | dv.  Any other block: nothing."""
+    if not blk.rotary:
+        return
+    if lora.is_active(blk.attn.c_attn):
+        raise NotImplementedError('LoRA adapters on a rotary block are not built')
+    C, H = cfg.n_embd, cfg.n_head
+    table = _rope_table(T, C // H, rows.device)
+    if rows.dtype == torch.float32 and not rope_rows_on():
+        ops.rope_(rows[:, :C], T, H, C // H, table, inverse=inverse)
+        ops.rope_(rows[:, C:2 * C], T, H, C // H, table, inverse=inverse)
+    else:
+        ops.rope_rows_(rows, T, H, C // H, table, inverse=inverse)
+
+
+def res_site(blk, site):
+    """The c_proj dropout site as the block applies it: flash MHA has no dropout behind out_proj, so a rotary block draws the site (the
+    stream ids keep their numbering) and runs without it."""
+    return (ops.NO_DROPOUT, site[1]) if blk.rotary else site
+
+
+# ---- one pre-LN GPT block (ha/attention.py:147-180), shared by GPT and haloop_amd.attention_audio's encoders -------------------
 def block_forward(images, blk, x, B, T, cfg, kv=None):
     """Inference: the residual stream x [B*T, C] is updated in place.  ``kv`` = (cache_k, cache_v, t0), one layer's fp32 cache
     [B, nh, Tc, hs] that holds positions [0, t0): the T new keys / values are stored behind them and attention runs over t0 + T keys."""
     C, H = cfg.n_embd, cfg.n_head
+    if blk.rotary and kv is not None:
+        raise NotImplementedError('a rotary block with a KV cache is not built (the cached keys would have to be kept rotated)')
     lo = lora.is_active(blk.attn.c_attn)
     qkv, h1 = ln_linear(images, x, blk.ln_1.weight, blk.ln_1.bias, blk.attn.c_attn.weight, bias=blk.attn.c_attn.bias, want_normed=lo)
     if lo:
         lora.lora_forward(blk.attn.c_attn, h1, qkv)
+    rope_qk_(blk, qkv, T, cfg)
     if kv is not None:
         cache_k, cache_v, t0 = kv
         ops.kv_cache_store(qkv[:, C:], C, cache_k, cache_v, B, T, H, C // H, t0)
@@ -224,10 +335,11 @@ def block_forward_train(images, blk, x0, B, T, cfg, sites):
     probabilities, c_proj output, MLP output; the output dropouts are GEMM epilogues."""
     C, H = cfg.n_embd, cfg.n_head
     qkv, h1 = ln_linear(images, x0, blk.ln_1.weight, blk.ln_1.bias, blk.attn.c_attn.weight, bias=blk.attn.c_attn.bias, want_normed=True)
-    s_att, s_res, s_mlp = sites.next(), sites.next(), sites.next()
+    s_att, s_res, s_mlp = sites.next(), res_site(blk, sites.next()), sites.next()
     lo = lora.is_active(blk.attn.c_attn)
     s_lo = sites.next_lora(blk.attn.c_attn.lora_dropout_p if lo else 0.0)
     lo_saved = (lora.lora_forward(blk.attn.c_attn, h1, qkv, s_lo), s_lo) if lo else None
+    rope_qk_(blk, qkv, T, cfg)                               # (the saved qkv is the rotated one: what the attention backward needs)
     y, lse, _ = ops.attention_fwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal, want_lse=True,
                                   drop=s_att[0], stream_id=s_att[1])
     # y and gelu(a) each feed one Linear now and its weight gradient later: both operand images come out of one read, and
@@ -281,6 +393,7 @@ def block_backward(images, blk, saved, dx, B, T, cfg, put, need_dx=True):
     dqkv = torch.empty_like(qkv)
     ops.attention_bwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], k.y, dy, k.lse, dqkv[:, :C], dqkv[:, C:2 * C], dqkv[:, 2 * C:],
                       B, H, C // H, T, T, causal=cfg.causal, drop=k.s_att[0], stream_id=k.s_att[1])
+    rope_qk_(blk, dqkv, T, cfg, inverse=True)
     dq_img, dq_img_t = grad_images(dqkv, C, want_dx=need_dx, want_dw=want(blk.attn.c_attn.weight))
     if want(blk.attn.c_attn.weight): put(blk.attn.c_attn.weight, linear_dw(dqkv, k.h1, dy_image_t=dq_img_t))
     if want(blk.attn.c_attn.bias): put(blk.attn.c_attn.bias, ops.colsum(dqkv))
@@ -336,6 +449,7 @@ def rows_block_forward(images, blk, x, B, T, cfg, train=False, s_att=(ops.NO_DRO
     b16 = C // H == 64 and attn_b16_on()
     qkv = ops.gemm_rows(h1b, w(blk.attn.c_attn), M, 3 * C, C, out_bf16=b16)
     u = lora.lora_rows_forward(images, blk.attn.c_attn, h1b, qkv, s_lo) if lora.is_active(blk.attn.c_attn) else None
+    rope_qk_(blk, qkv, T, cfg)
     q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
     if b16:
         y, lse, yb = ops.attention_fwd_b16(q, k, v, B, H, C // H, T, T, causal=cfg.causal, want_lse=train)
@@ -372,6 +486,7 @@ def block_forward_train_rm(images, blk, x0, B, T, cfg, sites):
     qkv = ops.gemm_split(h1i, w(blk.attn.c_attn), M, 3 * C, C)
     del h1i
     lo_saved = (lora.lora_rows_forward(images, blk.attn.c_attn, h1b, qkv, s_lo), s_lo) if lo else None
+    rope_qk_(blk, qkv, T, cfg)
     y, lse, yb = ops.attention_fwd_bf16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, H, C // H, T, T, causal=cfg.causal,
                                         drop=s_att[0], stream_id=s_att[1])
     x1 = ops.gemm_split_io((yb, None), w(blk.attn.c_proj), M, C, C, residual=x0)
@@ -430,6 +545,7 @@ def block_backward_rm(images, blk, saved, dx, dxb, B, T, cfg, put, need_dx=True)
     else:
         ops.attention_bwd_bf16(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], k.y, dy, k.lse, dqkvb[:, :C], dqkvb[:, C:2 * C], dqkvb[:, 2 * C:],
                                B, H, C // H, T, T, causal=cfg.causal, drop=k.s_att[0], stream_id=k.s_att[1])
+    rope_qk_(blk, dqkvb, T, cfg, inverse=True)
     dweight(blk.attn.c_attn.weight, dqkvb, k.h1b)
     d_ln1 = dinput(dqkvb, blk.attn.c_attn, C, 3 * C, out_bf16=b16_ln) if need_dx else None
     if saved.lora is not None:                           # the adapter: its gradients, and its share of d ln_1(x0)
@@ -468,6 +584,8 @@ class GPT(nn.Module):
     def __init__(self, config):
         super().__init__()
         self.config = config
+        if config.rotary_emb_dim:
+            raise NotImplementedError('a GPT of rotary blocks is not built (no arch of ha/init.py builds one): positions come from wpe')
         self.transformer = nn.ModuleDict(dict(
             wte=(StableEmbedding if config.stable_embedding else nn.Embedding)(config.vocab_size, config.n_embd),
             wpe=(StableEmbedding if config.stable_embedding else nn.Embedding)(config.block_size, config.n_embd),

@@ -16,7 +16,7 @@ an unmerged adapter has lora_dropout > 0, exactly as they do for config.dropout 
 ``forward_context`` / ``generate`` and ``Linear.forward`` apply the adapter unmerged and draw no dropout of any kind, as they never did
 for config.dropout.
 
-Not built: ``MergedLinear`` (the reference never instantiates it), adapters on other Linears.
+Not built: ``MergedLinear`` (the reference never instantiates it), adapters on other Linears, adapters on rotary blocks (``attn.Wqkv``).
 """
 import math
 
@@ -160,6 +160,8 @@ def lora_rows_backward(images, lin, h, u, dqkv, d_h, put, site=(ops.NO_DROPOUT, 
 def attach_to_c_attn(model, r=4, lora_alpha=32, lora_dropout=0.1):
     """Replace every module whose name ends in ``c_attn`` by a lora.Linear that SHARES its weight / bias tensors."""
     for key in [k for k, _ in model.named_modules()]:
+        if key.endswith('attn.Wqkv'):
+            raise NotImplementedError('LoRA adapters on rotary blocks (attn.Wqkv) are not built')
         if not key.endswith('c_attn'):
             continue
         parent_name, _, child = key.rpartition('.')

@@ -1074,6 +1074,19 @@ def rope_(x2d, T, heads, head_dim, table, t0=0, inverse=False):
     return x2d
 
 
+def rope_rows_(rows, T, heads, head_dim, table, t0=0, inverse=False):
+    """Rotate in place, in ONE launch, the q and the k column blocks of packed q | k | v rows [M, >= 2 * heads * head_dim] (fp32 or bf16;
+    a column slice of a wider buffer is fine): row r is at position t0 + r % T, v is never touched; ``inverse`` applies the transpose
+    (the backward, on dq | dk).  16-byte accesses only: head_dim % 8 == 0, aligned rows and row stride, else the library's argument error."""
+    if rows.dtype not in (torch.float32, torch.bfloat16) or not rows.is_cuda or rows.dim() != 2 or rows.stride(-1) != 1:
+        raise ValueError('rope_rows: expected float32 or bfloat16 HIP rows with a unit column stride')
+    if rows.shape[1] < 2 * heads * head_dim:
+        raise ValueError('rope_rows: the rows are narrower than the q and k column blocks')
+    check(lib().halo_rope_rows(ptr(rows), int(rows.dtype == torch.bfloat16), rows.stride(0), rows.shape[0], T, heads, head_dim, t0,
+                               ptr(table.cos), ptr(table.sin), table.T, int(inverse), _stream()), 'halo_rope_rows')
+    return rows
+
+
 def attention_cached_fwd(q, cache_k, cache_v, Tq, n_keys, causal=True):
     """q: rows [N*Tq, C] (a column slice is fine); cache_{k,v}: [N, heads, Tc, head_dim] fp32 holding n_keys valid keys.
     -> y [N*Tq, C]: attend_cached of ha/attention.py:64-93 (queries are the LAST Tq of the n_keys positions)."""

@@ -701,6 +701,15 @@ int halo_rope_table(float *cos_table, float *sin_table, int T, int head_dim, flo
 int halo_rope_interleaved(float *x, long row_stride, int n_rows, int T, int heads, int head_dim, int t0,
                           const float *cos_table, const float *sin_table, int table_rows, int inverse,
                           halo_stream_t stream);
+/* halo_rope_interleaved on the packed q | k | v rows of the GPT block forms (csrc/rope_rows.hip): ONE launch rotates in place the q and
+ * the k column blocks -- columns [0, 2 * heads * head_dim) of each of n_rows rows, 2 * heads heads of head_dim; v and anything beyond it
+ * is never touched.  Row r sits at position t0 + r % T; the tables are halo_rope_table's and must cover t0 + T rows; inverse != 0
+ * applies the transpose (sine negated: what the backward applies to dq | dk).  is_bf16 == 0: fp32 rows, the expressions of
+ * halo_rope_interleaved; != 0: bf16 rows, upcast, rotated in fp32, rounded to nearest even once.  16-byte accesses only:
+ * head_dim % 8 == 0, x and both tables 16-byte aligned, row_stride (elements) a multiple of 16 bytes -- anything else is HALO_EINVAL
+ * (there is no slow path). */
+int halo_rope_rows(void *x, int is_bf16, long row_stride, long n_rows, int T, int heads, int head_dim, int t0,
+                   const float *cos_table, const float *sin_table, int table_rows, int inverse, halo_stream_t stream);
 int halo_kv_cache_store(const float *src, long src_row_stride, long v_offset, void *cache_k, void *cache_v, int N,
                         int S, int heads, int head_dim, int cache_len, int t0, halo_stream_t stream);
 /* fp32 twin of halo_kv_cache_store: present[layer, 0|1, :, :, t0:t0+S, :] of ha/attention.py:66-67,129 */
