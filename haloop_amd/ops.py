@@ -883,7 +883,7 @@ def grad_sumsq_state():
 
 
 def clip_coef(partials, count, max_norm, coef, norm, applied_steps=None):
-    """applied_steps: optional device int32 counter advanced when the norm is finite (the Adam step count of applied updates)."""
+    """applied_steps: optional device 32-bit counter advanced when the norm is finite (the Adam step count of applied updates)."""
     check(lib().halo_clip_coef_step(ptr(partials), count, float(max_norm), ptr(coef), ptr(norm), ptr(applied_steps), _stream()),
           'halo_clip_coef_step')
 
