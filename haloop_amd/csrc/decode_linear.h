@@ -41,8 +41,10 @@ struct DecLinearArgs {
 // fragment alone (the lo half of the image is never read).  ACT: which activation bit of `flags` this variant honours (8: exact GELU,
 // the ASR decoder's; 2: tanh-GELU, the GPT block's).  No LayerNorm: K / 128 (/ 2 with two K-slices) k-steps per wave, walked 8 at a time
 // while that divides them, else 4 and a last 2 -- any even count.
-template <int NT, int KSW_LN, int PASSES = 3, int ACT = 8>
-__global__ __launch_bounds__(256) void dec_linear_kernel(const DecLinearArgs p) {
+// ARGS: DecLinearArgs, or a record derived from it that finishes the summed tiles itself (csrc/rnnt_decode.hip: the LSTM cell behind the
+// gate product) through ``template <int NT> void finish(float (*red)[NT][64][4], int nt0) const`` in place of the store below.
+template <int NT, int KSW_LN, int PASSES = 3, int ACT = 8, class ARGS = DecLinearArgs>
+__global__ __launch_bounds__(256) void dec_linear_kernel(const ARGS p) {
     __shared__ float red[4][NT][64][4];
     __shared__ float stat[4][16];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -165,6 +167,10 @@ __global__ __launch_bounds__(256) void dec_linear_kernel(const DecLinearArgs p) 
 #pragma unroll
         for (int e = 0; e < 4; ++e) red[wave][nt][lane][e] = acc[nt][e];
     __syncthreads();
+    if constexpr (!std::is_same<ARGS, DecLinearArgs>::value) {
+        p.template finish<NT>(red, nt0);
+        return;
+    }
     // D layout of the 16x16 MFMA: column = lane % 16 (feature), rows 4*(lane/16) + e
     for (int u = threadIdx.x; u < NT * 64; u += 256) {
         const int nt = u >> 6, l = u & 63;

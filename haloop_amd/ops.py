@@ -1318,6 +1318,28 @@ def gpt_sample(logits, cfg, state, tokens, next_ids, wte=None, wpe=None, x_next=
                                 wte.shape[1] if wte is not None else 0, ptr(x_next), _stream()), 'halo_gpt_sample')
 
 
+# ---- launches of the transducer's greedy decode (csrc/rnnt_decode.hip); none of these allocates ---------------------------------
+def rnnt_advance(f, g, g_bias, input_lengths, state, scores, tokens, frames, max_symbols, wte, x_next, live):
+    """One advance of every row (include/halo.h): f [N, T, V] transcription logits, g [N, V] prediction logits (bias apart), state int32
+    [5, >= N] = t | u | here | done | truncated, tokens / frames int64 [N, capacity], x_next [N, >= E] <- wte[k], live: one int32 word."""
+    N, T, V = f.shape
+    if f.stride(2) != 1 or tokens.stride(0) != frames.stride(0) or tokens.shape != frames.shape:
+        raise ValueError('rnnt_advance: f must be contiguous along V; tokens and frames must share shape and row stride')
+    if wte.shape[0] < V or g.shape != (N, V):
+        raise ValueError('rnnt_advance: g must be [N, V] and the embedding must have a row for every symbol')
+    check(lib().halo_rnnt_advance(ptr(f), f.stride(0), f.stride(1), N, T, V, ptr(g), g.stride(0), ptr(g_bias), ptr(input_lengths), ptr(state),
+                                  state.stride(0), ptr(scores), ptr(tokens), ptr(frames), tokens.stride(0), tokens.shape[1], int(max_symbols),
+                                  ptr(wte), wte.shape[1], ptr(x_next), x_next.stride(0), ptr(live), _stream()), 'halo_rnnt_advance')
+
+
+def rnnt_lstm_cell(xh, image, b_ih, b_hh, c, h_next, h_up):
+    """One LSTM layer at one step: xh [rows, 2H] = x | h_prev, image: the decode image of the gate-interleaved [W_ih | W_hh]
+    (include/halo.h); c [rows, H] in place; h -> h_next and h_up (row strides kept)."""
+    rows, H = c.shape
+    check(lib().halo_rnnt_lstm_cell(ptr(xh), xh.stride(0), rows, H, ptr(image), ptr(b_ih), ptr(b_hh), ptr(c), ptr(h_next), h_next.stride(0),
+                                    ptr(h_up), h_up.stride(0), _stream()), 'halo_rnnt_lstm_cell')
+
+
 # ---- channels-last conv front-end (ha/conv.py) -------------------------------------------------------------
 def conv_out_length(T, ks, stride, pad):
     return (T + 2 * pad - ks) // stride + 1

@@ -6,7 +6,7 @@ from . import _lib, functional as HF, ops
 from .ctc import ctc_reduce_mean
 from .rnn import Decoder, DropoutStream
 from .star import star_ctc_forward_score
-from .transducer import transducer_forward_score
+from .transducer import GreedyDecoder, transducer_forward_score
 
 
 class TemporalClassifier(nn.Module):
@@ -68,8 +68,28 @@ class Transducer(nn.Module):
         self.dropout = nn.Dropout(0.2)
         self.dropout_stream = DropoutStream()
 
-    def decode(self, features, input_lengths):
-        raise NotImplementedError()
+    def decode(self, features, input_lengths, condtarget_lengths=None, prompt=None):
+        """The ``Decodable`` call (ha/recognizer.py:12-34, as ha/loop.py:295-303 makes it): greedy transducer search with room for
+        ``condtarget_lengths.max() + 1`` symbols per row (the length guide ha/transformer.py:128 takes) ->
+        (hypotheses nested_tensor, output_lengths, frames [N, capacity] (-1 past a row's length), scores, None), in the form
+        TemporalClassifier.decode returns its five values.  The search itself is ``transducer.GreedyDecoder``, kept on the module."""
+        if condtarget_lengths is None:
+            # the reference's own two-argument signature, which raises there too (recognizer.py:92-93): no length guide
+            raise NotImplementedError('Transducer.decode needs condtarget_lengths (capacity = condtarget_lengths.max() + 1); '
+                                      'for a capacity of your own use haloop_amd.transducer.GreedyDecoder')
+        if prompt is not None:
+            raise NotImplementedError('Transducer.decode: prompts are not built')
+        if self.training:
+            raise NotImplementedError('Transducer.decode is an inference path: put the head in eval mode')
+        N, capacity = features.shape[0], int(condtarget_lengths.max()) + 1
+        dec = getattr(self, '_greedy_decoder', None)
+        if dec is None or dec.max_batch < N or dec.capacity < capacity or dec._state.device != features.device:
+            dec = GreedyDecoder(self, max(N, dec.max_batch if dec else 0), max(capacity, dec.capacity if dec else 0))
+            self._greedy_decoder = dec
+        tokens, lengths, frames, scores, _ = dec.decode(features, input_lengths, capacity)
+        lens = lengths.tolist()
+        hypotheses = torch.nested.nested_tensor([tokens[i, :n] for i, n in enumerate(lens)])
+        return hypotheses, torch.tensor(lens), frames, scores, None
 
     def forward(self, features, targets, input_lengths=None, target_lengths=None, star_penalty=None):   # star_penalty: ignored (:101)
         if not features.is_cuda:

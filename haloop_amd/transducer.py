@@ -7,10 +7,23 @@ backward kernel where the reference uses autograd through its log-space scan).  
 (:145-172) is the single-sequence form.  Any T: the reference pads its scan to 2 ** round(log2(T)) (:194) and raises when that is
 smaller than T; the recurrence it defines is computed here cell by cell along the anti-diagonals.  The probability-domain study
 versions (transducer_forward_score1-3, :10-142) are not built.
+
+``GreedyDecoder`` is greedy transducer search ([Graves12]) for ``recognizer.Transducer``, which the reference leaves unbuilt
+(ha/recognizer.py:92-93): per row, with F = classifier(features) and g the prediction network's logits for the symbols emitted so far
+(the zero prefix of training first), take k = argmax log_softmax(F[n, t] + g) (lowest index on ties; blank forced once
+``max_symbols_per_frame`` symbols were emitted at frame t); blank moves to the next frame, anything else is emitted and advances the
+prediction network.  The score is the sum of the log-probabilities of every move.  The fused path (csrc/rnnt_decode.hip) costs
+``1 + num_layers + 1`` launches per emitted symbol and none per blank frame; the general path runs the same search node by node on
+``rnn.Decoder.forward`` at T = 1 with torch's log_softmax.
 """
+import os
+
 import torch
 
-from . import _lib, ops
+from . import _lib, functional as HF, ops
+from .rnn import lstm_param_list
+
+SYNC_EVERY = 16          # GreedyDecoder.decode reads the live-row counter every this many advances
 
 
 class _Transducer(torch.autograd.Function):
@@ -45,3 +58,162 @@ def transducer_forward_score4(joint, targets):
     T, U1, _ = joint.shape
     dev = joint.device
     return transducer_forward_score(joint[None], targets[None], torch.tensor([T], device=dev), torch.tensor([U1 - 1], device=dev))[0]
+
+
+def _fused_default():
+    """HALO_RNNT_FUSED=0: the general path even where the fused launches apply (the measured pair: DESIGN.md 3.3j)."""
+    return os.environ.get('HALO_RNNT_FUSED', '1') != '0'
+
+
+class GreedyDecoder:
+    """Greedy search for a ``recognizer.Transducer`` head with preallocated row state and buffers for ``max_batch`` rows and
+    ``capacity`` symbols per row.  ``max_symbols_per_frame`` bounds the symbols emitted at one frame (a guard that a trained model does
+    not meet; it bounds an untrained one)."""
+
+    def __init__(self, head, max_batch, capacity, max_symbols_per_frame=10):
+        self.head = head
+        self.max_batch, self.capacity, self.max_symbols = int(max_batch), int(capacity), int(max_symbols_per_frame)
+        if self.max_batch < 1 or self.capacity < 1 or self.max_symbols < 1:
+            raise ValueError('GreedyDecoder: need max_batch >= 1, capacity >= 1 and max_symbols_per_frame >= 1')
+        lm = head.lm
+        E, H, L, V = lm.embedding.weight.shape[1], lm.hidden_dim, lm.num_layers, lm.num_classes
+        dev = lm.embedding.weight.device
+        mb = self.max_batch
+        with torch.inference_mode(False):          # ordinary tensors: they are updated in place inside and outside inference mode
+            self._state = torch.zeros(5, mb, device=dev, dtype=torch.int32)      # t | u | here | done | truncated, one word per row
+            self._scores = torch.zeros(mb, device=dev, dtype=torch.float32)
+            self._tokens = torch.zeros(mb, self.capacity, device=dev, dtype=torch.int64)
+            self._frames = torch.zeros(mb, self.capacity, device=dev, dtype=torch.int64)
+            self._live = torch.zeros(self.capacity, device=dev, dtype=torch.int32)   # one word per advance: rows still live after it
+            if E == H:
+                # [x | h_prev] rows of every layer, in two copies used alternately: a cell launch reads one and writes the other's h
+                self._xh = torch.zeros(2, L, mb, 2 * H, device=dev, dtype=torch.float32)
+                self._c = torch.zeros(L, mb, H, device=dev, dtype=torch.float32)
+                self._top = torch.zeros(mb, H, device=dev, dtype=torch.float32)
+                self._g = torch.zeros(mb, V, device=dev, dtype=torch.float32)
+        self._images = None    # (stamp, per-layer gate images, out_layer image)
+        self.iterations = 0    # of the last decode: advances (fused path) or lattice nodes visited in lockstep (general path)
+
+    @property
+    def fused(self):
+        """Whether the fused launches are in use (decided from the head, the math mode and HALO_RNNT_FUSED as they are now)."""
+        lm = self.head.lm
+        E, H = lm.embedding.weight.shape[1], lm.hidden_dim
+        if not _fused_default() or _lib.get_math_mode() == 'f32' or self.head.training or E != H or H % 512 != 0:
+            return False
+        return lm.num_classes <= 8192 and ops.decode_linear_supported(H, False) and ops.decode_linear_supported(2 * H, False)
+
+    def _stamp(self):
+        return tuple((p._version, p.data_ptr()) for p in self.head.lm.parameters()) + (_lib.weights_epoch(),)
+
+    @torch.no_grad()
+    def _decode_images(self):
+        """Decode images of every layer's [W_ih | W_hh], rows permuted so that feature tile j holds the four gates of hidden units
+        4 j .. 4 j + 3 (row 16 j + 4 q + i <- row q H + 4 j + i), and of the tied embedding; rebuilt when a parameter changes."""
+        stamp = self._stamp()
+        if self._images is None or self._images[0] != stamp:
+            lm = self.head.lm
+            H, p = lm.hidden_dim, lstm_param_list(lm.rnn)
+            layers = []
+            for l in range(lm.num_layers):
+                w = torch.cat([p[4 * l].detach().float(), p[4 * l + 1].detach().float()], 1)           # [4H, 2H]
+                w = w.view(4, H // 4, 4, 2 * H).permute(1, 0, 2, 3).reshape(4 * H, 2 * H).contiguous()
+                layers.append(ops.decode_image(w))
+            self._images = (stamp, layers, ops.decode_image(lm.embedding.weight.detach().float().contiguous()))
+        return self._images[1], self._images[2]
+
+    def _check(self, features, input_lengths):
+        if features.dim() != 3 or features.shape[1] < 1:
+            raise ValueError('GreedyDecoder: features must be [N, T, feat_dim] with T >= 1')
+        N = features.shape[0]
+        if N < 1 or N > self.max_batch:
+            raise ValueError(f'GreedyDecoder: batch {N} outside 1 .. max_batch = {self.max_batch}')
+        if input_lengths.shape != (N,):
+            raise ValueError(f'GreedyDecoder: input_lengths must be [{N}]')
+        if not features.is_cuda:
+            raise _lib.HaloError('haloop_amd.transducer.GreedyDecoder runs on the HIP device only (no CPU path)')
+        if self.head.training:
+            raise NotImplementedError('GreedyDecoder is an inference path: put the head in eval mode')
+
+    def decode(self, features, input_lengths, capacity=None):
+        """features [N, T, feat_dim], input_lengths [N] (clipped to T) -> (tokens [N, capacity] int64, lengths [N] int64, frames
+        [N, capacity] int64, scores [N] float32, truncated [N] bool); entries past a row's length are -1.  ``capacity``: search with
+        room for fewer symbols than the buffers hold (default: all of them)."""
+        self._check(features, input_lengths)
+        cap = self.capacity if capacity is None else int(capacity)
+        if cap < 1 or cap > self.capacity:
+            raise ValueError(f'GreedyDecoder: capacity {cap} outside 1 .. {self.capacity}')
+        with torch.no_grad():
+            N, T, _ = features.shape
+            dev = features.device
+            cl = self.head.classifier
+            f = HF.linear(features.float(), cl.weight, cl.bias).contiguous()                   # [N, T, V]
+            il = input_lengths.to(device=dev, dtype=torch.int32).clamp(0, T).contiguous()
+            self._state.zero_(); self._scores.zero_(); self._tokens.fill_(-1); self._frames.fill_(-1)
+            (self._decode_fused if self.fused else self._decode_general)(f, il, N, cap)
+            st = self._state
+            return (self._tokens[:N, :cap].clone(), st[1, :N].long(), self._frames[:N, :cap].clone(), self._scores[:N].clone(),
+                    st[4, :N] != 0)
+
+    # ---- the fused path: 1 + num_layers + 1 launches per emitted symbol ------------------------------------------------------------
+    def _lm_step(self, N, p, layers, head_image):
+        """The prediction network on the input rows of copy p -> g: every layer's cell launch reads copy p of its [x | h_prev] rows and
+        writes h to copy 1 - p (its own next h_prev) and to copy p of the layer above (that layer's x)."""
+        lm = self.head.lm
+        H, L, w = lm.hidden_dim, lm.num_layers, lstm_param_list(lm.rnn)
+        for l in range(L):
+            h_up = self._xh[p, l + 1, :N, :H] if l + 1 < L else self._top[:N]
+            ops.rnnt_lstm_cell(self._xh[p, l, :N], layers[l], w[4 * l + 2], w[4 * l + 3], self._c[l, :N], self._xh[1 - p, l, :N, H:], h_up)
+        ops.decode_linear(self._top[:N], head_image, lm.num_classes, self._g[:N])
+
+    def _decode_fused(self, f, il, N, cap):
+        lm = self.head.lm
+        layers, head_image = self._decode_images()
+        wte, E = lm.embedding.weight, lm.embedding.weight.shape[1]
+        self._xh.zero_(); self._c.zero_(); self._live.zero_()
+        self._xh[0, 0, :N, :E] = wte[0]                       # the zero prefix of training (recognizer.py:107)
+        p = 0
+        self._lm_step(N, p, layers, head_image)
+        for it in range(cap):                                  # a live row emits once per advance: after `cap` of them none is live
+            ops.rnnt_advance(f, self._g[:N], lm.out_layer.bias, il, self._state, self._scores, self._tokens[:N, :cap], self._frames[:N, :cap],
+                             self.max_symbols, wte, self._xh[1 - p, 0, :N], self._live[it:])
+            if it == cap - 1 or ((it + 1) % SYNC_EVERY == 0 and int(self._live[it].item()) == 0):
+                break
+            p = 1 - p
+            self._lm_step(N, p, layers, head_image)
+        self.iterations = it + 1
+        if int(self._live[it].item()) != 0:
+            raise _lib.HaloError('GreedyDecoder: rows still live after capacity advances')
+
+    # ---- the general path: the same search node by node on rnn.Decoder.forward at T = 1 ------------------------------------------------
+    def _decode_general(self, f, il, N, cap):
+        lm = self.head.lm
+        dev, V = f.device, f.shape[2]
+        rows, cols = torch.arange(N, device=dev), torch.arange(V, device=dev)
+        t, u, here = (torch.zeros(N, device=dev, dtype=torch.int64) for _ in range(3))
+        il = il.long()
+        done = il <= 0
+        scores = torch.zeros(N, device=dev, dtype=torch.float32)
+        g, state = lm.forward(torch.zeros(1, N, device=dev, dtype=torch.int64), lm.init_hidden(N))
+        self.iterations = 0
+        while not bool(done.all().item()):                      # one host read per lattice node
+            self.iterations += 1
+            lp = torch.log_softmax(f[rows, t.clamp(max=f.shape[1] - 1)] + g, -1)
+            top = lp.max(-1).values
+            k = torch.where(lp == top[:, None], cols, V).min(-1).values            # lowest index among equal maxima
+            k = torch.where(here == self.max_symbols, torch.zeros_like(k), k)
+            live = ~done
+            scores += torch.where(live, lp[rows, k], torch.zeros_like(top))
+            blank, emit = live & (k == 0), live & (k != 0)
+            e = emit.nonzero().view(-1)
+            self._tokens[e, u[e]] = k[e]
+            self._frames[e, u[e]] = t[e]
+            t, here, u = t + blank.long(), torch.where(blank, torch.zeros_like(here), here + emit.long()), u + emit.long()
+            if e.numel():
+                g1, (h1, c1) = lm.forward(torch.where(emit, k, torch.zeros_like(k)).view(1, N), state)
+                g = torch.where(emit[:, None], g1, g)
+                state = (torch.where(emit[None, :, None], h1, state[0]), torch.where(emit[None, :, None], c1, state[1]))
+            done = done | (t >= il) | (u >= cap)
+        st = self._state
+        st[0, :N], st[1, :N], st[2, :N], st[3, :N], st[4, :N] = t.int(), u.int(), here.int(), 1, (u >= cap).int()
+        self._scores[:N] = scores

@@ -812,6 +812,35 @@ int halo_gpt_sample(const float *logits, long ld, int B, int V, const int *cfg, 
                     float *x_next, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Greedy decode of the RNN transducer head (haloop_amd/transducer.py GreedyDecoder; [Graves12] greedy search over the additive joint of
+ * ha/recognizer.py:86-127, blank 0) as a launch sequence: per emitted symbol one halo_rnnt_advance, one halo_rnnt_lstm_cell per LSTM
+ * layer and one halo_decode_linear (out_layer, on the image of the tied embedding).  Blank frames cost no launch; every launch is finite
+ * (no grid barrier, no polling) and none reads a buffer another workgroup of the same launch writes.
+ *   halo_rnnt_advance    one workgroup per row n of f [N][T][V] (the transcription logits; strides in floats).  state: device int32
+ *                        [5][state_ld] = t | u | here | done | truncated, one word of each per row; a row with done != 0 is skipped.
+ *                        With l = g[n, :] + g_bias (g_bias may be NULL) and L = clamp(input_lengths[n], 0, T), the row walks its frames
+ *                        from t: lp = log_softmax(f[n, t] + l); k = 0 when here == max_symbols, else argmax lp (lowest index on ties).
+ *                        k == 0: scores[n] += lp[0], t += 1, here = 0, next frame -- the sums in frame order.  The first k != 0:
+ *                        tokens[n][u] = k, frames[n][u] = t, scores[n] += lp[k], u += 1, here += 1; u == capacity sets done and
+ *                        truncated, otherwise x_next[n][0 .. E) = wte[k] (layer 0's next input row).  t == L sets done.  Frames at or
+ *                        past L are never read.  *live += 1 for every row not done afterwards (the caller zeroes the word; a fresh
+ *                        word per launch needs no reset).  V <= 8192, E % 4 == 0; wte has V rows.
+ *   halo_rnnt_lstm_cell  one LSTM layer at one step for `rows` rows: gates = xh [W_ih | W_hh]^T + b_ih + b_hh with xh [rows][2 hidden] =
+ *                        x | h_prev (input size == hidden), then c = f c + i g, h = o tanh(c) (nn.LSTM's gate order i, f, g, o) in the same
+ *                        launch.  w_image: halo_decode_image of the [4 hidden][2 hidden] matrix whose row 16 j + 4 q + i is row
+ *                        q hidden + 4 j + i of [W_ih | W_hh] (one feature tile = the four gates of four units).  The split three-MFMA
+ *                        product of halo_decode_linear (2 hidden must pass halo_decode_linear_supported(k, 0)); the biases are indexed in
+ *                        nn.LSTM's layout.  c [rows][hidden] is updated in place (each element by one thread); h is written twice: to
+ *                        h_next (this layer's h_prev of the next step: the h half of the OTHER copy of its xh rows) and to h_up (the x
+ *                        half of the layer above in this step, or out_layer's input).  xh, c, h_next and h_up may not overlap. */
+int halo_rnnt_advance(const float *f, long f_row_stride, long f_frame_stride, int N, int T, int V, const float *g, long ldg,
+                      const float *g_bias, const int *input_lengths, int *state, long state_ld, float *scores, int64_t *tokens,
+                      int64_t *frames, long tokens_ld, int capacity, int max_symbols, const float *wte, int E, float *x_next, long ldx,
+                      int *live, halo_stream_t stream);
+int halo_rnnt_lstm_cell(const float *xh, long ldx, int rows, int hidden, const void *w_image, const float *b_ih, const float *b_hh,
+                        float *c, float *h_next, long ld_next, float *h_up, long ld_up, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Backward operators of the GPT / transformer training step (the autograd graph of ha/attention.py:205-232 as
  * `hal` runs it, ha/attention_loop.py:196-215: loss.backward()).
  *   halo_attention_bwd         gradient of halo_attention_fwd: dq, dk, dv (same row layouts as q, k, v; written, not
