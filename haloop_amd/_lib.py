@@ -111,6 +111,13 @@ SIGNATURES = {
     'halo_set_lstm_weights_stamp': (_i, [_u64]),
     'halo_lstm_persistent2_eligible': (_i, [_i, _i, _i, _i]),
     'halo_lstm_status_offset': (_sz, [_i] * 6),
+    'halo_ghost_tile': (_i, []),
+    'halo_ghost_sqnorm_workspace_bytes': (_sz, [_i, _i, _i]),
+    'halo_ghost_sqnorm': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'halo_set_lstm_keep_gate_gradients': (_i, [_i]),
+    'halo_get_lstm_keep_gate_gradients': (_i, []),
+    'halo_lstm_ghost_terms': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    'halo_relu_dropout_bwd': (_i, [_vp, _vp, _vp, _sz, _f, _vp]),
     'halo_lstm_persist_stamps': (_i, [_vp]),
     'halo_lstm_chain_events': (_i, [_vp, _vp]),
     'halo_lstm_chain_info': (_i, [_i, C.POINTER(_i), C.c_char_p, _i]),
@@ -232,6 +239,18 @@ SIGNATURES = {
     'halo_adamw': (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp, _vp]),
 }
 
+
+
+class GhostOperand(C.Structure):
+    """halo_ghost_operand (include/halo.h): element (n, t, k) at ptr[n * stride_n + t * stride_t + k], strides in floats."""
+    _fields_ = [('ptr', _vp), ('stride_n', _l), ('stride_t', _l), ('K', _i)]
+
+
+class GhostTerm(C.Structure):
+    """halo_ghost_term (include/halo.h)."""
+    _fields_ = [('a', GhostOperand), ('b', GhostOperand * 2), ('n_b', _i), ('n_bias', _i)]
+
+
 _lib = None
 
 
@@ -295,6 +314,15 @@ def set_gemm256(on):
 def set_lstm_interleave(on):
     """Two batch tiles per workgroup, interleaved, in the two-layer launches of a batch larger than one launch holds (include/halo.h)."""
     check(lib().halo_set_lstm_interleave(int(bool(on))), 'halo_set_lstm_interleave')
+
+
+def set_lstm_keep_gate_gradients(on):
+    """The persistent LSTM backward launches keep their fp32 gate gradients in the reserve (include/halo.h); off by default."""
+    check(lib().halo_set_lstm_keep_gate_gradients(int(bool(on))), 'halo_set_lstm_keep_gate_gradients')
+
+
+def get_lstm_keep_gate_gradients():
+    return bool(lib().halo_get_lstm_keep_gate_gradients())
 
 
 def set_lstm_persistent2(on):

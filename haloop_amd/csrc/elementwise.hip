@@ -496,6 +496,13 @@ int halo_subsample_bwd_slabs(float *dy, int slabs, const float *y, const float *
     return halo_flush_small_jobs(stream);
 }
 
+int halo_relu_dropout_bwd(const float *dy, const float *y, float *dpre, size_t n, float p_drop, halo_stream_t stream) {
+    HALO_CHECK_ARG(dy && y && dpre && n > 0 && p_drop >= 0.f && p_drop < 1.f);
+    const float scale = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
+    hipLaunchKernelGGL(relu_dropout_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dy, y, dpre, n, scale);
+    return halo_launch_status();
+}
+
 int halo_set_defer_small_jobs(int on) {
     HaloCtx &ctx = halo_ctx_cur();
     ctx.defer_small_jobs = on ? 1 : 0;

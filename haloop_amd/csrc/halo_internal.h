@@ -68,7 +68,9 @@ struct HaloCtx {
     uint64_t lstm_weights_stamp = 0, packF_stamp = 0;
     const float *packF_reserve = nullptr, *packF_w[3] = {nullptr, nullptr, nullptr};
     int packF_dims[5] = {0, 0, 0, 0, 0};
-    int mute_block = -1;                 // test hook (halo_debug_mute_workgroup): this workgroup of a persistent forward never publishes
+    int lstm_keep_dg = 0;                // halo_set_lstm_keep_gate_gradients: the persistent backwards store fp32 dG even where no launch reads it
+    const float *ghost_reserve = nullptr;   // the reserve in which the last whole halo_lstm_bwd left every layer's dG (halo_lstm_ghost_terms)
+    int mute_block = -1;                // test hook (halo_debug_mute_workgroup): this workgroup of a persistent forward never publishes
 };
 HaloCtx &halo_ctx_cur();
 // CUs of the current device (the device property, cached per device; <= 0: the query failed)

@@ -1228,10 +1228,11 @@ inline bool persist_emit_enabled() {
 }
 
 // HALO_LSTM_KEEP_DG=1: the persistent backward launches store their fp32 gate gradients back into the gates buffers even where no
-// launch reads them any more (the chain emits the operand images and bias partials itself) -- the behaviour before round 4's last day
+// launch reads them any more (the chain emits the operand images and bias partials itself) -- the behaviour before round 4's last day;
+// per context: halo_set_lstm_keep_gate_gradients (the per-utterance gradient norms read dG from there)
 inline bool keep_dg_switch() {
     static const bool on = getenv("HALO_LSTM_KEEP_DG") && getenv("HALO_LSTM_KEEP_DG")[0] == '1';
-    return on;
+    return on || halo_ctx_cur().lstm_keep_dg != 0;
 }
 
 inline bool pair_dw_enabled() {
@@ -1574,6 +1575,7 @@ int halo_lstm_fwd(const float *x, const float *const *w_ih, const float *const *
     HALO_CHECK_ARG(x && w_ih && w_hh && b_ih && b_hh && reserve);
     HALO_CHECK_ARG(T > 0 && B > 0 && in0 > 0 && H > 0 && L > 0);
     if (H % 16 != 0) return HALO_ENOTSUP;
+    halo_ctx_cur().ghost_reserve = nullptr;          // (the gates buffers hold activations again: halo_lstm_ghost_terms)
     hipStream_t st = (hipStream_t)stream;
     const size_t BH = (size_t)B * H, PH = bt16(B) * H;
     // what an earlier forward left for "its" backward (transposed weight images, operand images) is forgotten with every new forward,
@@ -1705,6 +1707,9 @@ int halo_lstm_bwd(const float *x, const float *const *w_ih, const float *const *
     HALO_CHECK_ARG(T > 0 && B > 0 && in0 > 0 && H > 0 && L > 0);
     if (H % 16 != 0) return HALO_ENOTSUP;
     halo_ctx_cur().lstm_dx_slabs_left = 1;
+    // a whole backward with the keep flag leaves every layer's fp32 gate gradients in the reserve (halo_lstm_ghost_terms asks for that)
+    halo_ctx_cur().ghost_reserve = nullptr;
+    const bool leaves_dg = layer_begin == 0 && layer_end == L && !fused_ok(H, L) && keep_dg_switch();
     hipStream_t st = (hipStream_t)stream;
     const size_t BH = (size_t)B * H, PG = bt16(B) * 4 * H;
     const bool x3 = use_x3(H);
@@ -1904,7 +1909,10 @@ int halo_lstm_bwd(const float *x, const float *const *w_ih, const float *const *
                                          img_inT, img_wT, bias_part0, din, dx, dw_ih, dw_hh, db_ih, db_hh, need_din, st));
         }
         top_end = lo;                 // the layers below (if any) follow, one launch each, fed by din
-        if (top_end <= layer_begin) return HALO_OK;
+        if (top_end <= layer_begin) {
+            if (leaves_dg) ctx.ghost_reserve = reserve;
+            return HALO_OK;
+        }
     }
     for (int l = top_end - 1; l >= layer_begin; --l) {
         HALO_CHECK_ARG(w_ih[l] && w_hh[l] && dw_ih[l] && dw_hh[l] && db_ih[l] && db_hh[l]);
@@ -1982,6 +1990,33 @@ int halo_lstm_bwd(const float *x, const float *const *w_ih, const float *const *
         HALO_TRY(lstm_bwd_layer_tail(x, w_ih, reserve, l, in0, T, B, H, L, p_drop, seed, offset, offset_dev, fused, emit, img_g, img_gT, img_hT,
                                      img_inT, img_wT, emit ? (const float *)((char *)workspace + bwd_flags_offset(T, B, in0, H, L) + PERSIST_FLAG_BYTES) : nullptr,
                                      din, dx, dw_ih, dw_hh, db_ih, db_hh, (l > 0 && !fused) || (l == 0 && dx), st));
+    }
+    if (leaves_dg) halo_ctx_cur().ghost_reserve = reserve;
+    return HALO_OK;
+}
+
+int halo_set_lstm_keep_gate_gradients(int on) {
+    halo_ctx_cur().lstm_keep_dg = on ? 1 : 0;
+    return HALO_OK;
+}
+int halo_get_lstm_keep_gate_gradients(void) { return halo_ctx_cur().lstm_keep_dg; }
+
+int halo_lstm_ghost_terms(const float *x, float *reserve, int T, int B, int in0, int H, int L, float p_drop, halo_ghost_term *terms_out) {
+    HALO_CHECK_ARG(x && reserve && terms_out && T > 0 && B > 0 && in0 > 0 && H > 0 && L > 0);
+    if (H % 16 != 0 || halo_ctx_cur().ghost_reserve != reserve) return HALO_ENOTSUP;
+    const size_t BH = (size_t)B * H;
+    for (int l = 0; l < L; ++l) {
+        const LayerBufs lb = layer_bufs(reserve, l, T, B, H);
+        halo_ghost_term tm = {};
+        tm.a = {lb.gates, (long)4 * H, (long)B * 4 * H, 4 * H};                      // dG [T][B][4H]
+        if (l == 0) tm.b[0] = {x, (long)in0, (long)B * in0, in0};
+        else {
+            const LayerBufs pb = layer_bufs(reserve, l - 1, T, B, H);                   // (the rule of lstm_bwd_layer_tail)
+            tm.b[0] = {p_drop > 0.f ? pb.ydrop : pb.h + BH, (long)H, (long)BH, H};
+        }
+        tm.b[1] = {lb.h, (long)H, (long)BH, H};                                         // rows 0 .. T-1: h_{t-1}
+        tm.n_b = 2; tm.n_bias = 2;
+        terms_out[l] = tm;
     }
     return HALO_OK;
 }

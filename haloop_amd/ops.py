@@ -569,6 +569,91 @@ def lstm_bwd(x_tm, w_ih, w_hh, dy, y_strides, y_relu, reserve, dhn=None, dcn=Non
     return dx, grads
 
 
+def relu_dropout_bwd(dy, y, p_drop):
+    """dpre = dy * (y > 0 ? 1 / (1 - p) : 0): the gradient at the pre-activation of relu + inverted dropout, the mask read off y."""
+    _f32c(dy, 'dy'); _f32c(y, 'y')
+    if dy.numel() != y.numel():
+        raise ValueError('haloop_amd.ops.relu_dropout_bwd: dy and y differ in size')
+    dpre = torch.empty_like(y)
+    check(lib().halo_relu_dropout_bwd(ptr(dy), ptr(y), ptr(dpre), y.numel(), float(p_drop), _stream()), 'halo_relu_dropout_bwd')
+    return dpre
+
+
+def _ghost_operand(t, time_major, N, T, name):
+    if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or (t.shape[2] > 1 and t.stride(2) != 1):
+        raise ValueError(f'{name}: expected a 3-d float32 HIP tensor with unit stride along K')
+    n_dim, t_dim = (1, 0) if time_major else (0, 1)
+    if t.shape[n_dim] != N or t.shape[t_dim] != T:
+        raise ValueError(f'{name}: shape {tuple(t.shape)} does not hold N = {N} utterances of T = {T} frames')
+    return _lib.GhostOperand(t.data_ptr(), t.stride(n_dim), t.stride(t_dim), t.shape[2])
+
+
+def ghost_term(a, bs=(), n_bias=0, time_major=False):
+    """One term of ``ghost_sqnorm``: ``a`` and up to two ``bs``, each [N, T, K] (or [T, N, K] when ``time_major``) with any batch / frame
+    strides, read in place; ``n_bias`` bias vectors with gradient sum_t a_t.  The record keeps its tensors alive."""
+    bs = tuple(bs)
+    if len(bs) > 2 or not 0 <= int(n_bias) <= 2:
+        raise ValueError('haloop_amd.ops.ghost_term: at most two b operands and two bias vectors')
+    N, T = (a.shape[1], a.shape[0]) if time_major else (a.shape[0], a.shape[1])
+    tm = _lib.GhostTerm()
+    tm.a = _ghost_operand(a, time_major, N, T, 'a')
+    for j, b in enumerate(bs):
+        tm.b[j] = _ghost_operand(b, time_major, N, T, f'b{j}')
+    tm.n_b, tm.n_bias = len(bs), int(n_bias)
+    tm.tensors = (a,) + bs
+    return tm
+
+
+def lstm_ghost_terms(x_tm, reserve, H, L, p_drop=0.0):
+    """The LSTM's terms (one per layer: dG against the layer's input and h_{t-1}, two biases), read off the ``reserve`` that ``lstm_fwd`` and a
+    whole ``lstm_bwd`` under ``_lib.set_lstm_keep_gate_gradients(True)`` have gone through (include/halo.h: halo_lstm_ghost_terms)."""
+    _f32c(x_tm, 'x')
+    T, B, in0 = x_tm.shape
+    arr = (_lib.GhostTerm * L)()
+    check(lib().halo_lstm_ghost_terms(ptr(x_tm), ptr(reserve), T, B, in0, H, L, float(p_drop), arr), 'halo_lstm_ghost_terms')
+    terms = []
+    for l in range(L):
+        tm = _lib.GhostTerm.from_buffer_copy(arr[l])
+        tm.tensors = (x_tm, reserve)
+        terms.append(tm)
+    return terms
+
+
+def ghost_sqnorm(terms, N, T, want_norm=False, workspace=None, out=None, norm_out=None):
+    """sq [n_terms, N]: per term and utterance, sum_{t,t'} <a_t, a_t'> (n_bias + sum_j <b^j_t, b^j_t'>) = the squared Frobenius norm of the
+    utterance's own gradient of the term's parameters (csrc/ghost_norm.hip: exact-f32 MFMA, one launch for all terms plus a fixed-order
+    sum).  ``want_norm``: also norm [N] = sqrt(sum over terms), from the same second launch.  ``workspace`` (ghost_sqnorm_workspace floats),
+    ``out`` and ``norm_out`` may be the caller's."""
+    terms = list(terms)
+    if not terms:
+        raise ValueError('haloop_amd.ops.ghost_sqnorm: no terms')
+    dev = terms[0].tensors[0].device
+    arr = (_lib.GhostTerm * len(terms))(*terms)
+    need = ghost_sqnorm_workspace(len(terms), N, T)
+    ws = workspace if workspace is not None else torch.empty(need, device=dev, dtype=torch.float32)
+    if ws.dtype != torch.float32 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError('haloop_amd.ops.ghost_sqnorm: the workspace is too small (ops.ghost_sqnorm_workspace)')
+    sq = out if out is not None else torch.empty(len(terms), N, device=dev, dtype=torch.float32)
+    _f32c(sq, 'out')
+    if sq.numel() != len(terms) * N:
+        raise ValueError('haloop_amd.ops.ghost_sqnorm: out must hold [n_terms, N] floats')
+    norm = norm_out if norm_out is not None else (torch.empty(N, device=dev, dtype=torch.float32) if want_norm else None)
+    if norm is not None and (_f32c(norm, 'norm_out').numel() != N):
+        raise ValueError('haloop_amd.ops.ghost_sqnorm: norm_out must hold N floats')
+    check(lib().halo_ghost_sqnorm(arr, len(terms), N, T, ptr(ws), ptr(sq), ptr(norm), _stream()), 'halo_ghost_sqnorm')
+    return (sq, norm) if norm is not None else sq
+
+
+def ghost_sqnorm_workspace(n_terms, N, T):
+    """Floats of workspace ``ghost_sqnorm`` needs (one partial per term, utterance and pair of frame tiles)."""
+    return max(1, lib().halo_ghost_sqnorm_workspace_bytes(n_terms, N, T) // 4)
+
+
+def ghost_tile():
+    """Frames per tile of the ghost-norm kernel."""
+    return int(lib().halo_ghost_tile())
+
+
 class defer_small_jobs:
     """``with ops.defer_small_jobs():`` -- the small fixed-order reductions at the end of a backward pass (the CTC head's partial sums, the
     two-layer LSTM launch's bias-gradient partials) are queued on the context instead of launched, and ride in the tail blocks of the conv

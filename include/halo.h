@@ -457,6 +457,46 @@ int halo_grad_sumsq_state(int *count, unsigned *covered);
 int halo_lstm_persistent2_eligible(int T, int B, int H, int L);
 size_t halo_lstm_status_offset(int backward, int T, int B, int in0, int H, int L);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-utterance squared gradient norms from one backward pass (csrc/ghost_norm.hip).   replaces: ha/grad_norm.py
+ * A term describes one group of parameters whose gradient for utterance n is sum_t a_t b_t^T (plus n_bias bias vectors with gradient
+ * sum_t a_t); the kernel evaluates
+ *     sq[term][n] = sum_{t,t' < T} <a_t, a_t'> * (n_bias + sum_j <b^j_t, b^j_t'>)
+ * from the operands where they lie: element (n, t, k) of an operand is ptr[n * stride_n + t * stride_t + k] (strides in floats, unit
+ * element stride, any K >= 1, any T >= 1; 16-byte loads where ptr and both strides allow them).  n_b in {0, 1, 2} operands b,
+ * n_bias in {0, 1, 2}.  Exact-f32 MFMA in every arithmetic mode.  Two launches: one workgroup per (term, n, pair of
+ * halo_ghost_tile()-frame tiles) writes one partial into workspace (halo_ghost_sqnorm_workspace_bytes), the second adds them in a
+ * fixed order into sq [n_terms][N] (optional) and writes norm[n] = sqrt(sum over terms) (optional; one of the two must be given).
+ * No atomics: the same inputs give the same bits.  HALO_ENOTSUP: N > 65535.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct halo_ghost_operand {
+    const float *ptr;
+    long stride_n, stride_t;
+    int K;
+} halo_ghost_operand;
+typedef struct halo_ghost_term {
+    halo_ghost_operand a;
+    halo_ghost_operand b[2];
+    int n_b, n_bias;
+} halo_ghost_term;
+int halo_ghost_tile(void);
+size_t halo_ghost_sqnorm_workspace_bytes(int n_terms, int N, int T);
+int halo_ghost_sqnorm(const halo_ghost_term *terms, int n_terms, int N, int T, float *workspace, float *sq, float *norm,
+                      halo_stream_t stream);
+/* on = 1: the persistent backward launches of the NEXT halo_lstm_bwd calls store their fp32 gate gradients back into the reserve's gates
+ * buffers even where they emit the GEMM operand images themselves (what HALO_LSTM_KEEP_DG=1 does process-wide).  Default 0.  Per context. */
+int halo_set_lstm_keep_gate_gradients(int on);
+int halo_get_lstm_keep_gate_gradients(void);
+/* The LSTM's terms for halo_ghost_sqnorm, one per layer, read off the reserve that a halo_lstm_fwd + a whole halo_lstm_bwd (layers 0 .. L,
+ * keep flag above set) of the same x / shape / p_drop have gone through: a = the layer's gate gradients [T][B][4H], b0 = the layer's input
+ * (x for layer 0, the dropped output of the layer below otherwise), b1 = h_{t-1}, n_bias = 2 (b_ih, b_hh); all time-major.
+ * terms_out: L records.  HALO_ENOTSUP when the last backward on this context did not leave complete gate gradients in this reserve
+ * (keep flag off, a partial layer range, the layer-diagonal fused schedule, or another forward since). */
+int halo_lstm_ghost_terms(const float *x, float *reserve, int T, int B, int in0, int H, int L, float p_drop, halo_ghost_term *terms_out);
+/* dpre = dy * (y > 0 ? 1 / (1 - p_drop) : 0): the gradient at the pre-activation of relu followed by inverted dropout, the mask read
+ * off the forward output y (what halo_subsample_bwd forms inside its product and need not store).  n floats each. */
+int halo_relu_dropout_bwd(const float *dy, const float *y, float *dpre, size_t n, float p_drop, halo_stream_t stream);
+
 /* Diagnostic: device buffer of uint64 [blocks][T][16] that the persistent forward fills with 100 MHz time stamps of its phases
  * (tools/persist_stamps.py reads them); NULL (default) turns the stamps off. */
 int halo_lstm_persist_stamps(void *device_buffer);
