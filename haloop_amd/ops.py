@@ -1269,15 +1269,21 @@ def star_ctc_bwd(em, targets, emission_lengths, target_lengths, star_penalty, wo
     return grad
 
 
-def transducer_fwd(joint, targets, joint_lengths, target_lengths, keep=False):
-    """joint [N, T, U+1, K] fp32 contiguous log-probabilities -> (losses [N], workspace or None)."""
-    N, T, U1, K = joint.shape
+def _check_transducer(name, K, T, U1, targets, joint_lengths, target_lengths):
     if targets.numel() and (int(targets.min()) < 0 or int(targets.max()) >= K):
-        raise ValueError('transducer: target label out of range')
+        raise ValueError(f'{name}: target label out of range')
     if joint_lengths.numel() and int(joint_lengths.min()) < 1:
-        raise ValueError('transducer: joint_lengths must be >= 1')
-    _check_lengths('transducer: joint_lengths', joint_lengths, T)
-    _check_lengths('transducer: target_lengths', target_lengths, U1 - 1)
+        raise ValueError(f'{name}: joint_lengths must be >= 1')
+    _check_lengths(f'{name}: joint_lengths', joint_lengths, T)
+    _check_lengths(f'{name}: target_lengths', target_lengths, U1 - 1)
+
+
+def transducer_fwd(joint, targets, joint_lengths, target_lengths, keep=False, checked=False):
+    """joint [N, T, U+1, K] fp32 contiguous log-probabilities -> (losses [N], workspace or None).  ``checked``: the caller has validated
+    the labels and lengths already (rnnt_joint_fwd's caller: the same lengths, targets of ones)."""
+    N, T, U1, K = joint.shape
+    if not checked:
+        _check_transducer('transducer', K, T, U1, targets, joint_lengths, target_lengths)
     losses = torch.empty(N, device=joint.device, dtype=torch.float32)
     ws = torch.empty(lib().halo_transducer_workspace_bytes(N, T, U1), device=joint.device, dtype=torch.uint8) if keep else None
     check(lib().halo_transducer_fwd(ptr(joint), N, T, U1, K, ptr(targets), ptr(joint_lengths), ptr(target_lengths), ptr(ws), ptr(losses),
@@ -1293,6 +1299,46 @@ def transducer_bwd(joint, targets, joint_lengths, target_lengths, workspace, los
     check(lib().halo_transducer_bwd(ptr(joint), N, T, U1, K, ptr(targets), ptr(joint_lengths), ptr(target_lengths), ptr(workspace),
                                     ptr(losses), ptr(grad_losses), ptr(grad), _stream()), 'halo_transducer_bwd')
     return grad
+
+
+# ---- the transducer loss over the additive joint f[:, :, None] + g[:, None] (csrc/rnnt_loss.hip): nothing of N T (U+1) V elements ----
+def _check_rnnt_joint(f, g, targets):
+    if f.dim() != 3 or g.dim() != 3 or f.shape[0] != g.shape[0] or f.shape[2] != g.shape[2]:
+        raise ValueError(f'rnnt_joint: f must be [N, T, V] and g [N, U+1, V], got {tuple(f.shape)} and {tuple(g.shape)}')
+    N, T, V = f.shape
+    U1 = g.shape[1]
+    if tuple(targets.shape) != (N, U1 - 1):
+        raise ValueError(f'rnnt_joint: targets must be [N, U] = [{N}, {U1 - 1}], got {tuple(targets.shape)}')
+    if f.dtype != torch.float32 or g.dtype != torch.float32 or (V > 1 and (f.stride(2) != 1 or g.stride(2) != 1)):
+        raise ValueError('rnnt_joint: f and g must be fp32 with unit stride along V')
+    return N, T, U1, V
+
+
+def rnnt_joint_fwd(f, g, targets, f_lengths, target_lengths):
+    """f [N, T, V], g [N, U+1, V] fp32 logits (row strides; unit stride along V), targets [N, U] int64, lengths [N] int32 ->
+    (lse [N, T, U+1], lp2 [N, T, U+1, 2]): the log-sum-exp of every cell of the additive joint and its blank / label log-probabilities."""
+    N, T, U1, V = _check_rnnt_joint(f, g, targets)
+    _check_transducer('rnnt_joint', V, T, U1, targets, f_lengths, target_lengths)
+    lse = torch.empty(N, T, U1, device=f.device, dtype=torch.float32)
+    lp2 = torch.empty(N, T, U1, 2, device=f.device, dtype=torch.float32)
+    check(lib().halo_rnnt_joint_fwd(ptr(f), f.stride(0), f.stride(1), ptr(g), g.stride(0), g.stride(1), N, T, U1, V, ptr(targets),
+                                    ptr(f_lengths), ptr(target_lengths), ptr(lse), ptr(lp2), _stream()), 'halo_rnnt_joint_fwd')
+    return lse, lp2
+
+
+def rnnt_joint_bwd(f, g, targets, f_lengths, target_lengths, lse, grad_lp2):
+    """grad_lp2 [N, T, U+1, 2] (transducer_bwd on lp2) -> (df [N, T, V] contiguous, dg [N, U+1, V] in g's layout where that is dense)."""
+    N, T, U1, V = _check_rnnt_joint(f, g, targets)
+    if tuple(lse.shape) != (N, T, U1) or tuple(grad_lp2.shape) != (N, T, U1, 2) or not lse.is_contiguous() or not grad_lp2.is_contiguous():
+        raise ValueError('rnnt_joint backward: lse must be [N, T, U+1] and grad_lp2 [N, T, U+1, 2], contiguous')
+    df = torch.empty(N, T, V, device=f.device, dtype=torch.float32)
+    dg = torch.empty_like(g)                      # keeps the strides of a dense g (a transposed view of time-major rows), else contiguous
+    if V > 1 and dg.stride(2) != 1:
+        dg = torch.empty(N, U1, V, device=f.device, dtype=torch.float32)
+    check(lib().halo_rnnt_joint_bwd(ptr(f), f.stride(0), f.stride(1), ptr(g), g.stride(0), g.stride(1), N, T, U1, V, ptr(targets),
+                                    ptr(f_lengths), ptr(target_lengths), ptr(lse), ptr(grad_lp2), ptr(df), df.stride(0), df.stride(1),
+                                    ptr(dg), dg.stride(0), dg.stride(1), _stream()), 'halo_rnnt_joint_bwd')
+    return df, dg
 
 
 # ---- fused launches of a greedy decode step (csrc/decode.hip) -------------------------------------------------

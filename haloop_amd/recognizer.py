@@ -1,4 +1,6 @@
 """Drop-in for ha/recognizer.py: the CTC head (TemporalClassifier, recognizer.py:37-83) and the RNN transducer head (Transducer, :86-127)."""
+import os
+
 import torch
 import torch.nn as nn
 
@@ -6,7 +8,7 @@ from . import _lib, functional as HF, ops
 from .ctc import ctc_reduce_mean
 from .rnn import Decoder, DropoutStream
 from .star import star_ctc_forward_score
-from .transducer import GreedyDecoder, transducer_forward_score
+from .transducer import GreedyDecoder, transducer_forward_score, transducer_loss
 
 
 class TemporalClassifier(nn.Module):
@@ -59,7 +61,11 @@ class Transducer(nn.Module):
     transducer loss.  The reference's live branch calls torchaudio's ``rnnt_loss(joint, ..., blank=0, reduction='mean',
     fused_log_softmax=True)`` (:121-126); torchaudio is not part of this build, and the loss here is the same quantity through the
     reference's own lattice: mean over the batch of ``transducer_forward_score(joint.log_softmax(-1), ...)`` -- the equality the
-    reference's tests assert (ha/transducer.py:210-231, 234-268) -- on the HIP lattice kernels, differentiable end to end."""
+    reference's tests assert (ha/transducer.py:210-231, 234-268) -- on the HIP lattice kernels, differentiable end to end.
+
+    ``fused_loss`` (HALO_RNNT_LOSS_FUSED=1 when the head is built; a caller may set the attribute): the same losses from
+    ``transducer.transducer_loss`` on the two factors of the joint, which builds no [N, T, U+1, V] tensor.  Off by
+    default."""
 
     def __init__(self, feat_dim=1024, vocab_size=256):
         super().__init__()
@@ -67,6 +73,7 @@ class Transducer(nn.Module):
         self.lm = Decoder(vocab_size, emb_dim=512, hidden_dim=512, num_layers=2, dropout=0.2)
         self.dropout = nn.Dropout(0.2)
         self.dropout_stream = DropoutStream()
+        self.fused_loss = os.environ.get('HALO_RNNT_LOSS_FUSED', '0') == '1'
 
     def decode(self, features, input_lengths, condtarget_lengths=None, prompt=None):
         """The ``Decodable`` call (ha/recognizer.py:12-34, as ha/loop.py:295-303 makes it): greedy transducer search with room for
@@ -103,6 +110,8 @@ class Transducer(nn.Module):
         drop = self.dropout_stream.next(self.dropout.p, self.training)
         feats = HF.dropout(features.float(), drop, _lib.HALO_STREAM_CLASSIFIER)
         feats = HF.linear(feats, self.classifier.weight, self.classifier.bias)          # (N, T, C)
+        if self.fused_loss:
+            return transducer_loss(feats, lm_outputs, targets, input_lengths.to(dev), target_lengths.to(dev)).mean(), {}
         joint = feats[:, :, None, :] + lm_outputs[:, None, :, :]                        # (N, T, U1, C): a broadcast add (glue)
         losses = transducer_forward_score(HF.log_softmax(joint), targets, input_lengths.to(dev), target_lengths.to(dev))
         return losses.mean(), {}

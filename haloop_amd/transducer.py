@@ -8,6 +8,12 @@ backward kernel where the reference uses autograd through its log-space scan).  
 smaller than T; the recurrence it defines is computed here cell by cell along the anti-diagonals.  The probability-domain study
 versions (transducer_forward_score1-3, :10-142) are not built.
 
+``transducer_loss(f, g, targets, f_lengths, target_lengths)`` is the same score for the additive joint f[:, :, None] + g[:, None] of
+``recognizer.Transducer``, taken from its two factors (what the reference's live branch gets from torchaudio's ``rnnt_loss(...,
+fused_log_softmax=True)``, ha/recognizer.py:121-126): csrc/rnnt_loss.hip computes every cell's log-sum-exp and its blank / label
+log-probabilities, the lattice kernels run on those, and the backward rebuilds the softmax for df and dg -- no [N, T, U+1, V] tensor in
+either direction.
+
 ``GreedyDecoder`` is greedy transducer search ([Graves12]) for ``recognizer.Transducer``, which the reference leaves unbuilt
 (ha/recognizer.py:92-93): per row, with F = classifier(features) and g the prediction network's logits for the symbols emitted so far
 (the zero prefix of training first), take k = argmax log_softmax(F[n, t] + g) (lowest index on ties; blank forced once
@@ -58,6 +64,61 @@ def transducer_forward_score4(joint, targets):
     T, U1, _ = joint.shape
     dev = joint.device
     return transducer_forward_score(joint[None], targets[None], torch.tensor([T], device=dev), torch.tensor([U1 - 1], device=dev))[0]
+
+
+class _TransducerLoss(torch.autograd.Function):
+    """csrc/rnnt_loss.hip around the lattice kernels: keeps f, g, lse [N, T, U+1], lp2 [N, T, U+1, 2], alpha and the losses."""
+
+    @staticmethod
+    def forward(ctx, f, g, targets, f_lengths, target_lengths):
+        fd, gd = _rows_fp32(f.detach()), _rows_fp32(g.detach())
+        lse, lp2 = ops.rnnt_joint_fwd(fd, gd, targets, f_lengths, target_lengths)
+        ones = torch.ones_like(targets)                # lp2 is a joint with K = 2: blank 0, the cell's own label 1
+        keep = f.requires_grad or g.requires_grad
+        losses, workspace = ops.transducer_fwd(lp2, ones, f_lengths, target_lengths, keep=keep, checked=True)
+        ctx.saved = (fd, gd, targets, ones, f_lengths, target_lengths, lse, lp2, workspace, losses) if keep else None
+        return losses.clone()
+
+    @staticmethod
+    def backward(ctx, grad_losses):
+        fd, gd, targets, ones, f_lengths, target_lengths, lse, lp2, workspace, losses = ctx.saved
+        d = ops.transducer_bwd(lp2, ones, f_lengths, target_lengths, workspace, losses, grad_losses.float().contiguous())
+        df, dg = ops.rnnt_joint_bwd(fd, gd, targets, f_lengths, target_lengths, lse, d)
+        return df, dg, None, None, None
+
+
+def _rows_fp32(x):
+    """fp32 rows with unit stride along the last dimension and rows that do not overlap; anything else (an expanded view, say) is copied."""
+    x = x.float()
+    return x if (x.shape[2] == 1 or x.stride(2) == 1) and _disjoint_rows(x) else x.contiguous()
+
+
+def _disjoint_rows(x):
+    """Rows V apart or more, nested batch-major (contiguous; [:, :, :V] of a wider buffer) or row-major (a transposed time-major tensor)."""
+    N, R, V = x.shape
+    ns, rs = x.stride(0), x.stride(1)
+    if (N > 1 and ns < V) or (R > 1 and rs < V):
+        return False
+    return N == 1 or R == 1 or ns >= (R - 1) * rs + V or rs >= (N - 1) * ns + V
+
+
+def transducer_loss(f, g, targets, f_lengths, target_lengths):
+    """f [N, T, V] transcription logits, g [N, U+1, V] prediction-network logits, targets [N, U], lengths [N] -> losses [N] =
+    transducer_forward_score((f[:, :, None] + g[:, None]).log_softmax(-1), targets, f_lengths, target_lengths), differentiable w.r.t. f
+    and g, without the [N, T, U+1, V] joint, its log-softmax or their gradients: every buffer is O(N T (U+1)) or the size of f / g.
+    f and g may be strided views with a contiguous last dimension (a slice of a wider buffer; the transposed time-major rows of
+    ``Decoder.forward_batch_first``): they are read, and g's gradient written, in place."""
+    if not f.is_cuda or not g.is_cuda:
+        raise _lib.HaloError('haloop_amd.transducer.transducer_loss runs on the HIP device only (no CPU path)')
+    dev = f.device
+    if f.dim() != 3 or g.dim() != 3 or f.shape[0] != g.shape[0] or f.shape[2] != g.shape[2]:
+        raise ValueError(f'transducer_loss: f must be [N, T, V] and g [N, U+1, V], got {tuple(f.shape)} and {tuple(g.shape)}')
+    N, U1 = g.shape[0], g.shape[1]
+    if tuple(targets.shape) != (N, U1 - 1):
+        raise ValueError(f'targets must be [N, U] = [{N}, {U1 - 1}], got {tuple(targets.shape)}')
+    fl = f_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    tl = target_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    return _TransducerLoss.apply(f, g, targets.to(device=dev, dtype=torch.int64).contiguous(), fl, tl)
 
 
 def _fused_default():

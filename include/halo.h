@@ -881,6 +881,34 @@ int halo_rnnt_lstm_cell(const float *xh, long ldx, int rows, int hidden, const v
                         float *c, float *h_next, long ld_next, float *h_up, long ld_up, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The RNN transducer's training loss over the additive joint z[n, t, u, k] = f[n, t, k] + g[n, u, k] (haloop_amd/transducer.py
+ * transducer_loss; the quantity of ha/recognizer.py:121-126, rnnt_loss(..., fused_log_softmax=True)) without a tensor of N T U1 V elements:
+ * halo_rnnt_joint_fwd, then halo_transducer_fwd / halo_transducer_bwd on lp2 as a joint with K = 2 and targets of ones, then
+ * halo_rnnt_joint_bwd.  f [N][T][V] and g [N][U1][V] are fp32 with unit stride along V and an n stride and a row stride in floats (rows
+ * may not overlap: a transposed view of time-major rows is fine); targets [N][U1 - 1] (labels outside [0, V) are treated as absent, never
+ * indexed); f_lengths / target_lengths [N] int32, clamped to [0, T] / [0, U1 - 1].  Exact fp32 in every math mode.  Limits: 1 <= N <= 65535,
+ * T >= 1, 2 <= U1 <= 7679 (the lattice kernels' bound), 1 <= V <= 8192.  Every launch is finite (no grid barrier, no polling) and no
+ * workgroup reads what another workgroup of its launch writes.
+ *   halo_rnnt_joint_fwd  for every cell t < f_lengths[n], u <= target_lengths[n]: lse[n][t][u] = log sum_k exp(z[k]), computed against the
+ *                        cell's own maximum; lp2[n][t][u][0] = z[0] - lse; lp2[n][t][u][1] = z[targets[n][u]] - lse for
+ *                        u < target_lengths[n], else 0.  Every other cell of lse [N][T][U1] and lp2 [N][T][U1][2] is written as 0 (a
+ *                        finite fill: the lattice's alpha sweep walks those cells, nothing reads them as data).
+ *   halo_rnnt_joint_bwd  with (gb, gy) = grad_lp2[n][t][u][0 .. 1] (halo_transducer_bwd's output) and p[k] = exp(z[k] - lse[n][t][u]), the
+ *                        gradient at the joint logit is dz[k] = gb [k == 0] + gy [k == targets[n][u]] - (gb + gy) p[k]; it is never stored:
+ *                        df[n][t][k] = sum_u dz[k] (in u order) and dg[n][u][k] = sum_t dz[k] (in t order), over the cells inside the
+ *                        lengths.  Two launches, each recomputing p; every output element is summed by one thread in a fixed order (no
+ *                        atomics: bit-reproducible from run to run).  Rows t >= f_lengths[n] of df and u > target_lengths[n] of dg are
+ *                        written as zeros.  df and dg are written through their own strides (same rules as f and g; they may not alias
+ *                        f, g, lse or grad_lp2). */
+int halo_rnnt_joint_fwd(const float *f, long f_n_stride, long f_t_stride, const float *g, long g_n_stride, long g_u_stride, int N, int T,
+                        int U1, int V, const int64_t *targets, const int *f_lengths, const int *target_lengths, float *lse, float *lp2,
+                        halo_stream_t stream);
+int halo_rnnt_joint_bwd(const float *f, long f_n_stride, long f_t_stride, const float *g, long g_n_stride, long g_u_stride, int N, int T,
+                        int U1, int V, const int64_t *targets, const int *f_lengths, const int *target_lengths, const float *lse,
+                        const float *grad_lp2, float *df, long df_n_stride, long df_t_stride, float *dg, long dg_n_stride,
+                        long dg_u_stride, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Backward operators of the GPT / transformer training step (the autograd graph of ha/attention.py:205-232 as
  * `hal` runs it, ha/attention_loop.py:196-215: loss.backward()).
  *   halo_attention_bwd         gradient of halo_attention_fwd: dq, dk, dv (same row layouts as q, k, v; written, not
