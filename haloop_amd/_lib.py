@@ -181,6 +181,9 @@ SIGNATURES = {
     'halo_decode_token': (_i, [_vp, _l, _i, _i, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     'halo_rnnt_advance': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _vp, _i, _vp, _l, _vp, _vp]),
     'halo_rnnt_lstm_cell': (_i, [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp]),
+    'halo_rnnt_beam_step': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'halo_rnnt_beam_keep': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp]),
     'halo_rnnt_joint_fwd': (_i, [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_rnnt_joint_bwd': (_i, [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _vp, _l, _l, _vp]),
     'halo_gpt_decode_linear_supported': (_i, [_i, _i]),

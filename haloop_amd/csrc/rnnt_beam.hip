@@ -1,0 +1,325 @@
+// Beam search of the RNN transducer head (haloop_amd/transducer.py BeamDecoder): alignment-length synchronous decoding with exact
+// merging ([Saon20]).  Every hypothesis of a row alive at alignment step i has consumed t frames and emitted u symbols with
+// t + u = i, so hypotheses that spell the same tokens sit at the same frame and merge by logaddexp.  Per alignment step
+//   1. rnnt_beam_step_kernel  one workgroup per row: the log-sum-exp of F[n, t_j] + g_j over V for each live hypothesis j, the blank and
+//                             label candidates, the merge, the W best, the row's running W best complete hypotheses, the new beam's
+//                             records, and (the gather) every new slot's [x | h_prev] rows and c from its parent's copy
+//   2. one halo_rnnt_lstm_cell per LSTM layer and halo_decode_linear (out_layer) on all N * W slots (csrc/rnnt_decode.hip, csrc/decode.hip)
+//   3. rnnt_beam_keep_kernel  a blank-extended slot takes (h, c, g) of its parent back
+// The state (h and c of every layer, g) is double-buffered by step parity: launch 1 and 3 read the copy of this step, which no launch of
+// the step writes, and write only the slots of their own row / their own slot of the other copy.  The W best are taken in W rounds of a
+// workgroup-wide arg-max over the candidates behind the last one taken, in the total order (score descending, candidate position
+// ascending): no list of W * V candidates is built.  The row's W * V joint logits are kept in LDS when they are 32 KiB or less (the
+// rounds then read LDS) and recomputed from L2 in every round otherwise, by the same operations: the same bits either way.  Besides
+// that LDS holds W-sized records only (< 1 KiB).  Every sum has a fixed order and no score goes through an atomic: the launch is
+// bit-reproducible.
+#include "halo_common.h"
+#include "halo_internal.h"
+
+namespace {
+
+constexpr int BEAM_MAX = 16, BEAM_THREADS = 256, BEAM_WAVES = BEAM_THREADS / 64;
+
+struct RnntBeamArgs {
+    const float *f;            // [N][T][V] transcription logits, strides f_rs (row) and f_ts (frame)
+    long f_rs, f_ts;
+    int T, V;
+    const float *g, *g_bias;   // [N * W][ldg] prediction logits of every slot without their bias; the bias [V] (may be NULL)
+    long ldg;
+    const int *il;             // [N] frames of each row (clipped to [0, T] here)
+    int step, W, capacity;
+    const float *score_in;     // the beam this step reads: [N][W] scores, [N][W] symbols emitted (-1: no hypothesis), [N][W][tok_ld]
+    const int *u_in, *tok_in;
+    float *score_out;          // the beam it writes
+    int *u_out, *tok_out;
+    long tok_ld;
+    int *parent, *last;        // [N][W] of the new beam: the parent's slot within the row (-1: no hypothesis), the new token (0: blank)
+    float *fin_score;          // [N][W] the row's best complete hypotheses, unordered: score, order of appending, length (-1: none)
+    int *fin_seq, *fin_len, *fin_tok, *fin_n;    // tokens [N][W][tok_ld]; fin_n [N]: hypotheses completed so far
+    const float *wte;          // [V][H] the embedding
+    int H, layers;
+    const float *h_in, *c_in;  // [layers][N * W][H] this step's state
+    float *xh, *c_out;         // [layers][N * W][2 H] = x | h_prev of the cells; [layers][N * W][H] the next state's c, before the cells
+    int *live;                 // one word: += 1 per row whose new beam is not empty
+    int cached;                // the row's W V joint logits are kept in LDS (BEAM_LDS_FLOATS or fewer), else recomputed from L2
+};
+
+constexpr int BEAM_LDS_FLOATS = 8192;      // 32 KiB of dynamic LDS, under the 64 KiB a launch gets without the opt-in
+
+__device__ __forceinline__ float logaddexpf_(float a, float b) {
+    const float m = fmaxf(a, b);
+    return m == -INFINITY ? m : m + log1pf(expf(-fabsf(a - b)));
+}
+
+// (sc, pos) stands before (osc, opos) in the order (score descending, position ascending)
+__device__ __forceinline__ bool before(float sc, int pos, float osc, int opos) { return sc > osc || (sc == osc && pos < opos); }
+
+__global__ __launch_bounds__(BEAM_THREADS) void rnnt_beam_step_kernel(const RnntBeamArgs p) {
+    __shared__ float s_score[BEAM_MAX], s_lse[BEAM_MAX], s_blank[BEAM_MAX], s_msc[BEAM_MAX], s_fsc[BEAM_MAX], sel_sc[BEAM_MAX];
+    __shared__ int s_u[BEAM_MAX], s_mj[BEAM_MAX], s_mk[BEAM_MAX], s_nm[BEAM_MAX], s_fseq[BEAM_MAX], s_flen[BEAM_MAX], s_fsrc[BEAM_MAX],
+        sel_pos[BEAM_MAX];
+    __shared__ float r_sc[2][BEAM_WAVES];
+    __shared__ int r_pos[2][BEAM_WAVES];
+    extern __shared__ float zs[];                                      // cached: z[j][v] = F[n, t_j, v] + (g_j[v] + bias[v])
+    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = p.W, V = p.V;
+    const long base = (long)n * W;
+    const int L = min(max(p.il[n], 0), p.T);
+    if (tid < BEAM_MAX) {
+        int u = -1;
+        float sc = -INFINITY;
+        if (tid < W) {
+            if (p.step == 0) {
+                if (tid == 0 && L > 0) { u = 0; sc = 0.f; }            // the empty hypothesis
+            } else {
+                u = p.u_in[base + tid];
+                sc = p.score_in[base + tid];
+            }
+            const int t = p.step - u;
+            if (u < 0 || u > p.capacity || t < 0 || t >= L) u = -1;    // t < L holds under the host's loop; never read a frame past it
+            if (p.step == 0) {                                         // the row's finals: none, or the empty one of a row of no frames
+                const bool empty = tid == 0 && L == 0;
+                s_fsc[tid] = empty ? 0.f : -INFINITY; s_fseq[tid] = 0; s_flen[tid] = empty ? 0 : -1;
+            } else {
+                s_fsc[tid] = p.fin_score[base + tid]; s_fseq[tid] = p.fin_seq[base + tid]; s_flen[tid] = p.fin_len[base + tid];
+            }
+        }
+        s_u[tid] = u; s_score[tid] = sc; s_mj[tid] = -1; s_nm[tid] = 0; s_fsrc[tid] = -1;
+    }
+    __syncthreads();
+    // the joint logit of hypothesis j (live) at v: the same operations whether it is read back from LDS or recomputed, so the same bits
+    auto logit = [&](int j, int v) {
+        return p.f[(long)n * p.f_rs + (long)(p.step - s_u[j]) * p.f_ts + v] + (p.g[(base + j) * p.ldg + v] + (p.g_bias ? p.g_bias[v] : 0.f));
+    };
+    auto z = [&](int j, int v) { return p.cached ? zs[j * V + v] : logit(j, v); };
+    // ---- 1. wave w: log-sum-exp of hypotheses w, w + 4, ... (fixed order: the lane's stride, then the wave's butterfly)
+    for (int j = wave; j < W; j += BEAM_WAVES) {
+        if (s_u[j] < 0) continue;
+        float m = -INFINITY;
+        for (int v = lane; v < V; v += 64) {
+            const float x = logit(j, v);
+            if (p.cached) zs[j * V + v] = x;                           // (read back by this lane below, by the others after the barrier)
+            m = fmaxf(m, x);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        float s = 0.f;
+        for (int v = lane; v < V; v += 64) s += expf(z(j, v) - m);
+        const float lse = m + logf(wave_sum(s));
+        if (lane == 0) {
+            s_lse[j] = lse;
+            s_blank[j] = s_score[j] + (z(j, 0) - lse);
+        }
+    }
+    __syncthreads();
+    // ---- 2. the merge: the blank extension of s and the extension of j by s's last token spell the same tokens when y_j = y_s[:-1]
+    {
+        const int s = tid / BEAM_MAX, j = tid % BEAM_MAX;
+        if (s < W && j < W && s_u[s] >= 1 && s_u[j] == s_u[s] - 1 && p.step - s_u[s] + 1 < L) {
+            const int *ts = p.tok_in + (base + s) * p.tok_ld, *tj = p.tok_in + (base + j) * p.tok_ld;
+            bool eq = true;
+            for (int x = 0; x < s_u[j]; ++x) eq = eq && ts[x] == tj[x];
+            const int k = ts[s_u[s] - 1];
+            if (eq && k >= 1 && k < V) {
+                s_mj[s] = j; s_mk[s] = k;
+                s_msc[s] = s_score[j] + (z(j, k) - s_lse[j]);
+                atomicAdd(&s_nm[j], 1);                                // (an integer count: only zero / nonzero is used)
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < W && s_mj[tid] >= 0) s_blank[tid] = logaddexpf_(s_blank[tid], s_msc[tid]);
+    // ---- 3. complete hypotheses (the blank at the row's last frame), in beam order, into the running W best: a later one displaces the
+    //         worst kept (lowest score, the latest among equals) only with a strictly higher score
+    if (tid == 0) {
+        int cnt = p.step == 0 ? (L == 0 ? 1 : 0) : p.fin_n[n];
+        bool any = p.step == 0;
+        for (int j = 0; j < W; ++j) {
+            if (s_u[j] < 0 || p.step - s_u[j] + 1 != L) continue;
+            const float sc = s_blank[j];
+            int slot = -1;
+            for (int w = 0; w < W && slot < 0; ++w) if (s_flen[w] < 0) slot = w;
+            if (slot < 0) {
+                int worst = 0;
+                for (int w = 1; w < W; ++w)
+                    if (s_fsc[w] < s_fsc[worst] || (s_fsc[w] == s_fsc[worst] && s_fseq[w] > s_fseq[worst])) worst = w;
+                if (sc > s_fsc[worst]) slot = worst;
+            }
+            if (slot >= 0) { s_fsc[slot] = sc; s_fseq[slot] = cnt; s_flen[slot] = s_u[j]; s_fsrc[slot] = j; }
+            cnt += 1; any = true;
+        }
+        if (any) p.fin_n[n] = cnt;
+    }
+    __syncthreads();
+    if (tid < W && (p.step == 0 || s_fsrc[tid] >= 0)) {
+        p.fin_score[base + tid] = s_fsc[tid]; p.fin_seq[base + tid] = s_fseq[tid]; p.fin_len[base + tid] = s_flen[tid];
+    }
+    for (int w = 0; w < W; ++w) {
+        const int j = s_fsrc[w];
+        if (j < 0) continue;
+        for (int x = tid; x < s_u[j]; x += BEAM_THREADS) p.fin_tok[(base + w) * p.tok_ld + x] = p.tok_in[(base + j) * p.tok_ld + x];
+    }
+    // ---- 4. the W best candidates, one per round: the first in the order among those behind the last one taken.  Positions: the blank
+    //         extension of j at j, the extension of j by k at W + j V + k.
+    float psc = INFINITY;
+    int ppos = -1, nsel = 0;
+    for (int r = 0; r < W; ++r) {
+        float bsc = -INFINITY;
+        int bpos = 0x7fffffff;
+        if (tid < W && s_u[tid] >= 0 && p.step - s_u[tid] + 1 != L) {
+            const float sc = s_blank[tid];
+            if (before(psc, ppos, sc, tid)) { bsc = sc; bpos = tid; }
+        }
+        for (int j = 0; j < W; ++j) {
+            if (s_u[j] < 0 || s_u[j] >= p.capacity) continue;
+            const float sj = s_score[j], lse = s_lse[j];
+            const bool merged = s_nm[j] != 0;
+            for (int k = 1 + tid; k < V; k += BEAM_THREADS) {
+                const float sc = sj + (z(j, k) - lse);
+                const int pos = W + j * V + k;
+                if (!before(psc, ppos, sc, pos) || !before(sc, pos, bsc, bpos)) continue;
+                if (merged) {
+                    bool gone = false;
+                    for (int s = 0; s < W; ++s) gone = gone || (s_mj[s] == j && s_mk[s] == k);
+                    if (gone) continue;
+                }
+                bsc = sc; bpos = pos;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float osc = __shfl_xor(bsc, o, 64);
+            const int opos = __shfl_xor(bpos, o, 64);
+            if (before(osc, opos, bsc, bpos)) { bsc = osc; bpos = opos; }
+        }
+        if (lane == 0) { r_sc[r & 1][wave] = bsc; r_pos[r & 1][wave] = bpos; }
+        __syncthreads();
+        bsc = r_sc[r & 1][0]; bpos = r_pos[r & 1][0];
+#pragma unroll
+        for (int w = 1; w < BEAM_WAVES; ++w)
+            if (before(r_sc[r & 1][w], r_pos[r & 1][w], bsc, bpos)) { bsc = r_sc[r & 1][w]; bpos = r_pos[r & 1][w]; }
+        if (bpos == 0x7fffffff) break;                                  // (uniform) no candidate is left
+        if (tid == 0) { sel_sc[r] = bsc; sel_pos[r] = bpos; }
+        psc = bsc; ppos = bpos; nsel = r + 1;
+    }
+    __syncthreads();
+    // ---- 5. the new beam's records
+    if (tid < W) {
+        int par = -1, k = 0, u = -1;
+        float sc = -INFINITY;
+        if (tid < nsel) {
+            const int pos = sel_pos[tid];
+            par = pos < W ? pos : (pos - W) / V;
+            k = pos < W ? 0 : (pos - W) % V;
+            u = s_u[par] + (k != 0);
+            sc = sel_sc[tid];
+        }
+        p.score_out[base + tid] = sc; p.u_out[base + tid] = u; p.parent[base + tid] = par; p.last[base + tid] = k;
+        s_mj[tid] = par < 0 ? tid : par; s_mk[tid] = k;                 // (reused) the gather's source: a slot without a hypothesis takes its own
+    }
+    if (nsel == 0) return;
+    __syncthreads();
+    if (tid == 0) atomicAdd(p.live, 1);
+    for (int idx = tid; idx < nsel * p.capacity; idx += BEAM_THREADS) {
+        const int r = idx / p.capacity, x = idx % p.capacity, par = s_mj[r], up = s_u[par];
+        if (x < up) p.tok_out[(base + r) * p.tok_ld + x] = p.tok_in[(base + par) * p.tok_ld + x];
+        else if (x == up && s_mk[r] != 0) p.tok_out[(base + r) * p.tok_ld + x] = s_mk[r];     // up < capacity: only such take labels
+    }
+    // ---- 6. the gather: slot r's cell inputs [wte[k] | h of its parent] and c of its parent, for every layer: 2 layers + 1 rows of H
+    //         floats per slot, all of the row's copies spread over the threads, four loads in flight per thread before their stores
+    const int H4 = p.H / 4, per = 2 * p.layers + 1, total = W * per * H4;
+    const long slots = (long)gridDim.x * W;
+    constexpr int GU = 4;
+    for (int i0 = tid; i0 < total; i0 += GU * BEAM_THREADS) {
+        f32x4 v[GU];
+        f32x4 *dst[GU];
+#pragma unroll
+        for (int e = 0; e < GU; ++e) {
+            const int idx = i0 + e * BEAM_THREADS;
+            dst[e] = nullptr;
+            if (idx >= total) continue;
+            const int r = idx / (per * H4), q = idx / H4 % per, x = idx % H4, par = s_mj[r];
+            if (q < p.layers) {                                         // h of layer q -> the h half of its [x | h] row
+                v[e] = reinterpret_cast<const f32x4 *>(p.h_in + ((long)q * slots + base + par) * p.H)[x];
+                dst[e] = reinterpret_cast<f32x4 *>(p.xh + ((long)q * slots + base + r) * 2 * p.H) + H4 + x;
+            } else if (q < 2 * p.layers) {                              // c of layer q - layers
+                v[e] = reinterpret_cast<const f32x4 *>(p.c_in + ((long)(q - p.layers) * slots + base + par) * p.H)[x];
+                dst[e] = reinterpret_cast<f32x4 *>(p.c_out + ((long)(q - p.layers) * slots + base + r) * p.H) + x;
+            } else {                                                    // the new token's embedding -> layer 0's x half
+                v[e] = reinterpret_cast<const f32x4 *>(p.wte + (long)s_mk[r] * p.H)[x];
+                dst[e] = reinterpret_cast<f32x4 *>(p.xh + (base + r) * 2 * p.H) + x;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < GU; ++e)
+            if (dst[e]) *dst[e] = v[e];
+    }
+}
+
+struct RnntKeepArgs {
+    int W, V, H, layers;
+    long slots, ldg;
+    const int *parent, *last;
+    const float *h_in, *c_in, *g_in;
+    float *h_out, *c_out, *g_out;
+};
+
+// one workgroup per slot: a blank-extended hypothesis keeps its parent's state (the cells and out_layer ran on every slot)
+__global__ __launch_bounds__(BEAM_THREADS) void rnnt_beam_keep_kernel(const RnntKeepArgs p) {
+    const long slot = blockIdx.x;
+    const int par = p.parent[slot];
+    if (par < 0 || par >= p.W || p.last[slot] != 0) return;
+    const long src = slot / p.W * p.W + par;
+    const int H4 = p.H / 4;
+    for (int l = 0; l < p.layers; ++l) {
+        const f32x4 *hs = reinterpret_cast<const f32x4 *>(p.h_in + ((long)l * p.slots + src) * p.H);
+        const f32x4 *cs = reinterpret_cast<const f32x4 *>(p.c_in + ((long)l * p.slots + src) * p.H);
+        f32x4 *hd = reinterpret_cast<f32x4 *>(p.h_out + ((long)l * p.slots + slot) * p.H);
+        f32x4 *cd = reinterpret_cast<f32x4 *>(p.c_out + ((long)l * p.slots + slot) * p.H);
+        for (int x = threadIdx.x; x < H4; x += BEAM_THREADS) { hd[x] = hs[x]; cd[x] = cs[x]; }
+    }
+    for (int v = threadIdx.x; v < p.V; v += BEAM_THREADS) p.g_out[slot * p.ldg + v] = p.g_in[src * p.ldg + v];
+}
+
+}  // namespace
+
+extern "C" {
+
+int halo_rnnt_beam_step(const float *f, long f_row_stride, long f_frame_stride, int N, int T, int V, const float *g, long ldg,
+                        const float *g_bias, const int *input_lengths, int step, int beam, int capacity, const float *scores_in,
+                        const int *u_in, const int *tokens_in, float *scores_out, int *u_out, int *tokens_out, long tokens_ld,
+                        int *parent, int *last, float *fin_scores, int *fin_seq, int *fin_lengths, int *fin_tokens, int *fin_n,
+                        const float *wte, int hidden, int layers, const float *h_in, const float *c_in, float *xh, float *c_out,
+                        int *live, halo_stream_t stream) {
+    HALO_CHECK_ARG(f && g && input_lengths && scores_in && u_in && tokens_in && scores_out && u_out && tokens_out && parent && last);
+    HALO_CHECK_ARG(fin_scores && fin_seq && fin_lengths && fin_tokens && fin_n && wte && h_in && c_in && xh && c_out && live);
+    HALO_CHECK_ARG(N > 0 && T > 0 && V > 0 && V <= 8192 && capacity > 0 && step >= 0 && beam >= 1 && beam <= BEAM_MAX);
+    HALO_CHECK_ARG(f_frame_stride >= V && f_row_stride >= (long)(T - 1) * f_frame_stride + V && ldg >= V && tokens_ld >= capacity);
+    HALO_CHECK_ARG(hidden > 0 && hidden % 4 == 0 && layers > 0);
+    HALO_CHECK_ARG(((uintptr_t)wte | (uintptr_t)h_in | (uintptr_t)c_in | (uintptr_t)xh | (uintptr_t)c_out) % 16 == 0);
+    HALO_CHECK_ARG(scores_in != scores_out && u_in != u_out && tokens_in != tokens_out && h_in != xh && c_in != c_out);
+    RnntBeamArgs p;
+    p.f = f; p.f_rs = f_row_stride; p.f_ts = f_frame_stride; p.T = T; p.V = V; p.g = g; p.g_bias = g_bias; p.ldg = ldg;
+    p.il = input_lengths; p.step = step; p.W = beam; p.capacity = capacity; p.score_in = scores_in; p.u_in = u_in; p.tok_in = tokens_in;
+    p.score_out = scores_out; p.u_out = u_out; p.tok_out = tokens_out; p.tok_ld = tokens_ld; p.parent = parent; p.last = last;
+    p.fin_score = fin_scores; p.fin_seq = fin_seq; p.fin_len = fin_lengths; p.fin_tok = fin_tokens; p.fin_n = fin_n; p.wte = wte;
+    p.H = hidden; p.layers = layers; p.h_in = h_in; p.c_in = c_in; p.xh = xh; p.c_out = c_out; p.live = live;
+    p.cached = (long)beam * V <= BEAM_LDS_FLOATS;
+    hipLaunchKernelGGL(rnnt_beam_step_kernel, dim3((unsigned)N), dim3(BEAM_THREADS), p.cached ? (size_t)beam * V * sizeof(float) : 0,
+                       (hipStream_t)stream, p);
+    return halo_launch_status();
+}
+
+int halo_rnnt_beam_keep(int slots, int beam, int V, int hidden, int layers, const int *parent, const int *last, const float *h_in,
+                        const float *c_in, const float *g_in, long ldg, float *h_out, float *c_out, float *g_out, halo_stream_t stream) {
+    HALO_CHECK_ARG(parent && last && h_in && c_in && g_in && h_out && c_out && g_out);
+    HALO_CHECK_ARG(slots > 0 && beam >= 1 && beam <= BEAM_MAX && slots % beam == 0 && V > 0 && ldg >= V && hidden > 0 && hidden % 4 == 0);
+    HALO_CHECK_ARG(layers > 0 && ((uintptr_t)h_in | (uintptr_t)c_in | (uintptr_t)h_out | (uintptr_t)c_out) % 16 == 0);
+    HALO_CHECK_ARG(h_in != h_out && c_in != c_out && g_in != g_out);
+    RnntKeepArgs p;
+    p.W = beam; p.V = V; p.H = hidden; p.layers = layers; p.slots = slots; p.ldg = ldg; p.parent = parent; p.last = last;
+    p.h_in = h_in; p.c_in = c_in; p.g_in = g_in; p.h_out = h_out; p.c_out = c_out; p.g_out = g_out;
+    hipLaunchKernelGGL(rnnt_beam_keep_kernel, dim3((unsigned)slots), dim3(BEAM_THREADS), 0, (hipStream_t)stream, p);
+    return halo_launch_status();
+}
+
+}  // extern "C"

@@ -1471,6 +1471,44 @@ def rnnt_lstm_cell(xh, image, b_ih, b_hh, c, h_next, h_up):
                                     ptr(h_up), h_up.stride(0), _stream()), 'halo_rnnt_lstm_cell')
 
 
+# ---- launches of the transducer's beam search (csrc/rnnt_beam.hip); none of these allocates ----------------------------------------
+def rnnt_beam_step(f, g, g_bias, input_lengths, step, capacity, rec_in, rec_out, parent, last, finals, wte, h_in, c_in, xh, c_out, live):
+    """One alignment step of every row (include/halo.h): f [N, T, V]; g [N * W, V] (bias apart); rec_in / rec_out = (scores [N, W] fp32,
+    u [N, W] int32, tokens [N, W, >= capacity] int32); parent / last [N, W] int32; finals = (scores, seq, lengths [N, W], tokens
+    [N, W, >= capacity], n [N]); h_in / c_in / c_out [layers, N * W, H], xh [layers, N * W, 2 H], all contiguous; live: one int32 word."""
+    N, T, V = f.shape
+    W = parent.shape[1]
+    layers, slots, H = h_in.shape
+    tensors = (g, *rec_in, *rec_out, parent, last, *finals, h_in, c_in, xh, c_out)
+    if f.stride(2) != 1 or not all(t.is_contiguous() for t in tensors):
+        raise ValueError('rnnt_beam_step: f must be contiguous along V and every other tensor contiguous')
+    if slots != N * W or g.shape != (slots, V) or wte.shape != (wte.shape[0], H) or wte.shape[0] < V or not wte.is_contiguous():
+        raise ValueError('rnnt_beam_step: g must be [N * W, V], the state [layers, N * W, H] and the embedding [>= V, H]')
+    if xh.shape != (layers, slots, 2 * H) or c_in.shape != h_in.shape or c_out.shape != h_in.shape:
+        raise ValueError('rnnt_beam_step: xh must be [layers, N * W, 2 H], c_in and c_out as h_in')
+    ld = rec_in[2].shape[2]
+    if any(t.shape != (N, W) for t in (rec_in[0], rec_in[1], rec_out[0], rec_out[1], parent, last, finals[0], finals[1], finals[2])) \
+            or any(t.shape != (N, W, ld) for t in (rec_in[2], rec_out[2], finals[3])) or finals[4].shape != (N,):
+        raise ValueError('rnnt_beam_step: records and finals must be [N, W] with tokens [N, W, ld]')
+    check(lib().halo_rnnt_beam_step(ptr(f), f.stride(0), f.stride(1), N, T, V, ptr(g), g.stride(0), ptr(g_bias), ptr(input_lengths), int(step), W,
+                                    int(capacity), ptr(rec_in[0]), ptr(rec_in[1]), ptr(rec_in[2]), ptr(rec_out[0]), ptr(rec_out[1]),
+                                    ptr(rec_out[2]), ld, ptr(parent), ptr(last), ptr(finals[0]), ptr(finals[1]), ptr(finals[2]),
+                                    ptr(finals[3]), ptr(finals[4]), ptr(wte), H, layers, ptr(h_in), ptr(c_in), ptr(xh), ptr(c_out), ptr(live),
+                                    _stream()), 'halo_rnnt_beam_step')
+
+
+def rnnt_beam_keep(parent, last, h_in, c_in, g_in, h_out, c_out, g_out):
+    """Blank-extended slots take their parent's h, c [layers, N * W, H] and g [N * W, V] from the step's input copy (include/halo.h)."""
+    N, W = parent.shape
+    layers, slots, H = h_in.shape
+    tensors = (parent, last, h_in, c_in, g_in, h_out, c_out, g_out)
+    if not all(t.is_contiguous() for t in tensors) or slots != N * W or g_in.shape[0] != slots or g_out.shape != g_in.shape \
+            or last.shape != parent.shape or any(t.shape != h_in.shape for t in (c_in, h_out, c_out)):
+        raise ValueError('rnnt_beam_keep: contiguous parent / last [N, W], state [layers, N * W, H] and g [N * W, V]')
+    check(lib().halo_rnnt_beam_keep(slots, W, g_in.shape[1], H, layers, ptr(parent), ptr(last), ptr(h_in), ptr(c_in), ptr(g_in), g_in.stride(0),
+                                    ptr(h_out), ptr(c_out), ptr(g_out), _stream()), 'halo_rnnt_beam_keep')
+
+
 # ---- channels-last conv front-end (ha/conv.py) -------------------------------------------------------------
 def conv_out_length(T, ks, stride, pad):
     return (T + 2 * pad - ks) // stride + 1

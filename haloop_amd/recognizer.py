@@ -8,7 +8,7 @@ from . import _lib, functional as HF, ops
 from .ctc import ctc_reduce_mean
 from .rnn import Decoder, DropoutStream
 from .star import star_ctc_forward_score
-from .transducer import GreedyDecoder, transducer_forward_score, transducer_loss
+from .transducer import BeamDecoder, GreedyDecoder, transducer_forward_score, transducer_loss
 
 
 class TemporalClassifier(nn.Module):
@@ -65,7 +65,11 @@ class Transducer(nn.Module):
 
     ``fused_loss`` (HALO_RNNT_LOSS_FUSED=1 when the head is built; a caller may set the attribute): the same losses from
     ``transducer.transducer_loss`` on the two factors of the joint, which builds no [N, T, U+1, V] tensor.  Off by
-    default."""
+    default.
+
+    ``beam_size`` (HALO_RNNT_BEAM when the head is built; a caller may set the attribute or pass ``decode(..., beam_size=W)``): 0, the
+    default, decodes greedily; W >= 1 runs ``transducer.BeamDecoder`` at that width, returns each row's best
+    hypothesis and keeps the whole n-best result of the last call as ``last_nbest``."""
 
     def __init__(self, feat_dim=1024, vocab_size=256):
         super().__init__()
@@ -74,8 +78,10 @@ class Transducer(nn.Module):
         self.dropout = nn.Dropout(0.2)
         self.dropout_stream = DropoutStream()
         self.fused_loss = os.environ.get('HALO_RNNT_LOSS_FUSED', '0') == '1'
+        self.beam_size = int(os.environ.get('HALO_RNNT_BEAM', '0'))
+        self.last_nbest = None
 
-    def decode(self, features, input_lengths, condtarget_lengths=None, prompt=None):
+    def decode(self, features, input_lengths, condtarget_lengths=None, prompt=None, beam_size=None):
         """The ``Decodable`` call (ha/recognizer.py:12-34, as ha/loop.py:295-303 makes it): greedy transducer search with room for
         ``condtarget_lengths.max() + 1`` symbols per row (the length guide ha/transformer.py:128 takes) ->
         (hypotheses nested_tensor, output_lengths, frames [N, capacity] (-1 past a row's length), scores, None), in the form
@@ -89,6 +95,9 @@ class Transducer(nn.Module):
         if self.training:
             raise NotImplementedError('Transducer.decode is an inference path: put the head in eval mode')
         N, capacity = features.shape[0], int(condtarget_lengths.max()) + 1
+        width = self.beam_size if beam_size is None else int(beam_size)
+        if width:
+            return self._decode_beam(features, input_lengths, N, capacity, width)
         dec = getattr(self, '_greedy_decoder', None)
         if dec is None or dec.max_batch < N or dec.capacity < capacity or dec._state.device != features.device:
             dec = GreedyDecoder(self, max(N, dec.max_batch if dec else 0), max(capacity, dec.capacity if dec else 0))
@@ -97,6 +106,22 @@ class Transducer(nn.Module):
         lens = lengths.tolist()
         hypotheses = torch.nested.nested_tensor([tokens[i, :n] for i, n in enumerate(lens)])
         return hypotheses, torch.tensor(lens), frames, scores, None
+
+    def _decode_beam(self, features, input_lengths, N, capacity, width):
+        """Beam search at ``width``: each row's best hypothesis in the five-value form (a merged hypothesis has no single alignment: the
+        third value is [None] * N); ``last_nbest`` = (tokens [N, W, capacity], lengths [N, W], scores [N, W], counts [N])."""
+        if width < 0:
+            raise ValueError(f'Transducer.decode: beam_size {width} is negative')
+        dec = getattr(self, '_beam_decoder', None)
+        if dec is None or dec.max_batch < N or dec.capacity < capacity or dec.beam < width or dec._device != features.device:
+            dec = BeamDecoder(self, max(N, dec.max_batch if dec else 0), max(capacity, dec.capacity if dec else 0),
+                              max(width, dec.beam if dec else 0))
+            self._beam_decoder = dec
+        self.last_nbest = dec.decode(features, input_lengths, capacity, width)
+        tokens, lengths, scores, _ = self.last_nbest
+        lens = lengths[:, 0].tolist()                           # every row returns at least one hypothesis
+        hypotheses = torch.nested.nested_tensor([tokens[i, 0, :n] for i, n in enumerate(lens)])
+        return hypotheses, torch.tensor(lens), [None] * N, scores[:, 0].clone(), None
 
     def forward(self, features, targets, input_lengths=None, target_lengths=None, star_penalty=None):   # star_penalty: ignored (:101)
         if not features.is_cuda:

@@ -21,6 +21,9 @@ either direction.
 prediction network.  The score is the sum of the log-probabilities of every move.  The fused path (csrc/rnnt_decode.hip) costs
 ``1 + num_layers + 1`` launches per emitted symbol and none per blank frame; the general path runs the same search node by node on
 ``rnn.Decoder.forward`` at T = 1 with torch's log_softmax.
+
+``BeamDecoder`` is beam search for the same head: alignment-length synchronous decoding with exact merging ([Saon20]), n-best lists whose
+scores sum the alignment paths of a hypothesis, on ``num_layers + 3`` launches per alignment step (csrc/rnnt_beam.hip).
 """
 import os
 
@@ -126,34 +129,9 @@ def _fused_default():
     return os.environ.get('HALO_RNNT_FUSED', '1') != '0'
 
 
-class GreedyDecoder:
-    """Greedy search for a ``recognizer.Transducer`` head with preallocated row state and buffers for ``max_batch`` rows and
-    ``capacity`` symbols per row.  ``max_symbols_per_frame`` bounds the symbols emitted at one frame (a guard that a trained model does
-    not meet; it bounds an untrained one)."""
-
-    def __init__(self, head, max_batch, capacity, max_symbols_per_frame=10):
-        self.head = head
-        self.max_batch, self.capacity, self.max_symbols = int(max_batch), int(capacity), int(max_symbols_per_frame)
-        if self.max_batch < 1 or self.capacity < 1 or self.max_symbols < 1:
-            raise ValueError('GreedyDecoder: need max_batch >= 1, capacity >= 1 and max_symbols_per_frame >= 1')
-        lm = head.lm
-        E, H, L, V = lm.embedding.weight.shape[1], lm.hidden_dim, lm.num_layers, lm.num_classes
-        dev = lm.embedding.weight.device
-        mb = self.max_batch
-        with torch.inference_mode(False):          # ordinary tensors: they are updated in place inside and outside inference mode
-            self._state = torch.zeros(5, mb, device=dev, dtype=torch.int32)      # t | u | here | done | truncated, one word per row
-            self._scores = torch.zeros(mb, device=dev, dtype=torch.float32)
-            self._tokens = torch.zeros(mb, self.capacity, device=dev, dtype=torch.int64)
-            self._frames = torch.zeros(mb, self.capacity, device=dev, dtype=torch.int64)
-            self._live = torch.zeros(self.capacity, device=dev, dtype=torch.int32)   # one word per advance: rows still live after it
-            if E == H:
-                # [x | h_prev] rows of every layer, in two copies used alternately: a cell launch reads one and writes the other's h
-                self._xh = torch.zeros(2, L, mb, 2 * H, device=dev, dtype=torch.float32)
-                self._c = torch.zeros(L, mb, H, device=dev, dtype=torch.float32)
-                self._top = torch.zeros(mb, H, device=dev, dtype=torch.float32)
-                self._g = torch.zeros(mb, V, device=dev, dtype=torch.float32)
-        self._images = None    # (stamp, per-layer gate images, out_layer image)
-        self.iterations = 0    # of the last decode: advances (fused path) or lattice nodes visited in lockstep (general path)
+class _HeadDecoder:
+    """What the decoders of a ``recognizer.Transducer`` head share: when the fused launches apply, and the decode images of the
+    prediction network (``self.head``; ``self._images`` = None or (stamp, per-layer gate images, out_layer image))."""
 
     @property
     def fused(self):
@@ -184,17 +162,48 @@ class GreedyDecoder:
         return self._images[1], self._images[2]
 
     def _check(self, features, input_lengths):
+        name = type(self).__name__
         if features.dim() != 3 or features.shape[1] < 1:
-            raise ValueError('GreedyDecoder: features must be [N, T, feat_dim] with T >= 1')
+            raise ValueError(f'{name}: features must be [N, T, feat_dim] with T >= 1')
         N = features.shape[0]
         if N < 1 or N > self.max_batch:
-            raise ValueError(f'GreedyDecoder: batch {N} outside 1 .. max_batch = {self.max_batch}')
+            raise ValueError(f'{name}: batch {N} outside 1 .. max_batch = {self.max_batch}')
         if input_lengths.shape != (N,):
-            raise ValueError(f'GreedyDecoder: input_lengths must be [{N}]')
+            raise ValueError(f'{name}: input_lengths must be [{N}]')
         if not features.is_cuda:
-            raise _lib.HaloError('haloop_amd.transducer.GreedyDecoder runs on the HIP device only (no CPU path)')
+            raise _lib.HaloError(f'haloop_amd.transducer.{name} runs on the HIP device only (no CPU path)')
         if self.head.training:
-            raise NotImplementedError('GreedyDecoder is an inference path: put the head in eval mode')
+            raise NotImplementedError(f'{name} is an inference path: put the head in eval mode')
+
+
+class GreedyDecoder(_HeadDecoder):
+    """Greedy search for a ``recognizer.Transducer`` head with preallocated row state and buffers for ``max_batch`` rows and
+    ``capacity`` symbols per row.  ``max_symbols_per_frame`` bounds the symbols emitted at one frame (a guard that a trained model does
+    not meet; it bounds an untrained one)."""
+
+    def __init__(self, head, max_batch, capacity, max_symbols_per_frame=10):
+        self.head = head
+        self.max_batch, self.capacity, self.max_symbols = int(max_batch), int(capacity), int(max_symbols_per_frame)
+        if self.max_batch < 1 or self.capacity < 1 or self.max_symbols < 1:
+            raise ValueError('GreedyDecoder: need max_batch >= 1, capacity >= 1 and max_symbols_per_frame >= 1')
+        lm = head.lm
+        E, H, L, V = lm.embedding.weight.shape[1], lm.hidden_dim, lm.num_layers, lm.num_classes
+        dev = lm.embedding.weight.device
+        mb = self.max_batch
+        with torch.inference_mode(False):          # ordinary tensors: they are updated in place inside and outside inference mode
+            self._state = torch.zeros(5, mb, device=dev, dtype=torch.int32)      # t | u | here | done | truncated, one word per row
+            self._scores = torch.zeros(mb, device=dev, dtype=torch.float32)
+            self._tokens = torch.zeros(mb, self.capacity, device=dev, dtype=torch.int64)
+            self._frames = torch.zeros(mb, self.capacity, device=dev, dtype=torch.int64)
+            self._live = torch.zeros(self.capacity, device=dev, dtype=torch.int32)   # one word per advance: rows still live after it
+            if E == H:
+                # [x | h_prev] rows of every layer, in two copies used alternately: a cell launch reads one and writes the other's h
+                self._xh = torch.zeros(2, L, mb, 2 * H, device=dev, dtype=torch.float32)
+                self._c = torch.zeros(L, mb, H, device=dev, dtype=torch.float32)
+                self._top = torch.zeros(mb, H, device=dev, dtype=torch.float32)
+                self._g = torch.zeros(mb, V, device=dev, dtype=torch.float32)
+        self._images = None    # (stamp, per-layer gate images, out_layer image)
+        self.iterations = 0    # of the last decode: advances (fused path) or lattice nodes visited in lockstep (general path)
 
     def decode(self, features, input_lengths, capacity=None):
         """features [N, T, feat_dim], input_lengths [N] (clipped to T) -> (tokens [N, capacity] int64, lengths [N] int64, frames
@@ -278,3 +287,198 @@ class GreedyDecoder:
         st = self._state
         st[0, :N], st[1, :N], st[2, :N], st[3, :N], st[4, :N] = t.int(), u.int(), here.int(), 1, (u >= cap).int()
         self._scores[:N] = scores
+
+
+BEAM_MAX = 16            # csrc/rnnt_beam.hip keeps a row's records in LDS arrays of this many entries
+
+
+class BeamDecoder(_HeadDecoder):
+    """Beam search for a ``recognizer.Transducer`` head: alignment-length synchronous decoding with exact merging ([Saon20] Saon,
+    Tueske, Audhkhasi, ICASSP 2020), with preallocated buffers for ``max_batch`` rows, ``beam`` hypotheses per row and
+    ``capacity`` symbols per hypothesis.  Per row, with F = classifier(features), L = clamp(input_lengths, 0, T), W = beam:
+
+        B = [the empty hypothesis, score 0, on the prediction network's output for the zero prefix of training]
+        for i in 0 .. L + capacity - 1, while B is not empty:        # hypothesis j stands at frame t_j = i - len(y_j) < L
+            lp_j = log_softmax(F[t_j] + g_j)
+            candidates: the blank extension of every j (complete at t_j + 1 == L: it joins the finals instead), then for every j with
+                        len(y_j) < capacity its extensions by k = 1 .. V-1; equal token sequences merge into the earliest (logaddexp)
+            B = the W best by (score descending, candidate position ascending)
+        the W best finals by (score descending, order of completion)
+
+    so a score sums the alignment paths the search kept of its hypothesis (all of them when nothing was pruned).  W = 1 is not greedy
+    search.  The fused path (csrc/rnnt_beam.hip) costs ``num_layers + 3`` launches per alignment step for the whole batch and reads one
+    word every ``SYNC_EVERY`` steps; the general path runs the same search on ``rnn.Decoder.forward`` at T = 1 over N * W rows with
+    torch operators, the candidates pruned on the host."""
+
+    def __init__(self, head, max_batch, capacity, beam=4):
+        self.head = head
+        self.max_batch, self.capacity, self.beam = int(max_batch), int(capacity), int(beam)
+        if self.max_batch < 1 or self.capacity < 1:
+            raise ValueError('BeamDecoder: need max_batch >= 1 and capacity >= 1')
+        if self.beam < 1 or self.beam > BEAM_MAX:
+            raise ValueError(f'BeamDecoder: beam {self.beam} outside 1 .. {BEAM_MAX}')
+        lm = head.lm
+        E, H, L, V = lm.embedding.weight.shape[1], lm.hidden_dim, lm.num_layers, lm.num_classes
+        dev = lm.embedding.weight.device
+        S, cap = self.max_batch * self.beam, self.capacity
+        i32 = dict(device=dev, dtype=torch.int32)
+        f32 = dict(device=dev, dtype=torch.float32)
+        with torch.inference_mode(False):          # ordinary tensors: they are updated in place inside and outside inference mode
+            if E == H:
+                # flat buffers, viewed per call at that call's N * W slots.  The beam's records and the state exist twice (step parity).
+                self._rec = [(torch.zeros(S, **f32), torch.zeros(S, **i32), torch.zeros(S * cap, **i32)) for _ in range(2)]
+                self._parent, self._last = torch.zeros(S, **i32), torch.zeros(S, **i32)
+                self._fin = (torch.zeros(S, **f32), torch.zeros(S, **i32), torch.zeros(S, **i32), torch.zeros(S * cap, **i32),
+                             torch.zeros(self.max_batch, **i32))
+                self._h, self._c = torch.zeros(2 * L * S * H, **f32), torch.zeros(2 * L * S * H, **f32)
+                self._g = torch.zeros(2 * S * V, **f32)
+                self._xh, self._top = torch.zeros(L * S * 2 * H, **f32), torch.zeros(S * H, **f32)
+                self._live = torch.zeros(64, **i32)                  # one word per alignment step; grown to T + capacity
+        self._device = dev      # of the buffers: a head moved since needs a new decoder
+        self._images = None
+        self.iterations = 0    # alignment steps of the last decode
+
+    def decode(self, features, input_lengths, capacity=None, beam=None):
+        """features [N, T, feat_dim], input_lengths [N] (clipped to T) -> (tokens [N, W, capacity] int64, -1 past a hypothesis's length
+        and in absent hypotheses; lengths [N, W] int64, -1: absent; scores [N, W] float32, best first, -inf: absent; counts [N] int64).
+        ``capacity`` / ``beam``: search with less room than the buffers hold (default: all of it)."""
+        self._check(features, input_lengths)
+        cap = self.capacity if capacity is None else int(capacity)
+        if cap < 1 or cap > self.capacity:
+            raise ValueError(f'BeamDecoder: capacity {cap} outside 1 .. {self.capacity}')
+        W = self.beam if beam is None else int(beam)
+        if W < 1 or W > BEAM_MAX or W > self.beam:
+            raise ValueError(f'BeamDecoder: beam {W} outside 1 .. {min(BEAM_MAX, self.beam)}')
+        with torch.no_grad():
+            N, T, _ = features.shape
+            cl = self.head.classifier
+            f = HF.linear(features.float(), cl.weight, cl.bias).contiguous()                   # [N, T, V]
+            il = input_lengths.to(device=features.device, dtype=torch.int32).clamp(0, T).contiguous()
+            scores, seq, lengths, tokens = (self._decode_fused if self.fused else self._decode_general)(f, il, N, W, cap)
+            # the finals by (score descending, order of completion): two stable sorts, absent hypotheses (length -1) last
+            absent = lengths < 0
+            o1 = torch.where(absent, torch.full_like(seq, 2 ** 31 - 1), seq).argsort(dim=1, stable=True)
+            key = torch.where(absent, torch.full_like(scores, float('inf')), -scores).gather(1, o1)
+            order = o1.gather(1, key.argsort(dim=1, stable=True))
+            lengths = lengths.gather(1, order).long()
+            scores = torch.where(lengths < 0, torch.full_like(scores, float('-inf')), scores.gather(1, order))
+            tokens = tokens[:, :, :cap].gather(1, order[:, :, None].expand(N, W, cap)).long()
+            past = torch.arange(cap, device=tokens.device)[None, None, :] >= lengths[:, :, None]
+            return tokens.masked_fill(past, -1), lengths, scores, (lengths >= 0).sum(1)
+
+    # ---- the fused path: num_layers + 3 launches per alignment step --------------------------------------------------------------------
+    def _cells(self, xh, c, h_out, top, g_out, layers, head_image):
+        """The prediction network on the [x | h_prev] rows of every slot: c [L, R, H] in place, h -> h_out [L, R, H] (and the x half of
+        the layer above / ``top``), out_layer -> g_out."""
+        lm = self.head.lm
+        H, L, w = lm.hidden_dim, lm.num_layers, lstm_param_list(lm.rnn)
+        for l in range(L):
+            h_up = xh[l + 1, :, :H] if l + 1 < L else top
+            ops.rnnt_lstm_cell(xh[l], layers[l], w[4 * l + 2], w[4 * l + 3], c[l], h_out[l], h_up)
+        ops.decode_linear(top, head_image, lm.num_classes, g_out)
+
+    def _decode_fused(self, f, il, N, W, cap):
+        lm = self.head.lm
+        layers, head_image = self._decode_images()
+        wte, H, L, V = lm.embedding.weight, lm.hidden_dim, lm.num_layers, lm.num_classes
+        R, ld, steps = N * W, self.capacity, f.shape[1] + cap
+        if self._live.numel() < steps:
+            self._live = torch.zeros(steps, device=self._live.device, dtype=torch.int32)
+        live = self._live[:steps]
+        live.zero_()
+        rec = [(s[:R].view(N, W), u[:R].view(N, W), t[:R * ld].view(N, W, ld)) for s, u, t in self._rec]
+        parent, last = self._parent[:R].view(N, W), self._last[:R].view(N, W)
+        fs, fq, fl, ft, fn = self._fin
+        fin = (fs[:R].view(N, W), fq[:R].view(N, W), fl[:R].view(N, W), ft[:R * ld].view(N, W, ld), fn[:N])
+        h, c = self._h[:2 * L * R * H].view(2, L, R, H), self._c[:2 * L * R * H].view(2, L, R, H)
+        g = self._g[:2 * R * V].view(2, R, V)
+        xh, top = self._xh[:L * R * 2 * H].view(L, R, 2 * H), self._top[:R * H].view(R, H)
+        xh.zero_(); c[0].zero_()
+        xh[0, :, :H] = wte[0]                                  # the zero prefix of training (recognizer.py:107), in every slot
+        self._cells(xh, c[0], h[0], top, g[0], layers, head_image)
+        for i in range(steps):                                 # a hypothesis at step i has t + u = i, t < L, u <= cap: none after L + cap
+            q = i & 1
+            ops.rnnt_beam_step(f, g[q], lm.out_layer.bias, il, i, cap, rec[q], rec[1 - q], parent, last, fin, wte, h[q], c[q], xh, c[1 - q],
+                               live[i:])
+            if i == steps - 1 or ((i + 1) % SYNC_EVERY == 0 and int(live[i].item()) == 0):
+                break
+            self._cells(xh, c[1 - q], h[1 - q], top, g[1 - q], layers, head_image)
+            ops.rnnt_beam_keep(parent, last, h[q], c[q], g[q], h[1 - q], c[1 - q], g[1 - q])
+        self.iterations = i + 1
+        if int(live[i].item()) != 0:
+            raise _lib.HaloError('BeamDecoder: rows still live after T + capacity alignment steps')
+        return fin[0].clone(), fin[1].clone(), fin[2].clone(), fin[3].clone()
+
+    # ---- the general path: the same search on rnn.Decoder.forward at T = 1 over N * W rows, pruned on the host ----------------------------
+    def _decode_general(self, f, il, N, W, cap):
+        lm = self.head.lm
+        dev, T, V = f.device, f.shape[1], f.shape[2]
+        R = N * W
+        Ls = il.tolist()
+        g, state = lm.forward(torch.zeros(1, R, device=dev, dtype=torch.int64), lm.init_hidden(R))
+        beams = [[((), 0.0)] if Ls[n] > 0 else [] for n in range(N)]          # hypothesis j of row n lives in slot n W + j
+        finals = [[((), 0.0)] if Ls[n] == 0 else [] for n in range(N)]
+        slot_row = torch.arange(R, device=dev) // W
+        self.iterations = 0
+        for i in range(T + cap):
+            if not any(beams):
+                break
+            self.iterations += 1
+            t = torch.zeros(R, dtype=torch.int64)
+            for n, B in enumerate(beams):
+                for j, (y, _) in enumerate(B):
+                    t[n * W + j] = i - len(y)
+            lp = torch.log_softmax(f[slot_row, t.to(dev)] + g, -1).double().cpu()       # one host read per alignment step
+            src, tok = torch.arange(R), torch.zeros(R, dtype=torch.int64)
+            for n, B in enumerate(beams):
+                if not B:
+                    continue
+                where = {y: j for j, (y, _) in enumerate(B)}
+                blank, labels, gone = [], [], []
+                for j, (y, s) in enumerate(B):
+                    blank.append(s + float(lp[n * W + j, 0]))
+                    labels.append(s + lp[n * W + j, 1:])
+                    gone.append(torch.zeros(V - 1, dtype=torch.bool))
+                complete = [i - len(y) + 1 == Ls[n] for y, _ in B]
+                for sidx, (y, _) in enumerate(B):            # the extension of y[:-1] by y[-1] merges into y's blank extension
+                    j = where.get(y[:-1]) if y and not complete[sidx] else None
+                    if j is not None:
+                        a, b = torch.tensor(blank[sidx], dtype=torch.float64), labels[j][y[-1] - 1]
+                        blank[sidx] = float(torch.logaddexp(a, b))
+                        gone[j][y[-1] - 1] = True
+                cand, vals = [], []                          # (parent, token) in candidate order, and their scores
+                for j, (y, _) in enumerate(B):
+                    if complete[j]:
+                        finals[n].append((y, blank[j]))
+                    else:
+                        cand.append((j, 0)); vals.append(torch.tensor([blank[j]], dtype=torch.float64))
+                for j, (y, _) in enumerate(B):
+                    if len(y) < cap:
+                        ks = (~gone[j]).nonzero().view(-1)
+                        cand += [(j, int(k) + 1) for k in ks]
+                        vals.append(labels[j][ks])
+                new = []
+                if cand:
+                    vals = torch.cat(vals)
+                    for a in torch.sort(-vals, stable=True).indices[:W].tolist():
+                        j, k = cand[a]
+                        src[n * W + len(new)], tok[n * W + len(new)] = n * W + j, k
+                        new.append((B[j][0] + ((k,) if k else ()), float(vals[a])))
+                beams[n] = new
+            if not any(beams):
+                break
+            src, tok = src.to(dev), tok.to(dev)
+            g, state = g[src], (state[0][:, src].contiguous(), state[1][:, src].contiguous())
+            g1, (h1, c1) = lm.forward(tok.view(1, R), state)
+            emit = tok != 0
+            g = torch.where(emit[:, None], g1, g)
+            state = (torch.where(emit[None, :, None], h1, state[0]), torch.where(emit[None, :, None], c1, state[1]))
+        scores = torch.full((N, W), float('-inf'), dtype=torch.float32)
+        seq, lengths = torch.zeros(N, W, dtype=torch.int32), torch.full((N, W), -1, dtype=torch.int32)
+        tokens = torch.zeros(N, W, cap, dtype=torch.int32)
+        for n, fin in enumerate(finals):
+            best = sorted(range(len(fin)), key=lambda a: (-fin[a][1], a))[:W]
+            for w, a in enumerate(best):
+                scores[n, w], seq[n, w], lengths[n, w] = fin[a][1], w, len(fin[a][0])
+                tokens[n, w, :len(fin[a][0])] = torch.tensor(fin[a][0], dtype=torch.int32)
+        return scores.to(dev), seq.to(dev), lengths.to(dev), tokens.to(dev)

@@ -881,6 +881,38 @@ int halo_rnnt_lstm_cell(const float *xh, long ldx, int rows, int hidden, const v
                         float *c, float *h_next, long ld_next, float *h_up, long ld_up, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Beam search of the RNN transducer head (haloop_amd/transducer.py BeamDecoder; alignment-length synchronous decoding with exact merging,
+ * [Saon20]) as a launch sequence: per alignment step one halo_rnnt_beam_step, one halo_rnnt_lstm_cell per LSTM layer and one
+ * halo_decode_linear on all N * beam slots, and one halo_rnnt_beam_keep.  Slot n * beam + r is hypothesis r of row n.  The beam's records
+ * (scores, symbols emitted, tokens) and the state (h and c [layers][N * beam][hidden], g [N * beam][ldg]) exist twice; a step reads one
+ * copy and writes the other, so no launch reads what another of its workgroups writes.
+ *   halo_rnnt_beam_step  one workgroup per row n of f [N][T][V].  Hypothesis j of the beam read (u_in[n][j] >= 0; at step 0 the records
+ *                        are not read: the beam is the empty hypothesis with score 0, or nothing when L = clamp(input_lengths[n], 0, T)
+ *                        is 0, and the row's finals are reset -- to the empty hypothesis with score 0 when L is 0) stands at frame
+ *                        t_j = step - u_j < L; lp_j = log_softmax(f[n, t_j] + g[slot j] + g_bias).  Candidates, in this order: the blank
+ *                        extension of every j (score + lp_j[0]; at t_j + 1 == L it is complete and goes to the finals instead), then for
+ *                        every j with u_j < capacity the extension by k = 1 .. V - 1.  The extension of j by k that spells the tokens of
+ *                        hypothesis s is merged into s's blank extension (logaddexp).  The `beam` best by (score descending, position
+ *                        ascending) become the new beam: scores_out, u_out, tokens_out [N][beam][tokens_ld], parent (the slot within the
+ *                        row it came from; -1: no hypothesis), last (the new token; 0: a blank extension).  The finals keep the row's
+ *                        `beam` best complete hypotheses, unordered: fin_scores (-inf: none), fin_seq (order of completion), fin_lengths
+ *                        (-1: none), fin_tokens [N][beam][tokens_ld], fin_n [N] (hypotheses completed so far); a later one displaces
+ *                        the worst kept only with a strictly higher score.  The gather: xh [layers][N * beam][2 hidden] of every new slot
+ *                        = wte[last] (layer 0's x half) | h_in of its parent (the h halves), c_out = c_in of its parent.  *live += 1 for
+ *                        every row whose new beam is not empty.  Frames at or past L are never read.  V <= 8192, beam <= 16, hidden % 4
+ *                        == 0; the sums have a fixed order: bit-reproducible.
+ *   halo_rnnt_beam_keep  one workgroup per slot: a slot with parent >= 0 and last == 0 takes h, c and g of its parent's slot from the
+ *                        copy the step read (h_in, c_in, g_in) into the copy the cells and out_layer wrote (h_out, c_out, g_out). */
+int halo_rnnt_beam_step(const float *f, long f_row_stride, long f_frame_stride, int N, int T, int V, const float *g, long ldg,
+                        const float *g_bias, const int *input_lengths, int step, int beam, int capacity, const float *scores_in,
+                        const int *u_in, const int *tokens_in, float *scores_out, int *u_out, int *tokens_out, long tokens_ld,
+                        int *parent, int *last, float *fin_scores, int *fin_seq, int *fin_lengths, int *fin_tokens, int *fin_n,
+                        const float *wte, int hidden, int layers, const float *h_in, const float *c_in, float *xh, float *c_out,
+                        int *live, halo_stream_t stream);
+int halo_rnnt_beam_keep(int slots, int beam, int V, int hidden, int layers, const int *parent, const int *last, const float *h_in,
+                        const float *c_in, const float *g_in, long ldg, float *h_out, float *c_out, float *g_out, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The RNN transducer's training loss over the additive joint z[n, t, u, k] = f[n, t, k] + g[n, u, k] (haloop_amd/transducer.py
  * transducer_loss; the quantity of ha/recognizer.py:121-126, rnnt_loss(..., fused_log_softmax=True)) without a tensor of N T U1 V elements:
  * halo_rnnt_joint_fwd, then halo_transducer_fwd / halo_transducer_bwd on lp2 as a joint with K = 2 and targets of ones, then
