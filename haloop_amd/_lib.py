@@ -186,6 +186,10 @@ SIGNATURES = {
     'halo_rnnt_beam_keep': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp]),
     'halo_rnnt_joint_fwd': (_i, [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_rnnt_joint_bwd': (_i, [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _vp, _l, _l, _vp]),
+    'halo_ctc_viterbi_workspace_bytes': (_sz, [_i, _i, _i]),
+    'halo_ctc_viterbi': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'halo_transducer_viterbi_workspace_bytes': (_sz, [_i, _i, _i]),
+    'halo_transducer_viterbi': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_gpt_decode_linear_supported': (_i, [_i, _i]),
     'halo_gpt_decode_linear': (_i, [_vp, _l, _i, _i, _vp, _f, _vp, _i, _vp, _l, _i, _vp]),
     'halo_gpt_decode_attention': (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _l, _vp]),

@@ -1,5 +1,8 @@
 """Drop-in for ha/ctc.py: the three CTC forward-score functions and ctc_reduce_mean, each a single
-launch of the wave-per-utterance alpha kernel with the flags that reproduce that variant."""
+launch of the wave-per-utterance alpha kernel with the flags that reproduce that variant.
+
+``ctc_viterbi`` is forced alignment, which the reference does not have: the best path of F.ctc_loss's lattice and its backtrace in one
+launch (csrc/viterbi.hip)."""
 import torch
 
 from . import _lib, ops
@@ -35,6 +38,33 @@ def ctc_forward_score3(emissions, targets, emission_lengths, target_lengths):
         em = em.contiguous()
     nll, _, _ = ops.ctc_fwd(em, True, targets.to(dev), emission_lengths.to(dev), target_lengths.to(dev), _SCORE3)
     return nll
+
+
+def ctc_viterbi(emissions, targets, emission_lengths, target_lengths):
+    """Forced alignment: emissions [T, N, C] log-probabilities (a strided view with a unit class stride is read in place, as
+    ctc_forward_score3 reads it), targets [N, S], emission_lengths [N] (None: T), target_lengths [N] ->
+
+        scores [N] float32       log-probability of the best alignment of the row's target, -inf when it has none
+        alignments [N, T] int64  the label of every frame (0 = blank), -1 at frames past the row's length and in infeasible rows
+        starts, ends [N, S] int32  first and last frame of every target token, -1 past the row's target length and in infeasible rows
+
+    over the lattice of ``functional.ctc_loss``.  Among equally good paths the result is fixed by the tie rules of include/halo.h
+    (stay, then s-1, then s-2; the final blank before the last label).  Not differentiable: the inputs are detached."""
+    if not emissions.is_cuda:
+        raise _lib.HaloError('haloop_amd.ctc.ctc_viterbi runs on the HIP device only (no CPU path)')
+    dev = emissions.device
+    em = emissions.detach().float()
+    if em.dim() != 3:
+        raise ValueError(f'ctc_viterbi: emissions must be [T, N, C], got {tuple(em.shape)}')
+    if em.stride(-1) != 1:
+        em = em.contiguous()
+    targets = targets.detach().to(dev)
+    S = targets.shape[1] if targets.dim() == 2 else -1
+    if S == 0:                                            # no token anywhere: one padding column the kernel never reads
+        targets = targets.new_zeros((targets.shape[0], 1))
+    il = None if emission_lengths is None else emission_lengths.to(dev)
+    scores, ali, starts, ends = ops.ctc_viterbi(em, True, targets, il, target_lengths.to(dev))
+    return (scores, ali, starts[:, :0], ends[:, :0]) if S == 0 else (scores, ali, starts, ends)
 
 
 def ctc_reduce_mean(losses, target_lengths):

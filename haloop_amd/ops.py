@@ -1269,11 +1269,11 @@ def star_ctc_bwd(em, targets, emission_lengths, target_lengths, star_penalty, wo
     return grad
 
 
-def _check_transducer(name, K, T, U1, targets, joint_lengths, target_lengths):
+def _check_transducer(name, K, T, U1, targets, joint_lengths, target_lengths, min_length=1):
     if targets.numel() and (int(targets.min()) < 0 or int(targets.max()) >= K):
         raise ValueError(f'{name}: target label out of range')
-    if joint_lengths.numel() and int(joint_lengths.min()) < 1:
-        raise ValueError(f'{name}: joint_lengths must be >= 1')
+    if joint_lengths.numel() and int(joint_lengths.min()) < min_length:
+        raise ValueError(f'{name}: joint_lengths must be >= {min_length}')
     _check_lengths(f'{name}: joint_lengths', joint_lengths, T)
     _check_lengths(f'{name}: target_lengths', target_lengths, U1 - 1)
 
@@ -1314,11 +1314,12 @@ def _check_rnnt_joint(f, g, targets):
     return N, T, U1, V
 
 
-def rnnt_joint_fwd(f, g, targets, f_lengths, target_lengths):
+def rnnt_joint_fwd(f, g, targets, f_lengths, target_lengths, min_length=1):
     """f [N, T, V], g [N, U+1, V] fp32 logits (row strides; unit stride along V), targets [N, U] int64, lengths [N] int32 ->
-    (lse [N, T, U+1], lp2 [N, T, U+1, 2]): the log-sum-exp of every cell of the additive joint and its blank / label log-probabilities."""
+    (lse [N, T, U+1], lp2 [N, T, U+1, 2]): the log-sum-exp of every cell of the additive joint and its blank / label log-probabilities.
+    ``min_length``: the smallest f_lengths entry accepted (the loss needs a frame; the aligner takes empty rows)."""
     N, T, U1, V = _check_rnnt_joint(f, g, targets)
-    _check_transducer('rnnt_joint', V, T, U1, targets, f_lengths, target_lengths)
+    _check_transducer('rnnt_joint', V, T, U1, targets, f_lengths, target_lengths, min_length)
     lse = torch.empty(N, T, U1, device=f.device, dtype=torch.float32)
     lp2 = torch.empty(N, T, U1, 2, device=f.device, dtype=torch.float32)
     check(lib().halo_rnnt_joint_fwd(ptr(f), f.stride(0), f.stride(1), ptr(g), g.stride(0), g.stride(1), N, T, U1, V, ptr(targets),
@@ -1339,6 +1340,52 @@ def rnnt_joint_bwd(f, g, targets, f_lengths, target_lengths, lse, grad_lp2):
                                     ptr(f_lengths), ptr(target_lengths), ptr(lse), ptr(grad_lp2), ptr(df), df.stride(0), df.stride(1),
                                     ptr(dg), dg.stride(0), dg.stride(1), _stream()), 'halo_rnnt_joint_bwd')
     return df, dg
+
+
+# ---- forced alignment: best paths of the two lattices and their backtraces (csrc/viterbi.hip) ---------------------------------------
+def ctc_viterbi(lp, time_major, targets, input_lengths, target_lengths):
+    """lp: [T,N,C] (time_major) or [N,T,C] fp32 log-probabilities, any strides with a unit class stride; targets [N,S] (S >= 1) ->
+    (scores [N] f32, alignments [N,T] int64, starts [N,S] int32, ends [N,S] int32) of F.ctc_loss's lattice (include/halo.h)."""
+    if lp.dtype != torch.float32 or lp.dim() != 3 or lp.stride(-1) != 1 or not lp.is_cuda:
+        raise ValueError('ctc_viterbi: log-probs must be a float32 HIP tensor of three dimensions with unit class stride')
+    if time_major:
+        T, N, Cn = lp.shape
+        st, sn = lp.stride(0), lp.stride(1)
+    else:
+        N, T, Cn = lp.shape
+        sn, st = lp.stride(0), lp.stride(1)
+    targets = _i64c(targets, 'targets')
+    if targets.dim() != 2 or targets.shape[0] != N or targets.shape[1] < 1:
+        raise ValueError(f'ctc_viterbi: targets must be [N, S >= 1] (padded) with N = {N}, got {tuple(targets.shape)}')
+    S = targets.shape[1]
+    tl = _i64c(target_lengths, 'target_lengths')
+    il = None if input_lengths is None else _i64c(input_lengths, 'input_lengths')
+    if tl.shape != (N,) or (il is not None and il.shape != (N,)):
+        raise ValueError(f'ctc_viterbi: lengths must be [{N}]')
+    dev = lp.device
+    ws = torch.empty(lib().halo_ctc_viterbi_workspace_bytes(T, N, S), device=dev, dtype=torch.uint8)
+    scores = torch.empty(N, device=dev, dtype=torch.float32)
+    ali = torch.empty(N, T, device=dev, dtype=torch.int64)
+    starts = torch.empty(N, S, device=dev, dtype=torch.int32)
+    ends = torch.empty(N, S, device=dev, dtype=torch.int32)
+    check(lib().halo_ctc_viterbi(ptr(lp), st, sn, T, N, Cn, ptr(targets), targets.stride(0), S, ptr(il), ptr(tl), ptr(ws), ptr(scores),
+                                 ptr(ali), ptr(starts), ptr(ends), _stream()), 'halo_ctc_viterbi')
+    return scores, ali, starts, ends
+
+
+def transducer_viterbi(joint, targets, joint_lengths, target_lengths, checked=False):
+    """joint [N, T, U+1, K] fp32 contiguous log-probabilities, targets [N, U] int64, lengths [N] int32 (a joint length of 0 is an empty
+    row) -> (scores [N] f32, frames [N, U] int32).  ``checked``: as ``transducer_fwd``."""
+    _f32c(joint, 'joint')
+    N, T, U1, K = joint.shape
+    if not checked:
+        _check_transducer('transducer_viterbi', K, T, U1, targets, joint_lengths, target_lengths, 0)
+    ws = torch.empty(lib().halo_transducer_viterbi_workspace_bytes(N, T, U1), device=joint.device, dtype=torch.uint8)
+    scores = torch.empty(N, device=joint.device, dtype=torch.float32)
+    frames = torch.empty(N, U1 - 1, device=joint.device, dtype=torch.int32)
+    check(lib().halo_transducer_viterbi(ptr(joint), N, T, U1, K, ptr(targets), ptr(joint_lengths), ptr(target_lengths), ptr(ws), ptr(scores),
+                                        ptr(frames), _stream()), 'halo_transducer_viterbi')
+    return scores, frames
 
 
 # ---- fused launches of a greedy decode step (csrc/decode.hip) -------------------------------------------------

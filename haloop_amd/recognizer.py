@@ -5,10 +5,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib, functional as HF, ops
-from .ctc import ctc_reduce_mean
+from .ctc import ctc_reduce_mean, ctc_viterbi
 from .rnn import Decoder, DropoutStream
 from .star import star_ctc_forward_score
-from .transducer import BeamDecoder, GreedyDecoder, transducer_forward_score, transducer_loss
+from .transducer import BeamDecoder, GreedyDecoder, transducer_align, transducer_forward_score, transducer_loss
 
 
 class TemporalClassifier(nn.Module):
@@ -34,6 +34,19 @@ class TemporalClassifier(nn.Module):
         hypotheses = torch.nested.nested_tensor([hyp[i, :n] for i, n in enumerate(lens)])
         output_lengths = torch.tensor(lens)
         return hypotheses, output_lengths, alignments, scores, None
+
+    def align(self, features, targets, input_lengths=None, target_lengths=None):
+        """Forced alignment of ``targets`` [N, S] to the frames of ``features`` [N, T, feat_dim] (lengths default to T and S as in
+        ``forward``): ``ctc.ctc_viterbi`` on this head's ``log_probs`` -> (scores [N], alignments [N, T], starts [N, S], ends [N, S]).
+        An inference path (eval mode only: alignment under dropout is not built); the reference has no aligner."""
+        if self.training:
+            raise NotImplementedError('TemporalClassifier.align is an inference path: put the head in eval mode')
+        N = features.shape[0]
+        if target_lengths is None:
+            target_lengths = torch.full((N,), targets.shape[1], dtype=torch.long)
+        with torch.no_grad():
+            logits = self.log_probs(features)
+            return ctc_viterbi(logits.permute(1, 0, 2), targets, input_lengths, target_lengths)
 
     def forward(self, features, targets, input_lengths=None, target_lengths=None, star_penalty=None,
                 measure_entropy=False):
@@ -122,6 +135,25 @@ class Transducer(nn.Module):
         lens = lengths[:, 0].tolist()                           # every row returns at least one hypothesis
         hypotheses = torch.nested.nested_tensor([tokens[i, 0, :n] for i, n in enumerate(lens)])
         return hypotheses, torch.tensor(lens), [None] * N, scores[:, 0].clone(), None
+
+    def align(self, features, targets, input_lengths, target_lengths, prompt=None):
+        """Forced alignment of ``targets`` [N, U]: the prediction network over the zero-prefixed targets and the classifier exactly as
+        ``forward`` runs them, then ``transducer.transducer_align`` on the two factors of the joint -> (scores [N], frames [N, U]: the
+        frame at which every target token is emitted, -1 past a row's target length).  An inference path (eval mode only)."""
+        if prompt is not None:
+            raise NotImplementedError('Transducer.align: prompts are not built')
+        if self.training:
+            raise NotImplementedError('Transducer.align is an inference path: put the head in eval mode')
+        if not features.is_cuda:
+            raise _lib.HaloError('haloop_amd.recognizer.Transducer runs on the HIP device only')
+        dev = features.device
+        N = features.shape[0]
+        with torch.no_grad():
+            targets = targets.to(dev)
+            lm_targets = torch.cat([targets.new_zeros((N, 1)), targets], dim=1)
+            lm_outputs, _ = self.lm.forward_batch_first(lm_targets, self.lm.init_hidden(N))
+            feats = HF.linear(features.float(), self.classifier.weight, self.classifier.bias)
+            return transducer_align(feats, lm_outputs, targets, input_lengths.to(dev), target_lengths.to(dev))
 
     def forward(self, features, targets, input_lengths=None, target_lengths=None, star_penalty=None):   # star_penalty: ignored (:101)
         if not features.is_cuda:

@@ -14,6 +14,10 @@ fused_log_softmax=True)``, ha/recognizer.py:121-126): csrc/rnnt_loss.hip compute
 log-probabilities, the lattice kernels run on those, and the backward rebuilds the softmax for df and dg -- no [N, T, U+1, V] tensor in
 either direction.
 
+``transducer_viterbi(joint, ...)`` and ``transducer_align(f, g, ...)`` are forced alignment on the same two routes (the dense joint;
+the two factors, no [N, T, U+1, V] tensor): the best path of the lattice and the frame at which it emits every target token
+(csrc/viterbi.hip).  The reference has neither.
+
 ``GreedyDecoder`` is greedy transducer search ([Graves12]) for ``recognizer.Transducer``, which the reference leaves unbuilt
 (ha/recognizer.py:92-93): per row, with F = classifier(features) and g the prediction network's logits for the symbols emitted so far
 (the zero prefix of training first), take k = argmax log_softmax(F[n, t] + g) (lowest index on ties; blank forced once
@@ -122,6 +126,44 @@ def transducer_loss(f, g, targets, f_lengths, target_lengths):
     fl = f_lengths.to(device=dev, dtype=torch.int32).contiguous()
     tl = target_lengths.to(device=dev, dtype=torch.int32).contiguous()
     return _TransducerLoss.apply(f, g, targets.to(device=dev, dtype=torch.int64).contiguous(), fl, tl)
+
+
+def transducer_viterbi(joint, targets, joint_lengths, target_lengths):
+    """Forced alignment on a dense joint: joint [N, T, U+1, K] log-probabilities ((f + g).log_softmax(-1)), targets [N, U],
+    joint_lengths [N] (0: an empty row), target_lengths [N] -> (scores [N] float32: the log-probability of the best alignment, -inf for an
+    empty row; frames [N, U] int32: the frame at which every target token is emitted -- ``GreedyDecoder``'s ``frames`` -- and -1 past the
+    row's target length).  Among equally good paths the blank arc is taken first (include/halo.h).  Not differentiable."""
+    if not joint.is_cuda:
+        raise _lib.HaloError('haloop_amd.transducer.transducer_viterbi runs on the HIP device only (no CPU path)')
+    dev = joint.device
+    if joint.dim() != 4:
+        raise ValueError(f'transducer_viterbi: joint must be [N, T, U+1, K], got {tuple(joint.shape)}')
+    N, T, U1, K = joint.shape
+    if tuple(targets.shape) != (N, U1 - 1):
+        raise ValueError(f'targets must be [N, U] = [{N}, {U1 - 1}], got {tuple(targets.shape)}')
+    jl = joint_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    tl = target_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    return ops.transducer_viterbi(joint.detach().float().contiguous(), targets.to(device=dev, dtype=torch.int64).contiguous(), jl, tl)
+
+
+def transducer_align(f, g, targets, f_lengths, target_lengths):
+    """``transducer_viterbi((f[:, :, None] + g[:, None]).log_softmax(-1), ...)`` from the two factors of the additive joint, f [N, T, V]
+    and g [N, U+1, V], under ``transducer_loss``'s input rules (strided views with a contiguous last dimension are read in place):
+    csrc/rnnt_loss.hip computes every cell's blank / label log-probabilities, the Viterbi launch runs on those -- no [N, T, U+1, V]
+    tensor.  -> (scores [N], frames [N, U])."""
+    if not f.is_cuda or not g.is_cuda:
+        raise _lib.HaloError('haloop_amd.transducer.transducer_align runs on the HIP device only (no CPU path)')
+    dev = f.device
+    if f.dim() != 3 or g.dim() != 3 or f.shape[0] != g.shape[0] or f.shape[2] != g.shape[2]:
+        raise ValueError(f'transducer_align: f must be [N, T, V] and g [N, U+1, V], got {tuple(f.shape)} and {tuple(g.shape)}')
+    N, U1 = g.shape[0], g.shape[1]
+    if tuple(targets.shape) != (N, U1 - 1):
+        raise ValueError(f'targets must be [N, U] = [{N}, {U1 - 1}], got {tuple(targets.shape)}')
+    fl = f_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    tl = target_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    targets = targets.to(device=dev, dtype=torch.int64).contiguous()
+    _, lp2 = ops.rnnt_joint_fwd(_rows_fp32(f.detach()), _rows_fp32(g.detach()), targets, fl, tl, min_length=0)
+    return ops.transducer_viterbi(lp2, torch.ones_like(targets), fl, tl, checked=True)   # lp2 is a joint with K = 2: the cell's label is 1
 
 
 def _fused_default():

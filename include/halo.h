@@ -941,6 +941,43 @@ int halo_rnnt_joint_bwd(const float *f, long f_n_stride, long f_t_stride, const 
                         long dg_u_stride, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Forced alignment: the best path (max-plus, "log 0" = -inf) of the two lattices and its backtrace, one workgroup per utterance
+ * (csrc/viterbi.hip).  The reference has no aligner (TemporalClassifier.decode, ha/recognizer.py:48-59, returns greedy
+ * alignments only): a capability of this library.  fp32, no atomics (bit-reproducible); every launch is finite (no grid barrier, no
+ * polling) and no workgroup reads what another workgroup of its launch writes.  Emissions are read from global memory a few frames
+ * ahead of the recursion, never staged whole: T is bounded by the workspace alone.
+ *   halo_ctc_viterbi         lp, targets, input_lengths (NULL: T), target_lengths as halo_ctc_fwd takes them (lengths clamped to [0, T] /
+ *                            [0, S]); F.ctc_loss's lattice: states 0 .. 2 tl, starts at state 0 or 1, ends at state 2 tl or 2 tl - 1 of
+ *                            frame il - 1, the skip s-2 -> s only into a label that differs from the label two states back;
+ *                            v[t][s] = max(v[t-1][s], v[t-1][s-1], v[t-1][s-2] if skip) + lp[t][ext[s]].  Ties: the smallest shift (stay,
+ *                            then s-1, then s-2); at the end state 2 tl before 2 tl - 1.  A label outside [0, C) is never indexed (its
+ *                            state is unreachable); targets past target_lengths[n] are never read.
+ *                            scores [N]: the best path's log-probability, -inf for an infeasible row; alignments [N][T] int64: the label
+ *                            of each frame's state (0 = blank), -1 at t >= il and in a whole infeasible row; starts / ends [N][S] int32:
+ *                            first / last frame of each target token's label state, -1 for u >= tl and in infeasible rows.  tl = 0: the
+ *                            all-blank path; il = 0: score 0 if tl = 0, else infeasible.
+ *                            workspace: halo_ctc_viterbi_workspace_bytes(T, N, S) bytes, 2 bits per (t, s) as [N][T][ceil((2S+1)/64)][2]
+ *                            uint64 (bit s % 64 of the two words = the shift into s at frame t).  Limits: 1 <= S <= 3839 (2S+1 <= 7679
+ *                            states, spread over the workgroup's threads: one wave up to 64 states, else up to 30 states per thread of
+ *                            256); HALO_ENOTSUP above.
+ *   halo_transducer_viterbi  joint, targets, joint_lengths, target_lengths as halo_transducer_fwd takes them (on halo_rnnt_joint_fwd's lp2:
+ *                            K = 2, targets of ones); lengths clamped to [0, T] / [0, U1 - 1]; cells outside them are never read:
+ *                            v[t][u] = max(v[t-1][u] + joint[t-1][u][0], v[t][u-1] + joint[t][u-1][y[u-1]]) along the anti-diagonals,
+ *                            scores [N] = v[Tn-1][Un] + joint[Tn-1][Un][0].  Tie: the blank predecessor (t-1, u).  frames [N][U1 - 1] int32:
+ *                            the frame at which target token u is emitted (GreedyDecoder's `frames`), -1 for u >= Un.  A row with Tn = 0
+ *                            (or a -inf score) gets score -inf and frames -1.
+ *                            workspace: halo_transducer_viterbi_workspace_bytes(N, T, U1) bytes, 1 bit per cell as
+ *                            [N][T + U1 - 1][ceil(U1/64)] uint64 (bit u % 64 of word [t + u][u / 64] set: entered by the label arc).
+ *                            Limits: 2 <= U1 <= 7679 as the lattice kernels. */
+size_t halo_ctc_viterbi_workspace_bytes(int T, int N, int S);
+int halo_ctc_viterbi(const float *lp, long stride_t, long stride_n, int T, int N, int C, const int64_t *targets, long tg_stride, int S,
+                     const int64_t *input_lengths, const int64_t *target_lengths, void *workspace, float *scores, int64_t *alignments,
+                     int *starts, int *ends, halo_stream_t stream);
+size_t halo_transducer_viterbi_workspace_bytes(int N, int T, int U1);
+int halo_transducer_viterbi(const float *joint, int N, int T, int U1, int K, const int64_t *targets, const int *joint_lengths,
+                            const int *target_lengths, void *workspace, float *scores, int *frames, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Backward operators of the GPT / transformer training step (the autograd graph of ha/attention.py:205-232 as
  * `hal` runs it, ha/attention_loop.py:196-215: loss.backward()).
  *   halo_attention_bwd         gradient of halo_attention_fwd: dq, dk, dv (same row layouts as q, k, v; written, not
