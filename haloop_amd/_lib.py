@@ -190,6 +190,9 @@ SIGNATURES = {
     'halo_ctc_viterbi': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_transducer_viterbi_workspace_bytes': (_sz, [_i, _i, _i]),
     'halo_transducer_viterbi': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'halo_edit_distance': (_i, [_vp, _l, _vp, _i, _i, _vp, _l, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    'halo_nbest_risk_fwd': (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    'halo_nbest_risk_bwd': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     'halo_gpt_decode_linear_supported': (_i, [_i, _i]),
     'halo_gpt_decode_linear': (_i, [_vp, _l, _i, _i, _vp, _f, _vp, _i, _vp, _l, _i, _vp]),
     'halo_gpt_decode_attention': (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _l, _vp]),
@@ -210,6 +213,7 @@ SIGNATURES = {
     'halo_cross_entropy_fwd_lse': (_i, [_vp, _vp, _vp, _vp, _i, _i, _l, _l, _vp]),
     'halo_cross_entropy_bwd': (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _l, _l, _vp]),
     'halo_embed_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'halo_embed_bwd_ordered': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'halo_add_rows_bcast': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'halo_im2col_cl': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'halo_col2im_cl': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -284,6 +284,19 @@ __global__ __launch_bounds__(256) void embed_bwd_wte_kernel(const int64_t *__res
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     for (int c = threadIdx.x; c < C; c += 256) atomicAdd(dwte + id * C + c, dx[(long)n * C + c]);
 }
+// dwte[v, c] = sum over the tokens n with ids[n] == v, in token order, of dx[n, c]: no atomics, every row written
+__global__ __launch_bounds__(256) void embed_bwd_ordered_kernel(const int64_t *__restrict__ ids, const float *__restrict__ dx,
+                                                                float *__restrict__ dwte, int n, int C, int vocab) {
+    const int v = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+    if (c >= C) return;
+    float acc = 0.f;
+    for (int t = 0; t < n; ++t) {
+        long id = ids[t];
+        id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+        if (id == v) acc += dx[(long)t * C + c];
+    }
+    dwte[(long)v * C + c] = acc;
+}
 // x[n, :] += p[n % T, :]   (StableEmbedding: the normalised position rows are shared by the batch, ha/attention.py:222-224)
 __global__ __launch_bounds__(256) void add_rows_bcast_kernel(float *__restrict__ x, const float *__restrict__ p, long n_elem, int T, int C) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -522,6 +535,12 @@ int halo_embed_bwd(const int64_t *ids, const float *dx, float *dwte, float *dwpe
         hipLaunchKernelGGL(embed_bwd_wpe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dx, dwpe, B, T, C, pos0,
                            accumulate_wpe);
     }
+    return halo_launch_status();
+}
+
+int halo_embed_bwd_ordered(const int64_t *ids, const float *dx, float *dwte, int n, int C, int vocab, halo_stream_t stream) {
+    HALO_CHECK_ARG(ids && dx && dwte && n > 0 && C > 0 && vocab > 0);
+    hipLaunchKernelGGL(embed_bwd_ordered_kernel, dim3(vocab, (C + 255) / 256), dim3(256), 0, (hipStream_t)stream, ids, dx, dwte, n, C, vocab);
     return halo_launch_status();
 }
 

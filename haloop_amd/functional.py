@@ -103,25 +103,29 @@ class _Linear(torch.autograd.Function):
 
 
 class _Embedding(torch.autograd.Function):
-    """nn.Embedding lookup (ha/rnn.py:38,45) on the HIP gather; the backward scatter-adds rows with float atomics."""
+    """nn.Embedding lookup (ha/rnn.py:38,45) on the HIP gather; the backward scatter-adds rows with float atomics, or, ``ordered``, sums
+    them in token order without atomics (bit-reproducible; the cost grows with vocabulary x tokens: include/halo.h)."""
 
     @staticmethod
-    def forward(ctx, ids, weight):
+    def forward(ctx, ids, weight, ordered=False):
         flat = ids.reshape(1, -1)
         ctx.save_for_backward(flat)
-        ctx.shape = weight.shape
+        ctx.shape, ctx.ordered = weight.shape, ordered
         return ops.embed_fwd(flat, weight, None).view(*ids.shape, weight.shape[1])
 
     @staticmethod
     def backward(ctx, dy):
         (flat,) = ctx.saved_tensors
+        dy2d = dy.reshape(-1, ctx.shape[1]).contiguous().float()
+        if ctx.ordered:
+            return None, ops.embed_bwd_ordered(flat, dy2d, ctx.shape[0]), None
         dw = torch.zeros(ctx.shape, device=dy.device, dtype=torch.float32)
-        ops.embed_bwd(flat, dy.reshape(-1, ctx.shape[1]).contiguous().float(), dw, None)
-        return None, dw
+        ops.embed_bwd(flat, dy2d, dw, None)
+        return None, dw, None
 
 
-def embedding(ids, weight):
-    return _Embedding.apply(ids, weight)
+def embedding(ids, weight, ordered_grad=False):
+    return _Embedding.apply(ids, weight, ordered_grad)
 
 
 def linear(x, w, b):

@@ -1388,6 +1388,54 @@ def transducer_viterbi(joint, targets, joint_lengths, target_lengths, checked=Fa
     return scores, frames
 
 
+# ---- edit distance and the risk of an n-best list (csrc/edit_distance.hip) -----------------------------------------------------------
+EDIT_DISTANCE_MAX_LEN = 1024     # HALO_EDIT_DISTANCE_MAX_LEN (include/halo.h)
+
+
+def edit_distance(hyp, hyp_lengths, ref, ref_lengths, group):
+    """hyp [P, Lh] int64 (any row stride, unit token stride), hyp_lengths [P] int32, ref [R, Lr] int64, ref_lengths [R] int32 contiguous,
+    P = R * group -> (errors [P] int32, counts [P, 3] int32 = ins, del, sub) under the tie rule of include/halo.h."""
+    for t, name in ((hyp, 'hyp'), (ref, 'ref')):
+        if t.dtype != torch.int64 or t.dim() != 2 or not t.is_cuda or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError(f'edit_distance: {name} must be a two-dimensional int64 HIP tensor with unit stride along the tokens')
+    P, R = hyp.shape[0], ref.shape[0]
+    for t, name, n in ((hyp_lengths, 'hyp_lengths', P), (ref_lengths, 'ref_lengths', R)):
+        if t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f'edit_distance: {name} must be a contiguous int32 HIP tensor of [{n}]')
+    if group < 1 or R * group != P or P < 1:
+        raise ValueError(f'edit_distance: {P} hypotheses are not {R} references x group {group}')
+    errors = torch.empty(P, device=hyp.device, dtype=torch.int32)
+    counts = torch.empty(P, 3, device=hyp.device, dtype=torch.int32)
+    check(lib().halo_edit_distance(ptr(hyp), max(hyp.stride(0), hyp.shape[1]), ptr(hyp_lengths), P, hyp.shape[1], ptr(ref),
+                                   max(ref.stride(0), ref.shape[1]), ptr(ref_lengths), R, ref.shape[1], group, ptr(errors), ptr(counts),
+                                   _stream()), 'halo_edit_distance')
+    return errors, counts
+
+
+def _check_nbest(losses, errors):
+    if losses.dim() != 2 or errors.dtype != torch.int32 or errors.shape != losses.shape or not errors.is_cuda or not errors.is_contiguous():
+        raise ValueError('nbest_risk: losses must be [N, W] float32 and errors [N, W] int32, contiguous HIP tensors')
+    return _f32c(losses, 'losses').shape
+
+
+def nbest_risk_fwd(losses, errors):
+    """losses [N, W] f32, errors [N, W] int32 (< 0: absent) -> risk [N] f32 (include/halo.h)."""
+    N, W = _check_nbest(losses, errors)
+    risk = torch.empty(N, device=losses.device, dtype=torch.float32)
+    check(lib().halo_nbest_risk_fwd(ptr(losses), ptr(errors), N, W, ptr(risk), _stream()), 'halo_nbest_risk_fwd')
+    return risk
+
+
+def nbest_risk_bwd(losses, errors, grad_risk):
+    """grad_risk [N] f32 -> dlosses [N, W] f32."""
+    N, W = _check_nbest(losses, errors)
+    if tuple(_f32c(grad_risk, 'grad_risk').shape) != (N,):
+        raise ValueError(f'nbest_risk: grad_risk must be [{N}]')
+    dlosses = torch.empty(N, W, device=losses.device, dtype=torch.float32)
+    check(lib().halo_nbest_risk_bwd(ptr(losses), ptr(errors), N, W, ptr(grad_risk), ptr(dlosses), _stream()), 'halo_nbest_risk_bwd')
+    return dlosses
+
+
 # ---- fused launches of a greedy decode step (csrc/decode.hip) -------------------------------------------------
 def decode_linear_supported(k, layernorm):
     return bool(lib().halo_decode_linear_supported(k, int(layernorm)))
@@ -1765,6 +1813,15 @@ def embed_bwd(ids, dx2d, dwte, dwpe, pos0=0, accumulate_wpe=False):
     vocab = dwte.shape[0] if dwte is not None else 1
     check(lib().halo_embed_bwd(ptr(ids), ptr(dx2d), ptr(dwte), ptr(dwpe), Bn, T, dx2d.shape[1], pos0, vocab,
                                int(accumulate_wpe), _stream()), 'halo_embed_bwd')
+
+
+def embed_bwd_ordered(ids, dx2d, vocab):
+    """ids (any shape, n tokens), dx2d [n, C] f32 -> dwte [vocab, C]: the scatter-add of embed_bwd in token order, no atomics."""
+    ids = _i64c(ids, 'input_ids')
+    _f32c(dx2d, 'dx')
+    dwte = torch.empty(vocab, dx2d.shape[1], device=dx2d.device, dtype=torch.float32)
+    check(lib().halo_embed_bwd_ordered(ptr(ids), ptr(dx2d), ptr(dwte), ids.numel(), dx2d.shape[1], vocab, _stream()), 'halo_embed_bwd_ordered')
+    return dwte
 
 
 def dwconv1d_cl_bwd(dy3d, x3d, weight, stride, pad, want_dx=True, has_bias=True):

@@ -4,11 +4,11 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, functional as HF, ops
+from . import _lib, functional as HF, ops, wer
 from .ctc import ctc_reduce_mean, ctc_viterbi
 from .rnn import Decoder, DropoutStream
 from .star import star_ctc_forward_score
-from .transducer import BeamDecoder, GreedyDecoder, transducer_align, transducer_forward_score, transducer_loss
+from .transducer import BeamDecoder, GreedyDecoder, nbest_risk, transducer_align, transducer_forward_score, transducer_loss
 
 
 class TemporalClassifier(nn.Module):
@@ -82,7 +82,11 @@ class Transducer(nn.Module):
 
     ``beam_size`` (HALO_RNNT_BEAM when the head is built; a caller may set the attribute or pass ``decode(..., beam_size=W)``): 0, the
     default, decodes greedily; W >= 1 runs ``transducer.BeamDecoder`` at that width, returns each row's best
-    hypothesis and keeps the whole n-best result of the last call as ``last_nbest``."""
+    hypothesis and keeps the whole n-best result of the last call as ``last_nbest``.
+
+    ``mwer_beam`` (HALO_RNNT_MWER when the head is built; a caller may set the attribute): 0, the default, leaves ``forward`` as it is;
+    W >= 1 makes ``forward`` of a head in training mode return ``mwer_forward(..., beam_size=W)``, minimum-word-error-rate fine-tuning
+    on the n-best lists of the beam search."""
 
     def __init__(self, feat_dim=1024, vocab_size=256):
         super().__init__()
@@ -92,6 +96,7 @@ class Transducer(nn.Module):
         self.dropout_stream = DropoutStream()
         self.fused_loss = os.environ.get('HALO_RNNT_LOSS_FUSED', '0') == '1'
         self.beam_size = int(os.environ.get('HALO_RNNT_BEAM', '0'))
+        self.mwer_beam = int(os.environ.get('HALO_RNNT_MWER', '0'))
         self.last_nbest = None
 
     def decode(self, features, input_lengths, condtarget_lengths=None, prompt=None, beam_size=None):
@@ -120,17 +125,21 @@ class Transducer(nn.Module):
         hypotheses = torch.nested.nested_tensor([tokens[i, :n] for i, n in enumerate(lens)])
         return hypotheses, torch.tensor(lens), frames, scores, None
 
-    def _decode_beam(self, features, input_lengths, N, capacity, width):
-        """Beam search at ``width``: each row's best hypothesis in the five-value form (a merged hypothesis has no single alignment: the
-        third value is [None] * N); ``last_nbest`` = (tokens [N, W, capacity], lengths [N, W], scores [N, W], counts [N])."""
-        if width < 0:
-            raise ValueError(f'Transducer.decode: beam_size {width} is negative')
+    def _beam_decoder_for(self, features, N, capacity, width):
+        """The head's ``BeamDecoder``, rebuilt when a call needs more room than it has (or another device)."""
         dec = getattr(self, '_beam_decoder', None)
         if dec is None or dec.max_batch < N or dec.capacity < capacity or dec.beam < width or dec._device != features.device:
             dec = BeamDecoder(self, max(N, dec.max_batch if dec else 0), max(capacity, dec.capacity if dec else 0),
                               max(width, dec.beam if dec else 0))
             self._beam_decoder = dec
-        self.last_nbest = dec.decode(features, input_lengths, capacity, width)
+        return dec
+
+    def _decode_beam(self, features, input_lengths, N, capacity, width):
+        """Beam search at ``width``: each row's best hypothesis in the five-value form (a merged hypothesis has no single alignment: the
+        third value is [None] * N); ``last_nbest`` = (tokens [N, W, capacity], lengths [N, W], scores [N, W], counts [N])."""
+        if width < 0:
+            raise ValueError(f'Transducer.decode: beam_size {width} is negative')
+        self.last_nbest = self._beam_decoder_for(features, N, capacity, width).decode(features, input_lengths, capacity, width)
         tokens, lengths, scores, _ = self.last_nbest
         lens = lengths[:, 0].tolist()                           # every row returns at least one hypothesis
         hypotheses = torch.nested.nested_tensor([tokens[i, 0, :n] for i, n in enumerate(lens)])
@@ -155,11 +164,69 @@ class Transducer(nn.Module):
             feats = HF.linear(features.float(), self.classifier.weight, self.classifier.bias)
             return transducer_align(feats, lm_outputs, targets, input_lengths.to(dev), target_lengths.to(dev))
 
+    def _search_nbest(self, features, input_lengths, capacity, width):
+        """The beam search of ``mwer_forward``: under ``no_grad``, on the head in eval mode (the decoders refuse a training head); every
+        module's mode is put back, also when the search raises."""
+        modes = [(m, m.training) for m in self.modules()]
+        self.eval()
+        try:
+            with torch.no_grad():
+                return self._beam_decoder_for(features, features.shape[0], capacity, width).decode(features, input_lengths, capacity, width)
+        finally:
+            for m, mode in modes:
+                m.training = mode
+
+    def mwer_forward(self, features, targets, input_lengths, target_lengths, beam_size=4, mle_weight=0.01):
+        """Minimum-word-error-rate training on n-best lists ([Prabhavalkar18], [Guo20]) -> (loss, info):
+
+            the W = beam_size best hypotheses of every row by ``transducer.BeamDecoder`` (no gradient, the head in eval mode for the search,
+                the features undropped, room for target_lengths.max() + 1 symbols as in ``decode``);
+            their error counts against ``targets`` by ``wer.edit_distance``;
+            their losses -log P(hypothesis | x) by ``transducer.transducer_loss`` on N * W rows: the prediction network over the
+                zero-prefixed hypotheses (padding and absent hypotheses as token 0, absent ones with length 0) against W views of the
+                row's ``feats``, which ``forward``'s dropout stream and classifier produce;
+            loss = mean_n ``transducer.nbest_risk``(losses, errors)[n] (+ mle_weight x the fused transducer loss of the reference, from
+                the same ``feats``, unless mle_weight is 0).
+
+        ``info``: ``nbest`` (the search's tuple: tokens [N, W, capacity], lengths [N, W], scores [N, W], counts [N]), ``errors`` [N, W]
+        int32, ``risk`` [N] and ``nbest_losses`` [N, W], detached.  The N * W views of ``feats`` are materialised once (W x the size of
+        ``feats``; the joint kernels take no group argument); their gradient is summed over W by the view's backward, not by an
+        index-add.  The prediction network takes its embedding gradient in token order (``ordered_grad``), not by the float atomics of the
+        ordinary lookup, so the whole step is bit-reproducible.  Rows with an input length of 0 are refused as in ``transducer_loss``."""
+        if not features.is_cuda:
+            raise _lib.HaloError('haloop_amd.recognizer.Transducer runs on the HIP device only')
+        dev = features.device
+        N, W = features.shape[0], int(beam_size)
+        targets, il, tl = targets.to(dev), input_lengths.to(dev), target_lengths.to(dev)
+        nbest = self._search_nbest(features, il, int(tl.max()) + 1, W)
+        tokens, lengths = nbest[0], nbest[1]                                             # [N, W, cap] (-1 padded), [N, W] (-1: absent)
+        errors, _ = wer.edit_distance(tokens, lengths, targets, tl, group=W)
+        errors = errors.view(N, W)
+
+        drop = self.dropout_stream.next(self.dropout.p, self.training)
+        feats = HF.dropout(features.float(), drop, _lib.HALO_STREAM_CLASSIFIER)
+        feats = HF.linear(feats, self.classifier.weight, self.classifier.bias)          # (N, T, C)
+        T, V = feats.shape[1], feats.shape[2]
+        hyps = tokens.clamp(min=0).view(N * W, -1)
+        lm_hyps = torch.cat([hyps.new_zeros((N * W, 1)), hyps], dim=1)
+        lm_outputs, _ = self.lm.forward_batch_first(lm_hyps, self.lm.init_hidden(N * W), ordered_grad=True)
+        rows = feats[:, None].expand(N, W, T, V).reshape(N * W, T, V)
+        losses = transducer_loss(rows, lm_outputs, hyps, il[:, None].expand(N, W).reshape(-1), lengths.clamp(min=0).view(-1)).view(N, W)
+        risk = nbest_risk(losses, errors)
+        loss = risk.mean()
+        if mle_weight != 0:
+            lm_targets = torch.cat([targets.new_zeros((N, 1)), targets], dim=1)
+            ref_outputs, _ = self.lm.forward_batch_first(lm_targets, self.lm.init_hidden(N), ordered_grad=True)
+            loss = loss + mle_weight * transducer_loss(feats, ref_outputs, targets, il, tl).mean()
+        return loss, {'nbest': nbest, 'errors': errors, 'risk': risk.detach(), 'nbest_losses': losses.detach()}
+
     def forward(self, features, targets, input_lengths=None, target_lengths=None, star_penalty=None):   # star_penalty: ignored (:101)
         if not features.is_cuda:
             raise _lib.HaloError('haloop_amd.recognizer.Transducer runs on the HIP device only')
         dev = features.device
         N = features.shape[0]
+        if self.mwer_beam > 0 and self.training:
+            return self.mwer_forward(features, targets, input_lengths, target_lengths, beam_size=self.mwer_beam)
         targets = targets.to(dev)
         hidden = self.lm.init_hidden(N)
         lm_targets = torch.cat([targets.new_zeros((N, 1)), targets], dim=1)              # input needs to start with 0 (:107)

@@ -121,8 +121,9 @@ class Decoder(nn.Module):
         output, state = self._run(emb, state)
         return output.view(-1, self.num_classes), state
 
-    def forward_batch_first(self, input, state):
-        emb = HF.embedding(input, self.embedding.weight).transpose(0, 1)   # (T, N, E)
+    def forward_batch_first(self, input, state, ordered_grad=False):
+        """``ordered_grad``: the embedding's gradient summed in token order, without atomics (functional.embedding)."""
+        emb = HF.embedding(input, self.embedding.weight, ordered_grad).transpose(0, 1)   # (T, N, E)
         output, state = self._run(emb, state)
         return output.transpose(0, 1), state
 

@@ -18,6 +18,9 @@ either direction.
 the two factors, no [N, T, U+1, V] tensor): the best path of the lattice and the frame at which it emits every target token
 (csrc/viterbi.hip).  The reference has neither.
 
+``nbest_risk(losses, errors)`` is the minimum-word-error-rate objective over an n-best list: the expected number of errors under the
+hypotheses' renormalised posterior, less its plain mean (csrc/edit_distance.hip).  The reference has no such objective.
+
 ``GreedyDecoder`` is greedy transducer search ([Graves12]) for ``recognizer.Transducer``, which the reference leaves unbuilt
 (ha/recognizer.py:92-93): per row, with F = classifier(features) and g the prediction network's logits for the symbols emitted so far
 (the zero prefix of training first), take k = argmax log_softmax(F[n, t] + g) (lowest index on ties; blank forced once
@@ -164,6 +167,32 @@ def transducer_align(f, g, targets, f_lengths, target_lengths):
     targets = targets.to(device=dev, dtype=torch.int64).contiguous()
     _, lp2 = ops.rnnt_joint_fwd(_rows_fp32(f.detach()), _rows_fp32(g.detach()), targets, fl, tl, min_length=0)
     return ops.transducer_viterbi(lp2, torch.ones_like(targets), fl, tl, checked=True)   # lp2 is a joint with K = 2: the cell's label is 1
+
+
+class _NbestRisk(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, losses, errors):
+        l = losses.detach().float().contiguous()
+        ctx.saved = (l, errors)
+        return ops.nbest_risk_fwd(l, errors)
+
+    @staticmethod
+    def backward(ctx, grad_risk):
+        l, errors = ctx.saved
+        return ops.nbest_risk_bwd(l, errors, grad_risk.float().contiguous()), None
+
+
+def nbest_risk(losses, errors):
+    """The minimum-word-error-rate risk of an n-best list ([Prabhavalkar18], [Guo20]; csrc/edit_distance.hip): losses
+    [N, W] = -log P(hypothesis | x) (``transducer_loss`` on the N * W hypotheses), errors [N, W] integers (``wer.edit_distance``; < 0: an
+    absent hypothesis), W <= ``BEAM_MAX`` -> risk [N] = sum_w p_w err_w - mean_w err_w with p = softmax(-losses) over the present
+    hypotheses of a row (0 for a row without one).  Differentiable w.r.t. ``losses``: d risk / d losses_w = -p_w (err_w - sum_v p_v err_v),
+    0 for an absent hypothesis; the mean is a baseline without a gradient.  fp32, bit-reproducible."""
+    if not losses.is_cuda or not errors.is_cuda:
+        raise _lib.HaloError('haloop_amd.transducer.nbest_risk runs on the HIP device only (no CPU path)')
+    if losses.dim() != 2 or errors.shape != losses.shape:
+        raise ValueError(f'nbest_risk: losses and errors must both be [N, W], got {tuple(losses.shape)} and {tuple(errors.shape)}')
+    return _NbestRisk.apply(losses, errors.to(device=losses.device, dtype=torch.int32).contiguous())
 
 
 def _fused_default():

@@ -978,6 +978,38 @@ int halo_transducer_viterbi(const float *joint, int N, int T, int U1, int K, con
                             const int *target_lengths, void *workspace, float *scores, int *frames, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Edit distance and the minimum-word-error-rate risk of an n-best list (csrc/edit_distance.hip).  The reference counts
+ * word errors on the host through kaldialign (ha/wer.py:28-52) and has no MWER objective ([Prabhavalkar18], [Guo20]): the risk is a
+ * capability of this library.  No atomics, no workspace (bit-reproducible); every launch is finite and no workgroup reads what another
+ * workgroup of its launch writes.
+ *   halo_edit_distance   batched Levenshtein distance with operation counts, one workgroup per pair.  hyp [P][hyp_stride] int64 (tokens
+ *                        0 .. Lh - 1 of a row, unit stride), hyp_lengths [P] int32; ref [R][ref_stride] int64, ref_lengths [R] int32;
+ *                        P = R * group, pair p is scored against reference p / group (the [N, W, capacity] n-best lists of the beam
+ *                        search against their rows' transcripts: group = W).  Lengths above Lh / Lr are clamped to them, a negative
+ *                        ref length to 0; tokens at or past a length are never read (padding may hold anything).
+ *                        errors [P] int32: the distance; counts [P][3] int32 = (ins, del, sub) in ha/wer.py's sense: ins = hypothesis
+ *                        tokens without a reference partner, del = reference tokens without a hypothesis partner, sub = partners that
+ *                        differ; ins + del + sub = errors.  hyp_lengths[p] < 0 (an absent hypothesis): errors -1, counts 0.
+ *                        Tie rule (the distance is unique, the counts are not): with D[i][j] the distance of the first i hypothesis
+ *                        tokens to the first j reference tokens, every cell keeps ONE predecessor among those that give its minimal
+ *                        total, taken in the order diagonal (i-1, j-1: match or substitution), deletion (i, j-1), insertion (i-1, j);
+ *                        the counts are those of the path these choices lead along from (Lh, Lr) back to (0, 0).  (The counts travel
+ *                        forward with the cost, which yields exactly that path's: no back-pointers, no backtrace.)
+ *                        Limits: 0 <= Lh, Lr <= HALO_EDIT_DISTANCE_MAX_LEN = 1024 tokens (one wave up to Lr = 64, else up to 4 reference
+ *                        columns per thread of 256); HALO_ENOTSUP above, nothing is launched.
+ *   halo_nbest_risk_fwd  losses [N][W] fp32 = -log P(hypothesis | x), errors [N][W] int32 (< 0: absent), W <= 16.  Over the present
+ *                        hypotheses of a row: p = softmax(-losses) (the maximum taken out before the exponentials),
+ *                        risk [N] = sum_w p_w err_w - mean_w err_w (the plain mean as the baseline, [Prabhavalkar18]; it has no gradient);
+ *                        a row without a present hypothesis has risk 0.
+ *   halo_nbest_risk_bwd  dlosses [N][W] = grad_risk[n] * -p_w (err_w - sum_v p_v err_v); 0 for an absent hypothesis.
+ *                        Both: fp32, one thread per row, sums in hypothesis order. */
+#define HALO_EDIT_DISTANCE_MAX_LEN 1024
+int halo_edit_distance(const int64_t *hyp, long hyp_stride, const int *hyp_lengths, int P, int Lh, const int64_t *ref, long ref_stride,
+                       const int *ref_lengths, int R, int Lr, int group, int *errors, int *counts, halo_stream_t stream);
+int halo_nbest_risk_fwd(const float *losses, const int *errors, int N, int W, float *risk, halo_stream_t stream);
+int halo_nbest_risk_bwd(const float *losses, const int *errors, int N, int W, const float *grad_risk, float *dlosses, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Backward operators of the GPT / transformer training step (the autograd graph of ha/attention.py:205-232 as
  * `hal` runs it, ha/attention_loop.py:196-215: loss.backward()).
  *   halo_attention_bwd         gradient of halo_attention_fwd: dq, dk, dv (same row layouts as q, k, v; written, not
@@ -1039,6 +1071,11 @@ int halo_cross_entropy_bwd(float *logits, const int64_t *targets, const float *l
                            long grad_stride, int rows, int V, long ld, long ignore_index, halo_stream_t stream);
 int halo_embed_bwd(const int64_t *ids, const float *dx, float *dwte, float *dwpe, int B, int T, int C, int pos0,
                    int vocab, int accumulate_wpe, halo_stream_t stream);
+/* The dwte half of halo_embed_bwd without atomics: dwte[v] = the sum, in token order, of the rows dx[n] with ids[n] == v (ids clamped to
+ * [0, vocab) as there); every row of dwte [vocab][C] is WRITTEN (rows no token names become 0).  One thread per (v, column) scans the n
+ * ids, so the cost is vocab x n id reads: made for the prediction network's small vocabularies and the few thousand tokens of an n-best
+ * list (rnn.Decoder.forward_batch_first(..., ordered_grad=True), Transducer.mwer_forward), whose gradients it makes bit-reproducible. */
+int halo_embed_bwd_ordered(const int64_t *ids, const float *dx, float *dwte, int n, int C, int vocab, halo_stream_t stream);
 /* x[n, :] += p[n % T, :]: tok_emb + pos_emb when both went through StableEmbedding's LayerNorm first (ha/attention.py:30-61,224) */
 int halo_add_rows_bcast(float *x, const float *p, int rows, int T, int C, halo_stream_t stream);
 
