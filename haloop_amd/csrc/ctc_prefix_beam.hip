@@ -1,0 +1,291 @@
+// CTC prefix beam search with exact merging (haloop_amd/ctc.py ctc_prefix_beam_search; [Hannun14], Graves' prefix search; DESIGN.md
+// 3.3p): the whole decode of a batch in one launch, one workgroup per utterance, the frame loop inside.  A beam member is a prefix y with
+// the log-mass of its alignments that end in blank (pb) and in its last label (pnb).  Per frame t < L
+//   1. every member's stay candidate (pb' = total + e[t, 0], pnb' = pnb + e[t, last]) and total = logaddexp(pb, pnb)
+//   2. the merge: the extension of j by k spells the prefix of stay candidate s exactly when y_s = y_j + [k].  A 32-bit hash of the
+//      prefixes shortlists the pairs (s, j); a wave compares their tokens, which alone decides; the extension's mass joins pnb'_s and the
+//      extension is no candidate.  Two members never extend to the same prefix, so there is no other merge.
+//   3. the W best of the stay candidates (position j) and the extensions (position W + j V + k, score e[t, k] + (pb_j if k == last_j else
+//      total_j), only from members shorter than the capacity), one per round: the first in the total order (score descending, position
+//      ascending) behind the last one taken, by a workgroup-wide arg-max over every thread's own first.  A thread owns the extensions by
+//      its classes and keeps its first across the rounds; only the owner of the candidate just taken looks for its next.  No list of
+//      W V candidates is built: a candidate's score is two operands away from the frame's emissions.  Candidates at -inf are never taken.
+//   4. the new beam's records and token rows, in the order taken, into the other copy of the beam (double-buffered by frame parity).
+// LDS: the records (W-sized, < 2 KiB static); the frame's V emissions, double-buffered so that frame t + 1 is requested from global memory
+// before frame t's rounds and lands in LDS behind them (E_LDS_FLOATS = 8192 floats = 32 KiB of dynamic LDS: V <= 4096; above that the
+// rounds read the emissions from L2 by the same operations, the same bits); the token rows of both copies of the beam as 16-bit tokens
+// (TOK_LDS_TOKENS = 12288 = 24 KiB: 2 W capacity <= 12288 and V <= 65536; otherwise they live in the caller's workspace as 32-bit
+// tokens, written and read by this workgroup alone).  58 KiB at most: under the 64 KiB a launch gets without the opt-in.
+// fp32, no float atomics (one integer atomicOr in LDS collects the shortlist: a bit set, whatever the order), every sum in a fixed
+// order: the launch is bit-reproducible.  Frames at or past L, and another row's frames, are never loaded.
+#include <type_traits>
+
+#include "halo_common.h"
+
+namespace {
+
+constexpr int BEAM_MAX = 16, BEAM_THREADS = 256, BEAM_WAVES = BEAM_THREADS / 64;
+constexpr int E_LDS_FLOATS = 8192;         // two frames of emissions in LDS: V <= 4096
+constexpr int TOK_LDS_TOKENS = 12288;      // both copies of the beam's token rows in LDS as 16-bit tokens: 2 W capacity <= 12288
+constexpr int PF = 4;                      // emissions of the next frame a thread holds in registers across a frame (V <= 1024: all of them)
+constexpr int V_MAX = 1 << 26;             // positions W + j V + k stay below 2^31
+
+struct CtcPrefixBeamArgs {
+    const float *e;                        // [T][N][V] log-probabilities, strides st (frame) and sn (row), unit class stride
+    long st, sn;
+    int T, V, W, cap;
+    const int64_t *il;                     // [N] frames of each row (NULL: T), clamped to [0, T] here
+    int *ws;                               // token rows [N][2][W][cap] when they do not fit LDS
+    int64_t *tokens, *lengths, *counts;    // [N][W][cap], [N][W], [N]
+    float *scores;                         // [N][W]
+};
+
+__device__ __forceinline__ float logaddexpf_(float a, float b) {
+    const float m = fmaxf(a, b);
+    return m == -INFINITY ? m : m + log1pf(expf(-fabsf(a - b)));
+}
+
+// (sc, pos) stands before (osc, opos) in the order (score descending, position ascending)
+__device__ __forceinline__ bool before(float sc, int pos, float osc, int opos) { return sc > osc || (sc == osc && pos < opos); }
+
+template <bool STAGED, bool TOK_LDS>
+__global__ __launch_bounds__(BEAM_THREADS) void ctc_prefix_beam_kernel(const CtcPrefixBeamArgs p) {
+    using tok_t = typename std::conditional<TOK_LDS, unsigned short, int>::type;
+    // the beam, twice (frame parity): masses, score, length, last token (0: the empty prefix), hash of the prefix and of the prefix without
+    // its last token
+    __shared__ float s_pb[2][BEAM_MAX], s_pnb[2][BEAM_MAX], s_sc[2][BEAM_MAX];
+    __shared__ int s_len[2][BEAM_MAX], s_last[2][BEAM_MAX], s_nb[2];
+    __shared__ unsigned s_hash[2][BEAM_MAX], s_hprev[2][BEAM_MAX];
+    // the frame: totals, the stay candidates' masses, the shortlist (bit j of word s), the member whose extension merged into s (-1: none)
+    __shared__ float s_tot[BEAM_MAX], s_spb[BEAM_MAX], s_spnb[BEAM_MAX], sel_sc[BEAM_MAX];
+    __shared__ int s_short[BEAM_MAX], s_mj[BEAM_MAX], sel_pos[BEAM_MAX];
+    __shared__ float r_sc[2][BEAM_WAVES];
+    __shared__ int r_pos[2][BEAM_WAVES];
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
+    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = p.W, V = p.V, cap = p.cap;
+    const int L = max(0, min(p.il ? (int)p.il[n] : p.T, p.T));
+    const float *rows = p.e + (long)n * p.sn;
+    float *s_e = reinterpret_cast<float *>(dyn);                       // STAGED: [2][V]
+    tok_t *tok;                                                        // [2][W][cap]
+    if constexpr (TOK_LDS) tok = reinterpret_cast<tok_t *>(dyn + (STAGED ? 2 * (size_t)V * sizeof(float) : 0));
+    else tok = reinterpret_cast<tok_t *>(p.ws) + (size_t)n * 2 * W * cap;
+    auto tok_row = [&](int copy, int j) { return tok + ((size_t)copy * W + j) * cap; };
+
+    if (tid < BEAM_MAX) {                                              // the empty prefix: every alignment of no frames ends "in blank"
+        s_pb[0][tid] = tid == 0 ? 0.f : -INFINITY; s_pnb[0][tid] = -INFINITY; s_sc[0][tid] = tid == 0 ? 0.f : -INFINITY;
+        s_len[0][tid] = 0; s_last[0][tid] = 0; s_hash[0][tid] = 0x811C9DC5u; s_hprev[0][tid] = 0u;
+        s_short[tid] = 0;
+        if (tid == 0) s_nb[0] = 1;
+    }
+    if constexpr (STAGED)
+        if (L > 0)
+            for (int k = tid; k < V; k += BEAM_THREADS) s_e[k] = rows[k];
+    __syncthreads();
+
+    int cur = 0;
+    for (int t = 0; t < L; ++t) {
+        const float *row = rows + (long)t * p.st;
+        const int eb = (t & 1) * V;
+        auto em = [&](int k) {
+            if constexpr (STAGED) return s_e[eb + k];
+            else return row[k];
+        };
+        // the next frame's emissions are requested here, before this frame's rounds; the addresses are clamped into the row's own frames
+        // and classes so that every load is issued unconditionally (what a clamp duplicates is dropped where it would be stored)
+        float nx[PF];
+        if constexpr (STAGED) {
+            const float *next = rows + (long)min(t + 1, L - 1) * p.st;
+#pragma unroll
+            for (int i = 0; i < PF; ++i) nx[i] = next[min(tid + i * BEAM_THREADS, V - 1)];
+        }
+        const int nb = s_nb[cur];
+        // ---- 1. totals and stay candidates; the shortlist of (s, j) with y_s possibly y_j + [last_s]
+        if (tid < BEAM_MAX) {
+            s_mj[tid] = -1;
+            if (tid < nb) {
+                const float pb = s_pb[cur][tid], pnb = s_pnb[cur][tid], tot = logaddexpf_(pb, pnb);
+                s_tot[tid] = tot;
+                s_spb[tid] = tot + em(0);
+                s_spnb[tid] = s_len[cur][tid] > 0 ? pnb + em(s_last[cur][tid]) : -INFINITY;
+            }
+        }
+        {
+            const int s = tid / BEAM_MAX, j = tid % BEAM_MAX;
+            if (s < nb && j < nb && s_len[cur][s] == s_len[cur][j] + 1 && s_hprev[cur][s] == s_hash[cur][j]) atomicOr(&s_short[s], 1 << j);
+        }
+        __syncthreads();
+        // ---- 2. the merge: wave w compares the tokens of the shortlisted pairs of s = w, w + 4, ...
+        for (int s = wave; s < nb; s += BEAM_WAVES) {
+            int mask = s_short[s];
+            while (mask) {                                              // (uniform over the wave)
+                const int j = __ffs(mask) - 1, lj = s_len[cur][j];
+                mask &= mask - 1;
+                const tok_t *ts = tok_row(cur, s), *tj = tok_row(cur, j);
+                bool differ = false;
+                for (int x = lane; x < lj; x += 64) differ = differ || ts[x] != tj[x];
+                if (__any(differ)) continue;
+                if (lane == 0) {
+                    const int k = s_last[cur][s];
+                    s_mj[s] = j;
+                    s_spnb[s] = logaddexpf_(s_spnb[s], em(k) + (k == s_last[cur][j] ? s_pb[cur][j] : s_tot[j]));
+                }
+                break;                                                  // beam members are distinct: no other j spells y_s[:-1]
+            }
+        }
+        __syncthreads();
+        // ---- 3. the W best candidates, one per round.  A thread owns the stay candidate tid and the extensions by its classes k = 1 + tid,
+        //         1 + tid + 256, ... of every member, whose scalars it holds in registers, and keeps the first of its candidates in the order
+        //         behind the last one taken; only the thread that owned the one just taken looks for its next (positions are unique).
+        const float stay_sc = tid < nb ? logaddexpf_(s_spb[tid], s_spnb[tid]) : -INFINITY;
+        float totv[BEAM_MAX], pbv[BEAM_MAX];
+        int lastv[BEAM_MAX];
+#pragma unroll
+        for (int j = 0; j < BEAM_MAX; ++j) {
+            const bool open = j < nb && s_len[cur][j] < cap;            // else no extension: every score of j is -inf
+            totv[j] = open ? s_tot[j] : -INFINITY; pbv[j] = open ? s_pb[cur][j] : -INFINITY; lastv[j] = open ? s_last[cur][j] : -1;
+        }
+        // the extensions merged away, one per stay candidate at most: (member, class), class -1 for none; bit k % 64 of merged_k says
+        // that some extension by a class congruent to k was (a filter in front of the exact comparison)
+        int gone_j[BEAM_MAX], gone_k[BEAM_MAX];
+        unsigned long long merged_k = 0;
+#pragma unroll
+        for (int s = 0; s < BEAM_MAX; ++s) {
+            gone_j[s] = s_mj[s];                                        // (-1 in slots without a member too)
+            gone_k[s] = gone_j[s] >= 0 ? s_last[cur][s] : -1;
+            if (gone_j[s] >= 0) merged_k |= 1ull << (gone_k[s] & 63);
+        }
+        auto first_behind = [&](float psc, int ppos, float &bsc, int &bpos) {
+            bsc = -INFINITY; bpos = 0x7fffffff;
+            if (stay_sc > -INFINITY && before(psc, ppos, stay_sc, tid)) { bsc = stay_sc; bpos = tid; }
+            for (int k = 1 + tid; k < V; k += BEAM_THREADS) {
+                const float ek = em(k);
+                unsigned gone = 0;                                      // bit j: the extension of j by k was merged away
+                if ((merged_k >> (k & 63)) & 1) {
+#pragma unroll
+                    for (int s = 0; s < BEAM_MAX; ++s) gone |= gone_k[s] == k ? 1u << (gone_j[s] & (BEAM_MAX - 1)) : 0u;
+                }
+#pragma unroll
+                for (int j = 0; j < BEAM_MAX; ++j) {
+                    const float sc = ek + (k == lastv[j] ? pbv[j] : totv[j]);
+                    const int pos = W + j * V + k;
+                    if (((gone >> j) & 1) || !(sc > -INFINITY) || !before(psc, ppos, sc, pos) || !before(sc, pos, bsc, bpos)) continue;
+                    bsc = sc; bpos = pos;
+                }
+            }
+        };
+        float lsc;
+        int lpos, nsel = 0;
+        first_behind(INFINITY, -1, lsc, lpos);
+        for (int r = 0; r < W; ++r) {
+            float bsc = lsc;
+            int bpos = lpos;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float osc = __shfl_xor(bsc, o, 64);
+                const int opos = __shfl_xor(bpos, o, 64);
+                if (before(osc, opos, bsc, bpos)) { bsc = osc; bpos = opos; }
+            }
+            if (lane == 0) { r_sc[r & 1][wave] = bsc; r_pos[r & 1][wave] = bpos; }
+            __syncthreads();
+            bsc = r_sc[r & 1][0]; bpos = r_pos[r & 1][0];
+#pragma unroll
+            for (int w = 1; w < BEAM_WAVES; ++w)
+                if (before(r_sc[r & 1][w], r_pos[r & 1][w], bsc, bpos)) { bsc = r_sc[r & 1][w]; bpos = r_pos[r & 1][w]; }
+            if (bpos == 0x7fffffff) break;                              // (uniform) no candidate is left
+            if (tid == 0) { sel_sc[r] = bsc; sel_pos[r] = bpos; }
+            nsel = r + 1;
+            if (lpos == bpos && r + 1 < W) first_behind(bsc, bpos, lsc, lpos);
+        }
+        __syncthreads();
+        // ---- 4. the new beam, in the order taken, into the other copy
+        const int nxt = cur ^ 1;
+        if (tid < BEAM_MAX) {
+            s_short[tid] = 0;
+            if (tid < nsel) {
+                const int pos = sel_pos[tid];
+                if (pos < W) {
+                    s_pb[nxt][tid] = s_spb[pos]; s_pnb[nxt][tid] = s_spnb[pos];
+                    s_len[nxt][tid] = s_len[cur][pos]; s_last[nxt][tid] = s_last[cur][pos];
+                    s_hash[nxt][tid] = s_hash[cur][pos]; s_hprev[nxt][tid] = s_hprev[cur][pos];
+                } else {
+                    const int par = (pos - W) / V, k = (pos - W) % V;
+                    s_pb[nxt][tid] = -INFINITY; s_pnb[nxt][tid] = sel_sc[tid];
+                    s_len[nxt][tid] = s_len[cur][par] + 1; s_last[nxt][tid] = k;
+                    s_hprev[nxt][tid] = s_hash[cur][par]; s_hash[nxt][tid] = s_hash[cur][par] * 0x9E3779B1u + (unsigned)k;
+                }
+                s_sc[nxt][tid] = sel_sc[tid];
+            }
+            if (tid == 0) s_nb[nxt] = nsel;
+        }
+        for (int r = wave; r < nsel; r += BEAM_WAVES) {                 // wave w copies the token rows of slots w, w + 4, ...
+            const int pos = sel_pos[r], par = pos < W ? pos : (pos - W) / V, lp = s_len[cur][par];
+            const tok_t *src = tok_row(cur, par);
+            tok_t *dst = tok_row(nxt, r);
+            for (int x = lane; x < lp; x += 64) dst[x] = src[x];
+            if (pos >= W && lane == 0) dst[lp] = (tok_t)((pos - W) % V);        // lp < cap: only such members are extended
+        }
+        if constexpr (STAGED) {
+            if (t + 1 < L) {
+                float *ne = s_e + (eb ^ V);                             // the other frame's buffer (eb is 0 or V)
+#pragma unroll
+                for (int i = 0; i < PF; ++i) {
+                    const int k = tid + i * BEAM_THREADS;
+                    if (k < V) ne[k] = nx[i];
+                }
+                const float *next = row + p.st;
+                for (int k = tid + PF * BEAM_THREADS; k < V; k += BEAM_THREADS) ne[k] = next[k];
+            }
+        }
+        __syncthreads();
+        cur = nxt;
+    }
+
+    // the beam after the last frame, in its order; a row of no frames keeps the empty prefix, score 0
+    const int nb = s_nb[cur];
+    const long base = (long)n * W;
+    if (tid < W) {
+        p.lengths[base + tid] = tid < nb ? s_len[cur][tid] : -1;
+        p.scores[base + tid] = tid < nb ? s_sc[cur][tid] : -INFINITY;
+    }
+    if (tid == 0) p.counts[n] = nb;
+    for (int idx = tid; idx < W * cap; idx += BEAM_THREADS) {
+        const int r = idx / cap, x = idx % cap;
+        p.tokens[base * cap + idx] = (r < nb && x < s_len[cur][r]) ? (int64_t)tok_row(cur, r)[x] : -1;
+    }
+}
+
+bool tokens_in_lds(int V, int beam, int capacity) { return V <= 65536 && 2 * (long)beam * capacity <= TOK_LDS_TOKENS; }
+
+bool valid_shape(int N, int T, int V, int beam, int capacity) {
+    return N > 0 && T > 0 && V >= 2 && V <= V_MAX && beam >= 1 && beam <= BEAM_MAX && capacity >= 1 && capacity <= T;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t halo_ctc_prefix_beam_workspace_bytes(int N, int T, int V, int beam, int capacity) {
+    if (!valid_shape(N, T, V, beam, capacity) || tokens_in_lds(V, beam, capacity)) return 0;
+    return (size_t)N * 2 * beam * capacity * sizeof(int);
+}
+
+int halo_ctc_prefix_beam(const float *emissions, long stride_t, long stride_n, int T, int N, int V, const int64_t *emission_lengths,
+                         int beam, int capacity, void *workspace, int64_t *tokens, int64_t *lengths, float *scores, int64_t *counts,
+                         halo_stream_t stream) {
+    HALO_CHECK_ARG(emissions && tokens && lengths && scores && counts);
+    HALO_CHECK_ARG(valid_shape(N, T, V, beam, capacity));
+    const bool staged = 2 * (long)V <= E_LDS_FLOATS, tok_lds = tokens_in_lds(V, beam, capacity);
+    HALO_CHECK_ARG(tok_lds || workspace);
+    CtcPrefixBeamArgs a;
+    a.e = emissions; a.st = stride_t; a.sn = stride_n; a.T = T; a.V = V; a.W = beam; a.cap = capacity; a.il = emission_lengths;
+    a.ws = (int *)workspace; a.tokens = tokens; a.lengths = lengths; a.counts = counts; a.scores = scores;
+    const size_t lds = (staged ? 2 * (size_t)V * sizeof(float) : 0) + (tok_lds ? 2 * (size_t)beam * capacity * sizeof(unsigned short) : 0);
+    const dim3 grid((unsigned)N), block(BEAM_THREADS);
+    if (staged && tok_lds) hipLaunchKernelGGL((ctc_prefix_beam_kernel<true, true>), grid, block, lds, (hipStream_t)stream, a);
+    else if (staged) hipLaunchKernelGGL((ctc_prefix_beam_kernel<true, false>), grid, block, lds, (hipStream_t)stream, a);
+    else if (tok_lds) hipLaunchKernelGGL((ctc_prefix_beam_kernel<false, true>), grid, block, lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((ctc_prefix_beam_kernel<false, false>), grid, block, lds, (hipStream_t)stream, a);
+    return halo_launch_status();
+}
+
+}  // extern "C"

@@ -2,7 +2,11 @@
 launch of the wave-per-utterance alpha kernel with the flags that reproduce that variant.
 
 ``ctc_viterbi`` is forced alignment, which the reference does not have: the best path of F.ctc_loss's lattice and its backtrace in one
-launch (csrc/viterbi.hip)."""
+launch (csrc/viterbi.hip).
+
+``ctc_prefix_beam_search`` is CTC prefix beam search with exact merging, n-best lists from CTC emissions in the format of
+``transducer.BeamDecoder.decode``: the whole batch in one launch (csrc/ctc_prefix_beam.hip).  ``haloop_amd.beam`` stays
+the reference's unmerged ha/beam.py."""
 import torch
 
 from . import _lib, ops
@@ -65,6 +69,44 @@ def ctc_viterbi(emissions, targets, emission_lengths, target_lengths):
     il = None if emission_lengths is None else emission_lengths.to(dev)
     scores, ali, starts, ends = ops.ctc_viterbi(em, True, targets, il, target_lengths.to(dev))
     return (scores, ali, starts[:, :0], ends[:, :0]) if S == 0 else (scores, ali, starts, ends)
+
+
+def ctc_prefix_beam_search(emissions, emission_lengths=None, beam=4, capacity=None):
+    """CTC prefix beam search with exact merging ([Hannun14], Graves' prefix search; csrc/ctc_prefix_beam.hip), the whole
+    batch in one launch: emissions [T, N, V] log-probabilities with class 0 the blank (a strided view with a unit class stride is read in
+    place, so the head's ``log_probs.permute(1, 0, 2)`` costs no copy; they are not normalised here), emission_lengths [N] (None: T;
+    clamped to [0, T]), ``beam`` = W from 1 to 16, ``capacity`` = the longest hypothesis, from 1 to T (None: T) ->
+
+        tokens [N, W, capacity] int64   -1 past a hypothesis's length and in absent hypotheses
+        lengths [N, W] int64            -1: an absent hypothesis
+        scores [N, W] float32           log of the mass the search kept of the hypothesis, best first; -inf: absent
+        counts [N] int64                hypotheses of the row
+
+    the format of ``transducer.BeamDecoder.decode``, so ``wer.edit_distance(group=W)``, ``wer.nbest_oracle`` and
+    ``transducer.nbest_risk`` take it as it is.  A member of the beam is a prefix with the masses of its alignments that end in blank and
+    in its last label; per frame every member stays or is extended by every label, an extension that spells another member's prefix is
+    merged into it, and the W best by (score descending, candidate position ascending) are kept: the definition and the tie rules are in
+    include/halo.h.  The empty hypothesis is an ordinary member of the list; a row of no frames returns it alone, score 0.  Without
+    pruning a score is ``-functional.ctc_loss(reduction='none')`` of its hypothesis, with pruning a lower bound.  Frames at or past a
+    row's length are never read.  Not differentiable: the inputs are detached."""
+    if emissions.dim() != 3 or emissions.shape[0] < 1 or emissions.shape[1] < 1 or emissions.shape[2] < 2:
+        raise ValueError(f'ctc_prefix_beam_search: emissions must be [T >= 1, N >= 1, V >= 2], got {tuple(emissions.shape)}')
+    T, N, _ = emissions.shape
+    W = int(beam)
+    if W < 1 or W > ops.BEAM_MAX:
+        raise ValueError(f'ctc_prefix_beam_search: beam {W} outside 1 .. {ops.BEAM_MAX}')
+    cap = T if capacity is None else int(capacity)
+    if cap < 1 or cap > T:
+        raise ValueError(f'ctc_prefix_beam_search: capacity {cap} outside 1 .. T = {T}')
+    if emission_lengths is not None and tuple(emission_lengths.shape) != (N,):
+        raise ValueError(f'ctc_prefix_beam_search: emission_lengths must be [{N}]')
+    if not emissions.is_cuda:
+        raise _lib.HaloError('haloop_amd.ctc.ctc_prefix_beam_search runs on the HIP device only (no CPU path)')
+    em = emissions.detach().float()
+    if em.stride(-1) != 1:
+        em = em.contiguous()
+    il = None if emission_lengths is None else emission_lengths.detach().to(em.device)
+    return ops.ctc_prefix_beam(em, il, W, cap)
 
 
 def ctc_reduce_mean(losses, target_lengths):

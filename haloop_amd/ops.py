@@ -1388,6 +1388,31 @@ def transducer_viterbi(joint, targets, joint_lengths, target_lengths, checked=Fa
     return scores, frames
 
 
+# ---- CTC prefix beam search: n-best lists from CTC emissions in one launch (csrc/ctc_prefix_beam.hip) ---------------------------------
+BEAM_MAX = 16                    # widths the two beam searches take (csrc/rnnt_beam.hip, csrc/ctc_prefix_beam.hip)
+
+
+def ctc_prefix_beam(emissions, emission_lengths, beam, capacity):
+    """emissions [T, N, V] fp32 log-probabilities, any time and batch strides with a unit class stride; emission_lengths [N] int64 or
+    None (T) -> (tokens [N, beam, capacity] int64, lengths [N, beam] int64, scores [N, beam] f32, counts [N] int64) (include/halo.h)."""
+    if emissions.dtype != torch.float32 or emissions.dim() != 3 or emissions.stride(-1) != 1 or not emissions.is_cuda:
+        raise ValueError('ctc_prefix_beam: emissions must be a float32 HIP tensor of three dimensions with unit class stride')
+    T, N, V = emissions.shape
+    il = None if emission_lengths is None else _i64c(emission_lengths, 'emission_lengths')
+    if il is not None and il.shape != (N,):
+        raise ValueError(f'ctc_prefix_beam: emission_lengths must be [{N}]')
+    dev = emissions.device
+    tokens = torch.empty(N, beam, capacity, device=dev, dtype=torch.int64)
+    lengths = torch.empty(N, beam, device=dev, dtype=torch.int64)
+    scores = torch.empty(N, beam, device=dev, dtype=torch.float32)
+    counts = torch.empty(N, device=dev, dtype=torch.int64)
+    nbytes = lib().halo_ctc_prefix_beam_workspace_bytes(N, T, V, beam, capacity)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    check(lib().halo_ctc_prefix_beam(ptr(emissions), emissions.stride(0), emissions.stride(1), T, N, V, ptr(il), beam, capacity, ptr(ws),
+                                     ptr(tokens), ptr(lengths), ptr(scores), ptr(counts), _stream()), 'halo_ctc_prefix_beam')
+    return tokens, lengths, scores, counts
+
+
 # ---- edit distance and the risk of an n-best list (csrc/edit_distance.hip) -----------------------------------------------------------
 EDIT_DISTANCE_MAX_LEN = 1024     # HALO_EDIT_DISTANCE_MAX_LEN (include/halo.h)
 

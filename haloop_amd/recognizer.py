@@ -5,18 +5,31 @@ import torch
 import torch.nn as nn
 
 from . import _lib, functional as HF, ops, wer
-from .ctc import ctc_reduce_mean, ctc_viterbi
+from .ctc import ctc_prefix_beam_search, ctc_reduce_mean, ctc_viterbi
 from .rnn import Decoder, DropoutStream
 from .star import star_ctc_forward_score
 from .transducer import BeamDecoder, GreedyDecoder, nbest_risk, transducer_align, transducer_forward_score, transducer_loss
 
 
 class TemporalClassifier(nn.Module):
+    """The CTC head (ha/recognizer.py:37-83).
+
+    ``beam_size`` (HALO_CTC_BEAM when the head is built; a caller may set the attribute or pass ``decode(..., beam_size=W)``): 0, the
+    default, decodes greedily as the reference does; W >= 1 runs ``ctc.ctc_prefix_beam_search`` at that width, returns
+    each row's best hypothesis and keeps the whole n-best result of the last call as ``last_nbest``.
+
+    ``mwer_beam`` (HALO_CTC_MWER when the head is built; a caller may set the attribute): 0, the default, leaves ``forward`` as it is;
+    W >= 1 makes ``forward`` of a head in training mode return ``mwer_forward(..., beam_size=W)``, minimum-word-error-rate fine-tuning
+    on the n-best lists of the prefix search."""
+
     def __init__(self, feat_dim=1024, vocab_size=256):
         super().__init__()
         self.classifier = nn.Linear(feat_dim, vocab_size)
         self.dropout = nn.Dropout(0.2)
         self.dropout_stream = DropoutStream()
+        self.beam_size = int(os.environ.get('HALO_CTC_BEAM', '0'))
+        self.mwer_beam = int(os.environ.get('HALO_CTC_MWER', '0'))
+        self.last_nbest = None
 
     def log_probs(self, features):
         if not features.is_cuda:
@@ -26,7 +39,10 @@ class TemporalClassifier(nn.Module):
         logits = HF.linear(features, self.classifier.weight, self.classifier.bias)
         return HF.log_softmax(logits)
 
-    def decode(self, features, input_lengths, target_lengths):
+    def decode(self, features, input_lengths, target_lengths, beam_size=None):
+        width = self.beam_size if beam_size is None else int(beam_size)
+        if width:
+            return self._decode_beam(features, input_lengths, width)
         # greedy, input_lengths ignored exactly like recognizer.py:48-59
         logits = self.log_probs(features)
         alignments, scores, hyp, hyp_len = ops.ctc_greedy(logits.detach().contiguous())
@@ -34,6 +50,74 @@ class TemporalClassifier(nn.Module):
         hypotheses = torch.nested.nested_tensor([hyp[i, :n] for i, n in enumerate(lens)])
         output_lengths = torch.tensor(lens)
         return hypotheses, output_lengths, alignments, scores, None
+
+    def _decode_beam(self, features, input_lengths, width):
+        """Prefix beam search at ``width`` on this head's ``log_probs``, honouring ``input_lengths`` (None: T), with room for T symbols:
+        each row's best hypothesis in the five-value form ``Transducer._decode_beam`` returns (a merged hypothesis has no single
+        alignment: the third value is [None] * N); ``last_nbest`` = (tokens [N, W, T], lengths [N, W], scores [N, W], counts [N])."""
+        if width < 0:
+            raise ValueError(f'TemporalClassifier.decode: beam_size {width} is negative')
+        if self.training:
+            raise NotImplementedError('TemporalClassifier.decode(beam_size >= 1) is an inference path: put the head in eval mode')
+        N = features.shape[0]
+        with torch.no_grad():
+            logits = self.log_probs(features)
+            self.last_nbest = ctc_prefix_beam_search(logits.permute(1, 0, 2), input_lengths, width)
+        tokens, lengths, scores, _ = self.last_nbest
+        lens = lengths[:, 0].tolist()                           # every row returns at least one hypothesis
+        hypotheses = torch.nested.nested_tensor([tokens[i, 0, :max(n, 0)] for i, n in enumerate(lens)])
+        return hypotheses, torch.tensor(lens), [None] * N, scores[:, 0].clone(), None
+
+    def _search_nbest(self, features, input_lengths, capacity, width):
+        """The search of ``mwer_forward``: under ``no_grad``, on the head in eval mode (no dropout, and nothing drawn from the dropout
+        stream); every module's mode is put back, also when the search raises."""
+        modes = [(m, m.training) for m in self.modules()]
+        self.eval()
+        try:
+            with torch.no_grad():
+                return ctc_prefix_beam_search(self.log_probs(features).permute(1, 0, 2), input_lengths, width, capacity)
+        finally:
+            for m, mode in modes:
+                m.training = mode
+
+    def mwer_forward(self, features, targets, input_lengths, target_lengths, beam_size=4, mle_weight=0.01):
+        """Minimum-word-error-rate training on n-best lists, the CTC twin of ``Transducer.mwer_forward`` ([Prabhavalkar18]; DESIGN.md
+        3.3o, 3.3p) -> (loss, info):
+
+            the W = beam_size best hypotheses of every row by ``ctc.ctc_prefix_beam_search`` (no gradient, the head in eval mode for the
+                search, the features undropped, room for min(T, target_lengths.max() + 1) symbols);
+            their error counts against ``targets`` by ``wer.edit_distance``;
+            their losses -log P(hypothesis | x) by ``functional.ctc_loss(reduction='none')`` on N * W rows: the hypotheses (padding and
+                absent hypotheses as token 0, absent ones with length 0) against W views of the row's log-probabilities, which
+                ``forward``'s dropout stream, classifier and log-softmax produce;
+            loss = mean_n ``transducer.nbest_risk``(losses, errors)[n] (+ mle_weight x the CTC loss of ``forward`` on the same
+                log-probabilities, unless mle_weight is 0).
+
+        ``info``: ``nbest`` (the search's tuple), ``errors`` [N, W] int32, ``risk`` [N] and ``nbest_losses`` [N, W], detached.  The empty
+        hypothesis is an ordinary member of a CTC n-best list (length 0, present).  The N * W views of the log-probabilities are
+        materialised once (W x their size; the lattice kernels take no group argument); their gradient is summed over W by the view's
+        backward, not by an index-add.  Every launch on the path is deterministic."""
+        if not features.is_cuda:
+            raise _lib.HaloError('haloop_amd.recognizer.TemporalClassifier runs on the HIP device only')
+        dev = features.device
+        N, T, W = features.shape[0], features.shape[1], int(beam_size)
+        targets, il, tl = targets.to(dev), input_lengths.to(dev), target_lengths.to(dev)
+        nbest = self._search_nbest(features, il, min(T, int(tl.max()) + 1), W)
+        tokens, lengths = nbest[0], nbest[1]                                             # [N, W, cap] (-1 padded), [N, W] (-1: absent)
+        errors, _ = wer.edit_distance(tokens, lengths, targets, tl, group=W)
+        errors = errors.view(N, W)
+
+        logits = self.log_probs(features)                                                # (N, T, C)
+        V = logits.shape[2]
+        hyps = tokens.clamp(min=0).view(N * W, -1)
+        rows = logits[:, None].expand(N, W, T, V).reshape(N * W, T, V)
+        losses = HF.ctc_loss(rows.permute(1, 0, 2), hyps, il[:, None].expand(N, W).reshape(-1), lengths.clamp(min=0).view(-1),
+                             reduction='none').view(N, W)
+        risk = nbest_risk(losses, errors)
+        loss = risk.mean()
+        if mle_weight != 0:
+            loss = loss + mle_weight * HF.ctc_loss(logits.permute(1, 0, 2), targets, il, tl)
+        return loss, {'nbest': nbest, 'errors': errors, 'risk': risk.detach(), 'nbest_losses': losses.detach()}
 
     def align(self, features, targets, input_lengths=None, target_lengths=None):
         """Forced alignment of ``targets`` [N, S] to the frames of ``features`` [N, T, feat_dim] (lengths default to T and S as in
@@ -54,6 +138,8 @@ class TemporalClassifier(nn.Module):
             input_lengths = torch.full((features.shape[0],), features.shape[1], dtype=torch.long)
         if target_lengths is None:
             target_lengths = torch.full((features.shape[0],), len(targets), dtype=torch.long)
+        if self.mwer_beam > 0 and self.training and star_penalty is None:
+            return self.mwer_forward(features, targets, input_lengths, target_lengths, beam_size=self.mwer_beam)
         logits = self.log_probs(features)
         if star_penalty is not None:
             # recognizer.py:74-82: the star-CTC branch reads self.star_penalty, which the reference's constructor never sets (so it raises

@@ -1010,6 +1010,42 @@ int halo_nbest_risk_fwd(const float *losses, const int *errors, int N, int W, fl
 int halo_nbest_risk_bwd(const float *losses, const int *errors, int N, int W, const float *grad_risk, float *dlosses, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CTC prefix beam search with exact merging ([Hannun14], Graves' prefix search; csrc/ctc_prefix_beam.hip): n-best lists
+ * from CTC emissions in the format of the transducer beam search.  The reference's own CTC beam (ha/beam.py, halo_ctc_beam above) never
+ * merges hypotheses that spell the same tokens; this search is a capability of this library.  One launch for the whole batch, one
+ * workgroup per utterance, the frame loop inside; fp32, no float atomics, every sum in a fixed order (bit-reproducible); the launch is
+ * finite and no workgroup reads what another workgroup writes.
+ *   halo_ctc_prefix_beam   emissions [T][N][V] fp32 log-probabilities, read in place (stride_t, stride_n in floats, unit class stride;
+ *                          they are not normalised here); emission_lengths [N] int64 (NULL: T), L = clamp(., 0, T); frames at or past L
+ *                          are never loaded.  Class 0 is the blank.  Per row, with W = beam and cap = capacity:
+ *                              beam = [((), pb = 0, pnb = -inf)]     pb / pnb: log-mass of the prefix's alignments ending in blank / in
+ *                                                                    its last label
+ *                              for t in 0 .. L-1:
+ *                                total_j = logaddexp(pb_j, pnb_j)
+ *                                candidates, in this order:
+ *                                  for j in beam order: stay (y_j, pb' = total_j + e[t][0], pnb' = pnb_j + e[t][last(y_j)], -inf for the
+ *                                      empty prefix)
+ *                                  for j in beam order, if len(y_j) < cap, for k = 1 .. V-1: extension (y_j + [k], pb' = -inf,
+ *                                      pnb' = e[t][k] + (pb_j if k == last(y_j) else total_j))
+ *                                an extension that spells the prefix of a stay candidate s is merged into it
+ *                                  (pnb'_s = logaddexp(pnb'_s, the extension's pnb')) and dropped.  Equality of prefixes is decided by
+ *                                  comparing tokens (a hash only shortlists).  Beam members are distinct, so this is the only merge.
+ *                                beam = the W best candidates by (logaddexp(pb', pnb') descending, candidate position ascending: a stay
+ *                                  before every extension, then beam order, then k); candidates at -inf are never kept
+ *                          Outputs, best first in that order: tokens [N][beam][capacity] int64 (-1 past a hypothesis's length and in absent
+ *                          hypotheses), lengths [N][beam] int64 (-1: absent), scores [N][beam] = logaddexp(pb, pnb) (-inf: absent),
+ *                          counts [N] int64.  L = 0: the empty hypothesis alone, score 0.  Without pruning a score is the CTC lattice total
+ *                          log P(y | x), what halo_ctc_fwd negates; with pruning a lower bound of it.
+ *                          Limits: 1 <= beam <= 16, 2 <= V <= 2^26, T >= 1, 1 <= capacity <= T.
+ *                          workspace: halo_ctc_prefix_beam_workspace_bytes(N, T, V, beam, capacity) bytes (NULL when that is 0): the
+ *                          token rows of the beam, [N][2][beam][capacity] int32, when they do not fit LDS (V > 65536 or
+ *                          2 beam capacity > 12288); 0 for an invalid shape. */
+size_t halo_ctc_prefix_beam_workspace_bytes(int N, int T, int V, int beam, int capacity);
+int halo_ctc_prefix_beam(const float *emissions, long stride_t, long stride_n, int T, int N, int V, const int64_t *emission_lengths,
+                         int beam, int capacity, void *workspace, int64_t *tokens, int64_t *lengths, float *scores, int64_t *counts,
+                         halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Backward operators of the GPT / transformer training step (the autograd graph of ha/attention.py:205-232 as
  * `hal` runs it, ha/attention_loop.py:196-215: loss.backward()).
  *   halo_attention_bwd         gradient of halo_attention_fwd: dq, dk, dv (same row layouts as q, k, v; written, not
