@@ -192,6 +192,8 @@ SIGNATURES = {
     'halo_transducer_viterbi': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_ctc_prefix_beam_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'halo_ctc_prefix_beam': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'halo_ctc_lm_beam_step': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _f, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp,
+                                   _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'halo_edit_distance': (_i, [_vp, _l, _vp, _i, _i, _vp, _l, _vp, _i, _i, _i, _vp, _vp, _vp]),
     'halo_nbest_risk_fwd': (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     'halo_nbest_risk_bwd': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),

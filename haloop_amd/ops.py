@@ -1629,6 +1629,34 @@ def rnnt_beam_keep(parent, last, h_in, c_in, g_in, h_out, c_out, g_out):
                                     ptr(h_out), ptr(c_out), ptr(g_out), _stream()), 'halo_rnnt_beam_keep')
 
 
+# ---- the per-frame launch of CTC prefix beam search with LM shallow fusion (csrc/ctc_lm_beam.hip); it does not allocate ---------------
+def ctc_lm_beam_step(emissions, emission_lengths, frame, capacity, lm_weight, insertion_bonus, g, g_bias, rec_in, rec_out, parent, last, wte,
+                     h_in, c_in, xh, c_out):
+    """Frame ``frame`` of every row (include/halo.h): emissions [T, N, V] fp32 with unit class stride; emission_lengths [N] int32;
+    g [N * W, V] (bias apart); rec_in / rec_out = (rec [N, W, 4] fp32, meta [N, W, 4] int32, tokens [N, W, >= capacity] int32); parent /
+    last [N, W] int32; h_in / c_in / c_out [layers, N * W, H], xh [layers, N * W, 2 H], all contiguous."""
+    T, N, V = emissions.shape
+    W = parent.shape[1]
+    layers, slots, H = h_in.shape
+    tensors = (g, *rec_in, *rec_out, parent, last, h_in, c_in, xh, c_out, emission_lengths)
+    if emissions.dtype != torch.float32 or emissions.stride(2) != 1 or not all(t.is_contiguous() for t in tensors):
+        raise ValueError('ctc_lm_beam_step: emissions must be fp32 with unit class stride and every other tensor contiguous')
+    if slots != N * W or g.shape != (slots, V) or wte.shape != (wte.shape[0], H) or wte.shape[0] < V or not wte.is_contiguous():
+        raise ValueError('ctc_lm_beam_step: g must be [N * W, V], the state [layers, N * W, H] and the embedding [>= V, H]')
+    if xh.shape != (layers, slots, 2 * H) or c_in.shape != h_in.shape or c_out.shape != h_in.shape:
+        raise ValueError('ctc_lm_beam_step: xh must be [layers, N * W, 2 H], c_in and c_out as h_in')
+    ld = rec_in[2].shape[2]
+    if any(t.shape != (N, W, 4) for t in (rec_in[0], rec_in[1], rec_out[0], rec_out[1])) or last.shape != (N, W) \
+            or any(t.shape != (N, W, ld) for t in (rec_in[2], rec_out[2])) or emission_lengths.shape != (N,) \
+            or emission_lengths.dtype != torch.int32:
+        raise ValueError('ctc_lm_beam_step: records must be [N, W, 4] with tokens [N, W, ld], parent / last [N, W], lengths [N] int32')
+    check(lib().halo_ctc_lm_beam_step(ptr(emissions), emissions.stride(0), emissions.stride(1), T, N, V, ptr(emission_lengths), int(frame), W,
+                                      int(capacity), float(lm_weight), float(insertion_bonus), ptr(g), g.stride(0), ptr(g_bias),
+                                      ptr(rec_in[0]), ptr(rec_in[1]), ptr(rec_in[2]), ptr(rec_out[0]), ptr(rec_out[1]), ptr(rec_out[2]), ld,
+                                      ptr(parent), ptr(last), ptr(wte), H, layers, ptr(h_in), ptr(c_in), ptr(xh), ptr(c_out), _stream()),
+          'halo_ctc_lm_beam_step')
+
+
 # ---- channels-last conv front-end (ha/conv.py) -------------------------------------------------------------
 def conv_out_length(T, ks, stride, pad):
     return (T + 2 * pad - ks) // stride + 1

@@ -6,6 +6,7 @@ import torch.nn as nn
 
 from . import _lib, functional as HF, ops, wer
 from .ctc import ctc_prefix_beam_search, ctc_reduce_mean, ctc_viterbi
+from .fusion import CTCFusionDecoder
 from .rnn import Decoder, DropoutStream
 from .star import star_ctc_forward_score
 from .transducer import BeamDecoder, GreedyDecoder, nbest_risk, transducer_align, transducer_forward_score, transducer_loss
@@ -20,7 +21,11 @@ class TemporalClassifier(nn.Module):
 
     ``mwer_beam`` (HALO_CTC_MWER when the head is built; a caller may set the attribute): 0, the default, leaves ``forward`` as it is;
     W >= 1 makes ``forward`` of a head in training mode return ``mwer_forward(..., beam_size=W)``, minimum-word-error-rate fine-tuning
-    on the n-best lists of the prefix search."""
+    on the n-best lists of the prefix search.
+
+    ``set_lm(lm, lm_weight, insertion_bonus)`` fuses an ``rnn.Decoder`` language model into the search of ``decode`` at a width
+    W >= 1 (``fusion.CTCFusionDecoder``); ``set_lm(None)`` takes it out again.  The LM is no submodule of the head:
+    ``state_dict()``, ``parameters()``, ``to()`` and ``train()`` do not see it."""
 
     def __init__(self, feat_dim=1024, vocab_size=256):
         super().__init__()
@@ -30,6 +35,22 @@ class TemporalClassifier(nn.Module):
         self.beam_size = int(os.environ.get('HALO_CTC_BEAM', '0'))
         self.mwer_beam = int(os.environ.get('HALO_CTC_MWER', '0'))
         self.last_nbest = None
+        self.last_parts = None
+        self._fusion = None    # None, or a dict (not a module: the LM stays out of this head's parameters and state_dict)
+
+    def set_lm(self, lm, lm_weight=0.5, insertion_bonus=0.0):
+        """Fuse ``lm`` (an ``rnn.Decoder`` over this head's classes, in eval mode, on the device; the caller moves it) into
+        ``decode(beam_size=W >= 1)``: candidates rank by their CTC mass + lm_weight * log P_LM + insertion_bonus * length, ``last_nbest``
+        holds the fused lists and ``last_parts`` their (ctc_scores, lm_scores).  ``set_lm(None)`` restores the unfused search.  Greedy
+        decoding and ``mwer_forward`` do not use the LM."""
+        if lm is None:
+            self._fusion, self.last_parts = None, None
+            return
+        V = self.classifier.out_features
+        if getattr(lm, 'num_classes', None) != V:
+            raise ValueError(f'TemporalClassifier.set_lm: the LM has {getattr(lm, "num_classes", None)} classes, the head {V}')
+        CTCFusionDecoder(lm, 1, 1, 1, lm_weight, insertion_bonus)      # the argument checks, now and not at the first decode
+        self._fusion = {'lm': lm, 'lm_weight': float(lm_weight), 'insertion_bonus': float(insertion_bonus), 'decoder': None}
 
     def log_probs(self, features):
         if not features.is_cuda:
@@ -60,9 +81,22 @@ class TemporalClassifier(nn.Module):
         if self.training:
             raise NotImplementedError('TemporalClassifier.decode(beam_size >= 1) is an inference path: put the head in eval mode')
         N = features.shape[0]
+        fusion = getattr(self, '_fusion', None)
         with torch.no_grad():
             logits = self.log_probs(features)
-            self.last_nbest = ctc_prefix_beam_search(logits.permute(1, 0, 2), input_lengths, width)
+            if fusion is None:
+                self.last_nbest = ctc_prefix_beam_search(logits.permute(1, 0, 2), input_lengths, width)
+            else:
+                if width > ops.BEAM_MAX:
+                    raise ValueError(f'TemporalClassifier.decode: beam_size {width} outside 1 .. {ops.BEAM_MAX}')
+                T, dec = logits.shape[1], fusion['decoder']
+                if dec is None or dec.max_batch < N or dec.capacity < T or dec.beam < width \
+                        or dec._device != fusion['lm'].embedding.weight.device:       # an LM moved since needs new buffers
+                    dec = CTCFusionDecoder(fusion['lm'], max(N, dec.max_batch if dec else 0), max(T, dec.capacity if dec else 0),
+                                           max(width, dec.beam if dec else 0))
+                    fusion['decoder'] = dec
+                self.last_nbest = dec.decode(logits.permute(1, 0, 2), input_lengths, T, width, fusion['lm_weight'], fusion['insertion_bonus'])
+                self.last_parts = dec.last_parts
         tokens, lengths, scores, _ = self.last_nbest
         lens = lengths[:, 0].tolist()                           # every row returns at least one hypothesis
         hypotheses = torch.nested.nested_tensor([tokens[i, 0, :max(n, 0)] for i, n in enumerate(lens)])

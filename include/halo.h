@@ -1046,6 +1046,50 @@ int halo_ctc_prefix_beam(const float *emissions, long stride_t, long stride_n, i
                          halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CTC prefix beam search with shallow fusion of an LSTM language model (haloop_amd/fusion.py CTCFusionDecoder; csrc/ctc_lm_beam.hip,
+ * DESIGN.md 3.3q) as a launch sequence: per frame one halo_ctc_lm_beam_step, one halo_rnnt_lstm_cell per LSTM layer and one
+ * halo_decode_linear on all N * beam slots, and one halo_rnnt_beam_keep.  Slot n * beam + r is member r of row n's beam.  The beam's
+ * records and the LM state (h and c [layers][N * beam][hidden], g [N * beam][ldg]) exist twice, by frame parity; a step reads one copy
+ * and writes the other.
+ *   Definition, per row, with e = emissions[:, n] (log-probabilities, class 0 the blank), L = clamp(emission_lengths[n], 0, T),
+ *   W = beam, cap = capacity, a = lm_weight, b = insertion_bonus.  A member is (y, pb, pnb, lm, lp, state): pb / pnb the CTC masses of
+ *   halo_ctc_prefix_beam, lm the LM's log-probability of y, lp = log_softmax(g + g_bias) over all V classes of the LM after it consumed
+ *   the start token and then y, state the LSTM state behind lp.
+ *       beam = [((), pb = 0, pnb = -inf, lm = 0, lp and state after one LM step on the start token from the zero state)]
+ *       for t in 0 .. L-1:
+ *         total_j = logaddexp(pb_j, pnb_j)
+ *         candidates, in this order:
+ *           for j in beam order: stay (y_j, pb' = total_j + e[t][0], pnb' = pnb_j + e[t][last(y_j)] (-inf for the empty prefix), lm' = lm_j)
+ *           for j in beam order, if len(y_j) < cap, for k = 1 .. V-1: extension (y_j + [k], pb' = -inf,
+ *               pnb' = e[t][k] + (pb_j if k == last(y_j) else total_j), lm' = lm_j + lp_j[k])
+ *         an extension that spells the prefix of a stay candidate s is merged into it: its CTC mass joins pnb'_s (logaddexp), s keeps its
+ *           own lm, and the extension is no candidate.  Equality of prefixes is decided by comparing tokens (a hash only shortlists).
+ *         beam = the W best candidates by (logaddexp(pb', pnb') + a lm' + b len(y') descending, candidate position ascending: stay j at
+ *           j, the extension of j by k at W + j V + k); a candidate whose CTC mass is -inf is never kept.  A kept extension takes one LM
+ *           step from its parent's state; a kept stay keeps its parent's lp and state.
+ *       result: the beam after frame L-1, best first.  L = 0: the empty hypothesis alone, every score 0.
+ *   With a = b = 0 this is halo_ctc_prefix_beam, token for token.
+ *   halo_ctc_lm_beam_step  frame `frame` of every row, one workgroup of 256 threads per row.  rec [N][beam][4] fp32 = pb | pnb | lm | the
+ *                          ranking value, meta [N][beam][4] int32 = length (-1: no member) | last token (0: the empty prefix) | hash of
+ *                          the prefix | hash of the prefix without its last token, tokens [N][beam][tokens_ld] int32; at frame 0 the
+ *                          input records are not read.  Outputs: the new beam's records in the order taken, parent (the slot within the
+ *                          row it came from; -1: no member) and last (the token appended; 0: a stay), and the gather of
+ *                          halo_rnnt_beam_step: xh [layers][N * beam][2 hidden] of every new slot = wte[last] (layer 0's x half) | h_in of
+ *                          its parent (the h halves), c_out = c_in of its parent.  A row with frame >= L passes its beam through
+ *                          unchanged (parent = own index, last = 0) and loads no emission; frames at or past L, other rows' frames and
+ *                          the gaps of a strided view are never loaded.  lp_j[k] = (g[slot j][k] + g_bias[k]) - lse_j with the
+ *                          log-sum-exp summed in one fixed order; an extension's ranking value is
+ *                          fma(a, lm_j + lp_j[k], pnb') + b (len(y_j) + 1), a stay's fma(a, lm_j, logaddexp(pb', pnb')) + b len(y_j).
+ *                          The row's beam * V LM logits are cached in LDS when (beam + 1) V <= 14336 floats and recomputed from L2
+ *                          by the same operations otherwise: the same bits.  fp32, no float atomics, bit-reproducible.
+ *                          Limits: 2 <= V <= 8192, 1 <= beam <= 16, hidden % 4 == 0, 1 <= capacity <= tokens_ld, 0 <= frame < T. */
+int halo_ctc_lm_beam_step(const float *emissions, long stride_t, long stride_n, int T, int N, int V, const int *emission_lengths, int frame,
+                          int beam, int capacity, float lm_weight, float insertion_bonus, const float *g, long ldg, const float *g_bias,
+                          const float *rec_in, const int *meta_in, const int *tokens_in, float *rec_out, int *meta_out, int *tokens_out,
+                          long tokens_ld, int *parent, int *last, const float *wte, int hidden, int layers, const float *h_in,
+                          const float *c_in, float *xh, float *c_out, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Backward operators of the GPT / transformer training step (the autograd graph of ha/attention.py:205-232 as
  * `hal` runs it, ha/attention_loop.py:196-215: loss.backward()).
  *   halo_attention_bwd         gradient of halo_attention_fwd: dq, dk, dv (same row layouts as q, k, v; written, not
