@@ -20,6 +20,7 @@
 #include "halo_common.h"
 #include "halo_internal.h"
 #include "decode_linear.h"
+#include "decode_attn.h"
 
 namespace {
 
@@ -59,27 +60,7 @@ struct DecAttnArgs {
 // Eight lanes share a key (lane = 8 * (key within the pass) + dim chunk), each holding DPL = HD / 8 dims (whole rotary pairs): a pass of
 // the wave scores eight keys (the partial dots meet by three xor shuffles) and, after the softmax, accumulates eight keys' p * v (the
 // eight key groups meet by three more) -- one vector load per lane and pass for K and one for V, nothing serial over the keys.
-template <int DPL>
-__device__ __forceinline__ void load_halfs(const __half *src, float *out) {
-    if constexpr (DPL == 2) {
-        const __half2 v = *reinterpret_cast<const __half2 *>(src);
-        out[0] = __low2float(v); out[1] = __high2float(v);
-    } else {
-        typedef unsigned uvec __attribute__((ext_vector_type(DPL == 4 ? 2 : 4)));
-#pragma unroll
-        for (int part = 0; part < (DPL == 16 ? 2 : 1); ++part) {
-            const uvec raw = *reinterpret_cast<const uvec *>(src + part * 8);
-#pragma unroll
-            for (int w = 0; w < (DPL == 4 ? 2 : 4); ++w) {
-                const unsigned u = raw[w];
-                const __half2 v = *reinterpret_cast<const __half2 *>(&u);
-                out[part * 8 + 2 * w] = __low2float(v);
-                out[part * 8 + 2 * w + 1] = __high2float(v);
-            }
-        }
-    }
-}
-
+// (load_halfs: decode_attn.h)
 template <int HD, int MAXK>
 __global__ __launch_bounds__(64) void dec_attention_pair_kernel(const DecAttnArgs p) {
     constexpr int DPL = HD / 8, PPL = DPL / 2, HALF = HD / 2;

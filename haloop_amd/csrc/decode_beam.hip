@@ -1,0 +1,361 @@
+// Beam search of the encoder-decoder ASR model (haloop_amd/transformer.py BeamDecoder; the definition: include/halo.h)
+// on the fused decode launches of decode.hip: a step runs the 5 launches per layer and the LayerNorm + lm_head product on slots = N * W
+// rows (slot n * W + r is hypothesis r of utterance n), with the two launches of this file in the places of dec_attention_pair_kernel and
+// dec_token_kernel:
+//   dec_beam_attention_kernel  both attentions of a step.  The cross-attention caches exist once per UTTERANCE (slot / W), not per slot.
+//                              The self-attention caches are never gathered: a kept hypothesis continues its parent's history by
+//                              reading position j < t from the cache row anc[slot][j] that computed it (the per-slot ancestor table of
+//                              this step), and stores position t into its own row.
+//   dec_beam_select_kernel     one workgroup per utterance: the log-sum-exp of every live slot, the W best of the W * V candidates in the
+//                              order (rank descending, position ascending), and the new beam: scores, lengths, flags, tokens (the
+//                              parent's row gathered, plus k), the next step's ancestor rows and input embeddings.
+// Everything the selection writes goes to the OTHER parity copy of the beam (step t reads copy t & 1): the gathers across the slots of an
+// utterance never read what this launch writes.  No float atomics, every sum in one order: two decodes are bit-equal.
+#include <hip/hip_fp16.h>
+#include "halo_common.h"
+#include "halo_internal.h"
+#include "decode_attn.h"
+
+namespace {
+
+struct BeamAttnArgs {
+    const float *a;          // [slots][4C]: cross query | self q | k | v
+    long a_rs;
+    int C, heads, hd, W, slots;
+    const __half *mem_k, *mem_v;     // [slots / W][heads][S][hd]: one per utterance
+    int S;
+    const int *mem_len;              // [slots / W]
+    __half *time_k, *time_v;         // [slots][heads][Tc][hd]
+    int Tc, n_keys;
+    const int *anc;                  // [slots][anc_ld]: the cache row that holds position j < n_keys - 1 of this slot's history
+    long anc_ld;
+    const float *cs, *sn;            // rotary tables [>= n_keys][hd/2]
+    float scale;
+    float *y;                        // [slots][2C]: cross output | self output
+    long y_rs;
+};
+
+// dec_attention_pair_kernel of decode.hip (eight lanes share a key, DPL = HD / 8 dims each; the same rotary tables, the same softmax, the
+// same order of every sum: with W = 1 and the identity table the same bits) over slots = N * W rows.
+// No race inside the launch: the table names positions < t = n_keys - 1 only, which earlier launches stored; position t of a slot is
+// stored by that slot's own wave into its own cache row and used by it from registers, and no slot reads position t of another slot.
+// So nothing needs ordering inside the launch.
+template <int HD, int MAXK>
+__global__ __launch_bounds__(64) void dec_beam_attention_kernel(const BeamAttnArgs p) {
+    constexpr int DPL = HD / 8, PPL = DPL / 2, HALF = HD / 2;
+    __shared__ float ps[MAXK];
+    const int h = blockIdx.x, n = blockIdx.y, self = blockIdx.z, lane = threadIdx.x;
+    const int c = lane & 7, jl = lane >> 3;
+    const int utt = n / p.W;
+    const float *qp = p.a + (long)n * p.a_rs + (self ? p.C : 0) + (long)h * HD;
+    const int n_keys = self ? p.n_keys : p.S, Tc = self ? p.Tc : p.S;
+    const int tq = n_keys - 1;
+    const float *cs = self ? p.cs : nullptr, *sn = p.sn;
+    float q[DPL];
+#pragma unroll
+    for (int i = 0; i < DPL; ++i) q[i] = qp[c * DPL + i];
+    if (cs) {
+#pragma unroll
+        for (int i = 0; i < PPL; ++i) {
+            const float cc = cs[(long)tq * HALF + c * PPL + i], sv = sn[(long)tq * HALF + c * PPL + i];
+            const float r0 = q[2 * i] * cc + (-q[2 * i + 1]) * sv, r1 = q[2 * i + 1] * cc + q[2 * i] * sv;
+            q[2 * i] = r0; q[2 * i + 1] = r1;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < DPL; ++i) q[i] *= p.scale;
+    const long row_elems = (long)Tc * HD;                               // one (row, head) plane of a cache
+    const long base = ((long)(self ? n : utt) * p.heads + h) * row_elems;
+    const __half *kb = self ? p.time_k : p.mem_k, *vb = self ? p.time_v : p.mem_v;
+    // self: this step's key / value chunk of this lane (fp32 rows, rounded to fp16 as the cache holds them); lanes of key group 0 store it
+    float kf[DPL], vf[DPL];
+    if (self) {
+#pragma unroll
+        for (int i = 0; i < DPL; ++i) {
+            const __half kh = __float2half(qp[p.C + c * DPL + i]), vh = __float2half(qp[2 * p.C + c * DPL + i]);
+            kf[i] = __half2float(kh); vf[i] = __half2float(vh);
+            if (jl == 0) {
+                p.time_k[base + (long)tq * HD + c * DPL + i] = kh;
+                p.time_v[base + (long)tq * HD + c * DPL + i] = vh;
+            }
+        }
+    }
+    const int klim = self ? n_keys : max(0, min(n_keys, p.mem_len ? p.mem_len[utt] : n_keys));
+    // the plane a key is read from: the utterance's (cross), the ancestor's row (self, j < tq; clamped: a bad table cannot leave the caches)
+    auto plane = [&](int j) {
+        if (!self) return base;
+        const int row = min(max(p.anc[(long)n * p.anc_ld + j], 0), p.slots - 1);
+        return ((long)row * p.heads + h) * row_elems;
+    };
+    for (int j0 = 0; j0 < klim; j0 += 8) {
+        const int j = j0 + jl;
+        float sc = 0.f;
+        if (j < klim) {
+            float k[DPL];
+            if (self && j == tq) {                                // this step's row: not from the store just issued
+#pragma unroll
+                for (int i = 0; i < DPL; ++i) k[i] = kf[i];
+            } else {
+                load_halfs<DPL>(kb + plane(j) + (long)j * HD + c * DPL, k);
+            }
+            if (cs) {
+#pragma unroll
+                for (int i = 0; i < PPL; ++i) {
+                    const float cc = cs[(long)j * HALF + c * PPL + i], sv = sn[(long)j * HALF + c * PPL + i];
+                    const float r0 = k[2 * i] * cc + (-k[2 * i + 1]) * sv, r1 = k[2 * i + 1] * cc + k[2 * i] * sv;
+                    k[2 * i] = r0; k[2 * i + 1] = r1;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < DPL; ++i) sc = fmaf(q[i], k[i], sc);
+        }
+        sc += __shfl_xor(sc, 1, 64);
+        sc += __shfl_xor(sc, 2, 64);
+        sc += __shfl_xor(sc, 4, 64);
+        if (c == 0 && j < klim) ps[j] = sc;
+    }
+    __syncthreads();
+    float mx = -INFINITY;
+    for (int j = lane; j < klim; j += 64) mx = fmaxf(mx, ps[j]);
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int j = lane; j < klim; j += 64) {
+        const float e = expf(ps[j] - mx);
+        ps[j] = e;
+        sum += e;
+    }
+    sum = wave_sum(sum);
+    __syncthreads();
+    const float inv = 1.0f / sum;
+    float acc[DPL];
+#pragma unroll
+    for (int i = 0; i < DPL; ++i) acc[i] = 0.f;
+    for (int j0 = 0; j0 < klim; j0 += 8) {
+        const int j = j0 + jl;
+        if (j < klim) {
+            float v[DPL];
+            if (self && j == tq) {
+#pragma unroll
+                for (int i = 0; i < DPL; ++i) v[i] = vf[i];
+            } else {
+                load_halfs<DPL>(vb + plane(j) + (long)j * HD + c * DPL, v);
+            }
+            const float pj = ps[j];
+#pragma unroll
+            for (int i = 0; i < DPL; ++i) acc[i] = fmaf(pj, v[i], acc[i]);
+        }
+    }
+    float *yp = p.y + (long)n * p.y_rs + (self ? p.C : 0) + (long)h * HD + c * DPL;
+#pragma unroll
+    for (int i = 0; i < DPL; ++i) {
+        float v = acc[i];
+        v += __shfl_xor(v, 8, 64);
+        v += __shfl_xor(v, 16, 64);
+        v += __shfl_xor(v, 32, 64);
+        if (jl == 0) yp[i] = v * inv;
+    }
+}
+
+constexpr int BEAM_MAX = 16, BEAM_THREADS = 256, BEAM_WAVES = BEAM_THREADS / 64;
+constexpr int BEAM_LDS_FLOATS = 8192;      // 32 KiB of dynamic LDS, under the 64 KiB a launch gets without the opt-in
+
+struct BeamSelArgs {
+    const float *logits;       // [N * W][ld]
+    long ld;
+    int V, W, t, capacity, etx;
+    float bonus;
+    const float *score_in;     // the beam this step reads: [N][W] log-probabilities (-inf: empty), lengths, finished flags,
+    const int *len_in, *fin_in, *tok_in, *anc_in;     // tokens [N][W][tok_ld], ancestor rows [N * W][anc_ld]
+    float *score_out, *rank_out;                      // the beam it writes
+    int *len_out, *fin_out, *tok_out, *anc_out;
+    long tok_ld, anc_ld;
+    const float *wte;          // [vocab][C]
+    int C;
+    float *y;                  // [N * W][C] <- wte[token] (NULL: the last step)
+    int cached;                // the utterance's W V logits are kept in LDS (BEAM_LDS_FLOATS or fewer), else re-read from L2
+};
+
+// (rank, pos) stands before (orank, opos) in the order (rank descending, position ascending)
+__device__ __forceinline__ bool before(float sc, int pos, float osc, int opos) { return sc > osc || (sc == osc && pos < opos); }
+
+enum { SLOT_EMPTY = 0, SLOT_LIVE = 1, SLOT_FINISHED = 2 };
+
+__global__ __launch_bounds__(BEAM_THREADS) void dec_beam_select_kernel(const BeamSelArgs p) {
+    __shared__ float s_score[BEAM_MAX], s_lse[BEAM_MAX], sel_rank[BEAM_MAX];
+    __shared__ int s_len[BEAM_MAX], s_state[BEAM_MAX], sel_pos[BEAM_MAX], s_par[BEAM_MAX], s_k[BEAM_MAX];
+    __shared__ float r_sc[2][BEAM_WAVES];
+    __shared__ int r_pos[2][BEAM_WAVES];
+    extern __shared__ float zs[];                                      // cached: zs[j][v] = logits of slot j
+    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = p.W, V = p.V;
+    const long base = (long)n * W;
+    if (tid < BEAM_MAX) {
+        float sc = -INFINITY;
+        int len = 0, st = SLOT_EMPTY;
+        if (tid < W) {
+            if (p.t == 0) {                                            // the records are not read: slot 0 holds [STX]
+                if (tid == 0) { sc = 0.f; st = SLOT_LIVE; }
+            } else {
+                sc = p.score_in[base + tid];
+                len = p.len_in[base + tid];
+                st = sc > -INFINITY ? (p.fin_in[base + tid] ? SLOT_FINISHED : SLOT_LIVE) : SLOT_EMPTY;
+                if (len < 0 || len > p.t) st = SLOT_EMPTY;             // (never under the host's loop) no token row is overrun
+            }
+        }
+        s_score[tid] = sc; s_len[tid] = len; s_state[tid] = st;
+    }
+    __syncthreads();
+    auto logit = [&](int j, int v) { return p.logits[(base + j) * p.ld + v]; };
+    auto z = [&](int j, int v) { return p.cached ? zs[j * V + v] : logit(j, v); };
+    // ---- 1. wave w: log-sum-exp of slots w, w + 4, ... (fixed order: the lane's stride, then the wave's butterfly)
+    for (int j = wave; j < W; j += BEAM_WAVES) {
+        if (s_state[j] != SLOT_LIVE) continue;
+        float m = -INFINITY;
+        for (int v = lane; v < V; v += 64) {
+            const float x = logit(j, v);
+            if (p.cached) zs[j * V + v] = x;                           // (read back by this lane below, by the others after the barrier)
+            m = fmaxf(m, x);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        float s = 0.f;
+        for (int v = lane; v < V; v += 64) s += expf(z(j, v) - m);
+        const float lse = m + logf(wave_sum(s));
+        if (lane == 0) s_lse[j] = lse;
+    }
+    __syncthreads();
+    // the candidate (j, k) of a live slot: its log-probability and its rank, by the same operations wherever they are needed
+    auto cand_score = [&](int j, int k) { return s_score[j] + (z(j, k) - s_lse[j]); };
+    auto cand_rank = [&](int j, int k, float sc) { return fmaf(p.bonus, (float)(s_len[j] + (k != p.etx)), sc); };
+    // ---- 2. the W best candidates, one per round: the first in the order among those behind the last one taken.  Position j V + k; a
+    //         finished slot has the one candidate (j, ETX).
+    float prank = INFINITY;
+    int ppos = -1, nsel = 0;
+    for (int r = 0; r < W; ++r) {
+        float brank = -INFINITY;
+        int bpos = 0x7fffffff;
+        if (tid < W && s_state[tid] == SLOT_FINISHED) {
+            const float rk = fmaf(p.bonus, (float)s_len[tid], s_score[tid]);
+            const int pos = tid * V + p.etx;
+            if (rk > -INFINITY && before(prank, ppos, rk, pos)) { brank = rk; bpos = pos; }
+        }
+        for (int j = 0; j < W; ++j) {
+            if (s_state[j] != SLOT_LIVE) continue;
+            for (int k = tid; k < V; k += BEAM_THREADS) {
+                const float rk = cand_rank(j, k, cand_score(j, k));
+                const int pos = j * V + k;
+                if (!(rk > -INFINITY) || !before(prank, ppos, rk, pos) || !before(rk, pos, brank, bpos)) continue;
+                brank = rk; bpos = pos;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float osc = __shfl_xor(brank, o, 64);
+            const int opos = __shfl_xor(bpos, o, 64);
+            if (before(osc, opos, brank, bpos)) { brank = osc; bpos = opos; }
+        }
+        if (lane == 0) { r_sc[r & 1][wave] = brank; r_pos[r & 1][wave] = bpos; }
+        __syncthreads();
+        brank = r_sc[r & 1][0]; bpos = r_pos[r & 1][0];
+#pragma unroll
+        for (int w = 1; w < BEAM_WAVES; ++w)
+            if (before(r_sc[r & 1][w], r_pos[r & 1][w], brank, bpos)) { brank = r_sc[r & 1][w]; bpos = r_pos[r & 1][w]; }
+        if (bpos == 0x7fffffff) break;                                  // (uniform) no candidate is left
+        if (tid == 0) { sel_rank[r] = brank; sel_pos[r] = bpos; }
+        prank = brank; ppos = bpos; nsel = r + 1;
+    }
+    __syncthreads();
+    // ---- 3. the new beam's records, in the order taken; a slot that took nothing is empty
+    if (tid < W) {
+        int par = -1, k = p.etx, len = 0, fin = 0;
+        float sc = -INFINITY, rk = -INFINITY;
+        if (tid < nsel) {
+            const int pos = sel_pos[tid];
+            par = pos / V; k = pos % V; rk = sel_rank[tid];
+            if (s_state[par] == SLOT_FINISHED) { sc = s_score[par]; len = s_len[par]; fin = 1; }
+            else { sc = cand_score(par, k); len = s_len[par] + (k != p.etx); fin = k == p.etx; }
+        }
+        p.score_out[base + tid] = sc; p.rank_out[base + tid] = rk; p.len_out[base + tid] = len; p.fin_out[base + tid] = fin;
+        s_par[tid] = par; s_k[tid] = k;
+    }
+    __syncthreads();
+    // ---- 4. tokens (without STX and ETX): the parent's row, plus k
+    for (int idx = tid; idx < nsel * p.capacity; idx += BEAM_THREADS) {
+        const int r = idx / p.capacity, x = idx % p.capacity, par = s_par[r], lp = s_len[par];
+        if (x < lp) p.tok_out[(base + r) * p.tok_ld + x] = p.tok_in[(base + par) * p.tok_ld + x];
+        else if (x == lp && s_state[par] == SLOT_LIVE && s_k[r] != p.etx) p.tok_out[(base + r) * p.tok_ld + x] = s_k[r];
+    }
+    // ---- 5. the next step's ancestor rows: the parent's history, then the parent's own row for position t (an empty slot: its own row)
+    for (int idx = tid; idx < W * (p.t + 1); idx += BEAM_THREADS) {
+        const int r = idx / (p.t + 1), x = idx % (p.t + 1), par = s_par[r];
+        int row = (int)base + (par < 0 ? r : par);
+        if (x < p.t && par >= 0) row = p.anc_in[(base + par) * p.anc_ld + x];
+        p.anc_out[(base + r) * p.anc_ld + x] = row;
+    }
+    // ---- 6. the next step's input rows
+    if (!p.y) return;
+    const int C4 = p.C / 4;
+    for (int idx = tid; idx < W * C4; idx += BEAM_THREADS) {
+        const int r = idx / C4, c = idx % C4;
+        reinterpret_cast<f32x4 *>(p.y + (base + r) * p.C)[c] = reinterpret_cast<const f32x4 *>(p.wte + (long)s_k[r] * p.C)[c];
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int halo_decode_beam_attention(const float *a, long a_row_stride, int slots, int beam, int heads, int head_dim, const void *mem_k,
+                               const void *mem_v, int S, const int *memory_lengths, void *time_k, void *time_v, int cache_len, int n_keys,
+                               const int *ancestors, long ancestors_ld, const float *cos_table, const float *sin_table, float *y,
+                               long y_row_stride, halo_stream_t stream) {
+    HALO_CHECK_ARG(a && mem_k && mem_v && time_k && time_v && y && slots > 0 && heads > 0 && S > 0 && beam >= 1 && slots % beam == 0);
+    HALO_CHECK_ARG(head_dim == 16 || head_dim == 32 || head_dim == 64 || head_dim == 128);
+    HALO_CHECK_ARG(n_keys >= 1 && n_keys <= cache_len && (!cos_table) == (!sin_table));
+    HALO_CHECK_ARG(n_keys == 1 || (ancestors && ancestors_ld >= n_keys - 1));
+    const int C = heads * head_dim, maxk = n_keys > S ? n_keys : S;
+    HALO_CHECK_ARG(a_row_stride >= 4L * C && y_row_stride >= 2L * C && maxk <= 8192 && slots <= 65535);
+    BeamAttnArgs p;
+    p.a = a; p.a_rs = a_row_stride; p.C = C; p.heads = heads; p.hd = head_dim; p.W = beam; p.slots = slots;
+    p.mem_k = (const __half *)mem_k; p.mem_v = (const __half *)mem_v; p.S = S; p.mem_len = memory_lengths;
+    p.time_k = (__half *)time_k; p.time_v = (__half *)time_v; p.Tc = cache_len; p.n_keys = n_keys;
+    p.anc = ancestors; p.anc_ld = ancestors_ld;
+    p.cs = cos_table; p.sn = sin_table; p.scale = 1.0f / sqrtf((float)head_dim); p.y = y; p.y_rs = y_row_stride;
+    const dim3 grid((unsigned)heads, (unsigned)slots, 2);
+    hipStream_t st = (hipStream_t)stream;
+#define HALO_BEAM_ATTN(HD)                                                                                      \
+    do {                                                                                                        \
+        if (maxk <= 1024) hipLaunchKernelGGL((dec_beam_attention_kernel<HD, 1024>), grid, dim3(64), 0, st, p);  \
+        else hipLaunchKernelGGL((dec_beam_attention_kernel<HD, 8192>), grid, dim3(64), 0, st, p);               \
+    } while (0)
+    if (head_dim == 64) HALO_BEAM_ATTN(64);
+    else if (head_dim == 128) HALO_BEAM_ATTN(128);
+    else if (head_dim == 32) HALO_BEAM_ATTN(32);
+    else HALO_BEAM_ATTN(16);
+#undef HALO_BEAM_ATTN
+    return halo_launch_status();
+}
+
+int halo_decode_beam_select(const float *logits, long ld, int N, int beam, int V, int t, int capacity, int etx, float length_bonus,
+                            const float *scores_in, const int *lengths_in, const int *finished_in, const int *tokens_in,
+                            const int *ancestors_in, float *scores_out, float *ranks_out, int *lengths_out, int *finished_out,
+                            int *tokens_out, int *ancestors_out, long tokens_ld, long ancestors_ld, const float *wte, int vocab, int C,
+                            float *y_next, halo_stream_t stream) {
+    HALO_CHECK_ARG(logits && scores_in && lengths_in && finished_in && tokens_in && ancestors_in);
+    HALO_CHECK_ARG(scores_out && ranks_out && lengths_out && finished_out && tokens_out && ancestors_out);
+    HALO_CHECK_ARG(N > 0 && beam >= 1 && beam <= BEAM_MAX && V > 0 && V <= 8192 && ld >= V && etx >= 0 && etx < V);
+    HALO_CHECK_ARG(t >= 0 && t < capacity && tokens_ld >= capacity && ancestors_ld > t && (long)N * beam <= 0x7fffffffL / V);
+    HALO_CHECK_ARG(scores_in != scores_out && lengths_in != lengths_out && finished_in != finished_out && tokens_in != tokens_out &&
+                   ancestors_in != ancestors_out);
+    HALO_CHECK_ARG(!y_next || (wte && vocab >= V && C > 0 && C % 4 == 0 && ((uintptr_t)wte | (uintptr_t)y_next) % 16 == 0));
+    BeamSelArgs p;
+    p.logits = logits; p.ld = ld; p.V = V; p.W = beam; p.t = t; p.capacity = capacity; p.etx = etx; p.bonus = length_bonus;
+    p.score_in = scores_in; p.len_in = lengths_in; p.fin_in = finished_in; p.tok_in = tokens_in; p.anc_in = ancestors_in;
+    p.score_out = scores_out; p.rank_out = ranks_out; p.len_out = lengths_out; p.fin_out = finished_out; p.tok_out = tokens_out;
+    p.anc_out = ancestors_out; p.tok_ld = tokens_ld; p.anc_ld = ancestors_ld; p.wte = wte; p.C = C; p.y = y_next;
+    p.cached = (long)beam * V <= BEAM_LDS_FLOATS;
+    hipLaunchKernelGGL(dec_beam_select_kernel, dim3((unsigned)N), dim3(BEAM_THREADS), p.cached ? (size_t)beam * V * sizeof(float) : 0,
+                       (hipStream_t)stream, p);
+    return halo_launch_status();
+}
+
+}  // extern "C"

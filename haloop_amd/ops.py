@@ -1523,6 +1523,45 @@ def decode_token(logits, tokens, t, plen, etx, alive, out_len, log_probs, sum_en
                                   wte.shape[1] if wte is not None else 0, ptr(y_next), _stream()), 'halo_decode_token')
 
 
+# ---- the two launches of the attention decoder's beam search (csrc/decode_beam.hip); neither allocates -----------------------------
+def decode_beam_attention(a, mem_k, mem_v, memory_lengths, time_k, time_v, n_keys, ancestors, table, out):
+    """decode_attention_pair over slots = N * W rows a [slots, 4C]: mem_k / mem_v [N, heads, S, hd] per utterance, time_k / time_v
+    [slots, heads, Tc, hd]; position j < n_keys - 1 is read from cache row ancestors[slot, j] (int32 [slots, >= n_keys - 1])."""
+    N, heads, S, hd = mem_k.shape
+    slots = time_k.shape[0]
+    if slots % N or a.shape[0] != slots or out.shape[0] != slots or ancestors.shape[0] != slots or ancestors.dtype != torch.int32 \
+            or ancestors.stride(1) != 1:
+        raise ValueError('decode_beam_attention: a, out, ancestors (int32) and the time caches must have N * W rows')
+    check(lib().halo_decode_beam_attention(ptr(a), a.stride(0), slots, slots // N, heads, hd, ptr(mem_k), ptr(mem_v), S, ptr(memory_lengths),
+                                           ptr(time_k), ptr(time_v), time_k.shape[2], n_keys, ptr(ancestors), ancestors.stride(0),
+                                           ptr(table.cos) if table else None, ptr(table.sin) if table else None, ptr(out), out.stride(0),
+                                           _stream()), 'halo_decode_beam_attention')
+    return out
+
+
+def decode_beam_select(logits, t, capacity, etx, length_bonus, beam_in, beam_out, ranks_out, wte=None, y_next=None):
+    """One step of the beam (include/halo.h) on logits [N * W, V]: beam_in / beam_out = (scores [N, W] fp32, lengths [N, W] int32,
+    finished [N, W] int32, tokens [N, W, >= capacity] int32, ancestors [N * W, > t] int32), two distinct copies; ranks_out [N, W] fp32;
+    y_next [N * W, C] <- wte[token]."""
+    N, W = ranks_out.shape
+    V = logits.shape[1]
+    tensors = (*beam_in, *beam_out, ranks_out)
+    if not all(x.is_contiguous() for x in tensors) or logits.shape[0] != N * W or logits.stride(1) != 1:
+        raise ValueError('decode_beam_select: logits must be [N * W, V] with unit class stride and every record contiguous')
+    for rec in (beam_in, beam_out):
+        if any(x.shape != (N, W) for x in rec[:3]) or rec[3].shape[:2] != (N, W) or rec[4].shape[0] != N * W \
+                or rec[0].dtype != torch.float32 or any(x.dtype != torch.int32 for x in rec[1:]):
+            raise ValueError('decode_beam_select: records are (scores f32, lengths, finished [N, W], tokens [N, W, ld], ancestors [N * W, ld] int32)')
+    if beam_in[3].shape != beam_out[3].shape or beam_in[4].shape != beam_out[4].shape:
+        raise ValueError('decode_beam_select: the two copies of the beam must have one shape')
+    if y_next is not None and (not y_next.is_contiguous() or not wte.is_contiguous() or y_next.shape != (N * W, wte.shape[1])):
+        raise ValueError('decode_beam_select: y_next must be a contiguous [N * W, C] and wte contiguous')
+    check(lib().halo_decode_beam_select(ptr(logits), logits.stride(0), N, W, V, int(t), int(capacity), int(etx), float(length_bonus),
+                                        *(ptr(x) for x in beam_in), ptr(beam_out[0]), ptr(ranks_out), *(ptr(x) for x in beam_out[1:]),
+                                        beam_in[3].shape[2], beam_in[4].shape[1], ptr(wte), wte.shape[0] if wte is not None else 0,
+                                        wte.shape[1] if wte is not None else 0, ptr(y_next), _stream()), 'halo_decode_beam_select')
+
+
 # ---- fused launches of a GPT sampling step (csrc/gpt_decode.hip); none of these allocates: they run inside a captured step ----------
 def gpt_decode_linear_supported(k, layernorm):
     return bool(lib().halo_gpt_decode_linear_supported(k, int(layernorm)))

@@ -22,7 +22,11 @@ proj outputs, MLP output) draws from a Philox stream keyed by torch.initial_seed
 dropout, not torch's bit stream; the output dropouts are GEMM epilogues, the probability dropout lives inside the
 attention kernels (forward and both backward sweeps recompute the same mask).
 
-Not built (raises): autograd through a bare Block / MultiHeadAttention call, ``kv_cache_parts`` on the public Block / MultiHeadAttention.forward (Decoder.decode drives the caches
+Beam search (the reference decodes greedily only): ``BeamDecoder`` on the fused decode launches over N * W rows,
+``Decoder.decode(..., beam_size=W)`` / HALO_ASR_BEAM, and ``CTCAttentionDecoder.decode(..., ctc_weight=c)`` re-ranking the lists with
+the CTC head.
+
+Not built (raises): prompts under beam search, autograd through a bare Block / MultiHeadAttention call, ``kv_cache_parts`` on the public Block / MultiHeadAttention.forward (Decoder.decode drives the caches
 itself), arbitrary attention masks (only the key-padding masks Block builds, transformer.py:476).
 """
 import os
@@ -427,6 +431,9 @@ class Decoder(nn.Module):
         self._images = WeightImages()
         self._graphs = {}                                                 # captured greedy decodes, see _decode_graph
         self.dropout_stream = DropoutStream()                             # Philox (seed, offset) per training forward
+        self.beam_size = int(os.environ.get('HALO_ASR_BEAM', '0'))        # decode(): 0 greedy, W >= 1 BeamDecoder's search
+        self.length_bonus = 0.0                                           # of that search
+        self._beams = {}                                                  # its BeamDecoder, built at the first beam decode
 
     def forward(self, features, targets, input_lengths=None, target_lengths=None, star_penalty=None, measure_entropy=False,
                 drop_labels=None, reduction='mean'):
@@ -653,9 +660,40 @@ class Decoder(nn.Module):
         return tuple(o.clone() for o in entry['outs'])
 
     @torch.no_grad()
-    def decode(self, features, input_lengths, target_lengths, prompt=None):
-        "Perform batched greedy decoding (ha/transformer.py:124-199)."
+    def _decode_beam(self, features, input_lengths, T, W):
+        """Beam search at width W with room for T steps (the greedy decode's step count): each row's best hypothesis in the greedy
+        decode's five-value form, the lists in ``last_nbest``."""
+        N = features.shape[0]
+        bd = self._beams.get('decoder')
+        if bd is None or bd.max_batch < N or bd.capacity < T or bd.beam < W or bd._device != self.wte.weight.device \
+                or bd.length_bonus != float(self.length_bonus):
+            bd = BeamDecoder(self, max(N, bd.max_batch if bd else 0), max(T, bd.capacity if bd else 0), max(W, bd.beam if bd else 0),
+                             self.length_bonus)
+            self._beams['decoder'] = bd
+        self.last_nbest = bd.decode(features, input_lengths, capacity=T, beam=W)
+        tokens, lengths, _, _ = self.last_nbest
+        # greedy's output_lengths count the steps a row was alive: its tokens and, where it closed, the ETX; greedy's outputs are
+        # tokens[1:output_lengths] (sic: a row that never closed loses its last token, ha/transformer.py:197) -- kept, so W = 1 is greedy
+        out_len = lengths[:, 0].clamp(min=0) + bd.last_finished[:, 0].long()
+        lens = out_len.tolist()
+        outputs = torch.nested.nested_tensor([tokens[i, 0, :max(n - 1, 0)] for i, n in enumerate(lens)])
+        nan = torch.full((N,), float('nan'), device=features.device)     # summed over all alive rows (sic) in greedy: no beam analogue
+        return outputs, out_len.to(input_lengths.dtype), [None] * N, bd.last_logprobs[:, 0].clone(), nan
+
+    @torch.no_grad()
+    def decode(self, features, input_lengths, target_lengths, prompt=None, beam_size=None):
+        """Perform batched greedy decoding (ha/transformer.py:124-199).  ``beam_size`` W >= 1 (default: the attribute ``beam_size``, read
+        from HALO_ASR_BEAM when the module is built; 0: greedy): ``BeamDecoder``'s search at width W with the attribute ``length_bonus``
+        and the greedy decode's step count; returns each row's best hypothesis (its plain log-probability, NaN for the entropy sum) and
+        keeps the lists as ``last_nbest``."""
         _require_inference(self, features)
+        width = self.beam_size if beam_size is None else int(beam_size)
+        if width < 0:
+            raise ValueError(f'Decoder.decode: beam_size {width} is negative')
+        if width:
+            if prompt is not None:
+                raise NotImplementedError('Decoder.decode(beam_size >= 1): prompts are not built')
+            return self._decode_beam(features, input_lengths, int(target_lengths.max().item()) + 1, width)
         dev = features.device
         N, S, C = features.shape
         T = int(target_lengths.max().item()) + 1
@@ -684,6 +722,230 @@ class Decoder(nn.Module):
         return outputs, output_lengths, alignments, log_probs, sum_entropies
 
 
+BEAM_MAX = 16            # csrc/decode_beam.hip keeps an utterance's records in LDS arrays of this many entries
+
+
+class BeamDecoder:
+    """Beam search for a ``Decoder`` (the reference decodes greedily only, so the definition is this library's own, fixed
+    in include/halo.h), with preallocated buffers for ``max_batch`` utterances, ``beam`` hypotheses each and ``capacity`` steps.  Per
+    utterance, with W = beam:
+
+        B = [slot 0: tokens [STX], log-probability 0, length 0]                    # the other slots are empty
+        for t in 0 .. capacity - 1:                                                # nothing ends early: no host read
+            lp_j = log_softmax(logits of live slot j)
+            candidates: (j, k) for every live j and k < V with score_j + lp_j[k] and length len_j + (k != ETX); (j, ETX) for every
+                        finished j, unchanged
+            B = the W best by (rank = fmaf(length_bonus, length, score) descending, position j V + k ascending), rank > -inf
+
+    W = 1 with length_bonus 0 is ``Decoder.decode``'s greedy search token for token.  The fused path costs ``5 * layers + 2`` launches per
+    step for the whole batch (csrc/decode.hip's products on N * W rows, csrc/decode_beam.hip's attention through a per-slot ancestor
+    table and its selection), replayed from a captured graph unless HALO_DECODE_GRAPH=0; the general path (f32 mode, widths the fused
+    products refuse, HALO_DECODE_FUSED=0) runs the same search on ``Decoder._decode_core``'s operators over N * W rows, the caches
+    gathered physically and the candidates pruned by a stable sort."""
+
+    def __init__(self, decoder, max_batch, capacity, beam=4, length_bonus=0.0):
+        self.decoder = decoder
+        self.max_batch, self.capacity, self.beam, self.length_bonus = int(max_batch), int(capacity), int(beam), float(length_bonus)
+        if self.max_batch < 1 or self.capacity < 1:
+            raise ValueError('BeamDecoder: need max_batch >= 1 and capacity >= 1')
+        if self.beam < 1 or self.beam > BEAM_MAX:
+            raise ValueError(f'BeamDecoder: beam {self.beam} outside 1 .. {BEAM_MAX}')
+        wte = decoder.wte.weight
+        dev, C, V, L = wte.device, wte.shape[1], decoder.lm_head.weight.shape[0], len(decoder.h)
+        R, cap = self.max_batch * self.beam, self.capacity
+        i32 = dict(device=dev, dtype=torch.int32)
+        f32 = dict(device=dev, dtype=torch.float32)
+        with torch.inference_mode(False):          # ordinary tensors: they are updated in place inside and outside inference mode
+            # flat buffers, viewed per call at that call's N * W slots.  The beam's records exist twice (step parity): log-probabilities,
+            # lengths, finished flags, tokens, ancestor rows
+            self._rec = [(torch.zeros(R, **f32), torch.zeros(R, **i32), torch.zeros(R, **i32), torch.zeros(R * cap, **i32),
+                          torch.zeros(R * cap, **i32)) for _ in range(2)]
+            self._rank = torch.zeros(R, **f32)
+            self._time = torch.zeros(L * 2 * R * C * cap, device=dev, dtype=torch.float16)
+            self._a, self._hid = torch.zeros(R * 4 * C, **f32), torch.zeros(R * 4 * C, **f32)
+            self._att, self._logits = torch.zeros(R * 2 * C, **f32), torch.zeros(R * V, **f32)
+            self._y, self._sa, self._sb = (torch.zeros(R * C, **f32) for _ in range(3))
+        self._device = dev      # of the buffers: a decoder moved since needs a new BeamDecoder
+        self._graphs = {}
+        self.last_logprobs = self.last_finished = None
+
+    @property
+    def fused(self):
+        return self.decoder._fused_decode_ok(self.decoder.wte.weight.shape[1])
+
+    @torch.no_grad()
+    def decode(self, features, input_lengths, capacity=None, beam=None):
+        """features [N, S, C], input_lengths [N] -> (tokens [N, W, capacity] int64 without STX and ETX, -1 past a hypothesis's length
+        and in absent hypotheses; lengths [N, W] int64, -1: absent; scores [N, W] float32 = the rank, best first, -inf: absent; counts
+        [N] int64).  ``last_logprobs`` [N, W]: the plain log-probabilities; ``last_finished`` [N, W]: the hypothesis closed with ETX.
+        ``capacity`` / ``beam``: search with less room than the buffers hold (default: all of it)."""
+        dec = self.decoder
+        _require_inference(dec, features)
+        if dec.wte.weight.device != self._device or features.device != self._device:
+            raise ValueError('BeamDecoder: the decoder or the features are not on the device of the buffers')
+        cap = self.capacity if capacity is None else int(capacity)
+        if cap < 1 or cap > self.capacity:
+            raise ValueError(f'BeamDecoder: capacity {cap} outside 1 .. {self.capacity}')
+        W = self.beam if beam is None else int(beam)
+        if W < 1 or W > self.beam:
+            raise ValueError(f'BeamDecoder: beam {W} outside 1 .. {self.beam}')
+        N, S, C = features.shape
+        if N < 1 or N > self.max_batch:
+            raise ValueError(f'BeamDecoder: {N} utterances outside 1 .. {self.max_batch}')
+        with torch.no_grad():
+            dev = features.device
+            mlen = input_lengths.to(device=dev, dtype=torch.int32).contiguous()
+            mem2d = features.reshape(N * S, C).float().contiguous()
+            if not self.fused:
+                scores, lengths, fin, tokens, ranks = self._core_general(mem2d, mlen, N, S, W, cap)
+            elif os.environ.get('HALO_DECODE_GRAPH', '1') != '0':
+                scores, lengths, fin, tokens, ranks = self._graph(mem2d, mlen, N, S, W, cap)
+            else:
+                scores, lengths, fin, tokens, ranks = (t.clone() for t in self._core_fused(mem2d, mlen, N, S, W, cap))
+            absent = ~(scores > float('-inf'))
+            lengths = torch.where(absent, torch.full_like(lengths, -1), lengths).long()
+            past = torch.arange(cap, device=dev)[None, None, :] >= lengths[:, :, None]
+            self.last_logprobs = scores
+            self.last_finished = (fin != 0) & ~absent
+            return tokens[:, :, :cap].long().masked_fill(past, -1), lengths, ranks, (~absent).sum(1)
+
+    # ---- the fused path: 5 * layers + 2 launches per step --------------------------------------------------------------------------
+    def _core_fused(self, mem2d, mlen, N, S, W, cap):
+        """All launches of one search, host-sync free (capturable); returns views of the final beam's records."""
+        dec = self.decoder
+        dev, C = mem2d.device, mem2d.shape[1]
+        L, heads, head_dim = len(dec.h), dec.h[0].heads, dec.h[0].head_dim
+        V = dec.lm_head.weight.shape[0]
+        layers, head_img = dec._decode_images()
+        R, ld = N * W, self.capacity
+        mem_cache = torch.empty((L, 2, N, heads, S, head_dim), dtype=torch.float16, device=dev)     # one per utterance, not per slot
+        kv_weights = tuple(w for block in dec.h for w in (block.mix_memory.k.weight, block.mix_memory.v.weight))
+        ops.decode_memory_caches(linear(dec._images, mem2d, kv_weights), mem_cache)
+        table = ops.RopeTable(cap, head_dim, dev)
+        rec = [(s[:R].view(N, W), n[:R].view(N, W), f[:R].view(N, W), t[:R * ld].view(N, W, ld), a[:R * ld].view(R, ld))
+               for s, n, f, t, a in self._rec]
+        ranks = self._rank[:R].view(N, W)
+        time_cache = self._time[:L * 2 * R * C * cap].view(L, 2, R, heads, cap, head_dim)
+        a, hid = self._a[:R * 4 * C].view(R, 4 * C), self._hid[:R * 4 * C].view(R, 4 * C)
+        att, logits = self._att[:R * 2 * C].view(R, 2 * C), self._logits[:R * V].view(R, V)
+        y = self._y[:R * C].view(R, C)
+        wte = dec.wte.weight.detach()
+        y.copy_(wte[STX].expand(R, C))                                       # later steps: written by decode_beam_select
+        # the residual stream as the pair (y, side) with K-sliced accumulating products, as in Decoder._decode_core_fused
+        ksplit = os.environ.get('HALO_DECODE_KSPLIT', '1') != '0' and (2 * C) % 512 == 0
+        sa, sb = (self._sa[:R * C].view(R, C), self._sb[:R * C].view(R, C)) if ksplit else (None, None)
+        for t in range(cap):
+            q = t & 1
+            side = None
+            for l, block in enumerate(dec.h):
+                w_qkv, w_proj, w_fc, w_fc2 = layers[l]
+                ops.decode_linear(y, w_qkv, 4 * C, a, ln_weight=block.ln_time.weight, x_side=side)
+                ops.decode_beam_attention(a, mem_cache[l, 0], mem_cache[l, 1], mlen, time_cache[l, 0], time_cache[l, 1], t + 1, rec[q][4],
+                                          table, att)
+                ops.decode_linear(att, w_proj, C, y, accumulate=True, side_in=side, side_out=sa)
+                ops.decode_linear(y, w_fc, 4 * C, hid, ln_weight=block.ln_chan.weight, gelu=True, x_side=sa)
+                ops.decode_linear(hid, w_fc2, C, y, accumulate=True, side_in=sa, side_out=sb)
+                side = sb
+            ops.decode_linear(y, head_img, V, logits, ln_weight=dec.ln_f.weight, x_side=side)
+            ops.decode_beam_select(logits, t, cap, ETX, self.length_bonus, rec[q], rec[1 - q], ranks, wte, y if t + 1 < cap else None)
+        s, n, f, tok, _ = rec[cap & 1]
+        return s, n, f, tok, ranks
+
+    def _graph(self, mem2d, mlen, N, S, W, cap):
+        """One HIP graph per (shape, width, parameter version), the sibling of ``Decoder._decode_graph``."""
+        dec = self.decoder
+        key = (N, S, W, cap, self.length_bonus, str(mem2d.device), _lib.get_math_mode())
+        stamp = tuple((p._version, p.data_ptr()) for p in dec.parameters())
+        entry = self._graphs.get(key)
+        if entry is None or entry['stamp'] != stamp:
+            static = (mem2d.clone(), mlen.clone())
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._core_fused(*static, N, S, W, cap)                  # warm-up: weight images are built outside the capture
+            torch.cuda.current_stream().wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                outs = self._core_fused(*static, N, S, W, cap)
+            # the graph reads the cached weight images by address: keep them alive as long as the graph
+            held = [list(m._images._cache.values()) for m in dec.modules() if hasattr(m, '_images')] + [getattr(dec, '_dec_images', None)]
+            if len(self._graphs) >= 8:
+                self._graphs.pop(next(iter(self._graphs)))
+            entry = dict(stamp=stamp, graph=graph, static=static, outs=outs, held=held)
+            self._graphs[key] = entry
+        for dst, src in zip(entry['static'], (mem2d, mlen)):
+            dst.copy_(src)
+        entry['graph'].replay()
+        return tuple(o.clone() for o in entry['outs'])
+
+    # ---- the general path: the same search on Decoder._decode_core's operators over N * W rows ---------------------------------------
+    def _core_general(self, mem2d, mlen, N, S, W, cap):
+        dec = self.decoder
+        dev, C = mem2d.device, mem2d.shape[1]
+        L, heads, head_dim = len(dec.h), dec.h[0].heads, dec.h[0].head_dim
+        V = dec.lm_head.weight.shape[0]
+        R = N * W
+        utt = torch.arange(N, device=dev).repeat_interleave(W)
+        mem_r = mem2d.view(N, S, C)[utt].reshape(R * S, C)
+        mlen_r = mlen[utt].contiguous()
+        mem_cache = torch.zeros((L, 2, R, heads, S, head_dim), dtype=torch.float16, device=dev)
+        time_cache = torch.zeros((L, 2, R, heads, cap, head_dim), dtype=torch.float16, device=dev)
+        for l, block in enumerate(dec.h):
+            mm = block.mix_memory
+            kv = linear(mm._images, mem_r, (mm.k.weight, mm.v.weight))
+            ops.kv_cache_store(kv, C, mem_cache[l, 0], mem_cache[l, 1], R, S, heads, head_dim, 0)
+        table = ops.RopeTable(cap, head_dim, dev)
+        ninf = float('-inf')
+        score = torch.full((N, W), ninf, device=dev)
+        score[:, 0] = 0.0
+        length = torch.zeros(N, W, dtype=torch.long, device=dev)
+        fin = torch.zeros(N, W, dtype=torch.bool, device=dev)
+        tokens = torch.zeros(N, W, cap, dtype=torch.long, device=dev)
+        rank = torch.full((N, W), ninf, device=dev)
+        cur = torch.full((R, 1), STX, dtype=torch.long, device=dev)
+        is_label = (torch.arange(V, device=dev) != ETX)
+        own = torch.arange(W, device=dev)[None, :].expand(N, W)
+        for t in range(cap):
+            y = ops.embed_fwd(cur, dec.wte.weight, None)
+            for l, block in enumerate(dec.h):
+                mm, mt = block.mix_memory, block.mix_time
+                xn = ops.layernorm_fwd(y, block.ln_time.weight)
+                a = linear(mt._images, xn, (mm.q.weight, mt.q.weight, mt.k.weight, mt.v.weight))
+                m = ops.attention_decode(a, mem_cache[l, 0], mem_cache[l, 1], S, key_lengths=mlen_r)
+                linear(mm._images, m, mm.proj.weight, out=y, accumulate=True)
+                s = ops.attention_decode_step(a[:, C:2 * C], a[:, 2 * C:3 * C], a[:, 3 * C:], time_cache[l, 0], time_cache[l, 1], t + 1,
+                                              table=table)
+                linear(mt._images, s, mt.proj.weight, out=y, accumulate=True)
+                h = linear(block._images, ops.layernorm_fwd(y, block.ln_chan.weight), block.mix_chan[0].weight, gelu='erf')
+                linear(block._images, h, block.mix_chan[2].weight, out=y, accumulate=True)
+            logits = linear(dec._images, ops.layernorm_fwd(y, dec.ln_f.weight), dec.lm_head.weight)
+            lp = torch.log_softmax(logits.float(), -1).view(N, W, V)
+            present = score > ninf
+            live, done = present & ~fin, present & fin
+            cand = torch.where(live[:, :, None], score[:, :, None] + lp, torch.full_like(lp, ninf))
+            cand[:, :, ETX] = torch.where(done, score, cand[:, :, ETX])                       # a finished slot: the one candidate (j, ETX)
+            newlen = length[:, :, None] + (is_label[None, None, :] & live[:, :, None]).long()
+            rk = cand + self.length_bonus * newlen.float()
+            rk = torch.where(rk.isnan(), torch.full_like(rk, ninf), rk)
+            top, idx = rk.view(N, W * V).sort(dim=1, descending=True, stable=True)             # equal ranks: position ascending
+            top, idx = top[:, :W], idx[:, :W]
+            taken = top > ninf
+            par, k = torch.where(taken, idx // V, own), idx % V
+            pfin, plen = done.gather(1, par), length.gather(1, par)
+            grow = taken & ~pfin & (k != ETX)
+            tokens = tokens.gather(1, par[:, :, None].expand(N, W, cap))
+            at = plen.clamp(max=cap - 1)[:, :, None]
+            tokens.scatter_(2, at, torch.where(grow[:, :, None], k[:, :, None], tokens.gather(2, at)))
+            score = torch.where(taken, cand.view(N, W * V).gather(1, idx), torch.full_like(top, ninf))
+            rank = torch.where(taken, top, torch.full_like(top, ninf))
+            length = torch.where(taken, plen + grow.long(), torch.zeros_like(plen))
+            fin = taken & (pfin | (k == ETX))
+            src = (torch.arange(N, device=dev)[:, None] * W + par).view(-1)
+            time_cache = time_cache.index_select(2, src)                                      # the parent's history, physically
+            cur = torch.where(taken, k, torch.full_like(k, ETX)).view(R, 1)
+        return score, length.int(), fin.int(), tokens.int(), rank
+
+
 class CTCAttentionDecoder(nn.Module):
     "CTC loss on the encoder, CE loss on the decoder (ha/transformer.py:34-57)"
     def __init__(self, *, vocab: int, head_dim: int, heads: int, p_drop: float, layers: int):
@@ -701,8 +963,47 @@ class CTCAttentionDecoder(nn.Module):
         recognizer_loss, recognizer_stats = self.recognizer(features, targets, input_lengths, target_lengths, star_penalty)
         return decoder_loss + 0.3 * recognizer_loss, {**decoder_stats, **recognizer_stats}
 
-    def decode(self, features, input_lengths, target_lengths, prompt=None):
-        return self.decoder.decode(features, input_lengths, target_lengths, prompt=prompt)
+    def decode(self, features, input_lengths, target_lengths, prompt=None, beam_size=None, ctc_weight=0.0):
+        """``Decoder.decode``.  With a beam (``beam_size`` or the decoder's attribute >= 1) and ``ctc_weight`` c > 0 the jointly trained
+        CTC head rescores the final lists: they are re-ranked by (1 - c) * rank + c * (-ctc_loss(hypothesis)), ties in the old order,
+        a hypothesis the lattice cannot spell (infinite loss) last; the search itself is unchanged.  ``last_nbest``: the re-ranked lists
+        (scores = the joint score), ``last_parts`` = (attention ranks, CTC log-probabilities) [N, W] in the new order; the returned
+        log-probability stays the decoder's own."""
+        width = self.decoder.beam_size if beam_size is None else int(beam_size)
+        out = self.decoder.decode(features, input_lengths, target_lengths, prompt=prompt, beam_size=beam_size)
+        if not width:
+            return out
+        self.last_nbest = self.decoder.last_nbest
+        c = float(ctc_weight)
+        if not c > 0.0:
+            return out
+        from . import functional as HF
+        tokens, lengths, ranks, counts = self.last_nbest
+        bd = self.decoder._beams['decoder']
+        N, W, cap = tokens.shape
+        dev = features.device
+        with torch.no_grad():
+            lp = self.recognizer.log_probs(features)                                         # [N, S, V]
+            S, V = lp.shape[1], lp.shape[2]
+            rows = lp[:, None].expand(N, W, S, V).reshape(N * W, S, V)                       # one call over N * W rows, as mwer_forward does
+            il = input_lengths.to(dev)[:, None].expand(N, W).reshape(-1)
+            ctc = -HF.ctc_loss(rows.permute(1, 0, 2), tokens.clamp(min=0).view(N * W, cap), il, lengths.clamp(min=0).view(-1),
+                               reduction='none').view(N, W)
+            absent = lengths < 0
+            joint = (1.0 - c) * ranks + c * ctc
+            joint = torch.where(absent | joint.isnan(), torch.full_like(joint, float('-inf')), joint)
+            # absent hypotheses stay behind the present ones, also behind those the lattice cannot spell: two stable sorts
+            order = (-joint).argsort(dim=1, stable=True)
+            order = order.gather(1, absent.gather(1, order).long().argsort(dim=1, stable=True))
+            pick = lambda t: t.gather(1, order)
+            tokens = tokens.gather(1, order[:, :, None].expand(N, W, cap))
+            lengths, fin, logp = pick(lengths), pick(bd.last_finished), pick(bd.last_logprobs)
+            self.last_nbest = (tokens, lengths, pick(joint), counts)
+            self.last_parts = (pick(ranks), pick(ctc))
+            out_len = lengths[:, 0].clamp(min=0) + fin[:, 0].long()
+            lens = out_len.tolist()
+            outputs = torch.nested.nested_tensor([tokens[i, 0, :max(n - 1, 0)] for i, n in enumerate(lens)])
+            return outputs, out_len.to(input_lengths.dtype), [None] * N, logp[:, 0].clone(), out[4]
 
 
 class AudioEncoder(nn.Module):

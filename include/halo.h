@@ -810,6 +810,51 @@ int halo_decode_token(const float *logits, long ld, int N, int V, int64_t *token
                       int vocab, int C, float *y_next, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Beam search of the encoder-decoder ASR model (haloop_amd/transformer.py BeamDecoder) on the fused decode launches.  The
+ * reference decodes greedily only (ha/transformer.py:124-199), so the definition is this library's own:
+ *
+ *   State: per utterance W = beam slots, each empty (log-probability -inf), live, or finished (it has emitted ETX).  Before step 0 slot 0
+ *   is live with tokens [STX], log-probability 0 and length 0; the others are empty.  The search runs `capacity` steps t = 0 ..
+ *   capacity - 1 and never ends early (no host read).
+ *   Candidates of a step: a live slot j with lp_j = log_softmax(logits_j) gives the V candidates (j, k) with log-probability
+ *   score_j + lp_j[k] and length len_j + (k != ETX); a finished slot gives the one candidate (j, ETX) with its log-probability and length
+ *   unchanged; an empty slot gives none.
+ *   Ranking: rank = fmaf(length_bonus, length, log-probability).  The W best are taken in the total order (rank descending, position
+ *   j V + k ascending); candidates of rank -inf are never taken, and a slot that takes nothing is empty.  A taken candidate becomes a new
+ *   slot, in the order taken, with its parent's tokens plus k; it is finished if its parent was or k == ETX.
+ *   Result: the beam after the last step, in that order (hypotheses that never closed keep finished == 0).
+ *   beam = 1 with length_bonus = 0 is the greedy decode token for token: the first-index arg-max, the log-probability m - lse summed.
+ *
+ * Slot n * beam + r is hypothesis r of utterance n.  A step is the 5 launches per layer and the LayerNorm + lm_head product of the greedy
+ * step on N * beam rows, with halo_decode_beam_attention in the place of halo_decode_attention_pair, and then halo_decode_beam_select.
+ *   halo_decode_beam_attention  halo_decode_attention_pair over slots = N * beam rows a [slots][4C].  Cross-attention reads the memory
+ *                            caches [N][heads][S][head_dim] of utterance slot / beam (one per utterance, not per slot) and
+ *                            memory_lengths[slot / beam].  Self-attention reads position j < n_keys - 1 from row ancestors[slot][j] of
+ *                            the time caches [slots][heads][cache_len][head_dim] (values outside [0, slots) are clamped) and stores
+ *                            position n_keys - 1 into the slot's own row; ancestors may be NULL at n_keys == 1.  No slot reads what
+ *                            another slot stores in the launch.  The sums run in halo_decode_attention_pair's order: with beam = 1 and
+ *                            the identity table the same bits.  head_dim 16 / 32 / 64 / 128, up to 8192 keys, slots <= 65535.
+ *   halo_decode_beam_select  one workgroup per utterance on logits [N * beam][ld]: one step of the definition above.  It reads the beam
+ *                            (scores_in [N][beam] log-probabilities, lengths_in, finished_in, tokens_in [N][beam][tokens_ld] without STX
+ *                            and ETX, ancestors_in [N * beam][ancestors_ld]; at t == 0 none of them is read) and writes the new one to
+ *                            the *_out buffers, which must be other buffers (the caller alternates two copies by step parity):
+ *                            scores_out (-inf: empty), ranks_out, lengths_out, finished_out, tokens_out, and the next step's table
+ *                            ancestors_out[r][0 .. t-1] = ancestors_in[parent][0 .. t-1], ancestors_out[r][t] = the parent's slot (an
+ *                            empty slot names itself); then y_next[slot] = wte[token] (ETX for an empty slot; y_next may be NULL).
+ *                            beam <= 16, V <= 8192, t < capacity <= tokens_ld, ancestors_ld > t.  The utterance's beam V logits stay in
+ *                            LDS when they are 8192 floats or fewer and are re-read by the same operations otherwise; no float atomics,
+ *                            every sum has one order: bit-reproducible. */
+int halo_decode_beam_attention(const float *a, long a_row_stride, int slots, int beam, int heads, int head_dim, const void *mem_k,
+                               const void *mem_v, int S, const int *memory_lengths, void *time_k, void *time_v, int cache_len, int n_keys,
+                               const int *ancestors, long ancestors_ld, const float *cos_table, const float *sin_table, float *y,
+                               long y_row_stride, halo_stream_t stream);
+int halo_decode_beam_select(const float *logits, long ld, int N, int beam, int V, int t, int capacity, int etx, float length_bonus,
+                            const float *scores_in, const int *lengths_in, const int *finished_in, const int *tokens_in,
+                            const int *ancestors_in, float *scores_out, float *ranks_out, int *lengths_out, int *finished_out,
+                            int *tokens_out, int *ancestors_out, long tokens_ld, long ancestors_ld, const float *wte, int vocab, int C,
+                            float *y_next, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused launches of one batched GPT sampling step (haloop_amd/generation.py; the T == 1 case of ha/attention.py:253-321 under a KV
  * cache): 5 launches per layer (LayerNorm + c_attn | cache store + attention | c_proj, accumulate | LayerNorm + c_fc + tanh-GELU |
  * mlp.c_proj, accumulate) and 2 per token (LayerNorm + lm_head | the draw), over the decode images of halo_decode_image.  Every per-step
