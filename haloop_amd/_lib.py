@@ -182,6 +182,10 @@ SIGNATURES = {
     'halo_decode_beam_attention': (_i, [_vp, _l, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp]),
     'halo_decode_beam_select': (_i, [_vp, _l, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _vp, _i,
                                      _i, _vp, _vp]),
+    'halo_ctc_prefix_scores': (_i, [_vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _l, _vp]),
+    'halo_decode_beam_select_joint': (_i, [_vp, _l, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _l, _l, _vp, _i, _i, _vp, _vp]),
+    'halo_ctc_prefix_advance': (_i, [_vp, _l, _l, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_rnnt_advance': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _vp, _i, _vp, _l, _vp, _vp]),
     'halo_rnnt_lstm_cell': (_i, [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp]),
     'halo_rnnt_beam_step': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -173,6 +173,13 @@ struct BeamSelArgs {
     int C;
     float *y;                  // [N * W][C] <- wte[token] (NULL: the last step)
     int cached;                // the utterance's W V logits are kept in LDS (BEAM_LDS_FLOATS or fewer), else re-read from L2
+    // the joint CTC/attention search (dec_beam_select_kernel<true>): rank = (1 - c) * rank + c * psi
+    float c, omc;              // ctc_weight and 1 - ctc_weight
+    const float *psi_cand;     // [N * W][psi_ld]: the CTC prefix score of every candidate of a live slot (csrc/ctc_prefix_score.hip)
+    long psi_ld;
+    const float *psi_in;       // [N][W]: the prefix score each slot carries (a finished slot's: its full CTC log-probability)
+    float *psi_out;
+    int *par_out, *last_out;   // [N][W]: the parent's slot index (-1: empty), the token taken
 };
 
 // (rank, pos) stands before (orank, opos) in the order (rank descending, position ascending)
@@ -180,8 +187,11 @@ __device__ __forceinline__ bool before(float sc, int pos, float osc, int opos) {
 
 enum { SLOT_EMPTY = 0, SLOT_LIVE = 1, SLOT_FINISHED = 2 };
 
+// JOINT: the candidates are ranked by the mix with their CTC prefix scores; everything else is the same code, so the plain launch keeps
+// its bits.  The mix is two products and a sum, each rounded (no fused multiply-add): c = 0 returns the plain rank bit for bit.
+template <bool JOINT>
 __global__ __launch_bounds__(BEAM_THREADS) void dec_beam_select_kernel(const BeamSelArgs p) {
-    __shared__ float s_score[BEAM_MAX], s_lse[BEAM_MAX], sel_rank[BEAM_MAX];
+    __shared__ float s_score[BEAM_MAX], s_lse[BEAM_MAX], sel_rank[BEAM_MAX], s_psi[BEAM_MAX];
     __shared__ int s_len[BEAM_MAX], s_state[BEAM_MAX], sel_pos[BEAM_MAX], s_par[BEAM_MAX], s_k[BEAM_MAX];
     __shared__ float r_sc[2][BEAM_WAVES];
     __shared__ int r_pos[2][BEAM_WAVES];
@@ -202,6 +212,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void dec_beam_select_kernel(const Bea
             }
         }
         s_score[tid] = sc; s_len[tid] = len; s_state[tid] = st;
+        if (JOINT) s_psi[tid] = (tid < W && p.t > 0 && st != SLOT_EMPTY) ? p.psi_in[base + tid] : (st == SLOT_LIVE ? 0.f : -INFINITY);
     }
     __syncthreads();
     auto logit = [&](int j, int v) { return p.logits[(base + j) * p.ld + v]; };
@@ -225,7 +236,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void dec_beam_select_kernel(const Bea
     __syncthreads();
     // the candidate (j, k) of a live slot: its log-probability and its rank, by the same operations wherever they are needed
     auto cand_score = [&](int j, int k) { return s_score[j] + (z(j, k) - s_lse[j]); };
-    auto cand_rank = [&](int j, int k, float sc) { return fmaf(p.bonus, (float)(s_len[j] + (k != p.etx)), sc); };
+    auto mix = [&](float rk, float psi) { return JOINT ? __fadd_rn(__fmul_rn(p.omc, rk), __fmul_rn(p.c, psi)) : rk; };
+    auto cand_rank = [&](int j, int k, float sc) {
+        const float rk = fmaf(p.bonus, (float)(s_len[j] + (k != p.etx)), sc);
+        return JOINT ? mix(rk, p.psi_cand[(base + j) * p.psi_ld + k]) : rk;
+    };
     // ---- 2. the W best candidates, one per round: the first in the order among those behind the last one taken.  Position j V + k; a
     //         finished slot has the one candidate (j, ETX).
     float prank = INFINITY;
@@ -234,7 +249,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void dec_beam_select_kernel(const Bea
         float brank = -INFINITY;
         int bpos = 0x7fffffff;
         if (tid < W && s_state[tid] == SLOT_FINISHED) {
-            const float rk = fmaf(p.bonus, (float)s_len[tid], s_score[tid]);
+            const float rk = mix(fmaf(p.bonus, (float)s_len[tid], s_score[tid]), JOINT ? s_psi[tid] : 0.f);
             const int pos = tid * V + p.etx;
             if (rk > -INFINITY && before(prank, ppos, rk, pos)) { brank = rk; bpos = pos; }
         }
@@ -275,6 +290,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void dec_beam_select_kernel(const Bea
             else { sc = cand_score(par, k); len = s_len[par] + (k != p.etx); fin = k == p.etx; }
         }
         p.score_out[base + tid] = sc; p.rank_out[base + tid] = rk; p.len_out[base + tid] = len; p.fin_out[base + tid] = fin;
+        if (JOINT) {
+            float psi = -INFINITY;
+            if (par >= 0) psi = s_state[par] == SLOT_FINISHED ? s_psi[par] : p.psi_cand[(base + par) * p.psi_ld + k];
+            p.psi_out[base + tid] = psi; p.par_out[base + tid] = par; p.last_out[base + tid] = k;
+        }
         s_par[tid] = par; s_k[tid] = k;
     }
     __syncthreads();
@@ -353,7 +373,36 @@ int halo_decode_beam_select(const float *logits, long ld, int N, int beam, int V
     p.score_out = scores_out; p.rank_out = ranks_out; p.len_out = lengths_out; p.fin_out = finished_out; p.tok_out = tokens_out;
     p.anc_out = ancestors_out; p.tok_ld = tokens_ld; p.anc_ld = ancestors_ld; p.wte = wte; p.C = C; p.y = y_next;
     p.cached = (long)beam * V <= BEAM_LDS_FLOATS;
-    hipLaunchKernelGGL(dec_beam_select_kernel, dim3((unsigned)N), dim3(BEAM_THREADS), p.cached ? (size_t)beam * V * sizeof(float) : 0,
+    p.c = 0.f; p.omc = 1.f; p.psi_cand = nullptr; p.psi_ld = 0; p.psi_in = nullptr; p.psi_out = nullptr; p.par_out = p.last_out = nullptr;
+    hipLaunchKernelGGL(dec_beam_select_kernel<false>, dim3((unsigned)N), dim3(BEAM_THREADS), p.cached ? (size_t)beam * V * sizeof(float) : 0,
+                       (hipStream_t)stream, p);
+    return halo_launch_status();
+}
+
+int halo_decode_beam_select_joint(const float *logits, long ld, int N, int beam, int V, int t, int capacity, int etx, float length_bonus,
+                                  float ctc_weight, const float *psi_cand, long psi_ld, const float *psi_in, float *psi_out,
+                                  const float *scores_in, const int *lengths_in, const int *finished_in, const int *tokens_in,
+                                  const int *ancestors_in, float *scores_out, float *ranks_out, int *lengths_out, int *finished_out,
+                                  int *tokens_out, int *ancestors_out, int *parents_out, int *last_out, long tokens_ld, long ancestors_ld,
+                                  const float *wte, int vocab, int C, float *y_next, halo_stream_t stream) {
+    HALO_CHECK_ARG(logits && scores_in && lengths_in && finished_in && tokens_in && ancestors_in);
+    HALO_CHECK_ARG(scores_out && ranks_out && lengths_out && finished_out && tokens_out && ancestors_out);
+    HALO_CHECK_ARG(psi_cand && psi_in && psi_out && parents_out && last_out && psi_in != psi_out && psi_ld >= V);
+    HALO_CHECK_ARG(ctc_weight >= 0.f && ctc_weight <= 1.f);
+    HALO_CHECK_ARG(N > 0 && beam >= 1 && beam <= BEAM_MAX && V > 0 && V <= 8192 && ld >= V && etx >= 0 && etx < V);
+    HALO_CHECK_ARG(t >= 0 && t < capacity && tokens_ld >= capacity && ancestors_ld > t && (long)N * beam <= 0x7fffffffL / V);
+    HALO_CHECK_ARG(scores_in != scores_out && lengths_in != lengths_out && finished_in != finished_out && tokens_in != tokens_out &&
+                   ancestors_in != ancestors_out);
+    HALO_CHECK_ARG(!y_next || (wte && vocab >= V && C > 0 && C % 4 == 0 && ((uintptr_t)wte | (uintptr_t)y_next) % 16 == 0));
+    BeamSelArgs p;
+    p.logits = logits; p.ld = ld; p.V = V; p.W = beam; p.t = t; p.capacity = capacity; p.etx = etx; p.bonus = length_bonus;
+    p.score_in = scores_in; p.len_in = lengths_in; p.fin_in = finished_in; p.tok_in = tokens_in; p.anc_in = ancestors_in;
+    p.score_out = scores_out; p.rank_out = ranks_out; p.len_out = lengths_out; p.fin_out = finished_out; p.tok_out = tokens_out;
+    p.anc_out = ancestors_out; p.tok_ld = tokens_ld; p.anc_ld = ancestors_ld; p.wte = wte; p.C = C; p.y = y_next;
+    p.cached = (long)beam * V <= BEAM_LDS_FLOATS;
+    p.c = ctc_weight; p.omc = 1.0f - ctc_weight; p.psi_cand = psi_cand; p.psi_ld = psi_ld; p.psi_in = psi_in; p.psi_out = psi_out;
+    p.par_out = parents_out; p.last_out = last_out;
+    hipLaunchKernelGGL(dec_beam_select_kernel<true>, dim3((unsigned)N), dim3(BEAM_THREADS), p.cached ? (size_t)beam * V * sizeof(float) : 0,
                        (hipStream_t)stream, p);
     return halo_launch_status();
 }

@@ -1562,6 +1562,93 @@ def decode_beam_select(logits, t, capacity, etx, length_bonus, beam_in, beam_out
                                         wte.shape[1] if wte is not None else 0, ptr(y_next), _stream()), 'halo_decode_beam_select')
 
 
+# ---- the three launches the joint CTC/attention search adds to a step (csrc/ctc_prefix_score.hip, decode_beam.hip); none allocates ------
+def _prefix_shapes(name, log_probs, input_lengths, states, W):
+    if log_probs.dim() != 3 or log_probs.dtype != torch.float32 or log_probs.stride(2) != 1:
+        raise ValueError(f'{name}: log_probs must be float32 [N, S, V] with unit class stride')
+    N, S, V = log_probs.shape
+    if input_lengths.shape != (N,) or input_lengths.dtype != torch.int32 or not input_lengths.is_contiguous():
+        raise ValueError(f'{name}: input_lengths must be a contiguous int32 [N]')
+    for st in states:
+        if st is not None and (st.shape != (N * W, S, 2) or st.dtype != torch.float32 or not st.is_contiguous()):
+            raise ValueError(f'{name}: states must be contiguous float32 [N * W, S, 2]')
+    return N, S, V
+
+
+def _prefix_records(name, N, W, ints, floats=()):
+    if any(x.shape != (N, W) or x.dtype != torch.int32 or not x.is_contiguous() for x in ints) \
+            or any(x.shape != (N, W) or x.dtype != torch.float32 or not x.is_contiguous() for x in floats):
+        raise ValueError(f'{name}: the records must be contiguous [N, W] tensors, int32 (float32: scores)')
+
+
+def ctc_prefix_scores(log_probs, input_lengths, states, t, etx, psi_cand, last_tokens=None, lengths=None, scores=None, finished=None):
+    """psi_cand [N * W, V] <- the CTC prefix score of every candidate of every live slot (include/halo.h), -inf in the rows of empty and
+    finished slots; log_probs [N, S, V], states [N * W, S, 2], the records [N, W] as decode_beam_select reads them (none at t == 0)."""
+    if psi_cand.dim() != 2 or psi_cand.dtype != torch.float32 or psi_cand.stride(1) != 1 or psi_cand.shape[0] % log_probs.shape[0]:
+        raise ValueError('ctc_prefix_scores: psi_cand must be float32 [N * W, V] with unit class stride')
+    W = psi_cand.shape[0] // log_probs.shape[0]
+    N, S, V = _prefix_shapes('ctc_prefix_scores', log_probs, input_lengths, (states,), W)
+    if psi_cand.shape[1] != V:
+        raise ValueError('ctc_prefix_scores: psi_cand and log_probs differ in the class count')
+    if int(t) > 0:
+        if any(x is None for x in (last_tokens, lengths, scores, finished)):
+            raise ValueError('ctc_prefix_scores: the records are needed after step 0')
+        _prefix_records('ctc_prefix_scores', N, W, (last_tokens, lengths, finished), (scores,))
+    check(lib().halo_ctc_prefix_scores(ptr(log_probs), log_probs.stride(0), log_probs.stride(1), N, W, S, V, ptr(input_lengths), ptr(states),
+                                       ptr(last_tokens), ptr(lengths), ptr(scores), ptr(finished), int(t), int(etx), ptr(psi_cand),
+                                       psi_cand.stride(0), _stream()), 'halo_ctc_prefix_scores')
+    return psi_cand
+
+
+def ctc_prefix_advance(log_probs, input_lengths, etx, states_out, states_in=None, parents=None, last_new=None, lengths_new=None,
+                       last_prev=None):
+    """states_out [N * W, S, 2] <- the state of every slot that took a label, from its parent's in states_in (parents, last_new,
+    lengths_new: what decode_beam_select_joint wrote; last_prev: the parents' last tokens).  parents None: the empty prefix's state into
+    slot 0 of every utterance."""
+    if log_probs.dim() != 3 or states_out.dim() != 3 or states_out.shape[0] % log_probs.shape[0]:
+        raise ValueError('ctc_prefix_advance: log_probs must be [N, S, V] and states [N * W, S, 2]')
+    W = states_out.shape[0] // log_probs.shape[0]
+    N, S, V = _prefix_shapes('ctc_prefix_advance', log_probs, input_lengths, (states_out, states_in), W)
+    if parents is not None:
+        if any(x is None for x in (states_in, last_new, lengths_new, last_prev)):
+            raise ValueError('ctc_prefix_advance: parents come with states_in, last_new, lengths_new and last_prev')
+        _prefix_records('ctc_prefix_advance', N, W, (parents, last_new, lengths_new, last_prev))
+    check(lib().halo_ctc_prefix_advance(ptr(log_probs), log_probs.stride(0), log_probs.stride(1), N, W, S, V, ptr(input_lengths), int(etx),
+                                        ptr(states_in), ptr(states_out), ptr(parents), ptr(last_new), ptr(lengths_new), ptr(last_prev),
+                                        _stream()), 'halo_ctc_prefix_advance')
+    return states_out
+
+
+def decode_beam_select_joint(logits, t, capacity, etx, length_bonus, ctc_weight, psi_cand, psi_in, psi_out, beam_in, beam_out, ranks_out,
+                             parents_out, last_out, wte=None, y_next=None):
+    """decode_beam_select with rank = (1 - ctc_weight) * rank + ctc_weight * psi: psi_cand [N * W, V] from ctc_prefix_scores, psi_in /
+    psi_out [N, W] float32 (two copies), parents_out / last_out [N, W] int32 <- the parent's slot index (-1: empty), the token taken."""
+    N, W = ranks_out.shape
+    V = logits.shape[1]
+    tensors = (*beam_in, *beam_out, ranks_out)
+    if not all(x.is_contiguous() for x in tensors) or logits.shape[0] != N * W or logits.stride(1) != 1:
+        raise ValueError('decode_beam_select_joint: logits must be [N * W, V] with unit class stride and every record contiguous')
+    for rec in (beam_in, beam_out):
+        if any(x.shape != (N, W) for x in rec[:3]) or rec[3].shape[:2] != (N, W) or rec[4].shape[0] != N * W \
+                or rec[0].dtype != torch.float32 or any(x.dtype != torch.int32 for x in rec[1:]):
+            raise ValueError('decode_beam_select_joint: records are (scores f32, lengths, finished [N, W], tokens [N, W, ld], ancestors [N * W, ld] int32)')
+    if beam_in[3].shape != beam_out[3].shape or beam_in[4].shape != beam_out[4].shape:
+        raise ValueError('decode_beam_select_joint: the two copies of the beam must have one shape')
+    if y_next is not None and (not y_next.is_contiguous() or not wte.is_contiguous() or y_next.shape != (N * W, wte.shape[1])):
+        raise ValueError('decode_beam_select_joint: y_next must be a contiguous [N * W, C] and wte contiguous')
+    if psi_cand.shape != (N * W, V) or psi_cand.dtype != torch.float32 or psi_cand.stride(1) != 1:
+        raise ValueError('decode_beam_select_joint: psi_cand must be float32 [N * W, V] with unit class stride')
+    _prefix_records('decode_beam_select_joint', N, W, (parents_out, last_out), (psi_in, psi_out))
+    if not 0.0 <= float(ctc_weight) <= 1.0:
+        raise ValueError(f'decode_beam_select_joint: ctc_weight {ctc_weight} outside [0, 1]')
+    check(lib().halo_decode_beam_select_joint(ptr(logits), logits.stride(0), N, W, V, int(t), int(capacity), int(etx), float(length_bonus),
+                                              float(ctc_weight), ptr(psi_cand), psi_cand.stride(0), ptr(psi_in), ptr(psi_out),
+                                              *(ptr(x) for x in beam_in), ptr(beam_out[0]), ptr(ranks_out), *(ptr(x) for x in beam_out[1:]),
+                                              ptr(parents_out), ptr(last_out), beam_in[3].shape[2], beam_in[4].shape[1], ptr(wte),
+                                              wte.shape[0] if wte is not None else 0, wte.shape[1] if wte is not None else 0, ptr(y_next),
+                                              _stream()), 'halo_decode_beam_select_joint')
+
+
 # ---- fused launches of a GPT sampling step (csrc/gpt_decode.hip); none of these allocates: they run inside a captured step ----------
 def gpt_decode_linear_supported(k, layernorm):
     return bool(lib().halo_gpt_decode_linear_supported(k, int(layernorm)))

@@ -660,9 +660,9 @@ class Decoder(nn.Module):
         return tuple(o.clone() for o in entry['outs'])
 
     @torch.no_grad()
-    def _decode_beam(self, features, input_lengths, T, W):
+    def _decode_beam(self, features, input_lengths, T, W, ctc_log_probs=None, ctc_weight=0.0):
         """Beam search at width W with room for T steps (the greedy decode's step count): each row's best hypothesis in the greedy
-        decode's five-value form, the lists in ``last_nbest``."""
+        decode's five-value form, the lists in ``last_nbest``.  With ``ctc_log_probs`` and a weight: the joint search."""
         N = features.shape[0]
         bd = self._beams.get('decoder')
         if bd is None or bd.max_batch < N or bd.capacity < T or bd.beam < W or bd._device != self.wte.weight.device \
@@ -670,7 +670,7 @@ class Decoder(nn.Module):
             bd = BeamDecoder(self, max(N, bd.max_batch if bd else 0), max(T, bd.capacity if bd else 0), max(W, bd.beam if bd else 0),
                              self.length_bonus)
             self._beams['decoder'] = bd
-        self.last_nbest = bd.decode(features, input_lengths, capacity=T, beam=W)
+        self.last_nbest = bd.decode(features, input_lengths, capacity=T, beam=W, ctc_log_probs=ctc_log_probs, ctc_weight=ctc_weight)
         tokens, lengths, _, _ = self.last_nbest
         # greedy's output_lengths count the steps a row was alive: its tokens and, where it closed, the ETX; greedy's outputs are
         # tokens[1:output_lengths] (sic: a row that never closed loses its last token, ha/transformer.py:197) -- kept, so W = 1 is greedy
@@ -723,6 +723,7 @@ class Decoder(nn.Module):
 
 
 BEAM_MAX = 16            # csrc/decode_beam.hip keeps an utterance's records in LDS arrays of this many entries
+PREFIX_MAX_FRAMES = 4096  # csrc/ctc_prefix_score.hip keeps two rows of S floats of a slot's state in 32 KiB of LDS
 
 
 class BeamDecoder:
@@ -741,7 +742,12 @@ class BeamDecoder:
     step for the whole batch (csrc/decode.hip's products on N * W rows, csrc/decode_beam.hip's attention through a per-slot ancestor
     table and its selection), replayed from a captured graph unless HALO_DECODE_GRAPH=0; the general path (f32 mode, widths the fused
     products refuse, HALO_DECODE_FUSED=0) runs the same search on ``Decoder._decode_core``'s operators over N * W rows, the caches
-    gathered physically and the candidates pruned by a stable sort."""
+    gathered physically and the candidates pruned by a stable sort.
+
+    Joint CTC/attention decoding (the definition: include/halo.h): ``decode(..., ctc_log_probs, ctc_weight=c)`` with c > 0
+    ranks every candidate by ``(1 - c) * rank + c * psi``, psi the CTC prefix score of the extended token sequence (for ETX and for a
+    finished slot: the full CTC log-probability of the hypothesis).  Three more launches a step (csrc/ctc_prefix_score.hip's scores, the
+    joint selection, the state advance): ``5 * layers + 4``; the general path takes scores and advance from the same launches."""
 
     def __init__(self, decoder, max_batch, capacity, beam=4, length_bonus=0.0):
         self.decoder = decoder
@@ -767,18 +773,37 @@ class BeamDecoder:
             self._y, self._sa, self._sb = (torch.zeros(R * C, **f32) for _ in range(3))
         self._device = dev      # of the buffers: a decoder moved since needs a new BeamDecoder
         self._graphs = {}
-        self.last_logprobs = self.last_finished = None
+        self.last_logprobs = self.last_finished = self.last_ctc = None
+        self._joint = None      # the joint search's buffers, allocated at its first use and again when S grows
+        self._joint_S = 0
+
+    def _joint_buffers(self, S):
+        """The prefix states (two copies by step parity), psi of the candidates and of the slots, parents and last tokens: allocated
+        once, for the largest S seen (graphs captured over the earlier buffers are dropped)."""
+        if self._joint is None or S > self._joint_S:
+            V = self.decoder.lm_head.weight.shape[0]
+            R = self.max_batch * self.beam
+            i32, f32 = dict(device=self._device, dtype=torch.int32), dict(device=self._device, dtype=torch.float32)
+            with torch.inference_mode(False):
+                self._joint = dict(state=[torch.zeros(R * S * 2, **f32) for _ in range(2)], cand=torch.zeros(R * V, **f32),
+                                   psi=[torch.zeros(R, **f32) for _ in range(2)], par=torch.zeros(R, **i32),
+                                   last=[torch.zeros(R, **i32) for _ in range(2)])
+            self._joint_S = S
+            self._graphs = {k: v for k, v in self._graphs.items() if 'joint' not in k}
+        return self._joint
 
     @property
     def fused(self):
         return self.decoder._fused_decode_ok(self.decoder.wte.weight.shape[1])
 
     @torch.no_grad()
-    def decode(self, features, input_lengths, capacity=None, beam=None):
+    def decode(self, features, input_lengths, capacity=None, beam=None, ctc_log_probs=None, ctc_weight=0.0):
         """features [N, S, C], input_lengths [N] -> (tokens [N, W, capacity] int64 without STX and ETX, -1 past a hypothesis's length
         and in absent hypotheses; lengths [N, W] int64, -1: absent; scores [N, W] float32 = the rank, best first, -inf: absent; counts
         [N] int64).  ``last_logprobs`` [N, W]: the plain log-probabilities; ``last_finished`` [N, W]: the hypothesis closed with ETX.
-        ``capacity`` / ``beam``: search with less room than the buffers hold (default: all of it)."""
+        ``capacity`` / ``beam``: search with less room than the buffers hold (default: all of it).
+        ``ctc_log_probs`` [N, S, V] float32 (the CTC head's, V the decoder's) with ``ctc_weight`` in (0, 1]: the joint search; scores
+        hold the joint rank, ``last_ctc`` [N, W] each hypothesis's psi (-inf: absent).  Without them the attention-only launches run."""
         dec = self.decoder
         _require_inference(dec, features)
         if dec.wte.weight.device != self._device or features.device != self._device:
@@ -792,16 +817,30 @@ class BeamDecoder:
         N, S, C = features.shape
         if N < 1 or N > self.max_batch:
             raise ValueError(f'BeamDecoder: {N} utterances outside 1 .. {self.max_batch}')
+        c = float(ctc_weight)
+        if not 0.0 <= c <= 1.0:
+            raise ValueError(f'BeamDecoder: ctc_weight {c} outside 0 .. 1')
+        x = None
+        if ctc_log_probs is not None and c > 0.0:
+            V = dec.lm_head.weight.shape[0]
+            if ctc_log_probs.shape != (N, S, V) or ctc_log_probs.dtype != torch.float32 or ctc_log_probs.device != features.device:
+                raise ValueError(f'BeamDecoder: ctc_log_probs must be float32 [{N}, {S}, {V}] on the device of the features')
+            if S > PREFIX_MAX_FRAMES:
+                raise ValueError(f'BeamDecoder: the joint search holds {PREFIX_MAX_FRAMES} frames at most, got {S}')
+            x = ctc_log_probs.detach().contiguous()
+            self._joint_buffers(S)
         with torch.no_grad():
             dev = features.device
             mlen = input_lengths.to(device=dev, dtype=torch.int32).contiguous()
             mem2d = features.reshape(N * S, C).float().contiguous()
             if not self.fused:
-                scores, lengths, fin, tokens, ranks = self._core_general(mem2d, mlen, N, S, W, cap)
+                outs = self._core_general(mem2d, mlen, N, S, W, cap, x, c)
             elif os.environ.get('HALO_DECODE_GRAPH', '1') != '0':
-                scores, lengths, fin, tokens, ranks = self._graph(mem2d, mlen, N, S, W, cap)
+                outs = self._graph(mem2d, mlen, N, S, W, cap, x, c)
             else:
-                scores, lengths, fin, tokens, ranks = (t.clone() for t in self._core_fused(mem2d, mlen, N, S, W, cap))
+                outs = tuple(t.clone() for t in self._core_fused(mem2d, mlen, N, S, W, cap, x, c))
+            scores, lengths, fin, tokens, ranks = outs[:5]
+            self.last_ctc = outs[5] if x is not None else None
             absent = ~(scores > float('-inf'))
             lengths = torch.where(absent, torch.full_like(lengths, -1), lengths).long()
             past = torch.arange(cap, device=dev)[None, None, :] >= lengths[:, :, None]
@@ -810,8 +849,9 @@ class BeamDecoder:
             return tokens[:, :, :cap].long().masked_fill(past, -1), lengths, ranks, (~absent).sum(1)
 
     # ---- the fused path: 5 * layers + 2 launches per step --------------------------------------------------------------------------
-    def _core_fused(self, mem2d, mlen, N, S, W, cap):
-        """All launches of one search, host-sync free (capturable); returns views of the final beam's records."""
+    def _core_fused(self, mem2d, mlen, N, S, W, cap, x=None, c=0.0):
+        """All launches of one search, host-sync free (capturable); returns views of the final beam's records (the joint search, x
+        given: and of the slots' psi)."""
         dec = self.decoder
         dev, C = mem2d.device, mem2d.shape[1]
         L, heads, head_dim = len(dec.h), dec.h[0].heads, dec.h[0].head_dim
@@ -834,6 +874,12 @@ class BeamDecoder:
         # the residual stream as the pair (y, side) with K-sliced accumulating products, as in Decoder._decode_core_fused
         ksplit = os.environ.get('HALO_DECODE_KSPLIT', '1') != '0' and (2 * C) % 512 == 0
         sa, sb = (self._sa[:R * C].view(R, C), self._sb[:R * C].view(R, C)) if ksplit else (None, None)
+        if x is not None:
+            jb = self._joint
+            state = [b[:R * S * 2].view(R, S, 2) for b in jb['state']]
+            psi_cand, par = jb['cand'][:R * V].view(R, V), jb['par'][:R].view(N, W)
+            psi, last = [b[:R].view(N, W) for b in jb['psi']], [b[:R].view(N, W) for b in jb['last']]
+            ops.ctc_prefix_advance(x, mlen, ETX, state[0])                   # the empty prefix's state into slot 0 of every utterance
         for t in range(cap):
             q = t & 1
             side = None
@@ -847,39 +893,51 @@ class BeamDecoder:
                 ops.decode_linear(hid, w_fc2, C, y, accumulate=True, side_in=sa, side_out=sb)
                 side = sb
             ops.decode_linear(y, head_img, V, logits, ln_weight=dec.ln_f.weight, x_side=side)
-            ops.decode_beam_select(logits, t, cap, ETX, self.length_bonus, rec[q], rec[1 - q], ranks, wte, y if t + 1 < cap else None)
+            if x is None:
+                ops.decode_beam_select(logits, t, cap, ETX, self.length_bonus, rec[q], rec[1 - q], ranks, wte, y if t + 1 < cap else None)
+                continue
+            s_in, n_in, f_in = rec[q][:3]
+            ops.ctc_prefix_scores(x, mlen, state[q], t, ETX, psi_cand, last[q], n_in, s_in, f_in)
+            ops.decode_beam_select_joint(logits, t, cap, ETX, self.length_bonus, c, psi_cand, psi[q], psi[1 - q], rec[q], rec[1 - q], ranks,
+                                         par, last[1 - q], wte, y if t + 1 < cap else None)
+            if t + 1 < cap:                                                  # (the last beam's states are read by nobody)
+                ops.ctc_prefix_advance(x, mlen, ETX, state[1 - q], state[q], par, last[1 - q], rec[1 - q][1], last[q])
         s, n, f, tok, _ = rec[cap & 1]
-        return s, n, f, tok, ranks
+        return (s, n, f, tok, ranks) if x is None else (s, n, f, tok, ranks, psi[cap & 1])
 
-    def _graph(self, mem2d, mlen, N, S, W, cap):
-        """One HIP graph per (shape, width, parameter version), the sibling of ``Decoder._decode_graph``."""
+    def _graph(self, mem2d, mlen, N, S, W, cap, x=None, c=0.0):
+        """One HIP graph per (shape, width, parameter version), the sibling of ``Decoder._decode_graph``; the joint search has graphs of
+        its own, with the log-probabilities copied into a static buffer."""
         dec = self.decoder
         key = (N, S, W, cap, self.length_bonus, str(mem2d.device), _lib.get_math_mode())
+        if x is not None:
+            key += ('joint', c)
         stamp = tuple((p._version, p.data_ptr()) for p in dec.parameters())
         entry = self._graphs.get(key)
         if entry is None or entry['stamp'] != stamp:
-            static = (mem2d.clone(), mlen.clone())
+            static = (mem2d.clone(), mlen.clone()) + ((x.clone(),) if x is not None else ())
+            args = (*static[:2], N, S, W, cap) + ((static[2], c) if x is not None else ())
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._core_fused(*static, N, S, W, cap)                  # warm-up: weight images are built outside the capture
+                self._core_fused(*args)                                  # warm-up: weight images are built outside the capture
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                outs = self._core_fused(*static, N, S, W, cap)
+                outs = self._core_fused(*args)
             # the graph reads the cached weight images by address: keep them alive as long as the graph
             held = [list(m._images._cache.values()) for m in dec.modules() if hasattr(m, '_images')] + [getattr(dec, '_dec_images', None)]
             if len(self._graphs) >= 8:
                 self._graphs.pop(next(iter(self._graphs)))
             entry = dict(stamp=stamp, graph=graph, static=static, outs=outs, held=held)
             self._graphs[key] = entry
-        for dst, src in zip(entry['static'], (mem2d, mlen)):
+        for dst, src in zip(entry['static'], (mem2d, mlen, x)):
             dst.copy_(src)
         entry['graph'].replay()
         return tuple(o.clone() for o in entry['outs'])
 
     # ---- the general path: the same search on Decoder._decode_core's operators over N * W rows ---------------------------------------
-    def _core_general(self, mem2d, mlen, N, S, W, cap):
+    def _core_general(self, mem2d, mlen, N, S, W, cap, x=None, c=0.0):
         dec = self.decoder
         dev, C = mem2d.device, mem2d.shape[1]
         L, heads, head_dim = len(dec.h), dec.h[0].heads, dec.h[0].head_dim
@@ -905,6 +963,11 @@ class BeamDecoder:
         cur = torch.full((R, 1), STX, dtype=torch.long, device=dev)
         is_label = (torch.arange(V, device=dev) != ETX)
         own = torch.arange(W, device=dev)[None, :].expand(N, W)
+        if x is not None:      # the joint search: scores and advance from the launches of the fused path (fp32 in every mode)
+            state = [torch.empty(R, S, 2, device=dev) for _ in range(2)]
+            psi_cand, psi = torch.empty(R, V, device=dev), torch.full((N, W), ninf, device=dev)
+            last = torch.zeros(N, W, dtype=torch.int32, device=dev)
+            ops.ctc_prefix_advance(x, mlen, ETX, state[0])
         for t in range(cap):
             y = ops.embed_fwd(cur, dec.wte.weight, None)
             for l, block in enumerate(dec.h):
@@ -926,6 +989,11 @@ class BeamDecoder:
             cand[:, :, ETX] = torch.where(done, score, cand[:, :, ETX])                       # a finished slot: the one candidate (j, ETX)
             newlen = length[:, :, None] + (is_label[None, None, :] & live[:, :, None]).long()
             rk = cand + self.length_bonus * newlen.float()
+            if x is not None:
+                ops.ctc_prefix_scores(x, mlen, state[t & 1], t, ETX, psi_cand, last, length.int(), score.contiguous(), fin.int())
+                pc = psi_cand.view(N, W, V).clone()
+                pc[:, :, ETX] = torch.where(done, psi, pc[:, :, ETX])                         # a finished slot carries its psi
+                rk = (1.0 - c) * rk + c * pc
             rk = torch.where(rk.isnan(), torch.full_like(rk, ninf), rk)
             top, idx = rk.view(N, W * V).sort(dim=1, descending=True, stable=True)             # equal ranks: position ascending
             top, idx = top[:, :W], idx[:, :W]
@@ -943,6 +1011,15 @@ class BeamDecoder:
             src = (torch.arange(N, device=dev)[:, None] * W + par).view(-1)
             time_cache = time_cache.index_select(2, src)                                      # the parent's history, physically
             cur = torch.where(taken, k, torch.full_like(k, ETX)).view(R, 1)
+            if x is not None:
+                psi = torch.where(taken, pc.view(N, W * V).gather(1, idx), torch.full_like(top, ninf))
+                new_last = cur.view(N, W).int()
+                if t + 1 < cap:
+                    ops.ctc_prefix_advance(x, mlen, ETX, state[1 - (t & 1)], state[t & 1], torch.where(taken, par, -1).int(), new_last,
+                                           length.int(), last)
+                last = new_last
+        if x is not None:
+            return score, length.int(), fin.int(), tokens.int(), rank, psi
         return score, length.int(), fin.int(), tokens.int(), rank
 
 
@@ -952,6 +1029,7 @@ class CTCAttentionDecoder(nn.Module):
         super().__init__()
         self.decoder = Decoder(vocab=vocab, head_dim=head_dim, heads=heads, p_drop=p_drop, layers=layers)
         self.recognizer = TemporalClassifier(feat_dim=head_dim * heads, vocab_size=vocab)
+        self.joint = os.environ.get('HALO_ASR_JOINT', '0') == '1'         # decode(beam_size, ctc_weight): one-pass joint search
 
     def forward(self, features, condtargets, input_lengths=None, condtarget_lengths=None, star_penalty=None,
                 measure_entropy=False, drop_labels=False):
@@ -963,18 +1041,37 @@ class CTCAttentionDecoder(nn.Module):
         recognizer_loss, recognizer_stats = self.recognizer(features, targets, input_lengths, target_lengths, star_penalty)
         return decoder_loss + 0.3 * recognizer_loss, {**decoder_stats, **recognizer_stats}
 
-    def decode(self, features, input_lengths, target_lengths, prompt=None, beam_size=None, ctc_weight=0.0):
+    def decode(self, features, input_lengths, target_lengths, prompt=None, beam_size=None, ctc_weight=0.0, joint=None):
         """``Decoder.decode``.  With a beam (``beam_size`` or the decoder's attribute >= 1) and ``ctc_weight`` c > 0 the jointly trained
         CTC head rescores the final lists: they are re-ranked by (1 - c) * rank + c * (-ctc_loss(hypothesis)), ties in the old order,
         a hypothesis the lattice cannot spell (infinite loss) last; the search itself is unchanged.  ``last_nbest``: the re-ranked lists
         (scores = the joint score), ``last_parts`` = (attention ranks, CTC log-probabilities) [N, W] in the new order; the returned
-        log-probability stays the decoder's own."""
+        log-probability stays the decoder's own.
+        ``joint=True`` (default: the attribute ``joint``, read from HALO_ASR_JOINT=1 when the module is built; off): the one-pass joint
+        search instead (``BeamDecoder.decode`` with the head's log-probabilities) -- every candidate extension is ranked
+        by (1 - c) * rank + c * its CTC prefix score while the search runs; ``last_nbest`` / ``last_parts`` as above, in the search's
+        order.  It needs a beam and c > 0 (``joint=True`` without them: ValueError)."""
         width = self.decoder.beam_size if beam_size is None else int(beam_size)
+        c = float(ctc_weight)
+        if joint and (width < 1 or not c > 0.0):
+            raise ValueError('CTCAttentionDecoder.decode(joint=True) needs beam_size >= 1 and ctc_weight > 0')
+        if (self.joint if joint is None else bool(joint)) and width >= 1 and c > 0.0:
+            if prompt is not None:
+                raise NotImplementedError('CTCAttentionDecoder.decode(joint=True): prompts are not built')
+            with torch.no_grad():
+                _require_inference(self.decoder, features)
+                lp =self.recognizer.log_probs(features).float()                             # [N, S, V]
+                out = self.decoder._decode_beam(features, input_lengths, int(target_lengths.max().item()) + 1, width,
+                                                ctc_log_probs=lp, ctc_weight=c)
+                bd = self.decoder._beams['decoder']
+                self.last_nbest = self.decoder.last_nbest
+                lengths = self.last_nbest[1]
+                self.last_parts = (bd.last_logprobs + float(self.decoder.length_bonus) * lengths.clamp(min=0).float(), bd.last_ctc)
+            return out
         out = self.decoder.decode(features, input_lengths, target_lengths, prompt=prompt, beam_size=beam_size)
         if not width:
             return out
         self.last_nbest = self.decoder.last_nbest
-        c = float(ctc_weight)
         if not c > 0.0:
             return out
         from . import functional as HF

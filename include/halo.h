@@ -855,6 +855,57 @@ int halo_decode_beam_select(const float *logits, long ld, int N, int beam, int V
                             float *y_next, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Joint CTC/attention beam search (BeamDecoder.decode(..., ctc_log_probs, ctc_weight)): the beam search above with every
+ * candidate ranked by a mix of the decoder's score and the CTC prefix score of the extended token sequence.  The library's own definition:
+ *
+ *   Per utterance n: x[t][k], t < T_n = input_lengths[n], the CTC head's log-probabilities; class 0 the blank; ETX the decoder's end token;
+ *   a hypothesis's tokens exclude STX and ETX.  A live slot with prefix g carries r[t][2], t < T_n: the log-mass of the CTC paths over
+ *   frames 0 .. t that spell exactly g and end in a non-blank (r[t][0]) or in a blank (r[t][1]).
+ *   The empty prefix: r[t][0] = -inf, r[t][1] = x[0][0] + ... + x[t][0], psi = 0.
+ *   Candidate scores of g, from g's state alone, with both[t] = logaddexp(r[t][0], r[t][1]):
+ *     psi(g, 0) = -inf (the lattice cannot spell a blank); psi(g, ETX) = both[T_n - 1] (the utterance spells exactly g: -ctc_loss(g));
+ *     every other k: phi[t] = r[t][1] if k is g's last token, else both[t], and
+ *     psi(g, k) = logsumexp({phi[t-1] + x[t][k] : 1 <= t < T_n} U {x[0][k] if g is empty}); an empty sum is -inf.
+ *   State of h = g.k, k not in {0, ETX}: q[0][0] = x[0][k] if g is empty, else -inf; q[0][1] = -inf; for t >= 1
+ *     q[t][0] = logaddexp(q[t-1][0], phi[t-1]) + x[t][k],  q[t][1] = logaddexp(q[t-1][0], q[t-1][1]) + x[t][0].
+ *   Ranking with ctc_weight = c in (0, 1]: a candidate (j, k) of a live slot has rank = (1 - c) * fmaf(length_bonus, length, logp) +
+ *   c * psi(g_j, k) (two products and a sum in fp32, each rounded); a finished slot's one candidate (j, ETX) uses its stored psi.  Everything
+ *   else is the search above: rank -inf is never taken, ties by position j V + k, slots in the order taken, `capacity` steps.  A taken
+ *   candidate's psi becomes its slot's psi, so a finished hypothesis ends with (1 - c) * rank + c * (-ctc_loss).
+ *
+ * fp32 in every arithmetic mode, no float atomics, every sum in one order.  Frames t >= T_n of x and of the states are never read or
+ * written.  S <= 4096, V <= 8192, beam <= 16 (HALO_ENOTSUP above).  log_probs [N][S][V] with strides (batch_stride, frame_stride, 1);
+ * states [N * beam][S][2], 8-byte aligned, two copies by step parity like the beam's records.
+ *   halo_ctc_prefix_scores   psi_cand[slot][k] for every class of every live slot (as halo_decode_beam_select reads the records: at t == 0
+ *                            none is read and slot 0 holds the empty prefix; a slot of length 0 holds the empty prefix, otherwise
+ *                            last_tokens[slot] is its last token); rows of empty and finished slots are -inf.  One workgroup per (slot,
+ *                            64 classes; 32 when V <= 32); both[] and r[.][1] are built once in LDS; threads are (class, one of 4 (8)
+ *                            contiguous frame stretches); a max pass and a sum pass, the stretches combined in order, one log per
+ *                            (slot, class).
+ *   halo_decode_beam_select_joint  halo_decode_beam_select (the same kernel body) with the rank above: psi_cand [N * beam][psi_ld], psi_in /
+ *                            psi_out [N][beam] (two copies; psi_in is not read at t == 0), and parents_out [N][beam] = the parent's slot index
+ *                            (-1: empty), last_out [N][beam] = the token taken (ETX for an empty slot).  ctc_weight in [0, 1]; with 0 and
+ *                            finite psi every output shared with halo_decode_beam_select has that launch's bits.
+ *   halo_ctc_prefix_advance  states_out[slot] for every slot that took a label (parents[slot] >= 0 and last_tokens_new[slot] not ETX), from
+ *                            states_in[parent]: g is empty iff lengths_new[slot] == 1, and its last token is last_tokens_prev[parent].
+ *                            Finished and empty slots are left alone.  parents == NULL: the empty prefix's state into slot 0 of every
+ *                            utterance (before step 0; states_in and the records may be NULL).  One wave per slot: 64 frames' operands
+ *                            are loaded at once, the serial chain runs over them lane by lane (its two log-sum-exps on the hardware
+ *                            exp2 / log2). */
+int halo_ctc_prefix_scores(const float *log_probs, long batch_stride, long frame_stride, int N, int beam, int S, int V,
+                           const int *input_lengths, const float *states, const int *last_tokens, const int *lengths, const float *scores,
+                           const int *finished, int t, int etx, float *psi_cand, long psi_ld, halo_stream_t stream);
+int halo_decode_beam_select_joint(const float *logits, long ld, int N, int beam, int V, int t, int capacity, int etx, float length_bonus,
+                                  float ctc_weight, const float *psi_cand, long psi_ld, const float *psi_in, float *psi_out,
+                                  const float *scores_in, const int *lengths_in, const int *finished_in, const int *tokens_in,
+                                  const int *ancestors_in, float *scores_out, float *ranks_out, int *lengths_out, int *finished_out,
+                                  int *tokens_out, int *ancestors_out, int *parents_out, int *last_out, long tokens_ld, long ancestors_ld,
+                                  const float *wte, int vocab, int C, float *y_next, halo_stream_t stream);
+int halo_ctc_prefix_advance(const float *log_probs, long batch_stride, long frame_stride, int N, int beam, int S, int V,
+                            const int *input_lengths, int etx, const float *states_in, float *states_out, const int *parents,
+                            const int *last_tokens_new, const int *lengths_new, const int *last_tokens_prev, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused launches of one batched GPT sampling step (haloop_amd/generation.py; the T == 1 case of ha/attention.py:253-321 under a KV
  * cache): 5 launches per layer (LayerNorm + c_attn | cache store + attention | c_proj, accumulate | LayerNorm + c_fc + tanh-GELU |
  * mlp.c_proj, accumulate) and 2 per token (LayerNorm + lm_head | the draw), over the decode images of halo_decode_image.  Every per-step
