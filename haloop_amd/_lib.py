@@ -9,6 +9,9 @@ LIB_PATH = os.path.join(_HERE, 'csrc', 'libhalo.so')
 HALO_ABI_VERSION = 21
 HALO_GPT_SAMPLE_STREAM = 0x47505453
 HALO_MLM_STREAM = 0x4D4C4D31
+HALO_SPECMASK_STREAM = 0x53504D4B
+HALO_FEATURES_FBANK = 0
+HALO_FEATURES_MFCC = 1
 HALO_GEMM_RELU = 1
 HALO_GEMM_GELU = 2
 HALO_GEMM_ACCUM = 4
@@ -165,6 +168,9 @@ SIGNATURES = {
     'halo_fbank_power': (_i, [_vp, _i, _i, _vp, _i, _vp]),
     'halo_fbank_log': (_i, [_vp, _l, _f, _vp]),
     'halo_fbank_spectrum_mel': (_i, [_vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp]),
+    'halo_features_batch': (_i, [_vp, _vp, _i, _l, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _f, _vp, _i, _vp, _vp]),
+    'halo_cmvn_batch': (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    'halo_spec_mask': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _u64, _u32, _vp]),
     'halo_star_ctc_workspace_bytes': (_sz, [_i, _i, _i]),
     'halo_star_ctc_fwd': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp]),
     'halo_star_ctc_bwd': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),

@@ -634,6 +634,51 @@ int halo_fbank_spectrum_mel(const float *frames, int n_frames, int padded, const
                             float eps, float *out, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Batched feature front-end.  replaces: the combinators fbank: / mfcc: / mask: of ha/data.py:103-151 (torchaudio.compliance.kaldi.fbank
+ * and .mfcc with their defaults, utterance CMVN :148-150, mask_along_axis_iid twice :109-121), which the reference runs per utterance in
+ * its DataLoader workers.  A ragged batch goes in, padded features and their lengths come out; every shape follows from N and the padded
+ * width L, ``lengths`` (device int64 [N], clamped to [0, L]) is read on the device only, and no launch uses atomics.
+ *   M   = 1 + (L - frame_len) / shift for L >= frame_len, else 0                     (the caller passes it; checked)
+ *   m_n = 1 + (lengths[n] - frame_len) / shift for lengths[n] >= frame_len, else 0   (snip edges)
+ *
+ *   halo_features_batch  waveforms [N, L] fp32 (anything may stand past lengths[n]: such a sample is never read) -> out [N, M, D] fp32
+ *                        and feature_lengths [N] int64 = m_n, ONE launch.  kind HALO_FEATURES_FBANK: D = num_bins log-mels;
+ *                        HALO_FEATURES_MFCC: D = num_ceps.  Rows m >= m_n are exact zeros; every element of out is written.
+ *                        Per frame: DC removal, pre-emphasis (the first sample against itself) and window in fp32 with the arithmetic
+ *                        of halo_fbank_frames; a 512-point real FFT in float64 (frame_len, shift <= 512); the filters; (float)
+ *                        log(max(., eps)); for MFCC the product with dct on those fp32 log-mels, in float64.  Tables (device):
+ *                          window   [frame_len] fp32
+ *                          twiddle  [770] float64: for the stage of half-size h = 1, 2, .. 128 and j < h, entry h - 1 + j holds
+ *                                   cos(pi j / h) at [h - 1 + j] and -sin(pi j / h) at [256 + h - 1 + j] (entries 255, 511 unused);
+ *                                   then cos(2 pi k / 512) at [512 + k] and -sin(2 pi k / 512) at [641 + k], k = 0 .. 128
+ *                          filters  [3][num_bins] int32: first bin lo, bin count, offset into weights of each triangle; weights
+ *                                   [n_weights] float64, the triangle's non-zero weights on bins lo .. lo + count - 1 (bins < 256)
+ *                          dct      [num_ceps][num_bins] float64, the lifter folded in (MFCC; else NULL)
+ *                        num_bins <= 128, n_weights <= 1024, num_ceps * num_bins <= 1024, and the tables must fit 64 KiB of LDS
+ *                        beside the 8 frames a workgroup transforms.
+ *   halo_cmvn_batch      in place on [N, M, D]: per utterance and column, minus the mean over the m_n valid rows, divided by the
+ *                        unbiased standard deviation (frames.std(dim=0)); float64 sums in one fixed order.  Rows >= m_n are not
+ *                        touched; m_n == 1 gives NaN in that row (0 / 0, as the reference's expression), m_n == 0 nothing.
+ *   halo_spec_mask       in place on [N, M, D]: one band of columns and one band of frames of every utterance set to 0.  For utterance n
+ *                            (r0, r1, r2, r3) = philox4x32_10(ctr = (n, 0, HALO_SPECMASK_STREAM, step), key = (lo32(seed), hi32(seed)))
+ *                            u_i = float32(r_i >> 8) * 2^-24
+ *                        and, every product and difference rounded to float32,
+ *                            columns: P = min(freq_param, D),   v = u0 * P, width = int(v), start = int(u1 * (D - v))
+ *                            frames:  P = min(time_param, m_n), v = u2 * P, width = int(v), start = int(u3 * (m_n - v))
+ *                        [start, start + width) is masked, on the m_n valid frames only.  This is mask_along_axis_iid's arithmetic on
+ *                        the unpadded utterance; the clamp of P to the axis size is the one departure (torchaudio refuses such a call). */
+#define HALO_FEATURES_FBANK 0
+#define HALO_FEATURES_MFCC 1
+#define HALO_SPECMASK_STREAM 0x53504D4Bu     /* 'SPMK': distinct from the dropout sites, HALO_GPT_SAMPLE_STREAM and HALO_MLM_STREAM */
+int halo_features_batch(const float *waveforms, const int64_t *lengths, int N, long L, int kind, int frame_len, int shift,
+                        float preemphasis, int remove_dc, const float *window, const double *twiddle, const int *filters,
+                        const double *weights, int n_weights, int num_bins, const double *dct, int num_ceps, float eps, float *out, int M,
+                        int64_t *feature_lengths, halo_stream_t stream);
+int halo_cmvn_batch(float *features, const int64_t *feature_lengths, int N, int M, int D, halo_stream_t stream);
+int halo_spec_mask(float *features, const int64_t *feature_lengths, int N, int M, int D, int freq_param, int time_param, uint64_t seed,
+                   uint32_t step, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The reference's two further lattices, one workgroup per utterance, forward score and gradient.
  *   halo_star_ctc_fwd     ha/star.py:65-166 star_ctc_forward_score(emissions [T, N, C] log-probabilities, targets [N, S], lengths,
  *                         star_penalty): losses [N] = -log of the 4S+3-state star lattice (stars are evaluated from the C symbols in
