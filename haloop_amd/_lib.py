@@ -10,6 +10,8 @@ HALO_ABI_VERSION = 21
 HALO_GPT_SAMPLE_STREAM = 0x47505453
 HALO_MLM_STREAM = 0x4D4C4D31
 HALO_SPECMASK_STREAM = 0x53504D4B
+HALO_SPEED_STREAM = 0x53504544
+HALO_RESAMPLE_MAX_RATIOS = 8
 HALO_FEATURES_FBANK = 0
 HALO_FEATURES_MFCC = 1
 HALO_GEMM_RELU = 1
@@ -171,6 +173,8 @@ SIGNATURES = {
     'halo_features_batch': (_i, [_vp, _vp, _i, _l, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _f, _vp, _i, _vp, _vp]),
     'halo_cmvn_batch': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'halo_spec_mask': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _u64, _u32, _vp]),
+    'halo_resample_lds_bytes': (_l, [_vp, _i]),
+    'halo_resample_batch': (_i, [_vp, _vp, _i, _l, _vp, _i, _vp, _l, _vp, _l, _vp, _i, _u64, _u32, _vp, _l, _vp, _vp, _vp]),
     'halo_star_ctc_workspace_bytes': (_sz, [_i, _i, _i]),
     'halo_star_ctc_fwd': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp]),
     'halo_star_ctc_bwd': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),

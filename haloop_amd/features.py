@@ -5,7 +5,9 @@
     mfcc_batch(waveforms, lengths)               kaldi MFCC (13 of 23) + utterance CMVN         2 launches
     spec_mask_(features, feature_lengths, seed=) the ``mask:`` augmentation, in place           1 launch
     mfcc(waveform)                               one utterance under torchaudio's signature
-    FrontEnd('mask:fbank')                       the feature part of a reference dataset string as an nn.Module
+    resample_batch(waveforms, lengths, orig_freq)  sinc resampling to 16 kHz (LabelFile's)      1 launch
+    speed_perturb(waveforms, lengths, seed=)     the ``speed:`` augmentation, drawn per utterance 1 launch
+    FrontEnd('mask:fbank:speed')                 a reference dataset string from the waveform up, as an nn.Module
 
 ``lengths`` stays on the device: every shape follows from the padded width L (``M = 1 + (L - 400) // 160`` frames), the per-utterance
 frame counts are written by the feature launch itself, and nothing on the path reads a value back (it captures into a graph).  Rows
@@ -13,8 +15,11 @@ past an utterance's own frames are exact zeros, as ``pad_sequence`` leaves them.
 ("Batched feature front-end") the contract and the mask's draw; ``fbank.fbank`` -- one utterance, two launches -- stays as it is.
 
 Parity: torchaudio is not part of this build, so MFCC PARITY IS UNPINNED (tests/frontend_ref.py restates kaldi's DCT and lifter on
-oracle/fbank_ref.py); only the log-mel stage underneath is pinned, to the g11_fbank vectors.
+oracle/fbank_ref.py); only the log-mel stage underneath is pinned, to the g11_fbank vectors.  RESAMPLING PARITY IS UNPINNED for the same
+reason: include/halo.h ("Waveform stage") states the arithmetic, torchaudio.functional.resample's defaults, and tests/resample_ref.py
+restates it in float64.  csrc/resample.hip holds that kernel.
 """
+import ctypes
 import math
 
 import torch
@@ -26,7 +31,7 @@ from ._lib import check, lib, ptr
 PADDED = 512                 # the FFT length csrc/frontend.hip is built for
 _EPS = float(torch.finfo(torch.float32).eps)
 _TABLES = {}
-_SPECS = ('fbank', 'mfcc', 'mask:fbank', 'mask:mfcc')
+_SPECS = ('fbank', 'mfcc', 'mask:fbank', 'mask:mfcc', 'fbank:speed', 'mfcc:speed', 'mask:fbank:speed', 'mask:mfcc:speed')
 
 
 def _twiddles():
@@ -155,6 +160,105 @@ def mfcc(waveform, channel=-1, **kwargs):
     return mfcc_batch(wav, lengths, cmvn=False, **kwargs)[0][0]
 
 
+def resample_taps(orig, new):
+    """One reduced ratio's packed filter, the layout include/halo.h states: (width, stride, phases [2, new] int32 -- first non-zero tap
+    and count of each phase --, taps [new, stride] float32).  torchaudio.functional.resample's defaults (sinc_interp_hann,
+    lowpass_filter_width 6, rolloff 0.99) evaluated in float64 and rounded once; the clamp zeroes every tap outside |t| < 6, and only the
+    run between a phase's first and last non-zero tap is kept.  orig == new is a copy: one tap of 1."""
+    if orig == new:
+        return 0, 1, torch.tensor([[0], [1]], dtype=torch.int32), torch.ones(1, 1)
+    base = min(orig, new) * 0.99
+    width = int(math.ceil(6 * orig / base))
+    k = torch.arange(-width, width + orig, dtype=torch.float64)[None, :] / orig
+    p = torch.arange(new, dtype=torch.float64)[:, None] / new
+    t = ((k - p) * base).clamp(-6.0, 6.0)
+    pt = math.pi * torch.where(t == 0, torch.ones_like(t), t)
+    dense = (torch.where(t == 0, torch.ones_like(t), torch.sin(pt) / pt) * torch.cos(math.pi * t / 12.0) ** 2 * (base / orig)).float()
+    nz = dense != 0
+    first = nz.int().argmax(dim=1)
+    count = dense.shape[1] - nz.flip(1).int().argmax(dim=1) - first
+    stride = int(count.max()) | 1                            # odd: consecutive phases on different LDS banks
+    cols = first[:, None] + torch.arange(stride)[None, :]
+    taps = torch.where(torch.arange(stride)[None, :] < count[:, None], dense.gather(1, cols.clamp(max=dense.shape[1] - 1)), torch.zeros(()))
+    return width, stride, torch.stack([first, count]).to(torch.int32), taps.contiguous()
+
+
+def _resample_tables(ratios, device):
+    """The launch's tables for a tuple of reduced ratios, built once per configuration on the host and kept on the device (as _tables):
+    (host int32 [R][6] descriptors, phases, taps).  ValueError where a ratio's table and input span do not fit the kernel's LDS."""
+    key = ('resample', tuple(ratios), str(device))
+    hit = _TABLES.get(key)
+    if hit is None:
+        desc, phases, taps = [], [], []
+        n_phases = n_taps = 0
+        for orig, new in ratios:
+            width, stride, ph, tp = resample_taps(orig, new)
+            desc += [orig, new, width, stride, n_phases, n_taps]
+            phases.append(ph.reshape(-1)); taps.append(tp.reshape(-1))
+            n_phases += ph.numel(); n_taps += tp.numel()
+            one = (ctypes.c_int * 6)(orig, new, width, stride, 0, 0)
+            if not 0 <= lib().halo_resample_lds_bytes(one, 1) <= 64 * 1024:
+                raise ValueError(f'resample: the ratio {orig}/{new} needs more LDS than the kernel has (its {new} x {stride} taps and the '
+                                 'input span of a tile must fit 64 KiB)')
+        hit = ((ctypes.c_int * len(desc))(*desc), torch.cat(phases).to(device), torch.cat(taps).to(device))
+        _TABLES[key] = hit
+    return hit
+
+
+def _resample(what, waveforms, lengths, ratios, index=None, draw=False, seed=0, step=0, want_indices=False):
+    wav, lengths = _check_inputs(what, waveforms, lengths)
+    N, L = wav.shape
+    desc, phases, taps = _resample_tables(ratios, wav.device)
+    L_out = max((new * L + orig - 1) // orig for orig, new in ratios)
+    out = torch.empty(N, L_out, device=wav.device)
+    out_lengths = torch.empty(N, dtype=torch.int64, device=wav.device)
+    indices = torch.empty(N, dtype=torch.int32, device=wav.device) if want_indices else None
+    check(lib().halo_resample_batch(ptr(wav), ptr(lengths), N, L, desc, len(ratios), ptr(phases), phases.numel(), ptr(taps), taps.numel(),
+                                    ptr(index), int(draw), seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF, ptr(out), L_out,
+                                    ptr(out_lengths), ptr(indices), ops._stream()), 'halo_resample_batch')
+    return out, out_lengths, indices
+
+
+def _reduced(orig_freq, new_freq):
+    if int(orig_freq) != orig_freq or int(new_freq) != new_freq or orig_freq < 1 or new_freq < 1:
+        raise ValueError(f'resample: the rates must be positive integers, got {orig_freq} and {new_freq}')
+    g = math.gcd(int(orig_freq), int(new_freq))
+    return int(orig_freq) // g, int(new_freq) // g
+
+
+def _resample_defaults(what, lowpass_filter_width, rolloff, resampling_method):
+    if lowpass_filter_width != 6 or rolloff != 0.99 or resampling_method != 'sinc_interp_hann':
+        raise NotImplementedError(f'haloop_amd.features.{what} builds the default filter of torchaudio.functional.resample only')
+
+
+def resample_batch(waveforms, lengths, orig_freq, new_freq=16000, lowpass_filter_width=6, rolloff=0.99, resampling_method='sinc_interp_hann'):
+    """torchaudio.functional.resample's defaults for a ragged batch, one launch (what LabelFile does to 22050 / 32000 / 44100 / 48000 Hz
+    audio, ha/data.py:33-39): waveforms [N, L] (row n valid up to lengths[n]; anything may stand behind), lengths [N] on the device ->
+    (out [N, ceil(L * new / orig)] float32, out_lengths [N] int64 = ceil(lengths * new / orig)).  Samples past out_lengths[n] are exact
+    zeros; equal rates give a copy.  Parity with torchaudio is unpinned (include/halo.h states the arithmetic)."""
+    _resample_defaults('resample_batch', lowpass_filter_width, rolloff, resampling_method)
+    return _resample('resample_batch', waveforms, lengths, (_reduced(orig_freq, new_freq),))[:2]
+
+
+def speed_perturb(waveforms, lengths, *, seed, step=0, factors=(0.95, 0.98, 1.0, 1.02, 1.05), sample_rate=16000, indices=None):
+    """The ``speed:`` combinator (ha/data.py:126-133, torchaudio.transforms.SpeedPerturbation(sample_rate, factors)) for a ragged batch, one
+    launch: every utterance draws one factor f on the device -- the library's Philox stream HALO_SPEED_STREAM keyed by ``(seed, step)``,
+    include/halo.h; ``indices`` (device int32 [N]) overrides the draw -- and is resampled from int(f * sample_rate) Hz to sample_rate.
+    -> (out [N, L_out] float32, out_lengths [N] int64, indices [N] int32: the factor each row took).  L_out follows from L and the
+    slowest factor alone ((20 L + 18) // 19 for the defaults), so nothing is read back and the call captures into a graph."""
+    factors = tuple(factors)
+    if not 1 <= len(factors) <= _lib.HALO_RESAMPLE_MAX_RATIOS:
+        raise ValueError(f'speed_perturb: 1 to {_lib.HALO_RESAMPLE_MAX_RATIOS} factors, got {len(factors)}')
+    if any(int(f * sample_rate) < 1 for f in factors):
+        raise ValueError(f'speed_perturb: every factor must be positive, got {factors}')
+    ratios = tuple(_reduced(int(f * sample_rate), sample_rate) for f in factors)
+    if indices is not None and (not indices.is_cuda or indices.dtype != torch.int32 or indices.shape != lengths.shape or not indices.is_contiguous()):
+        raise ValueError('speed_perturb: indices must be a contiguous int32 tensor [N] on the device')
+    if len(ratios) == 1:                                     # one factor: nothing to draw (the kernel reports index 0)
+        indices = None
+    return _resample('speed_perturb', waveforms, lengths, ratios, index=indices, draw=indices is None, seed=seed, step=step, want_indices=True)
+
+
 def spec_mask_(features, feature_lengths, *, seed, step=0, freq_param=None, time_param=7):
     """The ``mask:`` combinator (ha/data.py:103-123) in place on [N, M, D]: per utterance one band of at most ``freq_param`` (default
     D // 6) columns and one band of at most ``time_param`` of its own frames set to 0, drawn from the library's Philox stream keyed by
@@ -171,18 +275,24 @@ def spec_mask_(features, feature_lengths, *, seed, step=0, freq_param=None, time
 
 
 class FrontEnd(nn.Module):
-    """The feature part of a reference dataset string -- 'fbank', 'mfcc', 'mask:fbank', 'mask:mfcc' -- on the device.
-    ``front(waveforms [N, L], lengths [N], seed=, step=) -> (features [N, M, D], feature_lengths [N])``: at most three launches, and the
-    result goes straight into ``rnn.Encoder.forward`` / the AudioEncoders.  The masks are applied in training mode only."""
+    """A reference dataset string from the waveform up -- 'fbank', 'mfcc', 'mask:fbank', 'mask:mfcc', and each of them over 'speed'
+    ('mask:fbank:speed': combinators apply right to left, speed over the waveforms) -- on the device.
+    ``front(waveforms [N, L], lengths [N], seed=, step=) -> (features [N, M, D], feature_lengths [N])``: at most four launches, and the
+    result goes straight into ``rnn.Encoder.forward`` / the AudioEncoders.  Speed perturbation and the masks are applied in training
+    mode only; ``(seed, step)`` keys both draws, on distinct streams."""
 
     def __init__(self, spec):
         super().__init__()
         if spec not in _SPECS:
             raise ValueError(f'FrontEnd: unknown feature spec {spec!r}; supported: ' + ', '.join(repr(s) for s in _SPECS))
         self.spec = spec
-        self.mask, self.kind = spec.startswith('mask:'), spec.split(':')[-1]
+        parts = spec.split(':')
+        self.mask, self.speed = parts[0] == 'mask', parts[-1] == 'speed'
+        self.kind = parts[1 if self.mask else 0]
 
     def forward(self, waveforms, lengths, *, seed=0, step=0):
+        if self.speed and self.training:
+            waveforms, lengths, _ = speed_perturb(waveforms, lengths, seed=seed, step=step)
         features, feature_lengths = (fbank_batch if self.kind == 'fbank' else mfcc_batch)(waveforms, lengths)
         if self.mask and self.training:
             spec_mask_(features, feature_lengths, seed=seed, step=step)

@@ -679,6 +679,43 @@ int halo_spec_mask(float *features, const int64_t *feature_lengths, int N, int M
                    uint32_t step, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Waveform stage.  replaces: the resampling of LabelFile (ha/data.py:33-39, 59-62: 22050 / 32000 / 44100 / 48000 Hz audio to 16 kHz)
+ * and the speed: combinator (ha/data.py:126-133, 186-187, torchaudio.transforms.SpeedPerturbation(16000, [0.95, 0.98, 1.0, 1.02, 1.05])),
+ * which the reference runs per utterance in its DataLoader workers.  The arithmetic is torchaudio.functional.resample with its defaults
+ * (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99); PARITY WITH TORCHAUDIO IS UNPINNED (it is not part of this build), the
+ * definition is the one stated here.  For a ratio (orig, new) divided by its gcd:
+ *     base = min(orig, new) * 0.99,  width = ceil(6 * orig / base),  K = 2 * width + orig
+ *     t[p][k] = clamp(((k - width) / orig - p / new) * base, -6, 6)                                  p < new, k < K, float64
+ *     taps[p][k] = (float)((t == 0 ? 1 : sin(pi t) / (pi t)) * cos(pi t / 12)^2 * base / orig)
+ *     out_len = (new * len + orig - 1) / orig                                                        64-bit
+ *     out[q * new + p] = sum_k taps[p][k] * xpad[q * orig + k],  xpad[i] = x[i - width] inside [0, len), else 0
+ * orig == new is a copy: the table (width 0, K = 1, one tap of 1.0).  A speed factor f is the ratio (int(f * rate), rate).
+ *
+ *   halo_resample_batch  waveforms [N, L] fp32, lengths [N] int64 (device, clamped to [0, L]; a sample at or past lengths[n] is never
+ *                        read) -> out [N, L_out] fp32 and out_lengths [N] int64, ONE launch, no atomics, one summation order (taps
+ *                        in ascending k, fmaf), so a row's bits depend on neither the run nor the other rows.  Every element of out
+ *                        is written; elements at or past out_lengths[n] are exact zeros.  L_out = max over the R ratios of
+ *                        (new * L + orig - 1) / orig (the caller passes it; checked).  Tables:
+ *                          ratios   HOST int32 [R][6], R <= HALO_RESAMPLE_MAX_RATIOS: orig, new, width, stride, phase_off, tap_off
+ *                          phases   device int32 [n_phases]: at phase_off, [new] first non-zero tap k0 of each phase, then [new] counts
+ *                          taps     device fp32 [n_taps]: at tap_off + p * stride, taps[p][k0 .. k0 + count); count <= stride (an odd
+ *                                   stride keeps consecutive phases on different LDS banks).  The taps left out are exact zeros, so
+ *                                   the packed sum is the dense one.
+ *                        The ratio of row n: R == 1: ratios[0]; index != NULL: ratios[index[n]] (device int32 [N], clamped to
+ *                        [0, R)); else draw != 0 and
+ *                            (r0, ..) = philox4x32_10(ctr = (n, 0, HALO_SPEED_STREAM, step), key = (lo32(seed), hi32(seed)))
+ *                            u0 = float32(r0 >> 8) * 2^-24,  index = min(int(u0 * R), R - 1)          the product rounded to float32
+ *                        indices (device int32 [N], or NULL) receives the ratio each row took.  A workgroup stages one ratio's packed
+ *                        taps and the input span of 1024 outputs in LDS: halo_resample_lds_bytes(ratios, R) (-1: bad descriptors)
+ *                        must not exceed 64 KiB, else HALO_ENOTSUP. */
+#define HALO_RESAMPLE_MAX_RATIOS 8
+#define HALO_SPEED_STREAM 0x53504544u        /* 'SPED': distinct from HALO_SPECMASK_STREAM, HALO_GPT_SAMPLE_STREAM, HALO_MLM_STREAM, dropout */
+long halo_resample_lds_bytes(const int *ratios, int R);
+int halo_resample_batch(const float *waveforms, const int64_t *lengths, int N, long L, const int *ratios, int R, const int *phases,
+                        long n_phases, const float *taps, long n_taps, const int *index, int draw, uint64_t seed, uint32_t step,
+                        float *out, long L_out, int64_t *out_lengths, int *indices, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The reference's two further lattices, one workgroup per utterance, forward score and gradient.
  *   halo_star_ctc_fwd     ha/star.py:65-166 star_ctc_forward_score(emissions [T, N, C] log-probabilities, targets [N, S], lengths,
  *                         star_penalty): losses [N] = -log of the 4S+3-state star lattice (stars are evaluated from the C symbols in
