@@ -15,9 +15,10 @@
 //   The reference runs the t recurrence as a log-space parallel scan padded to 2**round(log2 T) (and raises when that is < T); the kernel
 //   walks the anti-diagonals of the lattice, any T.
 //
-// Gradients: the reference differentiates these functions with autograd; the kernels compute the same derivatives as state / cell
-// occupancies from a backward (beta) sweep over the saved alpha lattice (oracle/star_ref.py states both and is pinned to the
-// reference's autograd gradients).  fp32 throughout; logaddexp as torch defines it (halo_common.h).
+// Gradients: the reference differentiates these functions with autograd; the kernels compute the same derivatives as state / arc
+// occupancies from a backward sweep over the saved alpha lattice (oracle/star_ref.py states both and is pinned to the reference's
+// autograd gradients): star-CTC as exp(alpha + beta - logZ), the transducer by carrying the cell posteriors back through the local arc
+// weights (see transducer_grad_kernel).  fp32 throughout; logaddexp as torch defines it (halo_common.h).
 #include "halo_common.h"
 #include "halo_internal.h"
 
@@ -212,7 +213,13 @@ __global__ __launch_bounds__(256) void transducer_alpha_kernel(const TransducerA
     }
 }
 
-__global__ __launch_bounds__(256) void transducer_beta_grad_kernel(const TransducerArgs p) {
+// The gradient is minus the arc occupancies.  They are NOT formed as exp(alpha + beta - logZ): those three numbers have the magnitude
+// of the loss, and in fp32 their rounding (1e-4 at a loss of 2000 nats) becomes the occupancy's relative error.  Instead the posterior
+// of passing through a cell, q[t, u] (q = gout at the final cell), is carried back along the anti-diagonals with the local arc weights
+// of the forward's own logaddexp: cell (t', u') = logaddexp(bot, up) hands q * 1 / (1 + exp(up - bot)) to its label arc and
+// q * 1 / (1 + exp(bot - up)) to its blank arc -- differences of neighbouring alphas, exact to fp32 rounding whatever the loss (what
+// autograd through the reference's recurrence computes).  dynamic LDS: two diagonals of U1 + 1 floats.
+__global__ __launch_bounds__(256) void transducer_grad_kernel(const TransducerArgs p) {
     extern __shared__ float lds[];
     const int n = blockIdx.x, T = p.T, U1 = p.U1, K = p.K;
     float *dnext = lds, *dcur = lds + U1 + 1;
@@ -224,35 +231,50 @@ __global__ __launch_bounds__(256) void transducer_beta_grad_kernel(const Transdu
     const float logz = -p.losses[n], go = p.gout ? p.gout[n] : 1.f;
     for (long e = threadIdx.x; e < (long)T * U1 * K; e += blockDim.x) gn[e] = 0.f;
     if (!(logz > -1e30f && logz < INFINITY) || Tn < 1 || Tn > T || Un < 0 || Un >= U1) return;
-    for (int u = threadIdx.x; u <= U1; u += blockDim.x) dnext[u] = dcur[u] = -INFINITY;
+    for (int u = threadIdx.x; u <= U1; u += blockDim.x) dnext[u] = dcur[u] = 0.f;      // q past the lattice's last row / frame is 0
     __syncthreads();
     for (int d = Tn - 1 + Un; d >= 0; --d) {
         for (int u = threadIdx.x; u <= Un; u += blockDim.x) {
             const int t = d - u;
-            if (t < 0 || t >= Tn) { dcur[u] = -INFINITY; continue; }
+            if (t < 0 || t >= Tn) { dcur[u] = 0.f; continue; }
             const long cell = (long)t * U1 + u;
-            const float jb = jn[cell * K], a = an[cell];
-            float b;
+            float q;
             if (t == Tn - 1 && u == Un) {
-                b = jb;
+                q = go;
                 gn[cell * K] -= go;                                      // occupancy 1: every path ends with this blank
             } else {
-                const float via_blank = dnext[u] == -INFINITY ? -INFINITY : dnext[u] + jb;         // beta[t + 1, u]
-                b = via_blank;
-                if (via_blank != -INFINITY) gn[cell * K] -= go * expf(a + via_blank - logz);
-                if (u < Un) {
-                    const int64_t y = tg[u];
-                    const float jy = jn[cell * K + y];
-                    const float via_label = dnext[u + 1] == -INFINITY ? -INFINITY : dnext[u + 1] + jy;  // beta[t, u + 1]
-                    if (via_label != -INFINITY) {
-                        gn[cell * K + y] -= go * expf(a + via_label - logz);
-                        b = log_add_exp(b, via_label);
+                const float a = an[cell];
+                q = 0.f;
+                const float qb = dnext[u];                               // q[t + 1, u], entered by this cell's blank arc
+                if (qb != 0.f) {
+                    const float up = a + jn[cell * K];
+                    float w = 1.f;                                       // row 0 has no other way in
+                    if (u > 0) {
+                        const long below = cell + U1 - 1;                // (t + 1, u - 1)
+                        const float bot = an[below] + jn[below * K + tg[u - 1]];
+                        w = up == -INFINITY ? 0.f : 1.f / (1.f + expf(bot - up));
                     }
+                    const float c = qb * w;
+                    gn[cell * K] -= c;
+                    q += c;
+                }
+                const float ql = u < Un ? dnext[u + 1] : 0.f;            // q[t, u + 1], entered by this cell's label arc
+                if (ql != 0.f) {
+                    const int64_t y = tg[u];
+                    const float bot = a + jn[cell * K + y];
+                    float w = 1.f;                                       // frame 0 has no other way in
+                    if (t > 0) {
+                        const long left = cell - U1 + 1;                 // (t - 1, u + 1)
+                        const float up = an[left] + jn[left * K];
+                        w = bot == -INFINITY ? 0.f : 1.f / (1.f + expf(up - bot));
+                    }
+                    const float c = ql * w;
+                    gn[cell * K + y] -= c;                               // the same address as the blank's when y == 0
+                    q += c;
                 }
             }
-            dcur[u] = b;
+            dcur[u] = q;
         }
-        if (threadIdx.x == 0) dcur[Un + 1] = -INFINITY;
         __syncthreads();
         float *tmp = dnext; dnext = dcur; dcur = tmp;
     }
@@ -328,7 +350,7 @@ int halo_transducer_bwd(const float *joint, int N, int T, int U1, int K, const i
     TransducerArgs p;
     p.joint = joint; p.N = N; p.T = T; p.U1 = U1; p.K = K; p.targets = targets; p.j_len = joint_lengths; p.t_len = target_lengths;
     p.alpha = (float *)workspace; p.losses = (float *)losses; p.gout = grad_losses; p.grad = grad_joint;
-    hipLaunchKernelGGL(transducer_beta_grad_kernel, dim3(N), dim3(256), 2 * ((size_t)U1 + 1) * sizeof(float), (hipStream_t)stream, p);
+    hipLaunchKernelGGL(transducer_grad_kernel, dim3(N), dim3(256), 2 * ((size_t)U1 + 1) * sizeof(float), (hipStream_t)stream, p);
     return halo_launch_status();
 }
 

@@ -2,8 +2,8 @@
 HIP lattice kernels (csrc/lattice.hip).
 
 ``transducer_forward_score(joint, targets, joint_lengths, target_lengths)`` = ha/transducer.py:175-207: joint [N, T, U+1, K]
-log-probabilities ((f + g).log_softmax(-1)), symbol 0 blank, targets [N, U] -> losses [N]; differentiable w.r.t. ``joint`` (alpha-beta
-backward kernel where the reference uses autograd through its log-space scan).  ``transducer_forward_score4(joint, targets)``
+log-probabilities ((f + g).log_softmax(-1)), symbol 0 blank, targets [N, U] -> losses [N]; differentiable w.r.t. ``joint`` (a backward
+kernel that carries the cell posteriors through the local arc weights, where the reference uses autograd through its log-space scan).  ``transducer_forward_score4(joint, targets)``
 (:145-172) is the single-sequence form.  Any T: the reference pads its scan to 2 ** round(log2(T)) (:194) and raises when that is
 smaller than T; the recurrence it defines is computed here cell by cell along the anti-diagonals.  The probability-domain study
 versions (transducer_forward_score1-3, :10-142) are not built.

@@ -46,7 +46,7 @@ def star_ctc_forward_score(emissions, targets, emission_lengths, target_lengths,
         label:  i-3, i-1, i-2, and i-4 (the previous label) unless both labels are equal; NO self loop.
     Four virtual states before state 0 hold 0 at frame 0 (:93), so frame 1 can start in state 0 (from i-1) or state 3 (from i-4).
     The recursion runs over all T frames and all states; lengths only pick the read-out: frame emission_lengths, the last four states
-    of the first 4*target_lengths+3 (:153-162)."""
+    of the first 4*target_lengths+3 (:153-162); with target_lengths 0 those are the last virtual state and states 0, 1, 2."""
     T, N, C = emissions.shape
     S = targets.shape[1]
     em = star_emissions(emissions)
@@ -81,7 +81,8 @@ def star_ctc_forward_score(emissions, targets, emission_lengths, target_lengths,
     for n in range(N):
         t_last, s_last = int(emission_lengths[n]), 4 * int(target_lengths[n]) + 2
         a = alpha[t_last, n]
-        losses.append(-_lae(_lae(_lae(a[s_last], a[s_last - 1]), a[s_last - 2]), a[s_last - 3]))
+        first = a[s_last - 3] if s_last >= 3 else void    # an empty target: index -1 is the last virtual state, void after frame 0 (t_last >= 1)
+        losses.append(-_lae(_lae(_lae(a[s_last], a[s_last - 1]), a[s_last - 2]), first))
     losses = torch.stack(losses)
     return (losses, alpha) if return_alpha else losses
 
@@ -105,7 +106,7 @@ def star_ctc_grad(emissions, targets, emission_lengths, target_lengths, star_pen
         for k in range(1, S):
             same[4 * k + 3] = bool(targets[n, k] == targets[n, k - 1])
         beta = torch.full((S_,), float('-inf'), dtype=torch.float64)
-        beta[s_last - 3:s_last + 1] = 0.0
+        beta[max(s_last - 3, 0):s_last + 1] = 0.0                       # the virtual state of an empty target carries no gradient
         for t in range(Tn, 0, -1):
             occ = torch.exp(alpha[t, n] + beta - logz)               # posterior of being in state i at frame t
             g_star = torch.zeros(2 * C, dtype=torch.float64)

@@ -408,6 +408,7 @@ def test_product_side_synthetic_generators_match_the_oracle_side():
 
 # ---- star-CTC and transducer lattices (ha/star.py, ha/transducer.py): oracle/star_ref.py against the reference's own outputs ----
 STAR_CASES = ['random', 'repeat', 's1', 'nopenalty', 'padded']
+STAR_EDGE_CASES = ['empty_target', 'mixed']              # g8_star_edges.npz (make_golden_star_edges.py): rows with target_lengths == 0
 TRANSDUCER_CASES = ['batched', 'ragged', 'long']
 
 
@@ -416,10 +417,10 @@ def star_case_from_golden(g, name):
     return t('emissions'), t('targets'), t('il'), t('tl'), float(g[name + '.penalty'])
 
 
-@pytest.mark.parametrize('name', STAR_CASES + ['demo'])
+@pytest.mark.parametrize('name', STAR_CASES + ['demo'] + STAR_EDGE_CASES)
 def test_star_ctc_restatement_matches_reference(name):
     from oracle import star_ref
-    g = load_golden('g8_star')
+    g = load_golden('g8_star_edges' if name in STAR_EDGE_CASES else 'g8_star')
     em, tg, il, tl, pen = star_case_from_golden(g, name)
     losses = star_ref.star_ctc_forward_score(em, tg, il, tl, star_penalty=pen)
     np.testing.assert_allclose(losses.numpy(), g[name + '.losses'], rtol=2e-6, atol=1e-5)
