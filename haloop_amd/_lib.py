@@ -145,6 +145,8 @@ SIGNATURES = {
     'halo_ctc_head_train': (_i, [_vp, _vp, _vp, _f, _u64, _u32, _u32, _vp, _vp, _i, _i, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'halo_ctc_greedy': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'halo_stream_front': (_i, [_vp] * 16 + [_i] * 8 + [_vp]),
+    'halo_stream_head': (_i, [_vp] * 19 + [_i] * 6 + [_vp]),
     'halo_set_beam_vector_chunk': (_i, [_i]),
     'halo_logaddexp_aten': (_i, [_vp, _vp, _vp, _sz, _vp]),
     'halo_ctc_beam_workspace_bytes': (_sz, [_i] * 4),

@@ -881,6 +881,69 @@ def ctc_head_greedy(feats, weight, bias, want_lp=False):
     return (ali, scores, hyp, hyp_len, lp) if want_lp else (ali, scores, hyp, hyp_len)
 
 
+STREAM_ACTIVE, STREAM_BEGIN, STREAM_FINAL = 1, 2, 4        # per-stream flag bits of stream_front / stream_head (include/halo.h)
+
+
+def stream_front(frames, carry, length, flags, w, bias, y, n_steps, h, c, hyp, hyp_len, steps, score, last_label, truncated):
+    """The convolution of one streamed chunk (include/halo.h: halo_stream_front).  frames [B,Tc,F], carry [B,3,F] (updated in place),
+    length / flags [B] int32 on the device -> y [S,B,C] (S from ``y``) and n_steps [B] int32; beginning streams have their rows of the
+    state h / c [L,B,H], of hyp [B,capacity] int64 and of the hypothesis bookkeeping reset.  Every tensor is the caller's: nothing is
+    allocated."""
+    _f32c(frames, 'frames'); _f32c(carry, 'carry'); _f32c(w, 'subsample.weight'); _f32c(bias, 'subsample.bias'); _f32c(y, 'y')
+    _f32c(h, 'h'); _f32c(c, 'c')
+    B, Tc, F = frames.shape
+    S, Cc = y.shape[0], y.shape[2]
+    L, H = h.shape[0], h.shape[2]
+    if carry.shape != (B, 3, F) or y.shape[1] != B or w.shape != (Cc, F, 5) or h.shape[1] != B or c.shape != h.shape:
+        raise ValueError('stream_front: carry [B,3,F], y [S,B,C], weight [C,F,5] and h / c [L,B,H] do not fit frames [B,Tc,F]')
+    for t, dt, name in ((length, torch.int32, 'length'), (flags, torch.int32, 'flags'), (n_steps, torch.int32, 'n_steps'),
+                        (hyp_len, torch.int64, 'hyp_len'), (steps, torch.int64, 'steps'), (score, torch.float32, 'score'),
+                        (last_label, torch.int32, 'last_label'), (truncated, torch.bool, 'truncated')):
+        if t.dtype != dt or t.numel() != B or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f'stream_front: {name} must be a contiguous {dt} HIP tensor of {B} elements')
+    if hyp.dtype != torch.int64 or hyp.dim() != 2 or hyp.shape[0] != B or not hyp.is_cuda or not hyp.is_contiguous():
+        raise ValueError(f'stream_front: hyp must be a contiguous int64 HIP tensor [{B}, capacity]')
+    check(lib().halo_stream_front(ptr(frames), ptr(carry), ptr(length), ptr(flags), ptr(w), ptr(bias), ptr(y), ptr(n_steps), ptr(h), ptr(c),
+                                  ptr(hyp), ptr(hyp_len), ptr(steps), ptr(score), ptr(last_label), ptr(truncated), B, Tc, F, Cc, S, L, H,
+                                  hyp.shape[1], _stream()), 'halo_stream_front')
+    return y, n_steps
+
+
+def stream_head_fused(S, H, V):
+    """Whether ``stream_head`` runs the classifier product itself at this shape (else the caller hands it log-probs)."""
+    return ctc_head_supported(S, H, V, 0) and _lib.get_math_mode() != 'f32'
+
+
+def stream_head(feats, weight, bias, n_steps, flags, hn, cn, h, c, ali, step_scores, hyp, hyp_len, steps, score, last_label, truncated,
+                lp_out=None):
+    """The CTC head of one streamed chunk (include/halo.h: halo_stream_head): feats [B,S,H] -> classifier, log-softmax, best class per
+    step, the collapse continued across calls, and the commit of hn / cn into h / c for the streams that go on.  Where the fused product
+    does not apply (``stream_head_fused``) the log-probs come from ``gemm`` + ``log_softmax_fwd`` and the kernel runs collapse-only.
+    ``lp_out`` [B,S,V]: receives the log-probs."""
+    _f32c(feats, 'features')
+    B, S, H = feats.shape
+    V = weight.shape[0]
+    if not stream_head_fused(S, H, V):
+        logits = gemm(feats.view(B * S, H), weight, True, True, B * S, V, H, bias1=bias)
+        lp = log_softmax_fwd(logits).view(B, S, V)
+        if lp_out is not None:
+            lp_out.copy_(lp)
+        stream_collapse(lp, n_steps, flags, hn, cn, h, c, ali, step_scores, hyp, hyp_len, steps, score, last_label, truncated)
+        return
+    check(lib().halo_stream_head(ptr(feats), ptr(weight), ptr(bias), None, ptr(lp_out), ptr(n_steps), ptr(flags), ptr(hn), ptr(cn),
+                                 ptr(h), ptr(c), ptr(ali), ptr(step_scores), ptr(hyp), ptr(hyp_len), ptr(steps), ptr(score),
+                                 ptr(last_label), ptr(truncated), B, S, H, V, h.shape[0], hyp.shape[1], _stream()), 'halo_stream_head')
+
+
+def stream_collapse(lp, n_steps, flags, hn, cn, h, c, ali, step_scores, hyp, hyp_len, steps, score, last_label, truncated):
+    """``stream_head``'s collapse-only mode on log-probs [B,S,V] the caller holds (any V)."""
+    _f32c(lp, 'log-probs')
+    B, S, V = lp.shape
+    check(lib().halo_stream_head(None, None, None, ptr(lp), None, ptr(n_steps), ptr(flags), ptr(hn), ptr(cn), ptr(h), ptr(c), ptr(ali),
+                                 ptr(step_scores), ptr(hyp), ptr(hyp_len), ptr(steps), ptr(score), ptr(last_label), ptr(truncated),
+                                 B, S, h.shape[2], V, h.shape[0], hyp.shape[1], _stream()), 'halo_stream_head')
+
+
 def ctc_beam(em, beam, log_domain=True):
     """em [N,T,V] -> (seqs [N,beam,T] int64, lens [N,beam] int32, scores [N,beam])."""
     _f32c(em, 'emissions')

@@ -1,0 +1,305 @@
+"""Streaming LSTM-CTC recognition: audio pushed chunk by chunk, a partial transcript after every chunk.
+
+``rnn.Encoder`` is a stride-4 convolution (kernel 5, padding 3) under a unidirectional LSTM, so a step depends on one frame of
+look-ahead and on nothing later: the whole-utterance forward can be cut into chunks that carry a small state.  The reference has no
+streaming mode; what it computes on the whole utterance (``infer.LstmCtcRecognizer``) defines the result, and the concatenated steps
+of a stream are the steps of the whole-utterance forward of the same frames.
+
+Frame arithmetic (what makes the state small).  Step s of the convolution reads the padded frames 4s .. 4s+4, that is the frames
+4s-3 .. 4s+1 of the utterance.  A push takes a multiple of 4 frames, so after any number of pushes a stream has consumed 4m frames
+and emitted the steps 0 .. m-1, whose last one read up to frame 4m-3; step m needs the frames 4m-3 .. 4m+1: the last 3 consumed
+frames -- the carry -- and the next two.  At ``begin`` the carry is 3 zero frames, the convolution's left padding.
+
+    call                             convolution input             steps emitted
+    push                             [carry | chunk], no padding   chunk_frames / 4
+    finish with tail length tl       [carry | tail | 3 zeros]      floor((tl + 1) / 4) + 1
+
+Over a stream of T = 4m + tl frames the steps add up to m + floor((tl + 1) / 4) + 1 = floor((T + 1) / 4) + 1, which is
+``Encoder.subsampled_lengths(T)``.  Per stream the state is the carry [3, F], the LSTM's (h, c) [L, H], the label of the last step
+(the greedy collapse merges a repeat across a call boundary), the hypothesis so far with its length and score.
+
+A call is one short, static chain of launches for all ``max_streams`` slots: ``halo_stream_front`` (convolution, carry, resets),
+``ops.lstm_fwd`` with the persistent state as h0 / c0, ``halo_stream_head`` (classifier, log-softmax, collapse, state commit); rows
+that did not take part (``active`` False) are left bit-identical.  ``HALO_STREAM_FUSED=0`` runs the same computation on the general
+operators (``ops.subsample_fwd`` on the concatenated input, ``ops.gemm``, ``ops.log_softmax_fwd``, ``ops.ctc_greedy`` and torch
+operators for the merging), which is the comparator of tools/bench_streaming.py.  ``HALO_STREAM_GRAPH=1`` (or ``use_graph=True``)
+replays the push chain from one HIP graph.
+"""
+import os
+
+import torch
+
+from . import _lib, ops
+from .ops import NO_DROPOUT, STREAM_ACTIVE, STREAM_BEGIN, STREAM_FINAL
+from .rnn import lstm_param_list
+
+_NEVER, _OPEN, _CLOSED = 0, 1, 2
+_RING = 16          # pinned host slots for the per-call flags: a slot is rewritten only after the copy that read it has run
+
+
+class StreamingRecognizer:
+    """``max_streams`` slots of streaming greedy CTC recognition over ``encoder`` (an ``rnn.Encoder``) and ``recognizer`` (a
+    ``recognizer.TemporalClassifier``), both in eval mode.  Every buffer is allocated here, once.
+
+    push(frames [B, chunk_frames, F], active, begin): ``chunk_frames`` more frames for every active slot; ``begin`` starts a new
+        stream in a slot (allowed on an open slot too: it abandons that stream).  ``active`` / ``begin`` are host-side sequences of B
+        bools (or CPU bool tensors); ``active`` defaults to all slots, ``begin`` to none.
+    finish(tail [B, <= chunk_frames - 1, F], tail_lengths, rows): the last frames of the slots in ``rows`` (B host-side bools like
+        ``active``; default every open slot) and the convolution's right padding; the slots are closed and need ``begin`` again.
+    partial(): copies of (hyp [B, capacity] int64, hyp_len [B] int64, scores [B] fp32, steps [B] int64, truncated [B] bool).
+    last: (alignments [B, S] int64, step_scores [B, S] fp32, n_steps [B] int32[, log_probs [B, S, V]]) of the latest call, S =
+        chunk_frames / 4 for a push and one more for a finish; alignments and step_scores are zeros past a row's n_steps (log_probs
+        there mean nothing).  These are the recognizer's own buffers: the next call of the same kind overwrites them.
+
+    Neither call reads from the device or waits for it (the flags travel through a ring of pinned host slots; a slot is waited for
+    only if the device is a whole ring of calls behind).  ``use_graph``: None reads HALO_STREAM_GRAPH (default off)."""
+
+    def __init__(self, encoder, recognizer, max_streams, chunk_frames=16, capacity=256, use_graph=None):
+        if encoder.training or recognizer.training:
+            raise ValueError('StreamingRecognizer: put the encoder and the recognizer in eval mode')
+        conv = encoder.subsample
+        if (conv.kernel_size[0], conv.stride[0], conv.padding[0]) != (5, 4, 3) or conv.dilation[0] != 1 or conv.groups != 1:
+            raise NotImplementedError('StreamingRecognizer: only the subsample geometry kernel 5, stride 4, padding 3 is streamed')
+        if chunk_frames % 4 != 0 or not 4 <= chunk_frames <= 124:
+            raise ValueError(f'StreamingRecognizer: chunk_frames {chunk_frames} must be a multiple of 4 in 4 .. 124')
+        if max_streams < 1 or capacity < 1:
+            raise ValueError('StreamingRecognizer: max_streams and capacity must be positive')
+        self.encoder, self.recognizer = encoder, recognizer
+        self.max_streams, self.chunk_frames, self.capacity = int(max_streams), int(chunk_frames), int(capacity)
+        if use_graph is None:
+            use_graph = os.environ.get('HALO_STREAM_GRAPH', '0') == '1'
+        self.use_graph = bool(use_graph)
+        self.fused = os.environ.get('HALO_STREAM_FUSED', '1') != '0'
+        dev = conv.weight.device
+        if dev.type != 'cuda':
+            raise _lib.HaloError('haloop_amd.streaming.StreamingRecognizer runs on the HIP device only (no CPU path)')
+        _lib.lend_scratch(device=dev)
+        B, Tc, S = self.max_streams, self.chunk_frames, self.chunk_frames // 4
+        F, C = conv.in_channels, conv.out_channels
+        L, H, V = encoder.lstm.num_layers, encoder.lstm.hidden_size, recognizer.classifier.out_features
+        self._dims = (B, Tc, S, F, C, L, H, V)
+        f32 = dict(device=dev, dtype=torch.float32)
+        self._carry = torch.zeros(B, 3, F, **f32)
+        self._h, self._c = torch.zeros(L, B, H, **f32), torch.zeros(L, B, H, **f32)
+        self._hyp = torch.zeros(B, self.capacity, device=dev, dtype=torch.int64)
+        self._hyp_len = torch.zeros(B, device=dev, dtype=torch.int64)
+        self._steps = torch.zeros(B, device=dev, dtype=torch.int64)
+        self._score = torch.zeros(B, **f32)
+        self._last_label = torch.full((B,), -1, device=dev, dtype=torch.int32)
+        self._truncated = torch.zeros(B, device=dev, dtype=torch.bool)
+        self._n_steps = torch.zeros(B, device=dev, dtype=torch.int32)
+        self._meta = torch.zeros(2, B, device=dev, dtype=torch.int32)            # [0] flags, [1] lengths
+        self._pin = torch.zeros(_RING, 2, B, dtype=torch.int32).pin_memory()
+        self._pin_np = self._pin.numpy()
+        self._pin_events = [None] * _RING
+        self._pin_next = 0
+        self._frames = torch.zeros(B, Tc, F, **f32)                              # the graph's input; the frames of a finish without a tail
+        self._bufs = {}
+        for s in (S, S + 1):                                                     # a push's launch shape and a finish's
+            self._bufs[s] = dict(
+                y=torch.zeros(s, B, C, **f32), feats=torch.zeros(B, s, H, **f32), ali=torch.zeros(B, s, device=dev, dtype=torch.int64),
+                scores=torch.zeros(B, s, **f32), lp=torch.zeros(B, s, V, **f32), reserve=ops.lstm_reserve(s, B, C, H, L, dev))
+        self._state = [_NEVER] * B
+        self._graphs = {}
+        self._last = None
+
+    # ---------------------------------------------------------------------------------------------------------------- host side
+    def _bools(self, v, default, name):
+        B = self.max_streams
+        if v is None:
+            return [default] * B
+        if torch.is_tensor(v):
+            if v.is_cuda:
+                raise ValueError(f'StreamingRecognizer: {name} is host-side (a sequence of bools or a CPU bool tensor)')
+            v = v.tolist()
+        v = [bool(e) for e in v]
+        if len(v) != B:
+            raise ValueError(f'StreamingRecognizer: {name} has {len(v)} entries for {B} slots')
+        return v
+
+    def _stamp(self):
+        """Changes whenever an LSTM weight may have changed (as ``infer.LstmCtcRecognizer._stamp``)."""
+        key = (_lib.weights_epoch(),) + tuple((p.data_ptr(), p._version) for p in lstm_param_list(self.encoder.lstm))
+        return (hash(key) & 0x7fffffffffffffff) | 1
+
+    def _check_modes(self):
+        if self.encoder.training or self.recognizer.training:
+            raise ValueError('StreamingRecognizer: put the encoder and the recognizer in eval mode')
+
+    def _send_meta(self, flags, lengths):
+        """The call's flags and lengths -> the static device buffer, by an asynchronous copy from a pinned host slot."""
+        i = self._pin_next
+        self._pin_next = (i + 1) % _RING
+        if self._pin_events[i] is not None:
+            self._pin_events[i].synchronize()             # returns at once unless the device is _RING calls behind
+        else:
+            self._pin_events[i] = torch.cuda.Event()
+        self._pin_np[i, 0, :] = flags
+        self._pin_np[i, 1, :] = lengths
+        self._meta.copy_(self._pin[i], non_blocking=True)
+        self._pin_events[i].record()
+
+    @torch.no_grad()
+    def push(self, frames, active=None, begin=None, want_log_probs=False):
+        self._check_modes()
+        B, Tc, S, F = self._dims[:4]
+        if not torch.is_tensor(frames) or frames.shape != (B, Tc, F) or frames.dtype != torch.float32 or not frames.is_cuda:
+            raise ValueError(f'StreamingRecognizer.push: frames must be a float32 HIP tensor [{B}, {Tc}, {F}]')
+        active, begin = self._bools(active, True, 'active'), self._bools(begin, False, 'begin')
+        flags = [0] * B
+        for b in range(B):
+            if begin[b] and not active[b]:
+                raise ValueError(f'StreamingRecognizer.push: slot {b} begins without being active')
+            if active[b] and not begin[b] and self._state[b] != _OPEN:
+                raise ValueError(f'StreamingRecognizer.push: slot {b} is closed; pass begin to start a stream in it')
+            flags[b] = (STREAM_ACTIVE if active[b] else 0) | (STREAM_BEGIN if begin[b] else 0)
+        for b in range(B):
+            if begin[b]:
+                self._state[b] = _OPEN
+        self._call(frames.contiguous(), S, False, want_log_probs, flags, [Tc if a else 0 for a in active])
+
+    @torch.no_grad()
+    def finish(self, tail=None, tail_lengths=None, rows=None, want_log_probs=False):
+        self._check_modes()
+        B, Tc, S, F = self._dims[:4]
+        rows = [s == _OPEN for s in self._state] if rows is None else self._bools(rows, False, 'rows')
+        for b in range(B):
+            if rows[b] and self._state[b] != _OPEN:
+                raise ValueError(f'StreamingRecognizer.finish: slot {b} ' +
+                                 ('was never begun' if self._state[b] == _NEVER else 'is closed already'))
+        if tail is None:
+            if tail_lengths is not None and any(int(t) != 0 for t in tail_lengths):
+                raise ValueError('StreamingRecognizer.finish: tail_lengths without a tail')
+            tail, lengths = self._frames, [0] * B
+        else:
+            if not torch.is_tensor(tail) or tail.dim() != 3 or tail.shape[0] != B or tail.shape[2] != F or tail.shape[1] > Tc - 1 \
+                    or tail.dtype != torch.float32 or not tail.is_cuda:
+                raise ValueError(f'StreamingRecognizer.finish: tail must be a float32 HIP tensor [{B}, <= {Tc - 1}, {F}]')
+            if tail_lengths is None:
+                lengths = [tail.shape[1]] * B
+            else:
+                lengths = [int(t) for t in (tail_lengths.tolist() if torch.is_tensor(tail_lengths) else tail_lengths)]
+                if len(lengths) != B or any(not 0 <= t <= tail.shape[1] for b, t in enumerate(lengths) if rows[b]):
+                    raise ValueError('StreamingRecognizer.finish: tail_lengths must give 0 .. tail.shape[1] frames for every closing slot')
+            if tail.shape[1] == 0:
+                tail = self._frames
+        for b in range(B):
+            if rows[b]:
+                self._state[b] = _CLOSED
+        self._call(tail.contiguous(), S + 1, True, want_log_probs,
+                   [(STREAM_ACTIVE | STREAM_FINAL) if r else 0 for r in rows], [t if r else 0 for r, t in zip(rows, lengths)])
+
+    def partial(self):
+        return (self._hyp.clone(), self._hyp_len.clone(), self._score.clone(), self._steps.clone(), self._truncated.clone())
+
+    @property
+    def last(self):
+        return self._last
+
+    # -------------------------------------------------------------------------------------------------------------- device side
+    def _call(self, frames, S, final, want_lp, flags, lengths):
+        buf = self._bufs[S]
+        graph = None
+        if self.fused and self.use_graph and not final:
+            key = (bool(want_lp), _lib.get_math_mode(), self._stamp())
+            graph = self._graphs.get(key)
+            if graph is None:
+                graph = self._capture(S, want_lp, buf)
+                self._graphs = {key: graph}              # (one at a time: a changed weight or mode captures again)
+        self._send_meta(flags, lengths)
+        if not self.fused:
+            self._chain_general(frames, S, final, buf)
+        elif graph is not None:
+            if frames.data_ptr() != self._frames.data_ptr():
+                self._frames.copy_(frames)
+            graph.replay()
+        else:
+            self._chain(frames, S, want_lp, buf)
+        self._last = (buf['ali'], buf['scores'], self._n_steps) + ((buf['lp'],) if want_lp or not self.fused else ())
+
+    def _capture(self, S, want_lp, buf):
+        """The push chain as one HIP graph.  The warm-up run and the capture see every slot inactive, so they change no stream."""
+        self._meta.zero_()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._chain(self._frames, S, want_lp, buf)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._chain(self._frames, S, want_lp, buf)
+        return graph
+
+    def _lstm(self, y, S, buf):
+        B, H = self.max_streams, self._dims[6]
+        p = lstm_param_list(self.encoder.lstm)
+        _, hn, cn, _ = ops.lstm_fwd(y, p[0::4], p[1::4], p[2::4], p[3::4], h0=self._h, c0=self._c, y=buf['feats'], y_strides=(H, S * H),
+                                    y_relu=True, want_state=True, expect_backward=False, reserve=buf['reserve'],
+                                    weights_stamp=self._stamp())
+        return hn, cn
+
+    def _chain(self, frames, S, want_lp, buf):
+        conv, cls = self.encoder.subsample, self.recognizer.classifier
+        flags, length = self._meta[0], self._meta[1]
+        ops.stream_front(frames, self._carry, length, flags, conv.weight, conv.bias, buf['y'], self._n_steps, self._h, self._c,
+                         self._hyp, self._hyp_len, self._steps, self._score, self._last_label, self._truncated)
+        hn, cn = self._lstm(buf['y'], S, buf)
+        ops.stream_head(buf['feats'], cls.weight, cls.bias, self._n_steps, flags, hn, cn, self._h, self._c, buf['ali'], buf['scores'],
+                        self._hyp, self._hyp_len, self._steps, self._score, self._last_label, self._truncated,
+                        lp_out=buf['lp'] if want_lp else None)
+
+    def _chain_general(self, frames, S, final, buf):
+        """The same call on the general operators; the merging of the collapse and the choice of the state by torch operators."""
+        conv, cls = self.encoder.subsample, self.recognizer.classifier
+        B, _, _, F, C, L, H, V = self._dims
+        dev = frames.device
+        flags, length = self._meta[0], self._meta[1]
+        act, beg, fin = (flags & STREAM_ACTIVE) != 0, (flags & STREAM_BEGIN) != 0, (flags & STREAM_FINAL) != 0
+        self._h.masked_fill_(beg[None, :, None], 0.0)
+        self._c.masked_fill_(beg[None, :, None], 0.0)
+        self._hyp.masked_fill_(beg[:, None], 0)
+        self._hyp_len.masked_fill_(beg, 0)
+        self._steps.masked_fill_(beg, 0)
+        self._score.masked_fill_(beg, 0.0)
+        self._last_label.masked_fill_(beg, -1)
+        self._truncated.masked_fill_(beg, False)
+        Tc = frames.shape[1]
+        carry = self._carry.masked_fill(beg[:, None, None], 0.0)
+        fr = frames.masked_fill((torch.arange(Tc, device=dev)[None, :] >= length[:, None])[:, :, None], 0.0)
+        parts = [carry, fr]
+        if 4 * S + 1 > 3 + Tc:
+            parts.append(torch.zeros(B, 4 * S + 1 - 3 - Tc, F, device=dev, dtype=torch.float32))
+        y, _ = ops.subsample_fwd(torch.cat(parts, dim=1), conv.weight, conv.bias, NO_DROPOUT, pad=0)
+        n = torch.where(fin, (length + 1) // 4 + 1, length // 4)
+        n = torch.where(act, n, torch.zeros_like(n)).clamp(max=S).to(torch.int32)
+        live = torch.arange(S, device=dev)[None, :] < n[:, None]                                  # [B, S]
+        y = y.masked_fill(~live.t()[:, :, None], 0.0).contiguous()
+        if not final:
+            go = act & ~fin
+            self._carry.copy_(torch.where(go[:, None, None], frames[:, Tc - 3:], self._carry))
+        hn, cn = self._lstm(y, S, buf)
+        feats = buf['feats']
+        logits = ops.gemm(feats.view(B * S, H), cls.weight, True, True, B * S, V, H, bias1=cls.bias)
+        lp = ops.log_softmax_fwd(logits).view(B, S, V)
+        ali, scores, _, _ = ops.ctc_greedy(lp)
+        prev = torch.cat([self._last_label[:, None].to(torch.int64), ali[:, :-1]], dim=1)
+        keep = (ali != prev) & (ali != 0) & live
+        pos = self._hyp_len[:, None] + keep.cumsum(1) - 1
+        fits = keep & (pos < self.capacity)
+        ext = torch.cat([self._hyp, self._hyp.new_zeros(B, 1)], dim=1)                          # a spare column takes what is not kept
+        ext.scatter_(1, torch.where(fits, pos, torch.full_like(pos, self.capacity)), ali)
+        self._hyp.copy_(ext[:, :self.capacity])
+        self._truncated.logical_or_((keep & ~fits).any(1))
+        self._hyp_len.copy_((self._hyp_len + keep.sum(1)).clamp(max=self.capacity))
+        last = ali.gather(1, (n.to(torch.int64) - 1).clamp(min=0)[:, None])[:, 0].to(torch.int32)
+        self._last_label.copy_(torch.where(n > 0, last, self._last_label))
+        for s in range(S):                                                                      # in step order
+            self._score.add_(torch.where(live[:, s], scores[:, s], torch.zeros_like(self._score)))
+        self._steps.add_(n.to(torch.int64))
+        go = (act & ~fin)[None, :, None]
+        self._h.copy_(torch.where(go, hn, self._h))
+        self._c.copy_(torch.where(go, cn, self._c))
+        self._n_steps.copy_(n)
+        buf['ali'].copy_(ali.masked_fill(~live, 0))
+        buf['scores'].copy_(scores.masked_fill(~live, 0.0))
+        buf['lp'].copy_(lp.masked_fill(~live[:, :, None], 0.0))

@@ -616,6 +616,34 @@ int halo_ctc_greedy(const float *lp, int N, int T, int C, int64_t *alignments, f
                     int64_t *hyp, int64_t *hyp_len, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Streaming LSTM-CTC recognition (haloop_amd/streaming.py; the reference recognises whole utterances only): the two launches around
+ * halo_lstm_fwd of one chunk of B streams.  Per-stream flags: bit 0 active, bit 1 begin, bit 2 final.  A stream that is not active is
+ * left bit-identical by both launches.  fp32, no atomics, one workgroup per stream.
+ *
+ * halo_stream_front: the reference's subsample (kernel 5, stride 4, padding 3) over [carry | length[b] frames | zeros] with ReLU ->
+ *   y [S,B,C] time-major (steps at or past n_steps[b], and every step of an inactive stream, are zeros);
+ *   n_steps[b] = length/4, or floor((length + 1)/4) + 1 for a final stream (the right padding), 0 for an inactive one;
+ *   carry [B,3,F] of an active stream that goes on <- its last 3 frames.  A beginning stream reads its carry as zeros (the left
+ *   padding), and its rows of h / c [L,B,H], hyp [B,capacity], hyp_len, steps, score, last_label (-1) and truncated are reset.
+ *   frames [B,Tc,F], weight [C,F,5], bias [C].  S <= 64.
+ * halo_stream_head: per stream the first n_steps[b] steps of feats [B,S,H] -> Linear(H -> V) -> log_softmax -> first maximum per step
+ *   (alignments, step_scores [B,S]; zeros past n_steps) -> the greedy collapse continued from last_label[b] (a label equal to the
+ *   previous step's emits nothing, across calls too; blank = 0 emits nothing): tokens appended at hyp[b][hyp_len[b]] (row length
+ *   `capacity`; a token that does not fit is dropped and sets truncated[b]), score[b] += the step scores in step order, steps[b] +=
+ *   n_steps[b]; lp_out (optional) [B,S,V] receives the log-probs.  The rows of hn / cn [L,B,H] of active streams that are not final are
+ *   copied into h / c.  The fused product needs halo_ctc_head_supported(S, H, V, 0) and a math mode other than HALO_MATH_F32
+ *   (HALO_ENOTSUP otherwise).  Collapse-only mode: feats == NULL and lp_in [B,S,V] holds log-probs the caller computed (any V).
+ * ------------------------------------------------------------------------------------------ */
+int halo_stream_front(const float *frames, float *carry, const int *length, const int *flags, const float *weight, const float *bias,
+                      float *y, int *n_steps, float *h, float *c, int64_t *hyp, int64_t *hyp_len, int64_t *steps, float *score,
+                      int *last_label, unsigned char *truncated, int B, int Tc, int F, int C, int S, int L, int H, int capacity,
+                      halo_stream_t stream);
+int halo_stream_head(const float *feats, const float *weight, const float *bias, const float *lp_in, float *lp_out, const int *n_steps,
+                     const int *flags, const float *hn, const float *cn, float *h, float *c, int64_t *alignments, float *step_scores,
+                     int64_t *hyp, int64_t *hyp_len, int64_t *steps, float *score, int *last_label, unsigned char *truncated, int B,
+                     int S, int H, int V, int L, int capacity, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * 80-mel log filterbank front-end on the device (ha/data.py:136-140: torchaudio.compliance.kaldi.fbank(wav, num_mel_bins=80) with that
  * function's defaults; haloop_amd/fbank.py chains these with two halo_gemm_f32 products -- the real DFT and the mel filters).
  *   halo_fbank_frames  waveform [n_samples] -> frames [n_frames][padded]: frame f = samples [f*shift, f*shift + frame_len) (snip edges),
