@@ -112,6 +112,13 @@ __device__ __forceinline__ void mma_chunk3(const Frag3 (&f)[CHUNK3], f32x4 &acc0
     acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[1].ah, f[1].wh, acc1, 0, 0, 0);
 }
 
+// The exit of a rolled k-block loop whose last instruction is an MFMA: the compiler's hazard pass pads the straight-line path from an MFMA to
+// the first VALU read of its result with s_nop, but it left the exit of the single-pass loop below (mfma, s_cbranch, s_cbranch, s_branch,
+// v_accvgpr_read of the accumulator's LAST register: three wait states) unpadded, and that read then races the matrix pipe: batch rows
+// 4q + 3 of the step backward's recurrent sum came out short of their last k-block in some runs (tests/test_gpu_lstm_f64.py, bf16 mode,
+// H = 96 and 160).  The wait states are spelled out here, tied to the accumulator so that nothing moves across them.
+__device__ __forceinline__ void mfma_settle(f32x4 &acc) { asm volatile("s_nop 7\n\ts_nop 3" : "+a"(acc)); }
+
 // sum over k-blocks [0, nblk) of A-block x B-block; ap/bp point at this lane's 16 bytes of block 0
 template <bool X3, bool ONE = false>
 __device__ __forceinline__ f32x4 packed_dot(const char *ap, const char *bp, int nblk) {
@@ -137,6 +144,7 @@ __device__ __forceinline__ f32x4 packed_dot(const char *ap, const char *bp, int 
                 }
                 acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wh, acc0, 0, 0, 0);
             }
+            mfma_settle(acc0);
         }
     } else {
         if (nblk % (2 * CHUNK) == 0) {
@@ -157,6 +165,7 @@ __device__ __forceinline__ f32x4 packed_dot(const char *ap, const char *bp, int 
 #pragma unroll
                 for (int m = 0; m < 4; ++m) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], w[m], acc0, 0, 0, 0);
             }
+            mfma_settle(acc0);
         }
     }
     return acc0 + acc1;
