@@ -1,27 +1,26 @@
 // CTC prefix beam search with shallow fusion of an LSTM language model (haloop_amd/fusion.py CTCFusionDecoder): one frame
-// of every row per launch, one workgroup per row.  The search is csrc/ctc_prefix_beam.hip's (stays, extensions, the exact merge, W rounds
-// of a workgroup-wide arg-max in the order (ranking value descending, candidate position ascending)); a member carries besides its CTC
-// masses pb / pnb the LM's log-probability lm of its prefix, and slot n W + j holds the LM's logits g and LSTM state after that prefix, as
-// the slots of csrc/rnnt_beam.hip do.  Per frame t < L
-//   1. wave w: the log-sum-exp over V of g[slot j] + g_bias for members j = w, w + 4, ... (the lane's stride, then the wave's butterfly),
-//      so lp_j[k] = (g_j[k] + bias[k]) - lse_j
-//   2. totals, stay candidates, the hash shortlist and the merge by token comparison (CTC mass only: the stay keeps its own lm)
+// of every row per launch, one workgroup per row.  The search is csrc/ctc_prefix_beam.hip's on the pieces of beam_common.h; a member
+// carries besides its CTC masses pb / pnb the LM's log-probability lm of its prefix, and slot n W + j holds the LM's logits g and LSTM
+// state after that prefix.  Per frame t < L
+//   1. wave w: the log-sum-exp over V of g[slot j] + g_bias for members j = w, w + 4, ..., so lp_j[k] = (g_j[k] + bias[k]) - lse_j
+//   2. totals, stay candidates and the merge (CTC mass only: the stay keeps its own lm)
 //   3. the W best: an extension of j by k ranks at fma(a, lm_j + lp_j[k], e[t, k] + (pb_j if k == last_j else total_j)) + b (len_j + 1),
 //      a stay at fma(a, lm_j, logaddexp(pb', pnb')) + b len_j; candidates whose CTC mass is -inf are never taken.  A thread owns the
-//      extensions by its classes and keeps its first across the rounds; no list of W V candidates is built.
+//      extensions by its classes and keeps its first across the rounds.
 //   4. the new beam's records, tokens, parent and last (0: a stay) into the other copy
-//   5. the gather of rnnt_beam_step_kernel: [wte[last] | h of the parent] per layer and c of the parent, for the cell launches
+//   5. the gather of the LSTM state for the cell launches
 // A row with t >= L passes its beam through (parent = own index, last = 0) and loads no emission.  The launches that follow (one
 // halo_rnnt_lstm_cell per layer, halo_decode_linear, halo_rnnt_beam_keep) are csrc/rnnt_beam.hip's, unchanged.
 // LDS: the frame's V emissions and, when (W + 1) V <= LDS_FLOATS, the row's W V LM logits (56 KiB of dynamic LDS at most; otherwise the
-// logits are recomputed from L2 by the same operations, the same bits), besides W-sized records (< 2 KiB static): under the 64 KiB a launch
-// gets without the opt-in.  fp32, no float atomics (one integer atomicOr in LDS collects the shortlist), every sum in a fixed order.
+// logits are recomputed from L2), besides W-sized records (< 2 KiB static): under the 64 KiB a launch gets without the opt-in.
 #include "halo_common.h"
 #include "halo_internal.h"
+#include "beam_common.h"
 
 namespace {
 
-constexpr int BEAM_MAX = 16, BEAM_THREADS = 256, BEAM_WAVES = BEAM_THREADS / 64;
+using namespace beam;
+
 constexpr int LDS_FLOATS = 14336;          // 56 KiB of dynamic LDS: the frame's emissions (V <= 8192) and, when they fit too, W V logits
 
 struct CtcLmBeamArgs {
@@ -39,20 +38,9 @@ struct CtcLmBeamArgs {
     int *meta_out, *tok_out;
     long tok_ld;
     int *parent, *last;        // [N][W] of the new beam
-    const float *wte;          // [V][H] the embedding
-    int H, layers;
-    const float *h_in, *c_in;  // [layers][N * W][H] this frame's state
-    float *xh, *c_out;         // [layers][N * W][2 H] = x | h_prev of the cells; [layers][N * W][H] the next state's c, before the cells
+    StateGather state;         // this frame's state -> the cells' inputs
     int cached;                // the row's W V logits are kept in LDS, else recomputed from L2
 };
-
-__device__ __forceinline__ float logaddexpf_(float a, float b) {
-    const float m = fmaxf(a, b);
-    return m == -INFINITY ? m : m + log1pf(expf(-fabsf(a - b)));
-}
-
-// (sc, pos) stands before (osc, opos) in the order (ranking value descending, position ascending)
-__device__ __forceinline__ bool before(float sc, int pos, float osc, int opos) { return sc > osc || (sc == osc && pos < opos); }
 
 __global__ __launch_bounds__(BEAM_THREADS) void ctc_lm_beam_step_kernel(const CtcLmBeamArgs p) {
     // the beam read: masses, LM score, length, last token, hashes; the frame: lse, totals, the stay candidates' masses and rank, the
@@ -63,8 +51,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_lm_beam_step_kernel(const Ct
     __shared__ int s_len[BEAM_MAX], s_ltok[BEAM_MAX], s_short[BEAM_MAX], s_mj[BEAM_MAX], s_nm[BEAM_MAX], sel_pos[BEAM_MAX], s_src[BEAM_MAX],
         s_k[BEAM_MAX];
     __shared__ unsigned s_hash[BEAM_MAX], s_hprev[BEAM_MAX];
-    __shared__ float r_sc[2][BEAM_WAVES];
-    __shared__ int r_pos[2][BEAM_WAVES];
+    __shared__ FirstScratch s_first;
     extern __shared__ float dyn[];                                     // e[V] | cached: z[j][v] = g_j[v] + bias[v]
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = p.W, V = p.V, cap = p.cap;
     const long base = (long)n * W;
@@ -77,7 +64,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_lm_beam_step_kernel(const Ct
         unsigned hash = 0u, hprev = 0u;
         if (tid < W) {
             if (p.t == 0) {                                            // the empty prefix: every alignment of no frames ends "in blank"
-                if (tid == 0) { pb = 0.f; lm = 0.f; sc = 0.f; len = 0; hash = 0x811C9DC5u; }
+                if (tid == 0) { pb = 0.f; lm = 0.f; sc = 0.f; len = 0; hash = HASH_EMPTY; }
             } else {
                 const float *rf = p.rec_in + (base + tid) * 4;
                 const int *ri = p.meta_in + (base + tid) * 4;
@@ -109,19 +96,9 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_lm_beam_step_kernel(const Ct
     };
 
     if (active) {
-        // ---- 1. wave w: log-sum-exp of members w, w + 4, ... (fixed order: the lane's stride, then the wave's butterfly)
+        // ---- 1. wave w: log-sum-exp of members w, w + 4, ...
         for (int j = wave; j < nb; j += BEAM_WAVES) {
-            float m = -INFINITY;
-            for (int v = lane; v < V; v += 64) {
-                const float x = logit(j, v);
-                if (p.cached) zs[j * V + v] = x;                       // (read back by this lane below, by the others after the barrier)
-                m = fmaxf(m, x);
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-            float s = 0.f;
-            for (int v = lane; v < V; v += 64) s += expf(z(j, v) - m);
-            const float lse = m + logf(wave_sum(s));
+            const float lse = wave_lse(j, V, p.cached ? zs + j * V : nullptr, logit);
             if (lane == 0) s_lse[j] = lse;
         }
         // ---- 2. totals and stay candidates; the shortlist of (s, j) with y_s possibly y_j + [last_s]
@@ -132,27 +109,15 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_lm_beam_step_kernel(const Ct
             s_spnb[tid] = s_len[tid] > 0 ? pnb + s_e[s_ltok[tid]] : -INFINITY;
             s_bl[tid] = p.b * (float)(s_len[tid] + 1);
         }
-        {
-            const int s = tid / BEAM_MAX, j = tid % BEAM_MAX;
-            if (s < nb && j < nb && s_len[s] == s_len[j] + 1 && s_hprev[s] == s_hash[j]) atomicOr(&s_short[s], 1 << j);
-        }
+        shortlist_pair(nb, s_len, s_hash, s_hprev, s_short);
         __syncthreads();
         // the merge: wave w compares the tokens of the shortlisted pairs of s = w, w + 4, ...
         for (int s = wave; s < nb; s += BEAM_WAVES) {
-            int mask = s_short[s];
-            while (mask) {                                              // (uniform over the wave)
-                const int j = __ffs(mask) - 1, lj = s_len[j];
-                mask &= mask - 1;
-                const int *ts = p.tok_in + (base + s) * p.tok_ld, *tj = p.tok_in + (base + j) * p.tok_ld;
-                bool differ = false;
-                for (int x = lane; x < lj; x += 64) differ = differ || ts[x] != tj[x];
-                if (__any(differ)) continue;
-                if (lane == 0) {
-                    const int k = s_ltok[s];
-                    s_mj[s] = j; s_nm[j] = 1;
-                    s_spnb[s] = logaddexpf_(s_spnb[s], s_e[k] + (k == s_ltok[j] ? s_pb[j] : s_tot[j]));
-                }
-                break;                                                  // beam members are distinct: no other j spells y_s[:-1]
+            const int j = merged_member(s, s_short[s], s_len, [&](int m) { return p.tok_in + (base + m) * p.tok_ld; });
+            if (j >= 0 && lane == 0) {
+                const int k = s_ltok[s];
+                s_mj[s] = j; s_nm[j] = 1;
+                s_spnb[s] = logaddexpf_(s_spnb[s], s_e[k] + (k == s_ltok[j] ? s_pb[j] : s_tot[j]));
             }
         }
         __syncthreads();
@@ -167,7 +132,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_lm_beam_step_kernel(const Ct
             stay_sc = __fmaf_rn(p.a, s_lm[tid], ctc) + p.b * (float)s_len[tid];
         }
         auto first_behind = [&](float psc, int ppos, float &bsc, int &bpos) {
-            bsc = -INFINITY; bpos = 0x7fffffff;
+            bsc = -INFINITY; bpos = NO_CANDIDATE;
             if (stay_ok && before(psc, ppos, stay_sc, tid)) { bsc = stay_sc; bpos = tid; }
             for (int j = 0; j < nb; ++j) {
                 if (s_len[j] >= cap) continue;                          // no room: no extension
@@ -193,19 +158,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_lm_beam_step_kernel(const Ct
         for (int r = 0; r < W; ++r) {
             float bsc = lsc;
             int bpos = lpos;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float osc = __shfl_xor(bsc, o, 64);
-                const int opos = __shfl_xor(bpos, o, 64);
-                if (before(osc, opos, bsc, bpos)) { bsc = osc; bpos = opos; }
-            }
-            if (lane == 0) { r_sc[r & 1][wave] = bsc; r_pos[r & 1][wave] = bpos; }
-            __syncthreads();
-            bsc = r_sc[r & 1][0]; bpos = r_pos[r & 1][0];
-#pragma unroll
-            for (int w = 1; w < BEAM_WAVES; ++w)
-                if (before(r_sc[r & 1][w], r_pos[r & 1][w], bsc, bpos)) { bsc = r_sc[r & 1][w]; bpos = r_pos[r & 1][w]; }
-            if (bpos == 0x7fffffff) break;                              // (uniform) no candidate is left
+            first_in_workgroup(s_first, r, bsc, bpos);
+            if (bpos == NO_CANDIDATE) break;                            // (uniform) no candidate is left
             if (tid == 0) { sel_sc[r] = bsc; sel_pos[r] = bpos; }
             nsel = r + 1;
             if (lpos == bpos && r + 1 < W) first_behind(bsc, bpos, lsc, lpos);
@@ -228,7 +182,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_lm_beam_step_kernel(const Ct
             } else {
                 float ctc;
                 extension(par, k, ctc, lm);
-                pnb = ctc; len = s_len[par] + 1; ltok = k; hprev = s_hash[par]; hash = s_hash[par] * 0x9E3779B1u + (unsigned)k;
+                pnb = ctc; len = s_len[par] + 1; ltok = k; hprev = s_hash[par]; hash = hash_append(s_hash[par], k);
                 sc = sel_sc[tid];
             }
         }
@@ -240,40 +194,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_lm_beam_step_kernel(const Ct
         s_src[tid] = par < 0 ? tid : par; s_k[tid] = k;                 // the gather's source: a slot without a member takes its own
     }
     __syncthreads();
-    for (int idx = tid; idx < nsel * cap; idx += BEAM_THREADS) {
-        const int r = idx / cap, x = idx % cap, par = s_src[r], lp = s_len[par];
-        if (x < lp) p.tok_out[(base + r) * p.tok_ld + x] = p.tok_in[(base + par) * p.tok_ld + x];
-        else if (x == lp && s_k[r] != 0) p.tok_out[(base + r) * p.tok_ld + x] = s_k[r];        // lp < cap: only such members are extended
-    }
-    // ---- 5. the gather: slot r's cell inputs [wte[k] | h of its parent] and c of its parent, for every layer: 2 layers + 1 rows of H
-    //         floats per slot, all of the row's copies spread over the threads, four loads in flight per thread before their stores
-    const int H4 = p.H / 4, per = 2 * p.layers + 1, total = W * per * H4;
-    const long slots = (long)gridDim.x * W;
-    constexpr int GU = 4;
-    for (int i0 = tid; i0 < total; i0 += GU * BEAM_THREADS) {
-        f32x4 v[GU];
-        f32x4 *dst[GU];
-#pragma unroll
-        for (int e = 0; e < GU; ++e) {
-            const int idx = i0 + e * BEAM_THREADS;
-            dst[e] = nullptr;
-            if (idx >= total) continue;
-            const int r = idx / (per * H4), q = idx / H4 % per, x = idx % H4, par = s_src[r];
-            if (q < p.layers) {                                         // h of layer q -> the h half of its [x | h] row
-                v[e] = reinterpret_cast<const f32x4 *>(p.h_in + ((long)q * slots + base + par) * p.H)[x];
-                dst[e] = reinterpret_cast<f32x4 *>(p.xh + ((long)q * slots + base + r) * 2 * p.H) + H4 + x;
-            } else if (q < 2 * p.layers) {                              // c of layer q - layers
-                v[e] = reinterpret_cast<const f32x4 *>(p.c_in + ((long)(q - p.layers) * slots + base + par) * p.H)[x];
-                dst[e] = reinterpret_cast<f32x4 *>(p.c_out + ((long)(q - p.layers) * slots + base + r) * p.H) + x;
-            } else {                                                    // the new token's embedding -> layer 0's x half
-                v[e] = reinterpret_cast<const f32x4 *>(p.wte + (long)s_k[r] * p.H)[x];
-                dst[e] = reinterpret_cast<f32x4 *>(p.xh + (base + r) * 2 * p.H) + x;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < GU; ++e)
-            if (dst[e]) *dst[e] = v[e];
-    }
+    // lp < cap where a label is taken: only such members are extended
+    child_rows(p.tok_out + base * p.tok_ld, p.tok_in + base * p.tok_ld, p.tok_ld, nsel, cap, s_src, s_len, s_k,
+               [&](int r, int) { return s_k[r] != 0; });
+    // ---- 5. the gather: every new slot's cell inputs and c from its parent's
+    gather_state(p.state, base, W, s_src, s_k);
 }
 
 }  // namespace
@@ -296,7 +221,7 @@ int halo_ctc_lm_beam_step(const float *emissions, long stride_t, long stride_n, 
     p.e = emissions; p.st = stride_t; p.sn = stride_n; p.T = T; p.V = V; p.W = beam; p.cap = capacity; p.t = frame; p.il = emission_lengths;
     p.a = lm_weight; p.b = insertion_bonus; p.g = g; p.g_bias = g_bias; p.ldg = ldg; p.rec_in = rec_in; p.meta_in = meta_in;
     p.tok_in = tokens_in; p.rec_out = rec_out; p.meta_out = meta_out; p.tok_out = tokens_out; p.tok_ld = tokens_ld; p.parent = parent;
-    p.last = last; p.wte = wte; p.H = hidden; p.layers = layers; p.h_in = h_in; p.c_in = c_in; p.xh = xh; p.c_out = c_out;
+    p.last = last; p.state = {wte, h_in, c_in, xh, c_out, hidden, layers};
     p.cached = ((long)beam + 1) * V <= LDS_FLOATS;
     const size_t lds = (size_t)(p.cached ? beam + 1 : 1) * V * sizeof(float);
     hipLaunchKernelGGL(ctc_lm_beam_step_kernel, dim3((unsigned)N), dim3(BEAM_THREADS), lds, (hipStream_t)stream, p);

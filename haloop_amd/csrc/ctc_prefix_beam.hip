@@ -2,29 +2,28 @@
 // 3.3p): the whole decode of a batch in one launch, one workgroup per utterance, the frame loop inside.  A beam member is a prefix y with
 // the log-mass of its alignments that end in blank (pb) and in its last label (pnb).  Per frame t < L
 //   1. every member's stay candidate (pb' = total + e[t, 0], pnb' = pnb + e[t, last]) and total = logaddexp(pb, pnb)
-//   2. the merge: the extension of j by k spells the prefix of stay candidate s exactly when y_s = y_j + [k].  A 32-bit hash of the
-//      prefixes shortlists the pairs (s, j); a wave compares their tokens, which alone decides; the extension's mass joins pnb'_s and the
-//      extension is no candidate.  Two members never extend to the same prefix, so there is no other merge.
+//   2. the merge (beam_common.h): the mass of the extension of j that spells stay candidate s joins pnb'_s and the extension is no
+//      candidate.  Two members never extend to the same prefix, so there is no other merge.
 //   3. the W best of the stay candidates (position j) and the extensions (position W + j V + k, score e[t, k] + (pb_j if k == last_j else
-//      total_j), only from members shorter than the capacity), one per round: the first in the total order (score descending, position
-//      ascending) behind the last one taken, by a workgroup-wide arg-max over every thread's own first.  A thread owns the extensions by
-//      its classes and keeps its first across the rounds; only the owner of the candidate just taken looks for its next.  No list of
-//      W V candidates is built: a candidate's score is two operands away from the frame's emissions.  Candidates at -inf are never taken.
+//      total_j), only from members shorter than the capacity), one per round.  A thread owns the extensions by its classes and keeps its
+//      first across the rounds; only the owner of the candidate just taken looks for its next.  A candidate's score is two operands away
+//      from the frame's emissions.  Candidates at -inf are never taken.
 //   4. the new beam's records and token rows, in the order taken, into the other copy of the beam (double-buffered by frame parity).
 // LDS: the records (W-sized, < 2 KiB static); the frame's V emissions, double-buffered so that frame t + 1 is requested from global memory
 // before frame t's rounds and lands in LDS behind them (E_LDS_FLOATS = 8192 floats = 32 KiB of dynamic LDS: V <= 4096; above that the
 // rounds read the emissions from L2 by the same operations, the same bits); the token rows of both copies of the beam as 16-bit tokens
 // (TOK_LDS_TOKENS = 12288 = 24 KiB: 2 W capacity <= 12288 and V <= 65536; otherwise they live in the caller's workspace as 32-bit
 // tokens, written and read by this workgroup alone).  58 KiB at most: under the 64 KiB a launch gets without the opt-in.
-// fp32, no float atomics (one integer atomicOr in LDS collects the shortlist: a bit set, whatever the order), every sum in a fixed
-// order: the launch is bit-reproducible.  Frames at or past L, and another row's frames, are never loaded.
+// Frames at or past L, and another row's frames, are never loaded.
 #include <type_traits>
 
 #include "halo_common.h"
+#include "beam_common.h"
 
 namespace {
 
-constexpr int BEAM_MAX = 16, BEAM_THREADS = 256, BEAM_WAVES = BEAM_THREADS / 64;
+using namespace beam;
+
 constexpr int E_LDS_FLOATS = 8192;         // two frames of emissions in LDS: V <= 4096
 constexpr int TOK_LDS_TOKENS = 12288;      // both copies of the beam's token rows in LDS as 16-bit tokens: 2 W capacity <= 12288
 constexpr int PF = 4;                      // emissions of the next frame a thread holds in registers across a frame (V <= 1024: all of them)
@@ -40,14 +39,6 @@ struct CtcPrefixBeamArgs {
     float *scores;                         // [N][W]
 };
 
-__device__ __forceinline__ float logaddexpf_(float a, float b) {
-    const float m = fmaxf(a, b);
-    return m == -INFINITY ? m : m + log1pf(expf(-fabsf(a - b)));
-}
-
-// (sc, pos) stands before (osc, opos) in the order (score descending, position ascending)
-__device__ __forceinline__ bool before(float sc, int pos, float osc, int opos) { return sc > osc || (sc == osc && pos < opos); }
-
 template <bool STAGED, bool TOK_LDS>
 __global__ __launch_bounds__(BEAM_THREADS) void ctc_prefix_beam_kernel(const CtcPrefixBeamArgs p) {
     using tok_t = typename std::conditional<TOK_LDS, unsigned short, int>::type;
@@ -59,8 +50,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_prefix_beam_kernel(const Ctc
     // the frame: totals, the stay candidates' masses, the shortlist (bit j of word s), the member whose extension merged into s (-1: none)
     __shared__ float s_tot[BEAM_MAX], s_spb[BEAM_MAX], s_spnb[BEAM_MAX], sel_sc[BEAM_MAX];
     __shared__ int s_short[BEAM_MAX], s_mj[BEAM_MAX], sel_pos[BEAM_MAX];
-    __shared__ float r_sc[2][BEAM_WAVES];
-    __shared__ int r_pos[2][BEAM_WAVES];
+    __shared__ FirstScratch s_first;
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = p.W, V = p.V, cap = p.cap;
     const int L = max(0, min(p.il ? (int)p.il[n] : p.T, p.T));
@@ -73,7 +63,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_prefix_beam_kernel(const Ctc
 
     if (tid < BEAM_MAX) {                                              // the empty prefix: every alignment of no frames ends "in blank"
         s_pb[0][tid] = tid == 0 ? 0.f : -INFINITY; s_pnb[0][tid] = -INFINITY; s_sc[0][tid] = tid == 0 ? 0.f : -INFINITY;
-        s_len[0][tid] = 0; s_last[0][tid] = 0; s_hash[0][tid] = 0x811C9DC5u; s_hprev[0][tid] = 0u;
+        s_len[0][tid] = 0; s_last[0][tid] = 0; s_hash[0][tid] = HASH_EMPTY; s_hprev[0][tid] = 0u;
         s_short[tid] = 0;
         if (tid == 0) s_nb[0] = 1;
     }
@@ -109,27 +99,15 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_prefix_beam_kernel(const Ctc
                 s_spnb[tid] = s_len[cur][tid] > 0 ? pnb + em(s_last[cur][tid]) : -INFINITY;
             }
         }
-        {
-            const int s = tid / BEAM_MAX, j = tid % BEAM_MAX;
-            if (s < nb && j < nb && s_len[cur][s] == s_len[cur][j] + 1 && s_hprev[cur][s] == s_hash[cur][j]) atomicOr(&s_short[s], 1 << j);
-        }
+        shortlist_pair(nb, s_len[cur], s_hash[cur], s_hprev[cur], s_short);
         __syncthreads();
         // ---- 2. the merge: wave w compares the tokens of the shortlisted pairs of s = w, w + 4, ...
         for (int s = wave; s < nb; s += BEAM_WAVES) {
-            int mask = s_short[s];
-            while (mask) {                                              // (uniform over the wave)
-                const int j = __ffs(mask) - 1, lj = s_len[cur][j];
-                mask &= mask - 1;
-                const tok_t *ts = tok_row(cur, s), *tj = tok_row(cur, j);
-                bool differ = false;
-                for (int x = lane; x < lj; x += 64) differ = differ || ts[x] != tj[x];
-                if (__any(differ)) continue;
-                if (lane == 0) {
-                    const int k = s_last[cur][s];
-                    s_mj[s] = j;
-                    s_spnb[s] = logaddexpf_(s_spnb[s], em(k) + (k == s_last[cur][j] ? s_pb[cur][j] : s_tot[j]));
-                }
-                break;                                                  // beam members are distinct: no other j spells y_s[:-1]
+            const int j = merged_member(s, s_short[s], s_len[cur], [&](int m) { return tok_row(cur, m); });
+            if (j >= 0 && lane == 0) {
+                const int k = s_last[cur][s];
+                s_mj[s] = j;
+                s_spnb[s] = logaddexpf_(s_spnb[s], em(k) + (k == s_last[cur][j] ? s_pb[cur][j] : s_tot[j]));
             }
         }
         __syncthreads();
@@ -155,7 +133,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_prefix_beam_kernel(const Ctc
             if (gone_j[s] >= 0) merged_k |= 1ull << (gone_k[s] & 63);
         }
         auto first_behind = [&](float psc, int ppos, float &bsc, int &bpos) {
-            bsc = -INFINITY; bpos = 0x7fffffff;
+            bsc = -INFINITY; bpos = NO_CANDIDATE;
             if (stay_sc > -INFINITY && before(psc, ppos, stay_sc, tid)) { bsc = stay_sc; bpos = tid; }
             for (int k = 1 + tid; k < V; k += BEAM_THREADS) {
                 const float ek = em(k);
@@ -179,19 +157,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_prefix_beam_kernel(const Ctc
         for (int r = 0; r < W; ++r) {
             float bsc = lsc;
             int bpos = lpos;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float osc = __shfl_xor(bsc, o, 64);
-                const int opos = __shfl_xor(bpos, o, 64);
-                if (before(osc, opos, bsc, bpos)) { bsc = osc; bpos = opos; }
-            }
-            if (lane == 0) { r_sc[r & 1][wave] = bsc; r_pos[r & 1][wave] = bpos; }
-            __syncthreads();
-            bsc = r_sc[r & 1][0]; bpos = r_pos[r & 1][0];
-#pragma unroll
-            for (int w = 1; w < BEAM_WAVES; ++w)
-                if (before(r_sc[r & 1][w], r_pos[r & 1][w], bsc, bpos)) { bsc = r_sc[r & 1][w]; bpos = r_pos[r & 1][w]; }
-            if (bpos == 0x7fffffff) break;                              // (uniform) no candidate is left
+            first_in_workgroup(s_first, r, bsc, bpos);
+            if (bpos == NO_CANDIDATE) break;                            // (uniform) no candidate is left
             if (tid == 0) { sel_sc[r] = bsc; sel_pos[r] = bpos; }
             nsel = r + 1;
             if (lpos == bpos && r + 1 < W) first_behind(bsc, bpos, lsc, lpos);
@@ -211,18 +178,15 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_prefix_beam_kernel(const Ctc
                     const int par = (pos - W) / V, k = (pos - W) % V;
                     s_pb[nxt][tid] = -INFINITY; s_pnb[nxt][tid] = sel_sc[tid];
                     s_len[nxt][tid] = s_len[cur][par] + 1; s_last[nxt][tid] = k;
-                    s_hprev[nxt][tid] = s_hash[cur][par]; s_hash[nxt][tid] = s_hash[cur][par] * 0x9E3779B1u + (unsigned)k;
+                    s_hprev[nxt][tid] = s_hash[cur][par]; s_hash[nxt][tid] = hash_append(s_hash[cur][par], k);
                 }
                 s_sc[nxt][tid] = sel_sc[tid];
             }
             if (tid == 0) s_nb[nxt] = nsel;
         }
         for (int r = wave; r < nsel; r += BEAM_WAVES) {                 // wave w copies the token rows of slots w, w + 4, ...
-            const int pos = sel_pos[r], par = pos < W ? pos : (pos - W) / V, lp = s_len[cur][par];
-            const tok_t *src = tok_row(cur, par);
-            tok_t *dst = tok_row(nxt, r);
-            for (int x = lane; x < lp; x += 64) dst[x] = src[x];
-            if (pos >= W && lane == 0) dst[lp] = (tok_t)((pos - W) % V);        // lp < cap: only such members are extended
+            const int pos = sel_pos[r], par = pos < W ? pos : (pos - W) / V, k = pos < W ? 0 : (pos - W) % V, lp = s_len[cur][par];
+            for (int x = lane; x < lp + (k != 0); x += 64) child_token(tok_row(nxt, r), tok_row(cur, par), x, lp, k);
         }
         if constexpr (STAGED) {
             if (t + 1 < L) {

@@ -6,17 +6,20 @@
 //                              The self-attention caches are never gathered: a kept hypothesis continues its parent's history by
 //                              reading position j < t from the cache row anc[slot][j] that computed it (the per-slot ancestor table of
 //                              this step), and stores position t into its own row.
-//   dec_beam_select_kernel     one workgroup per utterance: the log-sum-exp of every live slot, the W best of the W * V candidates in the
-//                              order (rank descending, position ascending), and the new beam: scores, lengths, flags, tokens (the
-//                              parent's row gathered, plus k), the next step's ancestor rows and input embeddings.
+//   dec_beam_select_kernel     one workgroup per utterance, on the pieces of beam_common.h: the log-sum-exp of every live slot, the W
+//                              best of the W * V candidates by rank, and the new beam: scores, lengths, flags, tokens, the next step's
+//                              ancestor rows and input embeddings.
 // Everything the selection writes goes to the OTHER parity copy of the beam (step t reads copy t & 1): the gathers across the slots of an
 // utterance never read what this launch writes.  No float atomics, every sum in one order: two decodes are bit-equal.
 #include <hip/hip_fp16.h>
 #include "halo_common.h"
 #include "halo_internal.h"
 #include "decode_attn.h"
+#include "beam_common.h"
 
 namespace {
+
+using namespace beam;
 
 struct BeamAttnArgs {
     const float *a;          // [slots][4C]: cross query | self q | k | v
@@ -156,7 +159,6 @@ __global__ __launch_bounds__(64) void dec_beam_attention_kernel(const BeamAttnAr
     }
 }
 
-constexpr int BEAM_MAX = 16, BEAM_THREADS = 256, BEAM_WAVES = BEAM_THREADS / 64;
 constexpr int BEAM_LDS_FLOATS = 8192;      // 32 KiB of dynamic LDS, under the 64 KiB a launch gets without the opt-in
 
 struct BeamSelArgs {
@@ -182,9 +184,6 @@ struct BeamSelArgs {
     int *par_out, *last_out;   // [N][W]: the parent's slot index (-1: empty), the token taken
 };
 
-// (rank, pos) stands before (orank, opos) in the order (rank descending, position ascending)
-__device__ __forceinline__ bool before(float sc, int pos, float osc, int opos) { return sc > osc || (sc == osc && pos < opos); }
-
 enum { SLOT_EMPTY = 0, SLOT_LIVE = 1, SLOT_FINISHED = 2 };
 
 // JOINT: the candidates are ranked by the mix with their CTC prefix scores; everything else is the same code, so the plain launch keeps
@@ -193,8 +192,7 @@ template <bool JOINT>
 __global__ __launch_bounds__(BEAM_THREADS) void dec_beam_select_kernel(const BeamSelArgs p) {
     __shared__ float s_score[BEAM_MAX], s_lse[BEAM_MAX], sel_rank[BEAM_MAX], s_psi[BEAM_MAX];
     __shared__ int s_len[BEAM_MAX], s_state[BEAM_MAX], sel_pos[BEAM_MAX], s_par[BEAM_MAX], s_k[BEAM_MAX];
-    __shared__ float r_sc[2][BEAM_WAVES];
-    __shared__ int r_pos[2][BEAM_WAVES];
+    __shared__ FirstScratch s_first;
     extern __shared__ float zs[];                                      // cached: zs[j][v] = logits of slot j
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = p.W, V = p.V;
     const long base = (long)n * W;
@@ -217,20 +215,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void dec_beam_select_kernel(const Bea
     __syncthreads();
     auto logit = [&](int j, int v) { return p.logits[(base + j) * p.ld + v]; };
     auto z = [&](int j, int v) { return p.cached ? zs[j * V + v] : logit(j, v); };
-    // ---- 1. wave w: log-sum-exp of slots w, w + 4, ... (fixed order: the lane's stride, then the wave's butterfly)
+    // ---- 1. wave w: log-sum-exp of slots w, w + 4, ...
     for (int j = wave; j < W; j += BEAM_WAVES) {
         if (s_state[j] != SLOT_LIVE) continue;
-        float m = -INFINITY;
-        for (int v = lane; v < V; v += 64) {
-            const float x = logit(j, v);
-            if (p.cached) zs[j * V + v] = x;                           // (read back by this lane below, by the others after the barrier)
-            m = fmaxf(m, x);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        float s = 0.f;
-        for (int v = lane; v < V; v += 64) s += expf(z(j, v) - m);
-        const float lse = m + logf(wave_sum(s));
+        const float lse = wave_lse(j, V, p.cached ? zs + j * V : nullptr, logit);
         if (lane == 0) s_lse[j] = lse;
     }
     __syncthreads();
@@ -247,7 +235,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void dec_beam_select_kernel(const Bea
     int ppos = -1, nsel = 0;
     for (int r = 0; r < W; ++r) {
         float brank = -INFINITY;
-        int bpos = 0x7fffffff;
+        int bpos = NO_CANDIDATE;
         if (tid < W && s_state[tid] == SLOT_FINISHED) {
             const float rk = mix(fmaf(p.bonus, (float)s_len[tid], s_score[tid]), JOINT ? s_psi[tid] : 0.f);
             const int pos = tid * V + p.etx;
@@ -262,19 +250,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void dec_beam_select_kernel(const Bea
                 brank = rk; bpos = pos;
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float osc = __shfl_xor(brank, o, 64);
-            const int opos = __shfl_xor(bpos, o, 64);
-            if (before(osc, opos, brank, bpos)) { brank = osc; bpos = opos; }
-        }
-        if (lane == 0) { r_sc[r & 1][wave] = brank; r_pos[r & 1][wave] = bpos; }
-        __syncthreads();
-        brank = r_sc[r & 1][0]; bpos = r_pos[r & 1][0];
-#pragma unroll
-        for (int w = 1; w < BEAM_WAVES; ++w)
-            if (before(r_sc[r & 1][w], r_pos[r & 1][w], brank, bpos)) { brank = r_sc[r & 1][w]; bpos = r_pos[r & 1][w]; }
-        if (bpos == 0x7fffffff) break;                                  // (uniform) no candidate is left
+        first_in_workgroup(s_first, r, brank, bpos);
+        if (bpos == NO_CANDIDATE) break;                                // (uniform) no candidate is left
         if (tid == 0) { sel_rank[r] = brank; sel_pos[r] = bpos; }
         prank = brank; ppos = bpos; nsel = r + 1;
     }
@@ -299,11 +276,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void dec_beam_select_kernel(const Bea
     }
     __syncthreads();
     // ---- 4. tokens (without STX and ETX): the parent's row, plus k
-    for (int idx = tid; idx < nsel * p.capacity; idx += BEAM_THREADS) {
-        const int r = idx / p.capacity, x = idx % p.capacity, par = s_par[r], lp = s_len[par];
-        if (x < lp) p.tok_out[(base + r) * p.tok_ld + x] = p.tok_in[(base + par) * p.tok_ld + x];
-        else if (x == lp && s_state[par] == SLOT_LIVE && s_k[r] != p.etx) p.tok_out[(base + r) * p.tok_ld + x] = s_k[r];
-    }
+    child_rows(p.tok_out + base * p.tok_ld, p.tok_in + base * p.tok_ld, p.tok_ld, nsel, p.capacity, s_par, s_len, s_k,
+               [&](int r, int par) { return s_state[par] == SLOT_LIVE && s_k[r] != p.etx; });
     // ---- 5. the next step's ancestor rows: the parent's history, then the parent's own row for position t (an empty slot: its own row)
     for (int idx = tid; idx < W * (p.t + 1); idx += BEAM_THREADS) {
         const int r = idx / (p.t + 1), x = idx % (p.t + 1), par = s_par[r];
@@ -319,6 +293,28 @@ __global__ __launch_bounds__(BEAM_THREADS) void dec_beam_select_kernel(const Bea
         reinterpret_cast<f32x4 *>(p.y + (base + r) * p.C)[c] = reinterpret_cast<const f32x4 *>(p.wte + (long)s_k[r] * p.C)[c];
     }
 }
+
+// what both halo_decode_beam_select entry points check and pass on; the joint entry adds its own
+int beam_select_args(BeamSelArgs &p, const float *logits, long ld, int N, int beam, int V, int t, int capacity, int etx, float length_bonus,
+                     const float *scores_in, const int *lengths_in, const int *finished_in, const int *tokens_in, const int *ancestors_in,
+                     float *scores_out, float *ranks_out, int *lengths_out, int *finished_out, int *tokens_out, int *ancestors_out,
+                     long tokens_ld, long ancestors_ld, const float *wte, int vocab, int C, float *y_next) {
+    HALO_CHECK_ARG(logits && scores_in && lengths_in && finished_in && tokens_in && ancestors_in);
+    HALO_CHECK_ARG(scores_out && ranks_out && lengths_out && finished_out && tokens_out && ancestors_out);
+    HALO_CHECK_ARG(N > 0 && beam >= 1 && beam <= BEAM_MAX && V > 0 && V <= 8192 && ld >= V && etx >= 0 && etx < V);
+    HALO_CHECK_ARG(t >= 0 && t < capacity && tokens_ld >= capacity && ancestors_ld > t && (long)N * beam <= 0x7fffffffL / V);
+    HALO_CHECK_ARG(scores_in != scores_out && lengths_in != lengths_out && finished_in != finished_out && tokens_in != tokens_out &&
+                   ancestors_in != ancestors_out);
+    HALO_CHECK_ARG(!y_next || (wte && vocab >= V && C > 0 && C % 4 == 0 && ((uintptr_t)wte | (uintptr_t)y_next) % 16 == 0));
+    p.logits = logits; p.ld = ld; p.V = V; p.W = beam; p.t = t; p.capacity = capacity; p.etx = etx; p.bonus = length_bonus;
+    p.score_in = scores_in; p.len_in = lengths_in; p.fin_in = finished_in; p.tok_in = tokens_in; p.anc_in = ancestors_in;
+    p.score_out = scores_out; p.rank_out = ranks_out; p.len_out = lengths_out; p.fin_out = finished_out; p.tok_out = tokens_out;
+    p.anc_out = ancestors_out; p.tok_ld = tokens_ld; p.anc_ld = ancestors_ld; p.wte = wte; p.C = C; p.y = y_next;
+    p.cached = (long)beam * V <= BEAM_LDS_FLOATS;
+    return HALO_OK;
+}
+
+size_t beam_select_lds(const BeamSelArgs &p) { return p.cached ? (size_t)p.W * p.V * sizeof(float) : 0; }
 
 }  // namespace
 
@@ -360,22 +356,13 @@ int halo_decode_beam_select(const float *logits, long ld, int N, int beam, int V
                             const int *ancestors_in, float *scores_out, float *ranks_out, int *lengths_out, int *finished_out,
                             int *tokens_out, int *ancestors_out, long tokens_ld, long ancestors_ld, const float *wte, int vocab, int C,
                             float *y_next, halo_stream_t stream) {
-    HALO_CHECK_ARG(logits && scores_in && lengths_in && finished_in && tokens_in && ancestors_in);
-    HALO_CHECK_ARG(scores_out && ranks_out && lengths_out && finished_out && tokens_out && ancestors_out);
-    HALO_CHECK_ARG(N > 0 && beam >= 1 && beam <= BEAM_MAX && V > 0 && V <= 8192 && ld >= V && etx >= 0 && etx < V);
-    HALO_CHECK_ARG(t >= 0 && t < capacity && tokens_ld >= capacity && ancestors_ld > t && (long)N * beam <= 0x7fffffffL / V);
-    HALO_CHECK_ARG(scores_in != scores_out && lengths_in != lengths_out && finished_in != finished_out && tokens_in != tokens_out &&
-                   ancestors_in != ancestors_out);
-    HALO_CHECK_ARG(!y_next || (wte && vocab >= V && C > 0 && C % 4 == 0 && ((uintptr_t)wte | (uintptr_t)y_next) % 16 == 0));
     BeamSelArgs p;
-    p.logits = logits; p.ld = ld; p.V = V; p.W = beam; p.t = t; p.capacity = capacity; p.etx = etx; p.bonus = length_bonus;
-    p.score_in = scores_in; p.len_in = lengths_in; p.fin_in = finished_in; p.tok_in = tokens_in; p.anc_in = ancestors_in;
-    p.score_out = scores_out; p.rank_out = ranks_out; p.len_out = lengths_out; p.fin_out = finished_out; p.tok_out = tokens_out;
-    p.anc_out = ancestors_out; p.tok_ld = tokens_ld; p.anc_ld = ancestors_ld; p.wte = wte; p.C = C; p.y = y_next;
-    p.cached = (long)beam * V <= BEAM_LDS_FLOATS;
+    const int status = beam_select_args(p, logits, ld, N, beam, V, t, capacity, etx, length_bonus, scores_in, lengths_in, finished_in,
+                                        tokens_in, ancestors_in, scores_out, ranks_out, lengths_out, finished_out, tokens_out,
+                                        ancestors_out, tokens_ld, ancestors_ld, wte, vocab, C, y_next);
+    if (status != HALO_OK) return status;
     p.c = 0.f; p.omc = 1.f; p.psi_cand = nullptr; p.psi_ld = 0; p.psi_in = nullptr; p.psi_out = nullptr; p.par_out = p.last_out = nullptr;
-    hipLaunchKernelGGL(dec_beam_select_kernel<false>, dim3((unsigned)N), dim3(BEAM_THREADS), p.cached ? (size_t)beam * V * sizeof(float) : 0,
-                       (hipStream_t)stream, p);
+    hipLaunchKernelGGL(dec_beam_select_kernel<false>, dim3((unsigned)N), dim3(BEAM_THREADS), beam_select_lds(p), (hipStream_t)stream, p);
     return halo_launch_status();
 }
 
@@ -385,25 +372,16 @@ int halo_decode_beam_select_joint(const float *logits, long ld, int N, int beam,
                                   const int *ancestors_in, float *scores_out, float *ranks_out, int *lengths_out, int *finished_out,
                                   int *tokens_out, int *ancestors_out, int *parents_out, int *last_out, long tokens_ld, long ancestors_ld,
                                   const float *wte, int vocab, int C, float *y_next, halo_stream_t stream) {
-    HALO_CHECK_ARG(logits && scores_in && lengths_in && finished_in && tokens_in && ancestors_in);
-    HALO_CHECK_ARG(scores_out && ranks_out && lengths_out && finished_out && tokens_out && ancestors_out);
+    BeamSelArgs p;
+    const int status = beam_select_args(p, logits, ld, N, beam, V, t, capacity, etx, length_bonus, scores_in, lengths_in, finished_in,
+                                        tokens_in, ancestors_in, scores_out, ranks_out, lengths_out, finished_out, tokens_out,
+                                        ancestors_out, tokens_ld, ancestors_ld, wte, vocab, C, y_next);
+    if (status != HALO_OK) return status;
     HALO_CHECK_ARG(psi_cand && psi_in && psi_out && parents_out && last_out && psi_in != psi_out && psi_ld >= V);
     HALO_CHECK_ARG(ctc_weight >= 0.f && ctc_weight <= 1.f);
-    HALO_CHECK_ARG(N > 0 && beam >= 1 && beam <= BEAM_MAX && V > 0 && V <= 8192 && ld >= V && etx >= 0 && etx < V);
-    HALO_CHECK_ARG(t >= 0 && t < capacity && tokens_ld >= capacity && ancestors_ld > t && (long)N * beam <= 0x7fffffffL / V);
-    HALO_CHECK_ARG(scores_in != scores_out && lengths_in != lengths_out && finished_in != finished_out && tokens_in != tokens_out &&
-                   ancestors_in != ancestors_out);
-    HALO_CHECK_ARG(!y_next || (wte && vocab >= V && C > 0 && C % 4 == 0 && ((uintptr_t)wte | (uintptr_t)y_next) % 16 == 0));
-    BeamSelArgs p;
-    p.logits = logits; p.ld = ld; p.V = V; p.W = beam; p.t = t; p.capacity = capacity; p.etx = etx; p.bonus = length_bonus;
-    p.score_in = scores_in; p.len_in = lengths_in; p.fin_in = finished_in; p.tok_in = tokens_in; p.anc_in = ancestors_in;
-    p.score_out = scores_out; p.rank_out = ranks_out; p.len_out = lengths_out; p.fin_out = finished_out; p.tok_out = tokens_out;
-    p.anc_out = ancestors_out; p.tok_ld = tokens_ld; p.anc_ld = ancestors_ld; p.wte = wte; p.C = C; p.y = y_next;
-    p.cached = (long)beam * V <= BEAM_LDS_FLOATS;
     p.c = ctc_weight; p.omc = 1.0f - ctc_weight; p.psi_cand = psi_cand; p.psi_ld = psi_ld; p.psi_in = psi_in; p.psi_out = psi_out;
     p.par_out = parents_out; p.last_out = last_out;
-    hipLaunchKernelGGL(dec_beam_select_kernel<true>, dim3((unsigned)N), dim3(BEAM_THREADS), p.cached ? (size_t)beam * V * sizeof(float) : 0,
-                       (hipStream_t)stream, p);
+    hipLaunchKernelGGL(dec_beam_select_kernel<true>, dim3((unsigned)N), dim3(BEAM_THREADS), beam_select_lds(p), (hipStream_t)stream, p);
     return halo_launch_status();
 }
 

@@ -7,18 +7,17 @@
 //   2. one halo_rnnt_lstm_cell per LSTM layer and halo_decode_linear (out_layer) on all N * W slots (csrc/rnnt_decode.hip, csrc/decode.hip)
 //   3. rnnt_beam_keep_kernel  a blank-extended slot takes (h, c, g) of its parent back
 // The state (h and c of every layer, g) is double-buffered by step parity: launch 1 and 3 read the copy of this step, which no launch of
-// the step writes, and write only the slots of their own row / their own slot of the other copy.  The W best are taken in W rounds of a
-// workgroup-wide arg-max over the candidates behind the last one taken, in the total order (score descending, candidate position
-// ascending): no list of W * V candidates is built.  The row's W * V joint logits are kept in LDS when they are 32 KiB or less (the
-// rounds then read LDS) and recomputed from L2 in every round otherwise, by the same operations: the same bits either way.  Besides
-// that LDS holds W-sized records only (< 1 KiB).  Every sum has a fixed order and no score goes through an atomic: the launch is
-// bit-reproducible.
+// the step writes, and write only the slots of their own row / their own slot of the other copy.  The rounds, the log-sum-exp, the token
+// rows and the gather are beam_common.h's; every thread rescans its candidates in every round, and the merge compares tokens per thread.
+// The row's W * V joint logits are kept in LDS when they are 32 KiB or less (the rounds then read LDS) and recomputed from L2 in every
+// round otherwise.  Besides that LDS holds W-sized records only (< 1 KiB).
 #include "halo_common.h"
 #include "halo_internal.h"
+#include "beam_common.h"
 
 namespace {
 
-constexpr int BEAM_MAX = 16, BEAM_THREADS = 256, BEAM_WAVES = BEAM_THREADS / 64;
+using namespace beam;
 
 struct RnntBeamArgs {
     const float *f;            // [N][T][V] transcription logits, strides f_rs (row) and f_ts (frame)
@@ -36,30 +35,18 @@ struct RnntBeamArgs {
     int *parent, *last;        // [N][W] of the new beam: the parent's slot within the row (-1: no hypothesis), the new token (0: blank)
     float *fin_score;          // [N][W] the row's best complete hypotheses, unordered: score, order of appending, length (-1: none)
     int *fin_seq, *fin_len, *fin_tok, *fin_n;    // tokens [N][W][tok_ld]; fin_n [N]: hypotheses completed so far
-    const float *wte;          // [V][H] the embedding
-    int H, layers;
-    const float *h_in, *c_in;  // [layers][N * W][H] this step's state
-    float *xh, *c_out;         // [layers][N * W][2 H] = x | h_prev of the cells; [layers][N * W][H] the next state's c, before the cells
+    StateGather state;         // this step's state -> the cells' inputs
     int *live;                 // one word: += 1 per row whose new beam is not empty
     int cached;                // the row's W V joint logits are kept in LDS (BEAM_LDS_FLOATS or fewer), else recomputed from L2
 };
 
 constexpr int BEAM_LDS_FLOATS = 8192;      // 32 KiB of dynamic LDS, under the 64 KiB a launch gets without the opt-in
 
-__device__ __forceinline__ float logaddexpf_(float a, float b) {
-    const float m = fmaxf(a, b);
-    return m == -INFINITY ? m : m + log1pf(expf(-fabsf(a - b)));
-}
-
-// (sc, pos) stands before (osc, opos) in the order (score descending, position ascending)
-__device__ __forceinline__ bool before(float sc, int pos, float osc, int opos) { return sc > osc || (sc == osc && pos < opos); }
-
 __global__ __launch_bounds__(BEAM_THREADS) void rnnt_beam_step_kernel(const RnntBeamArgs p) {
     __shared__ float s_score[BEAM_MAX], s_lse[BEAM_MAX], s_blank[BEAM_MAX], s_msc[BEAM_MAX], s_fsc[BEAM_MAX], sel_sc[BEAM_MAX];
     __shared__ int s_u[BEAM_MAX], s_mj[BEAM_MAX], s_mk[BEAM_MAX], s_nm[BEAM_MAX], s_fseq[BEAM_MAX], s_flen[BEAM_MAX], s_fsrc[BEAM_MAX],
         sel_pos[BEAM_MAX];
-    __shared__ float r_sc[2][BEAM_WAVES];
-    __shared__ int r_pos[2][BEAM_WAVES];
+    __shared__ FirstScratch s_first;
     extern __shared__ float zs[];                                      // cached: z[j][v] = F[n, t_j, v] + (g_j[v] + bias[v])
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = p.W, V = p.V;
     const long base = (long)n * W;
@@ -91,20 +78,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void rnnt_beam_step_kernel(const Rnnt
         return p.f[(long)n * p.f_rs + (long)(p.step - s_u[j]) * p.f_ts + v] + (p.g[(base + j) * p.ldg + v] + (p.g_bias ? p.g_bias[v] : 0.f));
     };
     auto z = [&](int j, int v) { return p.cached ? zs[j * V + v] : logit(j, v); };
-    // ---- 1. wave w: log-sum-exp of hypotheses w, w + 4, ... (fixed order: the lane's stride, then the wave's butterfly)
+    // ---- 1. wave w: log-sum-exp of hypotheses w, w + 4, ...
     for (int j = wave; j < W; j += BEAM_WAVES) {
         if (s_u[j] < 0) continue;
-        float m = -INFINITY;
-        for (int v = lane; v < V; v += 64) {
-            const float x = logit(j, v);
-            if (p.cached) zs[j * V + v] = x;                           // (read back by this lane below, by the others after the barrier)
-            m = fmaxf(m, x);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        float s = 0.f;
-        for (int v = lane; v < V; v += 64) s += expf(z(j, v) - m);
-        const float lse = m + logf(wave_sum(s));
+        const float lse = wave_lse(j, V, p.cached ? zs + j * V : nullptr, logit);
         if (lane == 0) {
             s_lse[j] = lse;
             s_blank[j] = s_score[j] + (z(j, 0) - lse);
@@ -164,7 +141,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void rnnt_beam_step_kernel(const Rnnt
     int ppos = -1, nsel = 0;
     for (int r = 0; r < W; ++r) {
         float bsc = -INFINITY;
-        int bpos = 0x7fffffff;
+        int bpos = NO_CANDIDATE;
         if (tid < W && s_u[tid] >= 0 && p.step - s_u[tid] + 1 != L) {
             const float sc = s_blank[tid];
             if (before(psc, ppos, sc, tid)) { bsc = sc; bpos = tid; }
@@ -185,19 +162,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void rnnt_beam_step_kernel(const Rnnt
                 bsc = sc; bpos = pos;
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float osc = __shfl_xor(bsc, o, 64);
-            const int opos = __shfl_xor(bpos, o, 64);
-            if (before(osc, opos, bsc, bpos)) { bsc = osc; bpos = opos; }
-        }
-        if (lane == 0) { r_sc[r & 1][wave] = bsc; r_pos[r & 1][wave] = bpos; }
-        __syncthreads();
-        bsc = r_sc[r & 1][0]; bpos = r_pos[r & 1][0];
-#pragma unroll
-        for (int w = 1; w < BEAM_WAVES; ++w)
-            if (before(r_sc[r & 1][w], r_pos[r & 1][w], bsc, bpos)) { bsc = r_sc[r & 1][w]; bpos = r_pos[r & 1][w]; }
-        if (bpos == 0x7fffffff) break;                                  // (uniform) no candidate is left
+        first_in_workgroup(s_first, r, bsc, bpos);
+        if (bpos == NO_CANDIDATE) break;                                // (uniform) no candidate is left
         if (tid == 0) { sel_sc[r] = bsc; sel_pos[r] = bpos; }
         psc = bsc; ppos = bpos; nsel = r + 1;
     }
@@ -219,40 +185,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void rnnt_beam_step_kernel(const Rnnt
     if (nsel == 0) return;
     __syncthreads();
     if (tid == 0) atomicAdd(p.live, 1);
-    for (int idx = tid; idx < nsel * p.capacity; idx += BEAM_THREADS) {
-        const int r = idx / p.capacity, x = idx % p.capacity, par = s_mj[r], up = s_u[par];
-        if (x < up) p.tok_out[(base + r) * p.tok_ld + x] = p.tok_in[(base + par) * p.tok_ld + x];
-        else if (x == up && s_mk[r] != 0) p.tok_out[(base + r) * p.tok_ld + x] = s_mk[r];     // up < capacity: only such take labels
-    }
-    // ---- 6. the gather: slot r's cell inputs [wte[k] | h of its parent] and c of its parent, for every layer: 2 layers + 1 rows of H
-    //         floats per slot, all of the row's copies spread over the threads, four loads in flight per thread before their stores
-    const int H4 = p.H / 4, per = 2 * p.layers + 1, total = W * per * H4;
-    const long slots = (long)gridDim.x * W;
-    constexpr int GU = 4;
-    for (int i0 = tid; i0 < total; i0 += GU * BEAM_THREADS) {
-        f32x4 v[GU];
-        f32x4 *dst[GU];
-#pragma unroll
-        for (int e = 0; e < GU; ++e) {
-            const int idx = i0 + e * BEAM_THREADS;
-            dst[e] = nullptr;
-            if (idx >= total) continue;
-            const int r = idx / (per * H4), q = idx / H4 % per, x = idx % H4, par = s_mj[r];
-            if (q < p.layers) {                                         // h of layer q -> the h half of its [x | h] row
-                v[e] = reinterpret_cast<const f32x4 *>(p.h_in + ((long)q * slots + base + par) * p.H)[x];
-                dst[e] = reinterpret_cast<f32x4 *>(p.xh + ((long)q * slots + base + r) * 2 * p.H) + H4 + x;
-            } else if (q < 2 * p.layers) {                              // c of layer q - layers
-                v[e] = reinterpret_cast<const f32x4 *>(p.c_in + ((long)(q - p.layers) * slots + base + par) * p.H)[x];
-                dst[e] = reinterpret_cast<f32x4 *>(p.c_out + ((long)(q - p.layers) * slots + base + r) * p.H) + x;
-            } else {                                                    // the new token's embedding -> layer 0's x half
-                v[e] = reinterpret_cast<const f32x4 *>(p.wte + (long)s_mk[r] * p.H)[x];
-                dst[e] = reinterpret_cast<f32x4 *>(p.xh + (base + r) * 2 * p.H) + x;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < GU; ++e)
-            if (dst[e]) *dst[e] = v[e];
-    }
+    // up < capacity where a label is taken: only such hypotheses take labels
+    child_rows(p.tok_out + base * p.tok_ld, p.tok_in + base * p.tok_ld, p.tok_ld, nsel, p.capacity, s_mj, s_u, s_mk,
+               [&](int r, int) { return s_mk[r] != 0; });
+    // ---- 6. the gather: every new slot's cell inputs and c from its parent's
+    gather_state(p.state, base, W, s_mj, s_mk);
 }
 
 struct RnntKeepArgs {
@@ -301,8 +238,8 @@ int halo_rnnt_beam_step(const float *f, long f_row_stride, long f_frame_stride, 
     p.f = f; p.f_rs = f_row_stride; p.f_ts = f_frame_stride; p.T = T; p.V = V; p.g = g; p.g_bias = g_bias; p.ldg = ldg;
     p.il = input_lengths; p.step = step; p.W = beam; p.capacity = capacity; p.score_in = scores_in; p.u_in = u_in; p.tok_in = tokens_in;
     p.score_out = scores_out; p.u_out = u_out; p.tok_out = tokens_out; p.tok_ld = tokens_ld; p.parent = parent; p.last = last;
-    p.fin_score = fin_scores; p.fin_seq = fin_seq; p.fin_len = fin_lengths; p.fin_tok = fin_tokens; p.fin_n = fin_n; p.wte = wte;
-    p.H = hidden; p.layers = layers; p.h_in = h_in; p.c_in = c_in; p.xh = xh; p.c_out = c_out; p.live = live;
+    p.fin_score = fin_scores; p.fin_seq = fin_seq; p.fin_len = fin_lengths; p.fin_tok = fin_tokens; p.fin_n = fin_n;
+    p.state = {wte, h_in, c_in, xh, c_out, hidden, layers}; p.live = live;
     p.cached = (long)beam * V <= BEAM_LDS_FLOATS;
     hipLaunchKernelGGL(rnnt_beam_step_kernel, dim3((unsigned)N), dim3(BEAM_THREADS), p.cached ? (size_t)beam * V * sizeof(float) : 0,
                        (hipStream_t)stream, p);

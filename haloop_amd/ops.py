@@ -1452,7 +1452,7 @@ def transducer_viterbi(joint, targets, joint_lengths, target_lengths, checked=Fa
 
 
 # ---- CTC prefix beam search: n-best lists from CTC emissions in one launch (csrc/ctc_prefix_beam.hip) ---------------------------------
-BEAM_MAX = 16                    # widths the two beam searches take (csrc/rnnt_beam.hip, csrc/ctc_prefix_beam.hip)
+BEAM_MAX = 16                    # widths the beam searches take (csrc/beam_common.h BEAM_MAX)
 
 
 def ctc_prefix_beam(emissions, emission_lengths, beam, capacity):
@@ -1602,23 +1602,28 @@ def decode_beam_attention(a, mem_k, mem_v, memory_lengths, time_k, time_v, n_key
     return out
 
 
-def decode_beam_select(logits, t, capacity, etx, length_bonus, beam_in, beam_out, ranks_out, wte=None, y_next=None):
-    """One step of the beam (include/halo.h) on logits [N * W, V]: beam_in / beam_out = (scores [N, W] fp32, lengths [N, W] int32,
-    finished [N, W] int32, tokens [N, W, >= capacity] int32, ancestors [N * W, > t] int32), two distinct copies; ranks_out [N, W] fp32;
-    y_next [N * W, C] <- wte[token]."""
+def _check_beam_select(name, logits, beam_in, beam_out, ranks_out, wte, y_next):
     N, W = ranks_out.shape
     V = logits.shape[1]
     tensors = (*beam_in, *beam_out, ranks_out)
     if not all(x.is_contiguous() for x in tensors) or logits.shape[0] != N * W or logits.stride(1) != 1:
-        raise ValueError('decode_beam_select: logits must be [N * W, V] with unit class stride and every record contiguous')
+        raise ValueError(f'{name}: logits must be [N * W, V] with unit class stride and every record contiguous')
     for rec in (beam_in, beam_out):
         if any(x.shape != (N, W) for x in rec[:3]) or rec[3].shape[:2] != (N, W) or rec[4].shape[0] != N * W \
                 or rec[0].dtype != torch.float32 or any(x.dtype != torch.int32 for x in rec[1:]):
-            raise ValueError('decode_beam_select: records are (scores f32, lengths, finished [N, W], tokens [N, W, ld], ancestors [N * W, ld] int32)')
+            raise ValueError(f'{name}: records are (scores f32, lengths, finished [N, W], tokens [N, W, ld], ancestors [N * W, ld] int32)')
     if beam_in[3].shape != beam_out[3].shape or beam_in[4].shape != beam_out[4].shape:
-        raise ValueError('decode_beam_select: the two copies of the beam must have one shape')
+        raise ValueError(f'{name}: the two copies of the beam must have one shape')
     if y_next is not None and (not y_next.is_contiguous() or not wte.is_contiguous() or y_next.shape != (N * W, wte.shape[1])):
-        raise ValueError('decode_beam_select: y_next must be a contiguous [N * W, C] and wte contiguous')
+        raise ValueError(f'{name}: y_next must be a contiguous [N * W, C] and wte contiguous')
+    return N, W, V
+
+
+def decode_beam_select(logits, t, capacity, etx, length_bonus, beam_in, beam_out, ranks_out, wte=None, y_next=None):
+    """One step of the beam (include/halo.h) on logits [N * W, V]: beam_in / beam_out = (scores [N, W] fp32, lengths [N, W] int32,
+    finished [N, W] int32, tokens [N, W, >= capacity] int32, ancestors [N * W, > t] int32), two distinct copies; ranks_out [N, W] fp32;
+    y_next [N * W, C] <- wte[token]."""
+    N, W, V = _check_beam_select('decode_beam_select', logits, beam_in, beam_out, ranks_out, wte, y_next)
     check(lib().halo_decode_beam_select(ptr(logits), logits.stride(0), N, W, V, int(t), int(capacity), int(etx), float(length_bonus),
                                         *(ptr(x) for x in beam_in), ptr(beam_out[0]), ptr(ranks_out), *(ptr(x) for x in beam_out[1:]),
                                         beam_in[3].shape[2], beam_in[4].shape[1], ptr(wte), wte.shape[0] if wte is not None else 0,
@@ -1686,19 +1691,7 @@ def decode_beam_select_joint(logits, t, capacity, etx, length_bonus, ctc_weight,
                              parents_out, last_out, wte=None, y_next=None):
     """decode_beam_select with rank = (1 - ctc_weight) * rank + ctc_weight * psi: psi_cand [N * W, V] from ctc_prefix_scores, psi_in /
     psi_out [N, W] float32 (two copies), parents_out / last_out [N, W] int32 <- the parent's slot index (-1: empty), the token taken."""
-    N, W = ranks_out.shape
-    V = logits.shape[1]
-    tensors = (*beam_in, *beam_out, ranks_out)
-    if not all(x.is_contiguous() for x in tensors) or logits.shape[0] != N * W or logits.stride(1) != 1:
-        raise ValueError('decode_beam_select_joint: logits must be [N * W, V] with unit class stride and every record contiguous')
-    for rec in (beam_in, beam_out):
-        if any(x.shape != (N, W) for x in rec[:3]) or rec[3].shape[:2] != (N, W) or rec[4].shape[0] != N * W \
-                or rec[0].dtype != torch.float32 or any(x.dtype != torch.int32 for x in rec[1:]):
-            raise ValueError('decode_beam_select_joint: records are (scores f32, lengths, finished [N, W], tokens [N, W, ld], ancestors [N * W, ld] int32)')
-    if beam_in[3].shape != beam_out[3].shape or beam_in[4].shape != beam_out[4].shape:
-        raise ValueError('decode_beam_select_joint: the two copies of the beam must have one shape')
-    if y_next is not None and (not y_next.is_contiguous() or not wte.is_contiguous() or y_next.shape != (N * W, wte.shape[1])):
-        raise ValueError('decode_beam_select_joint: y_next must be a contiguous [N * W, C] and wte contiguous')
+    N, W, V = _check_beam_select('decode_beam_select_joint', logits, beam_in, beam_out, ranks_out, wte, y_next)
     if psi_cand.shape != (N * W, V) or psi_cand.dtype != torch.float32 or psi_cand.stride(1) != 1:
         raise ValueError('decode_beam_select_joint: psi_cand must be float32 [N * W, V] with unit class stride')
     _prefix_records('decode_beam_select_joint', N, W, (parents_out, last_out), (psi_in, psi_out))
