@@ -15,6 +15,12 @@
 // (TOK_LDS_TOKENS = 12288 = 24 KiB: 2 W capacity <= 12288 and V <= 65536; otherwise they live in the caller's workspace as 32-bit
 // tokens, written and read by this workgroup alone).  58 KiB at most: under the 64 KiB a launch gets without the opt-in.
 // Frames at or past L, and another row's frames, are never loaded.
+//
+// The carried search (halo_ctc_prefix_beam_advance, haloop_amd/ctc.py PrefixBeamStream) is the same kernel template with
+// CARRIED set: the frame loop is entered from a beam in global memory and left into it, so a stream's frames may arrive over any number
+// of launches.  A row's state is a BeamRecords header and its token rows: one copy of 16-bit tokens where the launch works on them in LDS
+// (loaded and stored once per launch), else both copies of 32-bit tokens, worked on in place, with the header naming the current copy.
+// The frame parity of the double buffers is local to a launch; the state is stored from whichever copy the launch ended on.
 #include <type_traits>
 
 #include "halo_common.h"
@@ -28,6 +34,16 @@ constexpr int E_LDS_FLOATS = 8192;         // two frames of emissions in LDS: V 
 constexpr int TOK_LDS_TOKENS = 12288;      // both copies of the beam's token rows in LDS as 16-bit tokens: 2 W capacity <= 12288
 constexpr int PF = 4;                      // emissions of the next frame a thread holds in registers across a frame (V <= 1024: all of them)
 constexpr int V_MAX = 1 << 26;             // positions W + j V + k stay below 2^31
+constexpr int STREAM_BEGIN_BIT = 2;        // bit 1 of the per-stream flags (include/halo.h: bit 0 active, bit 1 begin, bit 2 final)
+
+// the head of a row's carried state: the W records, the member count and (token rows in the state) the copy that is current
+struct BeamRecords {
+    float pb[BEAM_MAX], pnb[BEAM_MAX], sc[BEAM_MAX];
+    int len[BEAM_MAX], last[BEAM_MAX];
+    unsigned hash[BEAM_MAX], hprev[BEAM_MAX];
+    int nb, copy, pad[14];
+};
+static_assert(sizeof(BeamRecords) == 512, "the token rows behind the records stay 16-byte aligned");
 
 struct CtcPrefixBeamArgs {
     const float *e;                        // [T][N][V] log-probabilities, strides st (frame) and sn (row), unit class stride
@@ -37,9 +53,14 @@ struct CtcPrefixBeamArgs {
     int *ws;                               // token rows [N][2][W][cap] when they do not fit LDS
     int64_t *tokens, *lengths, *counts;    // [N][W][cap], [N][W], [N]
     float *scores;                         // [N][W]
+    // the carried search only
+    const int *nf;                         // [N] frames of each row in this launch (NULL: T), clamped to [0, T]
+    const int *flags;                      // [N] per-stream flags (NULL: no row begins)
+    unsigned char *state;                  // [N][state_bytes]
+    size_t state_bytes;
 };
 
-template <bool STAGED, bool TOK_LDS>
+template <bool STAGED, bool TOK_LDS, bool CARRIED>
 __global__ __launch_bounds__(BEAM_THREADS) void ctc_prefix_beam_kernel(const CtcPrefixBeamArgs p) {
     using tok_t = typename std::conditional<TOK_LDS, unsigned short, int>::type;
     // the beam, twice (frame parity): masses, score, length, last token (0: the empty prefix), hash of the prefix and of the prefix without
@@ -53,26 +74,60 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_prefix_beam_kernel(const Ctc
     __shared__ FirstScratch s_first;
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = p.W, V = p.V, cap = p.cap;
-    const int L = max(0, min(p.il ? (int)p.il[n] : p.T, p.T));
+    int L;
+    bool begin = true;                                                 // from the empty prefix (the whole-utterance search: always)
+    if constexpr (CARRIED) {
+        L = max(0, min(p.nf ? p.nf[n] : p.T, p.T));
+        begin = p.flags && (p.flags[n] & STREAM_BEGIN_BIT);
+        if (L == 0 && !begin) return;                                  // (uniform) the row does not take part: nothing of it is written
+    } else {
+        L = max(0, min(p.il ? (int)p.il[n] : p.T, p.T));
+    }
+    BeamRecords *st = nullptr;
+    unsigned short *st_tok = nullptr;                                  // TOK_LDS: the state's one copy of the token rows [W][cap]
+    if constexpr (CARRIED) {
+        st = reinterpret_cast<BeamRecords *>(p.state + (size_t)n * p.state_bytes);
+        st_tok = reinterpret_cast<unsigned short *>(st + 1);
+    }
     const float *rows = p.e + (long)n * p.sn;
     float *s_e = reinterpret_cast<float *>(dyn);                       // STAGED: [2][V]
     tok_t *tok;                                                        // [2][W][cap]
     if constexpr (TOK_LDS) tok = reinterpret_cast<tok_t *>(dyn + (STAGED ? 2 * (size_t)V * sizeof(float) : 0));
+    else if constexpr (CARRIED) tok = reinterpret_cast<tok_t *>(st + 1);
     else tok = reinterpret_cast<tok_t *>(p.ws) + (size_t)n * 2 * W * cap;
     auto tok_row = [&](int copy, int j) { return tok + ((size_t)copy * W + j) * cap; };
 
-    if (tid < BEAM_MAX) {                                              // the empty prefix: every alignment of no frames ends "in blank"
-        s_pb[0][tid] = tid == 0 ? 0.f : -INFINITY; s_pnb[0][tid] = -INFINITY; s_sc[0][tid] = tid == 0 ? 0.f : -INFINITY;
-        s_len[0][tid] = 0; s_last[0][tid] = 0; s_hash[0][tid] = HASH_EMPTY; s_hprev[0][tid] = 0u;
-        s_short[tid] = 0;
-        if (tid == 0) s_nb[0] = 1;
+    int cur = 0;
+    if (begin) {
+        if (tid < BEAM_MAX) {                                          // the empty prefix: every alignment of no frames ends "in blank"
+            s_pb[0][tid] = tid == 0 ? 0.f : -INFINITY; s_pnb[0][tid] = -INFINITY; s_sc[0][tid] = tid == 0 ? 0.f : -INFINITY;
+            s_len[0][tid] = 0; s_last[0][tid] = 0; s_hash[0][tid] = HASH_EMPTY; s_hprev[0][tid] = 0u;
+            s_short[tid] = 0;
+            if (tid == 0) s_nb[0] = 1;
+        }
+    } else if constexpr (CARRIED) {                                    // the beam the last launch left
+        if constexpr (!TOK_LDS) cur = st->copy & 1;                    // (the token rows stay where they are)
+        if (tid < BEAM_MAX) {
+            s_pb[cur][tid] = st->pb[tid]; s_pnb[cur][tid] = st->pnb[tid]; s_sc[cur][tid] = st->sc[tid];
+            // counts, lengths and tokens index memory: a state that no launch wrote (a row that never began) stays inside its own rows
+            s_len[cur][tid] = max(0, min(st->len[tid], cap)); s_last[cur][tid] = max(0, min(st->last[tid], V - 1));
+            s_hash[cur][tid] = st->hash[tid]; s_hprev[cur][tid] = st->hprev[tid];
+            s_short[tid] = 0;
+            if (tid == 0) s_nb[cur] = max(0, min(st->nb, W));
+        }
+        if constexpr (TOK_LDS) {
+            const int nb0 = min(st->nb, W);
+            for (int r = wave; r < nb0; r += BEAM_WAVES) {
+                const int lr = min(st->len[r], cap);
+                for (int x = lane; x < lr; x += 64) tok_row(0, r)[x] = st_tok[(size_t)r * cap + x];
+            }
+        }
     }
     if constexpr (STAGED)
         if (L > 0)
             for (int k = tid; k < V; k += BEAM_THREADS) s_e[k] = rows[k];
     __syncthreads();
 
-    int cur = 0;
     for (int t = 0; t < L; ++t) {
         const float *row = rows + (long)t * p.st;
         const int eb = (t & 1) * V;
@@ -216,12 +271,41 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_prefix_beam_kernel(const Ctc
         const int r = idx / cap, x = idx % cap;
         p.tokens[base * cap + idx] = (r < nb && x < s_len[cur][r]) ? (int64_t)tok_row(cur, r)[x] : -1;
     }
+    if constexpr (CARRIED) {                                           // the state, from the copy this launch ended on
+        if (tid < BEAM_MAX) {
+            const bool live = tid < nb;
+            st->pb[tid] = live ? s_pb[cur][tid] : -INFINITY; st->pnb[tid] = live ? s_pnb[cur][tid] : -INFINITY;
+            st->sc[tid] = live ? s_sc[cur][tid] : -INFINITY;
+            st->len[tid] = live ? s_len[cur][tid] : 0; st->last[tid] = live ? s_last[cur][tid] : 0;
+            st->hash[tid] = live ? s_hash[cur][tid] : HASH_EMPTY; st->hprev[tid] = live ? s_hprev[cur][tid] : 0u;
+            if (tid == 0) { st->nb = nb; st->copy = TOK_LDS ? 0 : cur; }
+        }
+        if constexpr (TOK_LDS) {
+            for (int r = wave; r < nb; r += BEAM_WAVES)
+                for (int x = lane; x < s_len[cur][r]; x += 64) st_tok[(size_t)r * cap + x] = tok_row(cur, r)[x];
+        }
+    }
 }
 
 bool tokens_in_lds(int V, int beam, int capacity) { return V <= 65536 && 2 * (long)beam * capacity <= TOK_LDS_TOKENS; }
 
 bool valid_shape(int N, int T, int V, int beam, int capacity) {
     return N > 0 && T > 0 && V >= 2 && V <= V_MAX && beam >= 1 && beam <= BEAM_MAX && capacity >= 1 && capacity <= T;
+}
+
+// the carried search: capacity is the longest hypothesis of the stream, whatever the frames of one launch
+bool valid_stream_shape(int V, int beam, int capacity) {
+    return V >= 2 && V <= V_MAX && beam >= 1 && beam <= BEAM_MAX && capacity >= 1 && capacity <= HALO_CTC_PREFIX_BEAM_MAX_CAPACITY;
+}
+
+template <bool CARRIED>
+void launch(const CtcPrefixBeamArgs &a, int N, bool staged, bool tok_lds, hipStream_t stream) {
+    const size_t lds = (staged ? 2 * (size_t)a.V * sizeof(float) : 0) + (tok_lds ? 2 * (size_t)a.W * a.cap * sizeof(unsigned short) : 0);
+    const dim3 grid((unsigned)N), block(BEAM_THREADS);
+    if (staged && tok_lds) hipLaunchKernelGGL((ctc_prefix_beam_kernel<true, true, CARRIED>), grid, block, lds, stream, a);
+    else if (staged) hipLaunchKernelGGL((ctc_prefix_beam_kernel<true, false, CARRIED>), grid, block, lds, stream, a);
+    else if (tok_lds) hipLaunchKernelGGL((ctc_prefix_beam_kernel<false, true, CARRIED>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((ctc_prefix_beam_kernel<false, false, CARRIED>), grid, block, lds, stream, a);
 }
 
 }  // namespace
@@ -243,12 +327,28 @@ int halo_ctc_prefix_beam(const float *emissions, long stride_t, long stride_n, i
     CtcPrefixBeamArgs a;
     a.e = emissions; a.st = stride_t; a.sn = stride_n; a.T = T; a.V = V; a.W = beam; a.cap = capacity; a.il = emission_lengths;
     a.ws = (int *)workspace; a.tokens = tokens; a.lengths = lengths; a.counts = counts; a.scores = scores;
-    const size_t lds = (staged ? 2 * (size_t)V * sizeof(float) : 0) + (tok_lds ? 2 * (size_t)beam * capacity * sizeof(unsigned short) : 0);
-    const dim3 grid((unsigned)N), block(BEAM_THREADS);
-    if (staged && tok_lds) hipLaunchKernelGGL((ctc_prefix_beam_kernel<true, true>), grid, block, lds, (hipStream_t)stream, a);
-    else if (staged) hipLaunchKernelGGL((ctc_prefix_beam_kernel<true, false>), grid, block, lds, (hipStream_t)stream, a);
-    else if (tok_lds) hipLaunchKernelGGL((ctc_prefix_beam_kernel<false, true>), grid, block, lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((ctc_prefix_beam_kernel<false, false>), grid, block, lds, (hipStream_t)stream, a);
+    a.nf = nullptr; a.flags = nullptr; a.state = nullptr; a.state_bytes = 0;
+    launch<false>(a, N, staged, tok_lds, (hipStream_t)stream);
+    return halo_launch_status();
+}
+
+size_t halo_ctc_prefix_beam_state_bytes(int V, int beam, int capacity) {
+    if (!valid_stream_shape(V, beam, capacity)) return 0;
+    const size_t rows = tokens_in_lds(V, beam, capacity) ? (size_t)beam * capacity * sizeof(unsigned short)
+                                                         : 2 * (size_t)beam * capacity * sizeof(int);
+    return sizeof(BeamRecords) + (rows + 15) / 16 * 16;
+}
+
+int halo_ctc_prefix_beam_advance(const float *emissions, long stride_t, long stride_n, int T, int N, int V, const int *n_frames,
+                                 const int *flags, int beam, int capacity, void *state, int64_t *tokens, int64_t *lengths, float *scores,
+                                 int64_t *counts, halo_stream_t stream) {
+    HALO_CHECK_ARG(emissions && state && tokens && lengths && scores && counts);
+    HALO_CHECK_ARG(N > 0 && T > 0 && valid_stream_shape(V, beam, capacity));
+    CtcPrefixBeamArgs a;
+    a.e = emissions; a.st = stride_t; a.sn = stride_n; a.T = T; a.V = V; a.W = beam; a.cap = capacity; a.il = nullptr;
+    a.ws = nullptr; a.tokens = tokens; a.lengths = lengths; a.counts = counts; a.scores = scores;
+    a.nf = n_frames; a.flags = flags; a.state = (unsigned char *)state; a.state_bytes = halo_ctc_prefix_beam_state_bytes(V, beam, capacity);
+    launch<true>(a, N, 2 * (long)V <= E_LDS_FLOATS, tokens_in_lds(V, beam, capacity), (hipStream_t)stream);
     return halo_launch_status();
 }
 

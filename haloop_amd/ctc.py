@@ -5,8 +5,9 @@ launch of the wave-per-utterance alpha kernel with the flags that reproduce that
 launch (csrc/viterbi.hip).
 
 ``ctc_prefix_beam_search`` is CTC prefix beam search with exact merging, n-best lists from CTC emissions in the format of
-``transducer.BeamDecoder.decode``: the whole batch in one launch (csrc/ctc_prefix_beam.hip).  ``haloop_amd.beam`` stays
-the reference's unmerged ha/beam.py."""
+``transducer.BeamDecoder.decode``: the whole batch in one launch (csrc/ctc_prefix_beam.hip).  ``PrefixBeamStream`` is
+the same search over emissions that arrive in chunks, its beam carried in device memory between calls.
+``haloop_amd.beam`` stays the reference's unmerged ha/beam.py."""
 import torch
 
 from . import _lib, ops
@@ -107,6 +108,64 @@ def ctc_prefix_beam_search(emissions, emission_lengths=None, beam=4, capacity=No
         em = em.contiguous()
     il = None if emission_lengths is None else emission_lengths.detach().to(em.device)
     return ops.ctc_prefix_beam(em, il, W, cap)
+
+
+class PrefixBeamStream:
+    """``ctc_prefix_beam_search`` over emissions that arrive in chunks (csrc/ctc_prefix_beam.hip): ``max_rows`` rows of
+    a width-``beam`` search whose beam survives between calls, so after every call the n-best list of a row is what
+    ``ctc_prefix_beam_search`` returns on the concatenation of the row's frames so far, bit for bit, at the cost of the new frames alone.
+    ``capacity`` is the longest hypothesis of a stream (1 .. ``ops.PREFIX_BEAM_MAX_CAPACITY``), whatever the length of a chunk.  The state
+    and the four outputs are allocated here, once.
+
+    advance(emissions [T, N, V], n_frames=None, begin=None): row n takes its first clamp(n_frames[n], 0, T) frames (a device int32 /
+        int64 tensor [N]; None: T) of the chunk, a strided view with a unit class stride read in place.  ``begin`` (a device bool / int32
+        tensor [N]; None: no row) starts a row from the empty prefix, whatever it held, before its frames.  A row with no frames and no
+        begin keeps its state and its n-best rows bit for bit.  Nothing is read from the device.  Returns (tokens [N, W, capacity],
+        lengths [N, W], scores [N, W], counts [N]) in ``ctc_prefix_beam_search``'s format as views of this object's buffers: the next
+        call overwrites them.  A row that never began holds no hypothesis (counts 0).
+    nbest(): copies of the same four.
+    Not differentiable: the inputs are detached."""
+
+    def __init__(self, max_rows, vocab_size, beam=4, capacity=256, device='cuda'):
+        N, V, W, cap = int(max_rows), int(vocab_size), int(beam), int(capacity)
+        if N < 1 or V < 2:
+            raise ValueError(f'PrefixBeamStream: max_rows {N} and vocab_size {V} must be at least 1 and 2')
+        if W < 1 or W > ops.BEAM_MAX:
+            raise ValueError(f'PrefixBeamStream: beam {W} outside 1 .. {ops.BEAM_MAX}')
+        if cap < 1 or cap > ops.PREFIX_BEAM_MAX_CAPACITY:
+            raise ValueError(f'PrefixBeamStream: capacity {cap} outside 1 .. {ops.PREFIX_BEAM_MAX_CAPACITY}')
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise _lib.HaloError('haloop_amd.ctc.PrefixBeamStream runs on the HIP device only (no CPU path)')
+        nbytes = ops.ctc_prefix_beam_state_bytes(V, W, cap)
+        if nbytes == 0:
+            raise ValueError(f'PrefixBeamStream: vocab_size {V} is more than the search takes')
+        self.max_rows, self.vocab_size, self.beam, self.capacity = N, V, W, cap
+        self.state = torch.zeros(N, nbytes, device=dev, dtype=torch.uint8)
+        self.tokens = torch.full((N, W, cap), -1, device=dev, dtype=torch.int64)
+        self.lengths = torch.full((N, W), -1, device=dev, dtype=torch.int64)
+        self.scores = torch.full((N, W), float('-inf'), device=dev, dtype=torch.float32)
+        self.counts = torch.zeros(N, device=dev, dtype=torch.int64)
+
+    def advance(self, emissions, n_frames=None, begin=None):
+        N, V = self.max_rows, self.vocab_size
+        if not torch.is_tensor(emissions) or emissions.dim() != 3 or emissions.shape[0] < 1 or tuple(emissions.shape[1:]) != (N, V):
+            raise ValueError(f'PrefixBeamStream.advance: emissions must be [T >= 1, {N}, {V}]')
+        for t, name, kinds in ((n_frames, 'n_frames', (torch.int32, torch.int64)), (begin, 'begin', (torch.bool, torch.int32))):
+            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (N,) or t.dtype not in kinds):
+                raise ValueError(f'PrefixBeamStream.advance: {name} must be a tensor [{N}] of ' + ' or '.join(str(k) for k in kinds))
+        if not emissions.is_cuda or any(t is not None and not t.is_cuda for t in (n_frames, begin)):
+            raise _lib.HaloError('haloop_amd.ctc.PrefixBeamStream runs on the HIP device only (no CPU path)')
+        em = emissions.detach().float()
+        if em.stride(-1) != 1:
+            em = em.contiguous()
+        nf = None if n_frames is None else n_frames.detach().clamp(0, em.shape[0]).to(torch.int32).contiguous()
+        flags = None if begin is None else (begin.detach() != 0).to(torch.int32).mul_(ops.STREAM_BEGIN)
+        ops.ctc_prefix_beam_advance(em, nf, flags, self.beam, self.capacity, self.state, self.tokens, self.lengths, self.scores, self.counts)
+        return self.tokens, self.lengths, self.scores, self.counts
+
+    def nbest(self):
+        return self.tokens.clone(), self.lengths.clone(), self.scores.clone(), self.counts.clone()
 
 
 def ctc_reduce_mean(losses, target_lengths):

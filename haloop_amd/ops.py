@@ -1476,6 +1476,39 @@ def ctc_prefix_beam(emissions, emission_lengths, beam, capacity):
     return tokens, lengths, scores, counts
 
 
+PREFIX_BEAM_MAX_CAPACITY = 8192  # HALO_CTC_PREFIX_BEAM_MAX_CAPACITY (include/halo.h)
+
+
+def ctc_prefix_beam_state_bytes(V, beam, capacity):
+    """Bytes of one row of the carried search's state; 0 for a shape the search does not take (include/halo.h)."""
+    return int(lib().halo_ctc_prefix_beam_state_bytes(V, beam, capacity))
+
+
+def ctc_prefix_beam_advance(emissions, n_frames, flags, beam, capacity, state, tokens, lengths, scores, counts):
+    """The carried CTC prefix beam search over one more chunk (include/halo.h: halo_ctc_prefix_beam_advance).  emissions [T, N, V] fp32
+    log-probabilities, any time and batch strides with a unit class stride; n_frames [N] int32 or None (T); flags [N] int32 (the
+    streaming flag bits, only STREAM_BEGIN is read) or None; state [N, ctc_prefix_beam_state_bytes(V, beam, capacity)] uint8.  The rows
+    that take part have their rows of state, tokens [N, beam, capacity] int64, lengths [N, beam] int64, scores [N, beam] f32 and counts
+    [N] int64 written in place.  Every tensor is the caller's: nothing is allocated."""
+    if emissions.dtype != torch.float32 or emissions.dim() != 3 or emissions.stride(-1) != 1 or not emissions.is_cuda:
+        raise ValueError('ctc_prefix_beam_advance: emissions must be a float32 HIP tensor of three dimensions with unit class stride')
+    T, N, V = emissions.shape
+    nbytes = ctc_prefix_beam_state_bytes(V, beam, capacity)
+    if nbytes == 0:
+        raise ValueError(f'ctc_prefix_beam_advance: V {V}, beam {beam}, capacity {capacity} outside what the search takes')
+    for t, dt, name in ((n_frames, torch.int32, 'n_frames'), (flags, torch.int32, 'flags')):
+        if t is not None and (t.dtype != dt or t.shape != (N,) or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError(f'ctc_prefix_beam_advance: {name} must be a contiguous {dt} HIP tensor [{N}]')
+    for t, dt, shape, name in ((state, torch.uint8, (N, nbytes), 'state'), (tokens, torch.int64, (N, beam, capacity), 'tokens'),
+                               (lengths, torch.int64, (N, beam), 'lengths'), (scores, torch.float32, (N, beam), 'scores'),
+                               (counts, torch.int64, (N,), 'counts')):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f'ctc_prefix_beam_advance: {name} must be a contiguous {dt} HIP tensor {list(shape)}')
+    check(lib().halo_ctc_prefix_beam_advance(ptr(emissions), emissions.stride(0), emissions.stride(1), T, N, V, ptr(n_frames), ptr(flags),
+                                             beam, capacity, ptr(state), ptr(tokens), ptr(lengths), ptr(scores), ptr(counts), _stream()),
+          'halo_ctc_prefix_beam_advance')
+
+
 # ---- edit distance and the risk of an n-best list (csrc/edit_distance.hip) -----------------------------------------------------------
 EDIT_DISTANCE_MAX_LEN = 1024     # HALO_EDIT_DISTANCE_MAX_LEN (include/halo.h)
 

@@ -24,12 +24,17 @@ that did not take part (``active`` False) are left bit-identical.  ``HALO_STREAM
 operators (``ops.subsample_fwd`` on the concatenated input, ``ops.gemm``, ``ops.log_softmax_fwd``, ``ops.ctc_greedy`` and torch
 operators for the merging), which is the comparator of tools/bench_streaming.py.  ``HALO_STREAM_GRAPH=1`` (or ``use_graph=True``)
 replays the push chain from one HIP graph.
+
+``beam=W`` (or ``HALO_STREAM_BEAM=W``, 1 .. 16) adds n-best partials: one more launch behind the head,
+``halo_ctc_prefix_beam_advance`` on the call's log-probs, carries a width-W CTC prefix beam per slot, so ``nbest()`` after every call
+is ``ctc.ctc_prefix_beam_search`` of the slot's log-probs so far.  The greedy path and ``last`` are unchanged by it.
 """
 import os
 
 import torch
 
 from . import _lib, ops
+from .ctc import PrefixBeamStream
 from .ops import NO_DROPOUT, STREAM_ACTIVE, STREAM_BEGIN, STREAM_FINAL
 from .rnn import lstm_param_list
 
@@ -46,15 +51,22 @@ class StreamingRecognizer:
         bools (or CPU bool tensors); ``active`` defaults to all slots, ``begin`` to none.
     finish(tail [B, <= chunk_frames - 1, F], tail_lengths, rows): the last frames of the slots in ``rows`` (B host-side bools like
         ``active``; default every open slot) and the convolution's right padding; the slots are closed and need ``begin`` again.
-    partial(): copies of (hyp [B, capacity] int64, hyp_len [B] int64, scores [B] fp32, steps [B] int64, truncated [B] bool).
+    partial(): copies of (hyp [B, capacity] int64, hyp_len [B] int64, scores [B] fp32, steps [B] int64, truncated [B] bool).  With a
+        beam these describe the best hypothesis of ``nbest()``: hyp is tokens[:, 0] with 0 past its length, and scores is that
+        hypothesis's log-mass -- the mass of every alignment of the prefix that the search kept, not the sum of the greedy path's step
+        scores; truncated[b] says that some member of slot b's beam has reached ``capacity`` (its extensions are refused from then on).
+    nbest(): with a beam, copies of (tokens [B, W, capacity] int64, lengths [B, W] int64, scores [B, W] fp32, counts [B] int64) in
+        ``ctc.ctc_prefix_beam_search``'s format; a closed slot stays readable until it begins again, a slot never begun holds no
+        hypothesis.  Without a beam: ValueError.
     last: (alignments [B, S] int64, step_scores [B, S] fp32, n_steps [B] int32[, log_probs [B, S, V]]) of the latest call, S =
         chunk_frames / 4 for a push and one more for a finish; alignments and step_scores are zeros past a row's n_steps (log_probs
         there mean nothing).  These are the recognizer's own buffers: the next call of the same kind overwrites them.
 
     Neither call reads from the device or waits for it (the flags travel through a ring of pinned host slots; a slot is waited for
-    only if the device is a whole ring of calls behind).  ``use_graph``: None reads HALO_STREAM_GRAPH (default off)."""
+    only if the device is a whole ring of calls behind).  ``use_graph``: None reads HALO_STREAM_GRAPH (default off).
+    ``beam``: None reads HALO_STREAM_BEAM (0 .. 16, default 0: the greedy object, launch for launch)."""
 
-    def __init__(self, encoder, recognizer, max_streams, chunk_frames=16, capacity=256, use_graph=None):
+    def __init__(self, encoder, recognizer, max_streams, chunk_frames=16, capacity=256, use_graph=None, beam=None):
         if encoder.training or recognizer.training:
             raise ValueError('StreamingRecognizer: put the encoder and the recognizer in eval mode')
         conv = encoder.subsample
@@ -70,6 +82,16 @@ class StreamingRecognizer:
             use_graph = os.environ.get('HALO_STREAM_GRAPH', '0') == '1'
         self.use_graph = bool(use_graph)
         self.fused = os.environ.get('HALO_STREAM_FUSED', '1') != '0'
+        if beam is None:
+            beam = os.environ.get('HALO_STREAM_BEAM', '0')
+        try:
+            self.beam = int(beam)
+        except ValueError:
+            raise ValueError(f'StreamingRecognizer: beam {beam!r} is not a number') from None
+        if not 0 <= self.beam <= ops.BEAM_MAX:
+            raise ValueError(f'StreamingRecognizer: beam {self.beam} outside 0 .. {ops.BEAM_MAX}')
+        if self.beam and self.capacity > ops.PREFIX_BEAM_MAX_CAPACITY:
+            raise ValueError(f'StreamingRecognizer: capacity {self.capacity} outside 1 .. {ops.PREFIX_BEAM_MAX_CAPACITY} with a beam')
         dev = conv.weight.device
         if dev.type != 'cuda':
             raise _lib.HaloError('haloop_amd.streaming.StreamingRecognizer runs on the HIP device only (no CPU path)')
@@ -99,6 +121,7 @@ class StreamingRecognizer:
             self._bufs[s] = dict(
                 y=torch.zeros(s, B, C, **f32), feats=torch.zeros(B, s, H, **f32), ali=torch.zeros(B, s, device=dev, dtype=torch.int64),
                 scores=torch.zeros(B, s, **f32), lp=torch.zeros(B, s, V, **f32), reserve=ops.lstm_reserve(s, B, C, H, L, dev))
+        self._beam = PrefixBeamStream(B, V, self.beam, self.capacity, device=dev) if self.beam else None
         self._state = [_NEVER] * B
         self._graphs = {}
         self._last = None
@@ -190,7 +213,17 @@ class StreamingRecognizer:
                    [(STREAM_ACTIVE | STREAM_FINAL) if r else 0 for r in rows], [t if r else 0 for r, t in zip(rows, lengths)])
 
     def partial(self):
-        return (self._hyp.clone(), self._hyp_len.clone(), self._score.clone(), self._steps.clone(), self._truncated.clone())
+        if self._beam is None:
+            return (self._hyp.clone(), self._hyp_len.clone(), self._score.clone(), self._steps.clone(), self._truncated.clone())
+        bm = self._beam
+        best, best_len = bm.tokens[:, 0], bm.lengths[:, 0].clamp(min=0)          # (-1: a slot that never began)
+        hyp = best.masked_fill(torch.arange(self.capacity, device=best.device)[None, :] >= best_len[:, None], 0)
+        return (hyp, best_len, bm.scores[:, 0].clone(), self._steps.clone(), (bm.lengths >= self.capacity).any(1))
+
+    def nbest(self):
+        if self._beam is None:
+            raise ValueError('StreamingRecognizer.nbest: constructed without a beam (beam=0)')
+        return self._beam.nbest()
 
     @property
     def last(self):
@@ -246,7 +279,15 @@ class StreamingRecognizer:
         hn, cn = self._lstm(buf['y'], S, buf)
         ops.stream_head(buf['feats'], cls.weight, cls.bias, self._n_steps, flags, hn, cn, self._h, self._c, buf['ali'], buf['scores'],
                         self._hyp, self._hyp_len, self._steps, self._score, self._last_label, self._truncated,
-                        lp_out=buf['lp'] if want_lp else None)
+                        lp_out=buf['lp'] if want_lp or self._beam is not None else None)
+        self._advance_beam(buf['lp'], flags)
+
+    def _advance_beam(self, lp, flags):
+        """The beam's launch on the call's log-probs [B, S, V], read in place as [S, B, V]: slot b takes its n_steps[b] steps."""
+        bm = self._beam
+        if bm is not None:
+            ops.ctc_prefix_beam_advance(lp.permute(1, 0, 2), self._n_steps, flags, bm.beam, bm.capacity, bm.state, bm.tokens, bm.lengths,
+                                        bm.scores, bm.counts)
 
     def _chain_general(self, frames, S, final, buf):
         """The same call on the general operators; the merging of the collapse and the choice of the state by torch operators."""
@@ -303,3 +344,4 @@ class StreamingRecognizer:
         buf['ali'].copy_(ali.masked_fill(~live, 0))
         buf['scores'].copy_(scores.masked_fill(~live, 0.0))
         buf['lp'].copy_(lp.masked_fill(~live[:, :, None], 0.0))
+        self._advance_beam(buf['lp'], flags)

@@ -1251,6 +1251,28 @@ int halo_ctc_prefix_beam(const float *emissions, long stride_t, long stride_n, i
                          int beam, int capacity, void *workspace, int64_t *tokens, int64_t *lengths, float *scores, int64_t *counts,
                          halo_stream_t stream);
 
+/* The same search with the beam carried between launches (haloop_amd/ctc.py PrefixBeamStream, streaming.py): a stream's
+ * frames arrive over any number of launches, and after each the n-best list of the frames so far is what halo_ctc_prefix_beam returns
+ * on their concatenation, bit for bit (one frame body, the same operations in the same order).
+ *   halo_ctc_prefix_beam_advance  row n takes its first clamp(n_frames[n], 0, T) frames of emissions [T][N][V] (NULL: T; strides as
+ *                          above, read in place).  flags [N]: the per-stream flags of the streaming launches (bit 0 active, bit 1 begin,
+ *                          bit 2 final), of which only begin is read; NULL: no row begins.  A beginning row starts from the empty prefix
+ *                          whatever its state held, then takes its frames.  A row with no frames and no begin is left bit-identical:
+ *                          its state row and its rows of the four outputs.  Every other row has its state row and its n-best rows
+ *                          written, in halo_ctc_prefix_beam's format; a row begun with no frames holds the empty hypothesis, score 0.
+ *                          state [N][halo_ctc_prefix_beam_state_bytes(V, beam, capacity)], opaque, the caller's to keep between
+ *                          launches of the same V, beam and capacity; a row needs no initialisation before it begins (zeros are an
+ *                          empty beam).  A row holds the beam's records (pb, pnb, score, length, last token, the two hashes), the
+ *                          member count and the token rows: 512 + 2 beam capacity bytes where the launch works on the token rows in LDS
+ *                          (V <= 65536 and 2 beam capacity <= 12288), else 512 + 8 beam capacity (the token rows rounded up to 16 bytes).  capacity is the longest hypothesis
+ *                          of the stream, independent of T: 1 <= capacity <= HALO_CTC_PREFIX_BEAM_MAX_CAPACITY (1 MiB + 512 bytes per row
+ *                          at beam 16).  Other limits as above; state_bytes is 0 for an invalid shape. */
+#define HALO_CTC_PREFIX_BEAM_MAX_CAPACITY 8192
+size_t halo_ctc_prefix_beam_state_bytes(int V, int beam, int capacity);
+int halo_ctc_prefix_beam_advance(const float *emissions, long stride_t, long stride_n, int T, int N, int V, const int *n_frames,
+                                 const int *flags, int beam, int capacity, void *state, int64_t *tokens, int64_t *lengths, float *scores,
+                                 int64_t *counts, halo_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * CTC prefix beam search with shallow fusion of an LSTM language model (haloop_amd/fusion.py CTCFusionDecoder; csrc/ctc_lm_beam.hip,
  * DESIGN.md 3.3q) as a launch sequence: per frame one halo_ctc_lm_beam_step, one halo_rnnt_lstm_cell per LSTM layer and one
