@@ -107,6 +107,7 @@ SIGNATURES = {
     'halo_set_lstm_bwd_mid_event': (_i, [_vp]),
     'halo_lstm_bwd_mid_event_recorded': (_i, []),
     'halo_set_lstm_expect_backward': (_i, [_i]),
+    'halo_set_lstm_bwd_from_fwd_images': (_i, [_i]),
     'halo_set_lstm_dx_slabs': (_i, [_i]),
     'halo_set_defer_small_jobs': (_i, [_i]),
     'halo_set_grad_sumsq': (_i, [_vp, _i]),
@@ -385,6 +386,11 @@ def weights_epoch():
 def set_lstm_expect_backward(on):
     """Whether a backward follows the LSTM forwards issued next (include/halo.h): inference switches it off."""
     check(lib().halo_set_lstm_expect_backward(int(bool(on))), 'halo_set_lstm_expect_backward')
+
+
+def set_lstm_bwd_from_fwd_images(on):
+    """The two-layer LSTM backward launch building its W^T fragments from the forward's weight images (include/halo.h) on / off."""
+    check(lib().halo_set_lstm_bwd_from_fwd_images(int(bool(on))), 'halo_set_lstm_bwd_from_fwd_images')
 
 
 def set_lstm_persistent_images(on):

@@ -132,6 +132,7 @@ __global__ __launch_bounds__(256) void sum_slabs_kernel(float *__restrict__ dy, 
 // rows [chunk * CH, +CH) of dy / y / col, 16 output channels, half of the K = F * ks columns.  dpre = dy * (y > 0 ? scale : 0) of its
 // rows x 16 channels goes to LDS (it is the A operand, read transposed: A[m = channel][k = row]); the B fragments B[k = row][n] are
 // read straight from col (4 rows x 16 columns = 4 x 64 contiguous bytes per wave instruction); fp32 MFMA 16x16x4, rows in order.
+// The tile's bias column sums are added row by row by 16 threads of the n-half 0 workgroup, inside the matrix loop, under its loads.
 // part[chunk][c][k] and bias_part[chunk][c] are summed over the chunks, in order, by subsample_bwd_reduce_kernel.
 // slabs > 1: dy is the sum of that many [rows][C] matrices slab_stride floats apart (halo_subsample_bwd_slabs).
 __global__ __launch_bounds__(256) void subsample_bwd_partial_kernel(const float *__restrict__ dy, const float *__restrict__ y,
@@ -142,30 +143,38 @@ __global__ __launch_bounds__(256) void subsample_bwd_partial_kernel(const float 
     const int chunk = blockIdx.x, c0 = blockIdx.y * 16, nh = blockIdx.z;
     const int row0 = chunk * CH, nrows = min(CH, rows - row0), CHP = (CH + 31) / 32 * 32;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lq = lane >> 4;
-    for (int u = threadIdx.x; u < CHP * 16; u += 256) {
-        const int r = u >> 4, c = u & 15;
-        float v = 0.f;
-        if (r < nrows) {
-            const long o = (long)(row0 + r) * C + c0 + c;
-            // dy left as K-slices by its producer: added in order, eight independent loads at a time
-            float g = dy[o];
-            for (int q0 = 1; q0 < slabs; q0 += 8) {
-                float gq[8];
+    // three elements per thread and round: their loads are unconditional (a row past the chunk reads the chunk's last row) and in flight
+    // together -- 6 elements per thread at B = 64 are two rounds of load latencies, not six
+    constexpr int NU = 3;
+    for (int u0 = threadIdx.x; u0 < CHP * 16; u0 += 256 * NU) {
+        long o[NU];
+        float g[NU], yv[NU];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) gq[q] = dy[o + min(q0 + q, slabs - 1) * slab_stride];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) g += q0 + q < slabs ? gq[q] : 0.f;
-            }
-            v = y[o] > 0.f ? g * scale : 0.f;
+        for (int j = 0; j < NU; ++j) {
+            const int r = (u0 + 256 * j) >> 4, c = threadIdx.x & 15;
+            o[j] = (long)(row0 + min(r, nrows - 1)) * C + c0 + c;
+            g[j] = dy[o[j]];
+            yv[j] = y[o[j]];
         }
-        dp[r * 17 + c] = v;
+        // dy left as K-slices by its producer: added in order, eight independent loads per element at a time
+        for (int q0 = 1; q0 < slabs; q0 += 8) {
+            float gq[NU][8];
+#pragma unroll
+            for (int j = 0; j < NU; ++j)
+#pragma unroll
+                for (int q = 0; q < 8; ++q) gq[j][q] = dy[o[j] + min(q0 + q, slabs - 1) * slab_stride];
+#pragma unroll
+            for (int j = 0; j < NU; ++j)
+#pragma unroll
+                for (int q = 0; q < 8; ++q) g[j] += q0 + q < slabs ? gq[j][q] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < NU; ++j) {
+            const int u = u0 + 256 * j, r = u >> 4, c = u & 15;
+            if (u < CHP * 16) dp[r * 17 + c] = r < nrows ? (yv[j] > 0.f ? g[j] * scale : 0.f) : 0.f;
+        }
     }
     __syncthreads();
-    if (nh == 0 && threadIdx.x < 16) {
-        float sum = 0.f;
-        for (int r = 0; r < nrows; ++r) sum += dp[r * 17 + threadIdx.x];
-        bias_part[(long)chunk * C + c0 + threadIdx.x] = sum;
-    }
     const int ntiles = K / 16, half = (ntiles + 1) / 2;
     const int t0 = nh == 0 ? 0 : half, t1 = nh == 0 ? half : ntiles;
     // this wave's n-tiles: t0 + wave, + 4, ... (at most 4 of them: K / 16 <= 32); a tile past the half is computed on the last valid
@@ -174,6 +183,7 @@ __global__ __launch_bounds__(256) void subsample_bwd_partial_kernel(const float 
     constexpr int MAXT = 4, KU = 8;
     f32x4 acc[MAXT];
     const float *cb[MAXT];
+    float bsum = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXT; ++i) {
         acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -189,11 +199,23 @@ __global__ __launch_bounds__(256) void subsample_bwd_partial_kernel(const float 
 #pragma unroll
             for (int i = 0; i < MAXT; ++i) b[u][i] = cb[i][ro];
         }
+        // the bias column sums of the tile ride under those loads: these 32 rows added in order, eight LDS reads at a time
+        if (nh == 0 && threadIdx.x < 16) {
+#pragma unroll
+            for (int j0 = 0; j0 < 4 * KU; j0 += 8) {
+                float v[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) v[q] = dp[(k0 + j0 + q) * 17 + threadIdx.x];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) bsum = k0 + j0 + q < nrows ? bsum + v[q] : bsum;
+            }
+        }
 #pragma unroll
         for (int u = 0; u < KU; ++u)
 #pragma unroll
             for (int i = 0; i < MAXT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[u][i], acc[i], 0, 0, 0);
     }
+    if (nh == 0 && threadIdx.x < 16) bias_part[(long)chunk * C + c0 + threadIdx.x] = bsum;
 #pragma unroll
     for (int i = 0; i < MAXT; ++i) {
         const int t = t0 + wave + 4 * i;
@@ -214,12 +236,20 @@ __global__ __launch_bounds__(256) void subsample_bwd_reduce_kernel(const float *
     }
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     float sum = 0.f;
-    if (i < CK) {
-        for (int q = 0; q < chunks; ++q) sum += part[(long)q * CK + i];
-        dw[i] = sum;
-    } else if (i - CK < C) {
-        for (int q = 0; q < chunks; ++q) sum += bias_part[(long)q * C + (i - CK)];
-        dbias[i - CK] = sum;
+    if (i < CK + C) {
+        // the chunks' partials, added in chunk order, eight independent loads at a time (chunks past the last: the last again, not added)
+        const bool w = i < CK;
+        const float *src = w ? part + i : bias_part + (i - CK);
+        const long stride = w ? CK : C;
+        for (int q0 = 0; q0 < chunks; q0 += 8) {
+            float v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] = src[min(q0 + q, chunks - 1) * stride];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) sum = q0 + q < chunks ? sum + v[q] : sum;
+        }
+        if (w) dw[i] = sum;
+        else dbias[i - CK] = sum;
     }
     if (ss) {           // the squared-norm partial of this block's 256 gradient elements (halo_set_grad_sumsq)
         const float q = wave_sum(sum * sum);

@@ -59,6 +59,8 @@ struct HaloCtx {
     int lstm_dx_slabs_left = 1;          // how many the last halo_lstm_bwd left unreduced there (1: dx itself)
     int lstm_expect_backward = 1;        // the two-layer forward also packs the backward's transposed weight images (halo_set_lstm_expect_backward)
     const float *packT_reserve = nullptr, *packT_w[3] = {nullptr, nullptr, nullptr};   // ... into this reserve, from these weights (host bookkeeping)
+    // ... or left them unwritten (halo_set_lstm_bwd_from_fwd_images): the backward launch then transposes its fragments out of these forward images
+    const char *packT_fwd[3] = {nullptr, nullptr, nullptr};
     const float *bwdflags_reserve = nullptr;   // ... and zeroed the backward launch's epoch words in this reserve (the backward then needs no prologue launch)
     const float *fwdT_src[2] = {nullptr, nullptr};
     const float *fwdT_reserve = nullptr;    // ... and in^T / W_ih^T of the pair's lower layer (the backward's operand launch then has nothing left to write)

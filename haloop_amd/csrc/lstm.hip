@@ -600,6 +600,8 @@ __global__ __launch_bounds__(256) void persist2_prologue_kernel(const Prologue2A
 // its two forward blocks (16 rows x 32 k each) straight from the registers it loaded, turns the tile through LDS and writes the two
 // transposed blocks (32 k x 16 columns each).  The backward of the same step then packs nothing (halo_lstm_bwd finds the images in the
 // reserve).  The states and the epoch words ride along in the tail blocks of the same launch.
+// tr[m] == nullptr: the transposed image of matrix m is not written (the backward launch builds its fragments from the forward image:
+// halo_lstm_persist2_bwd_from_fwd), and the launch moves a quarter fewer bytes per matrix.
 struct PackPairArgs {
     const float *w[3];
     char *fwd[3], *tr[3];
@@ -652,6 +654,7 @@ __global__ __launch_bounds__(256) void persist2_pack_pair_kernel(const PackPairA
     const float *w = a.w[m];
     const int i = lane & 15, kg = lane >> 4;
     const int g = R0 / H, jt = (R0 % H) / 16;
+    const bool with_tr = a.tr[m] != nullptr;                     // (wave-uniform)
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         const float *src = w + (long)(R0 + half * 16 + i) * H + C0 + kg * 8;
@@ -660,12 +663,15 @@ __global__ __launch_bounds__(256) void persist2_pack_pair_kernel(const PackPairA
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             hi[e] = (__bf16)v0[e]; hi[4 + e] = (__bf16)v1[e];
-            tile[wave][half * 16 + i][kg * 8 + e] = v0[e];
-            tile[wave][half * 16 + i][kg * 8 + 4 + e] = v1[e];
+            if (with_tr) {
+                tile[wave][half * 16 + i][kg * 8 + e] = v0[e];
+                tile[wave][half * 16 + i][kg * 8 + 4 + e] = v1[e];
+            }
         }
         *reinterpret_cast<bf16x8 *>(a.fwd[m] + (((long)(jt + half) * 4 + g) * nkb + C0 / 32) * 2048 + lane * 16) = hi;
     }
-    __builtin_amdgcn_wave_barrier();                             // the tile is this wave's own: LDS program order within the wave suffices
+    if (!with_tr) return;                                        // the backward launch transposes its own fragments out of the forward image
+    __builtin_amdgcn_wave_barrier();                            // the tile is this wave's own: LDS program order within the wave suffices
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -1382,7 +1388,12 @@ int lstm_fwd_persist2(const float *in, int in_dim, int lo, const float *const *w
         // a backward will follow (halo_set_lstm_expect_backward): its three transposed images come out of the same read of the weights
         float *wT = (float *)((char *)reserve + reserve_flags_offset(T, B, in0, H, L) + PERSIST_FLAG_BYTES);
         PackPairArgs pp;
-        for (int m = 0; m < 3; ++m) { pp.w[m] = pa.w[m]; pp.fwd[m] = (char *)pa.wdst[m]; pp.tr[m] = (char *)(wT + (size_t)m * 4 * H * H); }
+        // (not when the backward launch will transpose its own fragments out of the forward images: their place in the reserve stays unwritten)
+        const bool from_fwd = halo_lstm_persist2_bwd_from_fwd(T, B, H);
+        for (int m = 0; m < 3; ++m) {
+            pp.w[m] = pa.w[m]; pp.fwd[m] = (char *)pa.wdst[m]; pp.tr[m] = from_fwd ? nullptr : (char *)(wT + (size_t)m * 4 * H * H);
+            ctx.packT_fwd[m] = from_fwd ? (const char *)pa.wdst[m] : nullptr;
+        }
         pp.H = H;
         pp.tile_blocks = 3 * (4 * H / 32) * (H / 32) / 4;
         pp.rest = pa; pp.rest.w_units = 0;
@@ -1771,7 +1782,11 @@ int halo_lstm_bwd(const float *x, const float *const *w_ih, const float *const *
         const bool clean = have_T && ctx.bwdflags_reserve == reserve;
         ctx.bwdflags_reserve = nullptr;                        // one backward per forward finds them clean
         if (clean) flag_base = (char *)reserve_bwd_flags(reserve, T, B, in0, H, L);
-        if (have_T) {
+        // ... or only the forward images, out of which the launch then transposes its fragments itself
+        const bool from_fwd = have_T && ctx.packT_fwd[0] != nullptr;
+        if (from_fwd) {
+            wpT0 = (float *)ctx.packT_fwd[0]; wpT1 = (float *)ctx.packT_fwd[1]; wpTi = (float *)ctx.packT_fwd[2];
+        } else if (have_T) {
             float *wT = (float *)((char *)reserve + reserve_flags_offset(T, B, in0, H, L) + PERSIST_FLAG_BYTES);
             wpT0 = wT; wpT1 = wT + (size_t)4 * H * H; wpTi = wT + (size_t)8 * H * H;
         }
@@ -1796,6 +1811,7 @@ int halo_lstm_bwd(const float *x, const float *const *w_ih, const float *const *
         }
         Persist2Bwd a;
         a.wpT0 = (const char *)wpT0; a.wpT1 = (const char *)wpT1; a.wpTi = (const char *)wpTi;
+        a.from_fwd = from_fwd ? 1 : 0;
         a.dgp0 = (char *)dgp; a.dgp1 = (char *)dgp1;
         a.gates0 = l0.gates; a.gates1 = l1.gates; a.c0 = l0.c; a.c1 = l1.c;
         a.dc0 = dcarry; a.dc1 = dcarry1;

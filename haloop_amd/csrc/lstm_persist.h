@@ -112,6 +112,7 @@ struct Persist2Fwd {
 // mask applied), from one set of fragment loads.
 struct Persist2Bwd {
     const char *wpT0, *wpT1, *wpTi;   // packed W_hh0^T, W_hh1^T, W_ih1^T (tile jt, 4H/32 blocks; hi halves used)
+    int from_fwd;                     // wpT0 / wpT1 / wpTi are the FORWARD images instead (tile (jt, gate), H/32 blocks): the launch transposes its own fragments
     char *dgp0, *dgp1;                // packed gate-gradient images per layer [T][ceil(B/16)][4H/32] blocks
     float *gates0, *gates1;           // in: activated gates, out: gradients w.r.t. the pre-activations
     const float *c0, *c1;             // [T+1][B][H]
@@ -146,6 +147,9 @@ bool halo_lstm_persist2_ok(int T, int B, int H, int L);   // shape, arithmetic m
 // launches, which keep the epoch words)
 bool halo_lstm_persist2_dataflag();
 bool halo_lstm_persist2_fwd_armed(int T, int B, int H);
+// the two-layer backward of this shape builds its W^T fragments from the forward's weight images (halo_set_lstm_bwd_from_fwd_images; not the
+// interleaved launches): the packing launch of the forward then leaves the three transposed images unwritten
+bool halo_lstm_persist2_bwd_from_fwd(int T, int B, int H);
 void halo_lstm_persist2_enable(int on);
 void halo_lstm_interleave_enable(int on);
 int halo_lstm_persist2_fwd(const Persist2Fwd &a, hipStream_t st);

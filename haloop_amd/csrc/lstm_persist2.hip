@@ -443,8 +443,63 @@ __global__ __launch_bounds__(512, 2) void lstm_persist2_fwd_kernel(const Persist
 // fragment loads in waves 4-7; waves 0-3 contract layer 0's own gate gradients (image T-s+1 of dgp0) and, having half the matrix
 // work, pack and publish both layers' pieces and write the GEMM operand images.  As in the forward the halves run different loop
 // bodies with the same barriers.
+//
+// W^T fragments from the FORWARD images (FF; halo_set_lstm_bwd_from_fwd_images, default on).  The transposed images hold the forward
+// images' bf16 values, permuted, so the packing launch need not write them.  Forward block (jt', g, kb): lane l holds row g H + 16 jt' +
+// (l & 15), columns 32 kb + 8 (l >> 4) .. + 8.  Workgroup jt wants columns [16 jt, +16) of every gate row: lanes 32 (jt & 1) .. + 32 of
+// block (jt', g, jt / 2), one contiguous run of 512 bytes (16 rows x 16 columns).  K-block i of wave-quarter wq (gate rows wq H + 32 i
+// .. + 32: a quarter is one gate, KBW == H / 32) is the two runs of jt' = 2 i and 2 i + 1: the wave loads them as ONE 1 KiB access (lane
+// l: run l >> 5, row l & 15, columns 8 ((l >> 4) & 1) .. + 8), stores them as a [32 gate rows][16 columns] tile in its own KiB of LDS
+// and reads the tile back transposed (ds_read_b64_tr_b16, twice): lane (r = l & 15, kq = l >> 4) gets column r of rows 8 kq .. + 8,
+// which is lane l of block (jt, wq KBW + i) of the transposed image.  LDS instructions of one wave execute in order, so tile i + 1 is
+// stored behind the reads of tile i without a wait; sixteen loads of 1 KiB stay in flight, as in the plain prologue.
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+
+// byte offset of columns 8 half .. + 8 (16 bytes) of gate row krow in the staged tile of 32-byte rows.  The 4-row groups 2 and 3 (6 and 7)
+// are swapped, so that the two 16-lane groups of a 32-lane half (rows 8 apart) read different banks; the odd 4-row groups hold their two
+// column halves swapped, so that the eight lanes of a 16-byte store group (rows r .. r + 7 of one column half) cover all 32 banks.
+__device__ __forceinline__ int wT_tile_at(int krow, int half) {
+    const int qd = krow >> 2;
+    return ((qd ^ ((qd >> 1) & 1)) << 7) + ((krow & 3) << 5) + ((half ^ (qd & 1)) << 4);
+}
+// the staged tile is exchanged between the lanes of the wave: the compiler must keep the stores, the transposed reads and the next stores in order
+__device__ __forceinline__ void wT_tile_order() {
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
+}
+// fwdA (and fwdB when NIMG == 2: one ring of loads over both, no drain between them): forward images; stage: 1 KiB of LDS that is this
+// wave's own, 16-byte aligned; sink(n, fragment) for n = 0 .. NIMG KBW - 1 in order, fragment n of image n / KBW being k-block n % KBW.
+// Every lane of the wave must be active (the transposed read gathers across lanes).
+template <int KBW, int NIMG, typename Sink>
+__device__ __forceinline__ void wT_from_fwd(const char *fwdA, const char *fwdB, int jt, int wq, int lane, char *stage, Sink sink) {
+    constexpr int N = NIMG * KBW, RING = N < 16 ? N : 16;
+    constexpr long STEP = 8L * KBW * 2048;          // from jt' = 2 i to 2 i + 2: 2 tiles x 4 gates x KBW blocks
+    const long off = ((long)(((lane >> 5) * 4 + wq) * KBW + (jt >> 1))) * 2048 + (jt & 1) * 512 + (lane & 31) * 16;
+    const char *srcA = fwdA + off, *srcB = NIMG > 1 ? fwdB + off : nullptr;
+    auto load = [&](int n) { return *reinterpret_cast<const bf16x8 *>((n < KBW ? srcA : srcB) + (n % KBW) * STEP); };
+    char *st_at = stage + wT_tile_at((lane >> 5) * 16 + (lane & 15), (lane >> 4) & 1);
+    // lane 4 q + p of 16-lane group kq supplies the address of row 8 kq (+ 4) + q, columns 4 p .. + 4
+    const int kq = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+    lds_bf16x4 *rd0 = (lds_bf16x4 *)(stage + wT_tile_at(kq * 8 + q, p >> 1) + (p & 1) * 8);
+    lds_bf16x4 *rd1 = (lds_bf16x4 *)(stage + wT_tile_at(kq * 8 + 4 + q, p >> 1) + (p & 1) * 8);
+    bf16x8 ld[RING];
+#pragma unroll
+    for (int n = 0; n < RING; ++n) ld[n] = load(n);
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        *reinterpret_cast<bf16x8 *>(st_at) = ld[n % RING];
+        wT_tile_order();
+        const bf16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(rd0);
+        const bf16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(rd1);
+        wT_tile_order();
+        if (n + RING < N) ld[n % RING] = load(n + RING);
+        sink(n, bf16x8{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]});
+    }
+}
+
 struct Bwd2Shared {
-    float (*red)[4][256];             // [layer 0 recurrent | layer 1 recurrent | from layer 1 into layer 0][K-quarter]
+    float (*red)[4][256];            // [layer 0 recurrent | layer 1 recurrent | from layer 1 into layer 0][K-quarter]
     float (*dgbuf)[4][16][16];        // [layer][gate][batch row][hidden unit]
     int *s_abort;
     unsigned *s_published;
@@ -456,15 +511,19 @@ struct Bwd2Cell {
     __device__ __forceinline__ void update(float dh, float (&dg)[4]) { dcarry = persist2_bwd_cell(gv, cc, cprev, dcarry, dh, dg); }
 };
 
-template <int KC>
+template <int KC, bool FF>
 __device__ __forceinline__ void bwd2_layer0_waves(const Persist2Bwd &p, const Bwd2Shared sh, int jt, int bt, int wave, int lane, int u) {
     constexpr int KBW = 4 * KC, CH = 4, NCH = KBW / CH, NBUF = 3;     // three buffers of 4 fragments: 12 loads of 1 KiB in flight per wave
     const int wq = wave & 3;
     const int H = p.H, B = p.B, T = p.T, K = 4 * H;
     const int NJ = H / 16, NBT = (B + 15) / 16, nkb4 = K / 32, j0 = jt * 16;
     bf16x8 wr[KBW];                                  // K-quarter wq of W_hh0^T: columns j0..j0+15, k-blocks [wq*KBW, +KBW)
+    if (FF) {                                        // (wpT0: W_hh0's FORWARD image; red[0][wq] is this wave's own until barrier (A) of step 0)
+        wT_from_fwd<KBW, 1>(p.wpT0, nullptr, jt, wq, lane, reinterpret_cast<char *>(sh.red[0][wq]), [&](int i, bf16x8 f) { wr[i] = f; });
+    } else {
 #pragma unroll
-    for (int i = 0; i < KBW; ++i) wr[i] = *reinterpret_cast<const bf16x8 *>(p.wpT0 + ((long)jt * nkb4 + wq * KBW + i) * 2048 + lane * 16);
+        for (int i = 0; i < KBW; ++i) wr[i] = *reinterpret_cast<const bf16x8 *>(p.wpT0 + ((long)jt * nkb4 + wq * KBW + i) * 2048 + lane * 16);
+    }
     const int ci = u >> 4, cj = u & 15;
     const int b = bt * 16 + ci;
     const bool cell = b < B;
@@ -611,7 +670,7 @@ __device__ __forceinline__ void bwd2_layer0_waves(const Persist2Bwd &p, const Bw
     }
 }
 
-template <int KC>
+template <int KC, bool FF>
 __device__ __forceinline__ void bwd2_layer1_waves(const Persist2Bwd &p, const Bwd2Shared sh, char *wi_lds, int jt, int bt, int wave, int lane,
                                                   int u) {
     constexpr int KBW = 4 * KC, CH = 4, NCH = KBW / CH, NBUF = 3;     // three buffers of 4: 12 loads in flight (the registers also hold LDS fragments)
@@ -619,14 +678,28 @@ __device__ __forceinline__ void bwd2_layer1_waves(const Persist2Bwd &p, const Bw
     const int H = p.H, B = p.B, T = p.T, K = 4 * H;
     const int NBT = (B + 15) / 16, nkb4 = K / 32, j0 = jt * 16;
     bf16x8 wr[KBW];                                  // K-quarter wq of W_hh1^T
-#pragma unroll
-    for (int i = 0; i < KBW; ++i) wr[i] = *reinterpret_cast<const bf16x8 *>(p.wpT1 + ((long)jt * nkb4 + wq * KBW + i) * 2048 + lane * 16);
     char *my_wi = wi_lds + (long)wq * KBW * 1024 + lane * 16;                     // K-quarter wq of W_ih1^T: read back by this lane only
+    if (FF) {                                        // (wpT1, wpTi: the FORWARD images; red[1][wq] is this wave's own until barrier (A) of step 0)
+        bf16x8 pend[4];                              // four W_ih1^T fragments go to their slots together: one wait for their transposed reads
+        wT_from_fwd<KBW, 2>(p.wpT1, p.wpTi, jt, wq, lane, reinterpret_cast<char *>(sh.red[1][wq]), [&](int n, bf16x8 f) {
+            if (n < KBW) wr[n] = f;
+            else {
+                pend[n & 3] = f;
+                if ((n & 3) == 3) {
 #pragma unroll
-    for (int i = 0; i < KBW; ++i) {
-        *reinterpret_cast<bf16x8 *>(my_wi + i * 1024) =
-            *reinterpret_cast<const bf16x8 *>(p.wpTi + ((long)jt * nkb4 + wq * KBW + i) * 2048 + lane * 16);
-        if ((i & 15) == 15) __builtin_amdgcn_sched_barrier(0);     // sixteen fragments in flight at a time: W_hh1^T already fills half the registers
+                    for (int k = 0; k < 4; ++k) *reinterpret_cast<bf16x8 *>(my_wi + (n - KBW - 3 + k) * 1024) = pend[k];
+                }
+            }
+        });
+    } else {
+#pragma unroll
+        for (int i = 0; i < KBW; ++i) wr[i] = *reinterpret_cast<const bf16x8 *>(p.wpT1 + ((long)jt * nkb4 + wq * KBW + i) * 2048 + lane * 16);
+#pragma unroll
+        for (int i = 0; i < KBW; ++i) {
+            *reinterpret_cast<bf16x8 *>(my_wi + i * 1024) =
+                *reinterpret_cast<const bf16x8 *>(p.wpTi + ((long)jt * nkb4 + wq * KBW + i) * 2048 + lane * 16);
+            if ((i & 15) == 15) __builtin_amdgcn_sched_barrier(0);     // sixteen fragments in flight at a time: W_hh1^T already fills half the registers
+        }
     }
     const int ci = u >> 4, cj = u & 15;
     const int b = bt * 16 + ci;
@@ -734,9 +807,9 @@ __device__ __forceinline__ void bwd2_layer1_waves(const Persist2Bwd &p, const Bw
     }
 }
 
-template <int KC>
+template <int KC, bool FF>
 __global__ __launch_bounds__(512, 2) void lstm_persist2_bwd_kernel(const Persist2Bwd p) {
-    __shared__ float red[3][4][256];
+    __shared__ __attribute__((aligned(16))) float red[3][4][256];    // (FF: a wave's [l][wq] KiB also stages its W^T tiles ahead of step 0)
     __shared__ __attribute__((aligned(16))) float dgbuf[2][4][16][16];
     __shared__ int s_abort;
     __shared__ unsigned s_published;
@@ -751,8 +824,8 @@ __global__ __launch_bounds__(512, 2) void lstm_persist2_bwd_kernel(const Persist
     if (blockIdx.x == 0 && tid == 0 && p.abort_word != p.flags) __hip_atomic_store(p.abort_word, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (wave == 0) stamp(p.stamps, p.T + 1, 0, 14, lane);            // (diagnostic: launch entry / exit of this workgroup)
     const Bwd2Shared sh = {red, dgbuf, &s_abort, &s_published};
-    if (wave < 4) bwd2_layer0_waves<KC>(p, sh, jt, bt, wave, lane, tid & 255);
-    else bwd2_layer1_waves<KC>(p, sh, wi_lds, jt, bt, wave, lane, tid & 255);
+    if (wave < 4) bwd2_layer0_waves<KC, FF>(p, sh, jt, bt, wave, lane, tid & 255);
+    else bwd2_layer1_waves<KC, FF>(p, sh, wi_lds, jt, bt, wave, lane, tid & 255);
     if (wave == 0) stamp(p.stamps, p.T + 1, 0, 15, lane);
 }
 
@@ -798,6 +871,17 @@ bool halo_lstm_persist2_dataflag() {
     return on;
 }
 bool halo_lstm_persist2_fwd_armed(int T, int B, int H) { return halo_lstm_persist2_dataflag() && !pairs_for(T, B, H); }
+
+// the backward launch builds its W^T fragments from the forward images (lstm_persist2_bwd_kernel<KC, true>); the interleaved launches do not
+static int bwd_from_fwd_switch = -1;
+bool halo_lstm_persist2_bwd_from_fwd(int T, int B, int H) {
+    if (bwd_from_fwd_switch < 0) {
+        const char *e = getenv("HALO_LSTM_BWD_FROM_FWD");
+        bwd_from_fwd_switch = (e && e[0] == '0') ? 0 : 1;
+    }
+    return bwd_from_fwd_switch && !pairs_for(T, B, H);
+}
+extern "C" int halo_set_lstm_bwd_from_fwd_images(int on) { bwd_from_fwd_switch = on ? 1 : 0; return HALO_OK; }
 
 template <typename A, typename F, typename FX>
 int launch_groups(const A &a0, int steps, F launch_one, FX launch_pairs) {
@@ -849,12 +933,16 @@ int halo_lstm_persist2_bwd(const Persist2Bwd &a0, hipStream_t st) {
     const int kc = a0.H / 128;
     const int dyn = max(4 * 4 * kc * 1024, PERSIST_ONE_PER_CU_LDS);     // 4 quarters x KBW fragments of 1 KiB (at least: one workgroup per CU)
     return launch_groups(a0, a0.T + 1, [&](const Persist2Bwd &a, int blocks) {
-        switch (kc) {
-            case 2: return halo_persist_launch<lstm_persist2_bwd_kernel<2>>(a, blocks, dyn, st);
-            case 4: return halo_persist_launch<lstm_persist2_bwd_kernel<4>>(a, blocks, dyn, st);
-            case 6: return halo_persist_launch<lstm_persist2_bwd_kernel<6>>(a, blocks, dyn, st);
-            case 8: return halo_persist_launch<lstm_persist2_bwd_kernel<8>>(a, blocks, dyn, st);
+        switch (kc * 2 + (a.from_fwd ? 1 : 0)) {
+            case 4: return halo_persist_launch<lstm_persist2_bwd_kernel<2, false>>(a, blocks, dyn, st);
+            case 5: return halo_persist_launch<lstm_persist2_bwd_kernel<2, true>>(a, blocks, dyn, st);
+            case 8: return halo_persist_launch<lstm_persist2_bwd_kernel<4, false>>(a, blocks, dyn, st);
+            case 9: return halo_persist_launch<lstm_persist2_bwd_kernel<4, true>>(a, blocks, dyn, st);
+            case 12: return halo_persist_launch<lstm_persist2_bwd_kernel<6, false>>(a, blocks, dyn, st);
+            case 13: return halo_persist_launch<lstm_persist2_bwd_kernel<6, true>>(a, blocks, dyn, st);
+            case 16: return halo_persist_launch<lstm_persist2_bwd_kernel<8, false>>(a, blocks, dyn, st);
+            case 17: return halo_persist_launch<lstm_persist2_bwd_kernel<8, true>>(a, blocks, dyn, st);
             default: return (int)HALO_ENOTSUP;
         }
-    }, [&](const Persist2Bwd &a) { return halo_lstm_persist2x_bwd(a, st); });
+    }, [&](const Persist2Bwd &a) { return a.from_fwd ? (int)HALO_ENOTSUP : halo_lstm_persist2x_bwd(a, st); });    // (the interleaved launches read the transposed images)
 }

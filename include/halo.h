@@ -430,6 +430,11 @@ int halo_set_lstm_weights_stamp(uint64_t stamp);
  * backward's three transposed images from the same read of the weights, into the reserve, and halo_lstm_bwd called with that reserve
  * and those weight pointers packs nothing.  Inference callers switch it off (0): the forward then packs its own three only. */
 int halo_set_lstm_expect_backward(int on);
+/* The transposed images hold the forward images' bf16 values, permuted.  On (the default): that packing launch leaves them unwritten (a
+ * fifth fewer bytes) and the two-layer backward launch builds its W^T fragments from the forward images instead, transposing 16 x 16 tiles
+ * through LDS ahead of its first step.  Same fragments, same results.  Not for the interleaved launches (halo_set_lstm_interleave), which
+ * keep their images.  HALO_LSTM_BWD_FROM_FWD=0 / halo_set_lstm_bwd_from_fwd_images(0): six images, as before.  Process-wide. */
+int halo_set_lstm_bwd_from_fwd_images(int on);
 /* n > 1: the caller's dx buffer of the NEXT halo_lstm_bwd calls has room for n matrices [T*B][in0] and its consumer can add K-slices
  * (halo_subsample_bwd_slabs): the two-layer launch's input-gradient product (layer_begin = 0) may then leave up to n unreduced slices there
  * instead of running a reduce launch.  halo_lstm_dx_slabs_left() after the call says how many it left (1: dx is the gradient itself, as
