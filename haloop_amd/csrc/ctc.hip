@@ -3,6 +3,7 @@
 // shapes (2S+1 <= 64) the whole recursion is a single wavefront with no cross-wave traffic.
 #include <float.h>
 #include "halo_common.h"
+#include "ctc_head_dev.h"
 
 namespace {
 
@@ -19,8 +20,6 @@ struct CtcArgs {
     float *alpha;   // [N,T,2S+1]
     float *nll;     // [N]
 };
-
-__device__ __forceinline__ int ext_label(const int64_t *tg, int s) { return (s & 1) ? (int)tg[s >> 1] : 0; }
 
 __global__ void ctc_alpha_kernel(const CtcArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -156,7 +155,7 @@ __global__ void ctc_beta_grad_kernel(const CtcBwdArgs p) {
         }
         __syncthreads();
         for (int c = threadIdx.x; c < p.C; c += blockDim.x) {
-            // log-sum over the states that emit class c
+            // log-sum over the states that emit class c (libm: the fast form is ctc_head_dev.h's class_log_sum_fast)
             float m = ninf;
             if (c == 0) { for (int s = 0; s < states; s += 2) m = fmaxf(m, ab[s]); }
             else        { for (int s = 1; s < states; s += 2) if ((int)tg[s >> 1] == c) m = fmaxf(m, ab[s]); }
@@ -179,18 +178,7 @@ __global__ void ctc_beta_grad_kernel(const CtcBwdArgs p) {
 // The utterance's [T,C] log-prob rows are staged into LDS once; the lattice row lives in registers,
 // one state per lane, and the s-1 / s-2 (s+1 / s+2) neighbours come from wave shuffles, so the
 // T-step recursion has no memory round trips in its dependency chain.
-
-// log(e^a + e^b) on the hardware exp2/log2 units (v_exp_f32 / v_log_f32): ~1e-7 absolute error per call,
-// an order below the lattice's own fp32 rounding over T steps; the serial chain is ~10x shorter than
-// with the libm-accurate expf/log1pf, which is what bounds a one-wave-per-utterance recursion.  Measured against float64
-// (tests/test_gpu_ctc_f64.py): at T = 480, 63 states, the wave forward's 1600-nat loss comes out 6.6e-4 off; at T = 70 and T = 32 both wave
-// kernels are 1.4e-5 (losses) and 2e-5 (gradients) off -- to the printed digit what a float32 run of the same recursion with libm loses,
-// so the fast forms add nothing measurable.
-__device__ __forceinline__ float log_add_exp_fast(float a, float b) {
-    if (isinf(a) && a == b) return a;
-    const float m = fmaxf(a, b);
-    return m + __logf(1.0f + __expf(-fabsf(a - b)));
-}
+// (log_add_exp_fast: ctc_head_dev.h)
 
 __global__ __launch_bounds__(64) void ctc_alpha_wave_kernel(const CtcArgs p) {
     extern __shared__ __attribute__((aligned(16))) float lp_s[];   // [T*C]
@@ -292,19 +280,8 @@ __global__ __launch_bounds__(256) void ctc_beta_grad_wave_kernel(const CtcBwdArg
         const int t = idx / C, c = idx % C;
         float g = 0.f;
         if (t < il) {
-            const float *row = ab + t * S_;
-            float m = ninf;
-            if (c == 0) { for (int s = 0; s < states; s += 2) m = fmaxf(m, row[s]); }
-            else        { for (int s = 1; s < states; s += 2) if ((int)tg[s >> 1] == c) m = fmaxf(m, row[s]); }
-            float lcab = ninf;
-            if (m > ninf) {
-                float sum = 0.f;
-                if (c == 0) { for (int s = 0; s < states; s += 2) sum += __expf(row[s] - m); }
-                else        { for (int s = 1; s < states; s += 2) if ((int)tg[s >> 1] == c) sum += __expf(row[s] - m); }
-                lcab = m + __logf(sum);
-            }
-            const float l = lp_s[idx];
-            g = (__expf(l) - __expf(lcab + nll - l)) * go;
+            const float lcab = class_log_sum_fast(ab + t * S_, tg, states, c);
+            g = grad_at_log_prob_fast(lp_s[idx], lcab, nll, go);
         }
         grad[(long)t * p.gstride_t + c] = g;
     }

@@ -13,7 +13,7 @@
 #include <float.h>
 #include "halo_common.h"
 #include "halo_internal.h"
-#include "lstm_persist_dev.h"
+#include "ctc_head_dev.h"
 #include <type_traits>
 
 namespace {
@@ -27,30 +27,6 @@ __device__ unsigned long long g_head_stamps[2][1024][16];
 #endif
 
 constexpr int NW = 16;                   // waves per workgroup: K-slices of the H-deep contraction / column tiles of the H-wide outputs
-constexpr int LDT = 33;                  // padded leading dimension of the [32][32] tiles in LDS
-
-__device__ __forceinline__ float log_add_exp_fast2(float a, float b) {       // as ctc.hip's wave kernels
-    if (isinf(a) && a == b) return a;
-    const float m = fmaxf(a, b);
-    return m + __logf(1.0f + __expf(-fabsf(a - b)));
-}
-__device__ __forceinline__ int ext_label2(const int64_t *tg, int s) { return (s & 1) ? (int)tg[s >> 1] : 0; }
-// log(e^a + e^b + e^c) the way ATen's CTC loss writes it (max, three exponentials, one log: LossCTC.cpp): the exponentials are
-// independent, so a lattice step pays one exp and one log latency instead of two of each.  All -inf -> -inf.
-__device__ __forceinline__ float log_add_exp_fast3(float a, float b, float c) {
-    const float m = fmaxf(a, fmaxf(b, c));
-    if (m == -INFINITY) return -INFINITY;
-    return m + __logf(__expf(a - m) + __expf(b - m) + __expf(c - m));
-}
-// the whole wave shifted by one lane on the VALU (DPP wave_shr:1 / wave_shl:1) instead of through the LDS crossbar of a
-// ds_bpermute-based __shfl_up / __shfl_down; lane 0 (63) keeps `x` itself, like the shuffles
-__device__ __forceinline__ float wave_up1(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, x), __builtin_bit_cast(int, x), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float wave_down1(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, x), __builtin_bit_cast(int, x), 0x130, 0xf, 0xf, false));
-}
-
 struct HeadFwdArgs {
     const float *feats, *w, *bias;
     DropoutCfg drop;
@@ -65,12 +41,6 @@ struct HeadFwdArgs {
     float *scores;
     int B, T, H, V, S, ks, stride, pad;
 };
-
-__device__ __forceinline__ int feature_length(long il, int ks, int stride, int pad, int T) {
-    const float o = (float)(il + 2 * pad - ks);
-    const int f = (int)floorf(o / (float)stride + 1.0f);          // float arithmetic like ha/rnn.py:13-18
-    return max(0, min(f, T));
-}
 
 constexpr int KC = 256;                  // K-chunk staged through LDS per pass
 constexpr int LDK = KC + 1;              // row stride in floats: lanes (row r, k) hit bank (r + k) % 32 -> conflict-free fragment reads
@@ -132,7 +102,7 @@ __global__ __launch_bounds__(1024) void ctc_head_fwd_kernel(const HeadFwdArgs p)
     }
     HST(0, 1);
 #pragma unroll
-    for (int e = 0; e < 16; ++e) red[wave * 1024 + ((e & 3) + 8 * (e >> 2) + 4 * kh) * 32 + r] = acc[e];
+    for (int e = 0; e < 16; ++e) red[wave * 1024 + acc_row(e, kh) * 32 + r] = acc[e];
     __syncthreads();
     {
         const int i = tid >> 5, j = tid & 31;
@@ -145,14 +115,7 @@ __global__ __launch_bounds__(1024) void ctc_head_fwd_kernel(const HeadFwdArgs p)
     // ---- log-softmax over the classes: 32 lanes per frame ----
     {
         const int i = tid >> 5, j = tid & 31;
-        const float x = tile[i][j];
-        float m = x;
-#pragma unroll
-        for (int d = 16; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 32));
-        float s = j < V ? expf(x - m) : 0.f;
-#pragma unroll
-        for (int d = 16; d >= 1; d >>= 1) s += __shfl_xor(s, d, 32);
-        const float lpv = x - m - logf(s);
+        const float lpv = log_softmax32(tile[i][j], j < V);
         __syncthreads();
         tile[i][j] = lpv;
         if (p.lp && i < T && j < V) p.lp[((long)n * T + i) * V + j] = lpv;
@@ -160,32 +123,10 @@ __global__ __launch_bounds__(1024) void ctc_head_fwd_kernel(const HeadFwdArgs p)
     __syncthreads();
     HST(0, 2);
     if (GREEDY) {
-        // one lane per frame (T <= 32): arg max over the classes (first maximum, like torch.max), then unique_consecutive + drop blanks
-        if (wave == 0) {
-            const int t = lane;
-            int best = -1;
-            float bv = -INFINITY;
-            if (t < T) {
-                best = 0; bv = tile[t][0];
-                for (int c = 1; c < V; ++c) {
-                    const float v = tile[t][c];
-                    if (v > bv) { bv = v; best = c; }
-                }
-                p.ali[(long)n * T + t] = best;
-                p.scores[(long)n * T + t] = bv;
-            }
-            int left = __shfl_up(best, 1, 64);
-            if (lane == 0) left = -1;
-            const bool keep = (t < T) && best != left && best != 0;
-            const unsigned long long mask = __ballot(keep);
-            const int pos = __popcll(mask & ((1ull << lane) - 1ull)), count = __popcll(mask);
-            if (keep) p.hyp[(long)n * T + pos] = best;
-            if (t < T && t >= count) p.hyp[(long)n * T + t] = 0;          // the padding the separate fill launch wrote
-            if (lane == 0) p.hyp_len[n] = count;
-        }
+        if (wave == 0) greedy_collapse(tile, n, T, V, lane, p.ali, p.scores, p.hyp, p.hyp_len);
         return;
     }
-    // ---- CTC alpha (F.ctc_loss semantics, as ctc_alpha_wave_kernel with flags 0), wave 0: one lattice state per lane ----
+    // ---- CTC alpha (F.ctc_loss semantics; which recursion lives where: ctc_head_dev.h), wave 0: one lattice state per lane ----
     if (wave == 0) {
         const int S_ = 2 * p.S + 1;
         const int64_t *tg = p.targets + (long)n * p.tg_stride;
@@ -193,7 +134,7 @@ __global__ __launch_bounds__(1024) void ctc_head_fwd_kernel(const HeadFwdArgs p)
         const int tl = max(0, min((int)p.tl[n], p.S));
         const int states = 2 * tl + 1;
         float *alpha = p.alpha + (long)n * T * S_;
-        const int lab = lane < S_ ? ext_label2(tg, lane) : 0;
+        const int lab = lane < S_ ? ext_label(tg, lane) : 0;
         const int lab2 = __shfl_up(lab, 2, 64);
         const bool can_skip = lane >= 2 && lab != 0 && lab != lab2;
         const int tlast = il - 1, slast = 2 * tl, sprev = tl > 0 ? 2 * tl - 1 : -1;
@@ -216,33 +157,13 @@ __global__ __launch_bounds__(1024) void ctc_head_fwd_kernel(const HeadFwdArgs p)
             if (t == tlast) { ra = __shfl(prev, slast, 64); rb = sprev >= 0 ? __shfl(prev, sprev, 64) : -INFINITY; }
         }
         HST(0, 3);
-        unsigned old = 0;
-        if (lane == 0) {
-            const float out = il == 0 ? (tl == 0 ? 0.f : INFINITY) : -log_add_exp_fast2(ra, rb);
-            // nll travels to the workgroup that finishes last: write-through store, drained, then the ticket (Guideline 16 R1)
-            __hip_atomic_store(p.nll + n, out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const float out = il == 0 ? (tl == 0 ? 0.f : INFINITY) : -log_add_exp_fast(ra, rb);
+        const bool last = loss_ticket(p.nll, n, out, p.ticket, p.B, lane, [&] {
             p.flen[n] = il;
             p.grad_out[n] = 1.0f / (fmaxf((float)p.tl[n], 1.0f) * (float)p.B);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            old = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        old = __builtin_amdgcn_readfirstlane(old);
+        });
         HST(0, 4);
-        if (old == (unsigned)p.B - 1u) {
-            // reduction='mean' (ha/recognizer.py:71): mean_n(nll[n] / max(tl[n], 1)); the whole wave loads (one utterance per lane and
-            // pass), partial sums combine in a fixed order
-            float s = 0.f;
-            for (int i0 = 0; i0 < p.B; i0 += 64) {
-                const int i = i0 + lane;
-                float v = 0.f;
-                if (i < p.B) v = __hip_atomic_load(p.nll + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / fmaxf((float)p.tl[i], 1.0f);
-                s += wave_sum(v);
-            }
-            if (lane == 0) {
-                *p.loss = s / (float)p.B;
-                __hip_atomic_store(p.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next call
-            }
-        }
+        if (last) loss_mean_last(p.nll, p.tl, p.B, p.loss, p.ticket, lane);
     }
 }
 
@@ -307,8 +228,8 @@ __global__ __launch_bounds__(512) void ctc_head_bwd_kernel(const HeadBwdArgs p) 
     __syncthreads();
     HST(1, 1);
     const float nll = p.nll[n], go = p.grad_out[n];
-    if (wave == 0 && il > 0) {            // beta recursion, one state per lane (as ctc_beta_grad_wave_kernel)
-        const int lab = lane < S_ ? ext_label2(tg, lane) : 0;
+    if (wave == 0 && il > 0) {            // beta recursion, one state per lane
+        const int lab = lane < S_ ? ext_label(tg, lane) : 0;
         const int labn2 = __shfl_down(lab, 2, 64);
         const bool can_skip = lane + 2 < states && labn2 != 0 && labn2 != lab;
         float nxt = -INFINITY;
@@ -335,23 +256,10 @@ __global__ __launch_bounds__(512) void ctc_head_bwd_kernel(const HeadBwdArgs p) 
         const int t = u >> 5, c = u & 31;
         float g = 0.f;
         if (t < il && c < V) {
-            const float *row = ab[t];
-            float m = -INFINITY;
-            if (c == 0) { for (int s = 0; s < states; s += 2) m = fmaxf(m, row[s]); }
-            else        { for (int s = 1; s < states; s += 2) if ((int)tg[s >> 1] == c) m = fmaxf(m, row[s]); }
-            float lcab = -INFINITY;
-            if (m > -INFINITY) {
-                float sum = 0.f;
-                if (c == 0) { for (int s = 0; s < states; s += 2) sum += __expf(row[s] - m); }
-                else        { for (int s = 1; s < states; s += 2) if ((int)tg[s >> 1] == c) sum += __expf(row[s] - m); }
-                lcab = m + __logf(sum);
-            }
-            const float l = lps[t][c];
-            g = (__expf(l) - __expf(lcab + nll - l)) * go;
+            const float lcab = class_log_sum_fast(ab[t], tg, states, c);
+            g = grad_at_log_prob_fast(lps[t][c], lcab, nll, go);
         }
-        float gs = g;
-#pragma unroll
-        for (int d = 16; d >= 1; d >>= 1) gs += __shfl_xor(gs, d, 32);
+        const float gs = sum32(g);
         if (t < T && c < V) dl[t][c] = g - expf(lps[t][c]) * gs;
     }
     __syncthreads();
@@ -375,7 +283,7 @@ __global__ __launch_bounds__(512) void ctc_head_bwd_kernel(const HeadBwdArgs p) 
             for (int s = 0; s < 16; ++s) dx = __builtin_amdgcn_mfma_f32_32x32x2f32(dl[r][2 * s + kh], wv[s], dx, 0, 0, 0);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = (e & 3) + 8 * (e >> 2) + 4 * kh;
+                const int row = acc_row(e, kh);
                 if (row < T) {
                     float v = dx[e];
                     if (p.drop.threshold) v *= mask_s[row * Hs + m0 + r];
@@ -399,7 +307,7 @@ __global__ __launch_bounds__(512) void ctc_head_bwd_kernel(const HeadBwdArgs p) 
             for (int s = 0; s < 16; ++s) dwp = __builtin_amdgcn_mfma_f32_32x32x2f32(dl[2 * s + kh][r], fv[s], dwp, 0, 0, 0);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = (e & 3) + 8 * (e >> 2) + 4 * kh;
+                const int row = acc_row(e, kh);
                 if (row < V) p.dw_part[((long)n * V + row) * H + c0 + r] = dwp[e];
             }
         }
@@ -438,7 +346,6 @@ struct HeadTrainArgs {
 };
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-constexpr int TNW = 8, TNT = 64 * TNW;    // 512 threads: 256 VGPRs per lane hold two passes of fragments and two prefetched product tiles
 
 __global__ __launch_bounds__(TNT) void ctc_head_train_kernel(const HeadTrainArgs p) {
     extern __shared__ __attribute__((aligned(16))) float dynt[];      // [red: TNW x 1024 floats][mask: 32 x Hs bytes]
@@ -484,7 +391,8 @@ __global__ __launch_bounds__(TNT) void ctc_head_train_kernel(const HeadTrainArgs
     load_job(min(wave, njobs - 1), pre0);
     load_job(min(wave + TNW, njobs - 1), pre1);
     // ---- partial logits over this slice's K range: wave w takes k-steps (16 deep) w, w + 8, ..., two per pass; lane (r, kh) loads
-    //      elements 8 kh .. 8 kh + 7 of row r of both operands (the MFMA's own layout) and draws the row's mask under the loads ----
+    //      elements 8 kh .. 8 kh + 7 of row r of both operands (the MFMA's own layout) and draws the row's mask under the loads
+    //      (ctc_head_dev.h's head_logits_x3 with the Philox draw between its loads and its MFMAs: sharing it moved this kernel's registers) ----
     f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
@@ -538,17 +446,12 @@ __global__ __launch_bounds__(TNT) void ctc_head_train_kernel(const HeadTrainArgs
     const int il = feature_length(p.il[n], p.ks, p.stride, p.pad, T);
     const int tl = max(0, min((int)p.tl[n], p.S));
     const int states = 2 * tl + 1;
-    if (tid < 64) lab_s[tid] = tid < S_ ? ext_label2(tg, tid) : 0;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) red[wave * 1024 + ((e & 3) + 8 * (e >> 2) + 4 * kh) * 32 + r] = acc[e];
+    if (tid < 64) lab_s[tid] = tid < S_ ? ext_label(tg, tid) : 0;
+    head_put_acc(acc, red, wave, r, kh);
     __syncthreads();
     float sum[2];
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        sum[q] = 0.f;
-#pragma unroll
-        for (int w = 0; w < TNW; ++w) sum[q] += red[w * 1024 + tid + TNT * q];
-    }
+    for (int q = 0; q < 2; ++q) sum[q] = head_sum_waves(red, q);
     HST(0, 2);
     if (SL > 1) {
         // the slices' partial sums meet in global memory.  Every value travels as the 8-byte pair (value, epoch of this launch): one
@@ -615,16 +518,7 @@ __global__ __launch_bounds__(TNT) void ctc_head_train_kernel(const HeadTrainArgs
     {
         float lpv[2];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const float x = tile[(tid >> 5) + 16 * q][tj];
-            float m = x;
-#pragma unroll
-            for (int d = 16; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 32));
-            float s = tj < V ? expf(x - m) : 0.f;
-#pragma unroll
-            for (int d = 16; d >= 1; d >>= 1) s += __shfl_xor(s, d, 32);
-            lpv[q] = x - m - logf(s);
-        }
+        for (int q = 0; q < 2; ++q) lpv[q] = log_softmax32(tile[(tid >> 5) + 16 * q][tj], tj < V);
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -721,12 +615,9 @@ __global__ __launch_bounds__(TNT) void ctc_head_train_kernel(const HeadTrainArgs
                     for (unsigned bits = cmask[c]; bits; bits &= bits - 1u) sm += al[t][2 * (__builtin_ctz(bits)) + 1];
                 }
                 const float lcab = sm > 0.f ? (be[t][64] + __builtin_amdgcn_logf(sm)) * LN2 : -INFINITY;
-                const float l = tile[t][c];
-                g = (__expf(l) - __expf(lcab + nll - l)) * go;
+                g = grad_at_log_prob_fast(tile[t][c], lcab, nll, go);
             }
-            float gs = g;
-#pragma unroll
-            for (int d = 16; d >= 1; d >>= 1) gs += __shfl_xor(gs, d, 32);
+            const float gs = sum32(g);
             if (t < T && c < V) dl[t][c] = g - expf(tile[t][c]) * gs;
         }
     }
@@ -746,7 +637,7 @@ __global__ __launch_bounds__(TNT) void ctc_head_train_kernel(const HeadTrainArgs
             const unsigned char *mcol = mk + m0 + r;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int row = isw ? (i & 3) + 8 * (i >> 2) + 4 * kh : 16 * (i >> 3) + 8 * kh + (i & 7);
+                const int row = isw ? acc_row(i, kh) : 16 * (i >> 3) + 8 * kh + (i & 7);
                 mb[i] = mcol[min(row, T - 1) * Hs];
             }
         } else {
@@ -775,7 +666,7 @@ __global__ __launch_bounds__(TNT) void ctc_head_train_kernel(const HeadTrainArgs
         }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int rowc = (e & 3) + 8 * (e >> 2);                 // + 4 kh: the accumulator element's row; beyond T / V: beyond the descriptor
+            const int rowc = acc_row(e, 0);                          // + 4 kh: the accumulator element's row; beyond T / V: beyond the descriptor
             const int off = lane_o + rowc * H * 4 + ti * 128;
             const float ov = isw ? (mb[e] ? o[e] * drop.scale : 0.f) : o[e];      // (a scalar first: bit_cast of a vector ELEMENT reads element 0)
             if (isw) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ov), df_rs, off, 0, 0);
@@ -799,30 +690,10 @@ __global__ __launch_bounds__(TNT) void ctc_head_train_kernel(const HeadTrainArgs
     }
     HST(0, 7);
     }   // (!failed)
-    // ---- the utterance's loss terms and, in the workgroup that finishes last, the mean (as ctc_head_fwd_kernel) ----
-    if (y == 0 && wave == 0) {
-        unsigned old = 0;
-        if (lane == 0) {
-            __hip_atomic_store(p.nll + n, s_nll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            p.flen[n] = il;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            old = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        old = __builtin_amdgcn_readfirstlane(old);
-        if (old == (unsigned)p.B - 1u) {
-            float s = 0.f;
-            for (int i0 = 0; i0 < p.B; i0 += 64) {
-                const int i = i0 + lane;
-                float v = 0.f;
-                if (i < p.B) v = __hip_atomic_load(p.nll + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / fmaxf((float)p.tl[i], 1.0f);
-                s += wave_sum(v);
-            }
-            if (lane == 0) {
-                *p.loss = s / (float)p.B;
-                __hip_atomic_store(p.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(p.ticket + 1, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+    // ---- the utterance's loss terms and, in the workgroup that finishes last, the mean and the launch count ----
+    if (y == 0 && wave == 0 && loss_ticket(p.nll, n, s_nll, p.ticket, p.B, lane, [&] { p.flen[n] = il; })) {
+        loss_mean_last(p.nll, p.tl, p.B, p.loss, p.ticket, lane);
+        if (lane == 0) __hip_atomic_store(p.ticket + 1, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -836,58 +707,13 @@ __global__ __launch_bounds__(TNT) void ctc_head_greedy2_kernel(const HeadFwdArgs
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int T = p.T, H = p.H, V = p.V;
     const int r = lane & 31, kh = lane >> 5;
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    const int nks = H / 16;
-    const long frow = ((long)n * T + min(r, T - 1)) * H, wrow = (long)min(r, V - 1) * H;
-    for (int i0 = wave; i0 < nks; i0 += 2 * TNW) {
-        f32x4 fa[2][2], wb[2][2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int kb = 16 * min(i0 + TNW * u, nks - 1) + 8 * kh;
-            fa[u][0] = *reinterpret_cast<const f32x4 *>(p.feats + frow + kb);
-            fa[u][1] = *reinterpret_cast<const f32x4 *>(p.feats + frow + kb + 4);
-            wb[u][0] = *reinterpret_cast<const f32x4 *>(p.w + wrow + kb);
-            wb[u][1] = *reinterpret_cast<const f32x4 *>(p.w + wrow + kb + 4);
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const bool on = i0 + TNW * u < nks;
-            const bool arow = on && r < T, brow = on && r < V;
-            float a8[8], b8[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                a8[e] = arow ? fa[u][0][e] : 0.f; a8[4 + e] = arow ? fa[u][1][e] : 0.f;
-                b8[e] = brow ? wb[u][0][e] : 0.f; b8[4 + e] = brow ? wb[u][1][e] : 0.f;
-            }
-            bf16x8 ahi, alo, bhi, blo;
-            split8(a8, ahi, alo);
-            split8(b8, bhi, blo);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi, blo, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alo, bhi, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi, bhi, acc, 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) redg[wave * 1024 + ((e & 3) + 8 * (e >> 2) + 4 * kh) * 32 + r] = acc[e];
-    __syncthreads();
+    const f32x16 acc = head_logits_x3(p.feats, (long)n * T, T, p.w, V, H, H / 16, wave, r, kh);
     const int tj = tid & 31;
     float lpv[2];
+    head_put_acc(acc, redg, wave, r, kh);
+    __syncthreads();
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        float sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < TNW; ++w) sum += redg[w * 1024 + tid + TNT * q];
-        const float x = (tj < V) ? sum + p.bias[tj] : -INFINITY;
-        float m = x;
-#pragma unroll
-        for (int d = 16; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 32));
-        float sm = tj < V ? expf(x - m) : 0.f;
-#pragma unroll
-        for (int d = 16; d >= 1; d >>= 1) sm += __shfl_xor(sm, d, 32);
-        lpv[q] = x - m - logf(sm);
-    }
+    for (int q = 0; q < 2; ++q) lpv[q] = log_softmax32((tj < V) ? head_sum_waves(redg, q) + p.bias[tj] : -INFINITY, tj < V);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const int ti = (tid >> 5) + 16 * q;
@@ -895,29 +721,7 @@ __global__ __launch_bounds__(TNT) void ctc_head_greedy2_kernel(const HeadFwdArgs
         if (p.lp && ti < T && tj < V) p.lp[((long)n * T + ti) * V + tj] = lpv[q];
     }
     __syncthreads();
-    // one lane per frame (T <= 32): arg max over the classes (first maximum, like torch.max), then unique_consecutive + drop blanks
-    if (wave == 0) {
-        const int t = lane;
-        int best = -1;
-        float bv = -INFINITY;
-        if (t < T) {
-            best = 0; bv = tile[t][0];
-            for (int c = 1; c < V; ++c) {
-                const float v = tile[t][c];
-                if (v > bv) { bv = v; best = c; }
-            }
-            p.ali[(long)n * T + t] = best;
-            p.scores[(long)n * T + t] = bv;
-        }
-        int left = __shfl_up(best, 1, 64);
-        if (lane == 0) left = -1;
-        const bool keep = (t < T) && best != left && best != 0;
-        const unsigned long long mask = __ballot(keep);
-        const int pos = __popcll(mask & ((1ull << lane) - 1ull)), count = __popcll(mask);
-        if (keep) p.hyp[(long)n * T + pos] = best;
-        if (t < T && t >= count) p.hyp[(long)n * T + t] = 0;
-        if (lane == 0) p.hyp_len[n] = count;
-    }
+    if (wave == 0) greedy_collapse(tile, n, T, V, lane, p.ali, p.scores, p.hyp, p.hyp_len);
 }
 
 // dW[v][k] = sum_n dw_part[n][v][k], db[v] = sum_n db_part[n][v]: small_jobs.h kind 1 (a block takes 64 consecutive elements, its four
@@ -925,6 +729,25 @@ __global__ __launch_bounds__(TNT) void ctc_head_greedy2_kernel(const HeadFwdArgs
 __global__ __launch_bounds__(256) void ctc_head_reduce_kernel(const HaloSmallJobs q) {
     __shared__ float part[4][64];
     halo_small_jobs_block(q, blockIdx.x, part);
+}
+
+// slices of H per utterance: as many as keep the grid within `cus` workgroups (4 at B = 64 on 256 CUs), whole 32-column tiles per slice
+int head_slices(int B, int H, int cus) {
+    int slices = 1;
+    while (slices < 8 && (H / 32) % (2 * slices) == 0 && (long)B * 2 * slices <= cus) slices *= 2;
+    return slices;
+}
+
+// the fixed-order sum of the per-utterance dW / db partials: queued for a later launch's tail blocks when the caller defers small
+// reductions (small_jobs.h), this launch otherwise
+int head_reduce_partials(float *dw_part, float *db_part, float *dweight, float *dbias, int B, int V, int H, hipStream_t stream) {
+    HaloSmallJob j = {};
+    j.kind = 1; j.n = B; j.m = V; j.len = (long)V * H; j.a = dw_part; j.b = db_part; j.o1 = dweight; j.o2 = dbias;
+    if (halo_defer_small_job(j)) return HALO_OK;
+    HaloSmallJobs q = {};
+    q.n = 1; q.job[0] = j; q.job[0].blocks = q.blocks = halo_small_job_blocks(j);
+    hipLaunchKernelGGL(ctc_head_reduce_kernel, dim3((unsigned)q.blocks), dim3(256), 0, stream, q);
+    return halo_launch_status();
 }
 
 }  // namespace
@@ -991,33 +814,19 @@ int halo_ctc_head_bwd(const float *features, const float *weight, float p_drop, 
     a.lp = lp; a.alpha = alpha; a.nll = nll; a.grad_out = grad_out;
     a.dfeats = dfeatures; a.dw_part = (float *)workspace; a.db_part = a.dw_part + (size_t)B * V * H;
     a.B = B; a.T = T; a.H = H; a.V = V; a.S = S;
-    // slices of H per utterance: as many as keep the grid within the chip's CUs (4 at B = 64), whole 32-column tiles per slice
-    int slices = 1;
-    while (slices < 8 && (H / 32) % (2 * slices) == 0 && (long)B * 2 * slices <= 256) slices *= 2;
+    const int slices = head_slices(B, H, 256);               // (a full chip's CUs: these workgroups wait for nobody)
     const size_t mask_bytes = p_drop > 0.f ? (size_t)T * (H / slices) * sizeof(float) : 0;       // <= 128 KiB at T = 32, H = 1024
     if (mask_bytes > 32 * 1024 * 4) return HALO_ENOTSUP;
     if (halo_launch_lds<ctc_head_bwd_kernel>(dim3(B, slices), dim3(512), (int)mask_bytes, (hipStream_t)stream, a) != HALO_OK) return HALO_ELAUNCH;
     int rc = halo_launch_status();
     if (rc != HALO_OK) return rc;
-    const long VH = (long)V * H;
-    // the fixed-order sum of the partials: queued for a later launch's tail blocks when the caller defers small reductions (small_jobs.h)
-    HaloSmallJob j = {};
-    j.kind = 1; j.n = B; j.m = V; j.len = VH; j.a = a.dw_part; j.b = a.db_part; j.o1 = dweight; j.o2 = dbias;
-    if (halo_defer_small_job(j)) return HALO_OK;
-    HaloSmallJobs q = {};
-    q.n = 1; q.job[0] = j; q.job[0].blocks = q.blocks = halo_small_job_blocks(j);
-    hipLaunchKernelGGL(ctc_head_reduce_kernel, dim3((unsigned)q.blocks), dim3(256), 0, (hipStream_t)stream, q);
-    return halo_launch_status();
+    return head_reduce_partials(a.dw_part, a.db_part, dweight, dbias, B, V, H, (hipStream_t)stream);
 }
 
 static int head_train_slices(int B, int H) {
-    // slices of H per utterance: as many as keep the grid within the chip's CUs (4 at B = 64), whole 32-column tiles per slice.  All
-    // B * slices workgroups must be resident at once (the slices of an utterance wait for each other): one per CU of THIS device (a
+    // all B * slices workgroups must be resident at once (the slices of an utterance wait for each other): one per CU of THIS device (a
     // partitioned or CU-masked gfx950 reports fewer than 256); a batch that does not fit runs one slice per utterance, which waits for nobody
-    const int cus = halo_cu_count() > 0 ? halo_cu_count() : 1;
-    int slices = 1;
-    while (slices < 8 && (H / 32) % (2 * slices) == 0 && (long)B * 2 * slices <= cus) slices *= 2;
-    return slices;
+    return head_slices(B, H, halo_cu_count() > 0 ? halo_cu_count() : 1);
 }
 
 size_t halo_ctc_head_train_workspace_bytes(int B, int H, int V) { return halo_ctc_head_workspace_bytes(B, H, V); }
@@ -1053,13 +862,7 @@ int halo_ctc_head_train(const float *features, const float *weight, const float 
     if (halo_launch_lds<ctc_head_train_kernel>(dim3(B, slices), dim3(TNT), (int)lds, (hipStream_t)stream, a) != HALO_OK) return HALO_ELAUNCH;
     int rc = halo_launch_status();
     if (rc != HALO_OK) return rc;
-    HaloSmallJob j = {};
-    j.kind = 1; j.n = B; j.m = V; j.len = (long)V * H; j.a = a.dw_part; j.b = a.db_part; j.o1 = dweight; j.o2 = dbias;
-    if (halo_defer_small_job(j)) return HALO_OK;
-    HaloSmallJobs q = {};
-    q.n = 1; q.job[0] = j; q.job[0].blocks = q.blocks = halo_small_job_blocks(j);
-    hipLaunchKernelGGL(ctc_head_reduce_kernel, dim3((unsigned)q.blocks), dim3(256), 0, (hipStream_t)stream, q);
-    return halo_launch_status();
+    return head_reduce_partials(a.dw_part, a.db_part, dweight, dbias, B, V, H, (hipStream_t)stream);
 }
 
 #ifdef HALO_HEAD_STAMPS

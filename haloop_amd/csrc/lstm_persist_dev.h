@@ -4,20 +4,16 @@
 #include <hip/hip_runtime.h>
 #include "halo_common.h"
 #include "lstm_persist.h"
+#include "dev_util.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NWAVE = 8;
-constexpr unsigned long long SPIN_TIMEOUT_TICKS = 20000000ull;   // 0.2 s of the 100 MHz s_memrealtime counter
 
 enum YMode { Y_NONE = 0, Y_PLAIN = 1, Y_RELU = 2, Y_DROPOUT = 3 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0x7fffffff, 0x00020000);
-}
 // 16-byte write-through / L1-bypassing accesses (aux 16 = sc1)
 __device__ __forceinline__ bf16x8 load_sc1(__amdgpu_buffer_rsrc_t r, int byte_off) {
     return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 16));
@@ -140,15 +136,5 @@ __device__ __forceinline__ float persist2_add_masked(float a, float b, float m) 
 __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
-
-__device__ __forceinline__ void split8(const float *x, bf16x8 &hi, bf16x8 &lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 h = (__bf16)x[e];
-        hi[e] = h;
-        lo[e] = (__bf16)(x[e] - (float)h);
-    }
-}
-
 
 }  // namespace

@@ -13,7 +13,7 @@
 #include <float.h>
 #include "halo_common.h"
 #include "halo_internal.h"
-#include "lstm_persist_dev.h"
+#include "ctc_head_dev.h"
 
 namespace {
 
@@ -131,8 +131,6 @@ struct HeadArgs {
     int B, S, H, V, L, capacity;
 };
 
-constexpr int TNW = 8, TNT = 64 * TNW, LDT = 33;
-
 // the steps' best classes are in best_s / bv_s: continue the stream's collapse (one lane: at most MAX_STEPS dependent steps), commit the state
 __device__ __forceinline__ void head_finish(const HeadArgs &p, int b, int n, bool active, bool final, const int *best_s, const float *bv_s) {
     const int tid = threadIdx.x;
@@ -184,58 +182,13 @@ __global__ __launch_bounds__(TNT) void stream_head_fused_kernel(const HeadArgs p
         return;
     }
     const int r = lane & 31, kh = lane >> 5;
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    const int nks = H / 16;
-    const long frow = ((long)b * S + min(r, n - 1)) * H, wrow = (long)min(r, V - 1) * H;
-    for (int i0 = wave; i0 < nks; i0 += 2 * TNW) {
-        f32x4 fa[2][2], wb[2][2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int kb = 16 * min(i0 + TNW * u, nks - 1) + 8 * kh;
-            fa[u][0] = *reinterpret_cast<const f32x4 *>(p.feats + frow + kb);
-            fa[u][1] = *reinterpret_cast<const f32x4 *>(p.feats + frow + kb + 4);
-            wb[u][0] = *reinterpret_cast<const f32x4 *>(p.w + wrow + kb);
-            wb[u][1] = *reinterpret_cast<const f32x4 *>(p.w + wrow + kb + 4);
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const bool on = i0 + TNW * u < nks;
-            const bool arow = on && r < n, brow = on && r < V;
-            float a8[8], b8[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                a8[e] = arow ? fa[u][0][e] : 0.f; a8[4 + e] = arow ? fa[u][1][e] : 0.f;
-                b8[e] = brow ? wb[u][0][e] : 0.f; b8[4 + e] = brow ? wb[u][1][e] : 0.f;
-            }
-            bf16x8 ahi, alo, bhi, blo;
-            split8(a8, ahi, alo);
-            split8(b8, bhi, blo);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi, blo, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alo, bhi, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi, bhi, acc, 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) redg[wave * 1024 + ((e & 3) + 8 * (e >> 2) + 4 * kh) * 32 + r] = acc[e];
-    __syncthreads();
+    const f32x16 acc = head_logits_x3(p.feats, (long)b * S, n, p.w, V, H, H / 16, wave, r, kh);
     const int tj = tid & 31;
     float lpv[2];
+    head_put_acc(acc, redg, wave, r, kh);
+    __syncthreads();
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        float sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < TNW; ++w) sum += redg[w * 1024 + tid + TNT * q];
-        const float x = (tj < V) ? sum + p.bias[tj] : -INFINITY;
-        float m = x;
-#pragma unroll
-        for (int d = 16; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 32));
-        float sm = tj < V ? expf(x - m) : 0.f;
-#pragma unroll
-        for (int d = 16; d >= 1; d >>= 1) sm += __shfl_xor(sm, d, 32);
-        lpv[q] = x - m - logf(sm);
-    }
+    for (int q = 0; q < 2; ++q) lpv[q] = log_softmax32((tj < V) ? head_sum_waves(redg, q) + p.bias[tj] : -INFINITY, tj < V);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const int ti = (tid >> 5) + 16 * q;
@@ -244,13 +197,9 @@ __global__ __launch_bounds__(TNT) void stream_head_fused_kernel(const HeadArgs p
     }
     __syncthreads();
     if (tid < n) {                        // one lane per step: the first maximum, like torch.max and halo_ctc_greedy
-        int best = 0;
-        float bv = tile[tid][0];
-        for (int cc = 1; cc < V; ++cc) {
-            const float v = tile[tid][cc];
-            if (v > bv) { bv = v; best = cc; }
-        }
-        best_s[tid] = best; bv_s[tid] = bv;
+        float bv;
+        best_s[tid] = row_argmax(tile, tid, V, bv);
+        bv_s[tid] = bv;
     }
     __syncthreads();
     head_finish(p, b, n, active, final, best_s, bv_s);

@@ -6,8 +6,8 @@ rule shows up as a case that no longer reaches its path (``ctc_paths`` restates 
     forward   single-wave kernel iff 2S+1 <= 64 and T*C*4 <= 60 KiB                 else ctc_alpha_kernel, block = min(1024, roundup64(2S+3))
     backward  single-wave kernel iff 2S+1 <= 64 and (T*C + T*(2S+1))*4 <= 60 KiB    else ctc_beta_grad_kernel, block = min(1024, roundup64(max(2S+1, C) + 2))
 
-and the head's slicing from head_train_slices (csrc/head.hip): slices double while slices < 8, (H/32) % (2 slices) == 0 and
-B * 2 slices <= the device's CU count.
+and the head's slicing from head_slices (csrc/head.hip), to which head_train_slices passes the device's CU count: slices double while
+slices < 8, (H/32) % (2 slices) == 0 and B * 2 slices <= the device's CU count.
 """
 import numpy as np
 import torch

@@ -81,7 +81,7 @@ def ctc(lp, targets, il, tl, dtype='float64'):
 
 # --------------------------------------------------------------------------------------------------------------------- head
 def feature_lengths(il, T, ks=5, stride=4, pad=3):
-    """The reference's rule (ha/rnn.py:13-18; halo_ctc_prepare, feature_length() in csrc/head.hip): floor((il + 2 pad - ks) / stride + 1)
+    """The reference's rule (ha/rnn.py:13-18; halo_ctc_prepare, feature_length() in csrc/ctc_head_dev.h): floor((il + 2 pad - ks) / stride + 1)
     in float32 arithmetic, clamped to [0, T]."""
     o = (np.asarray(il).astype(np.int64) + 2 * pad - ks).astype(np.float32)
     f = np.floor(o / np.float32(stride) + np.float32(1.0)).astype(np.int64)
@@ -96,7 +96,7 @@ def bf16_round(x32):
 
 
 def _split(x, dt):
-    """split8() of csrc/lstm_persist_dev.h: the operand as fp32, hi = bf16(x), lo = bf16(x - hi) (the difference is exact in fp32)."""
+    """split8() of csrc/dev_util.h: the operand as fp32, hi = bf16(x), lo = bf16(x - hi) (the difference is exact in fp32)."""
     x32 = np.asarray(x).astype(np.float32)
     hi = bf16_round(x32)
     lo = bf16_round(x32 - hi)
@@ -125,13 +125,13 @@ def head(feats, W, b, mask, il, targets, tl, ks=5, stride=4, pad=3, dtype='float
     ``split`` is the rounding the kernels apply to the operands of the three products (logits, dfeats, dW):
 
     None       exact: ctc_head_fwd_kernel / ctc_head_bwd_kernel (the 'f32' math mode) multiply fp32 operands on the exact-f32 MFMA
-               (v_mfma_f32_32x32x2f32, head.hip:127, 375, 399); x = feats * mask is an fp32 product (head.hip:118, 392).
+               (v_mfma_f32_32x32x2f32, head.hip:97, 283, 307); x = feats * mask is an fp32 product (head.hip:88, 300).
     'bf16x3'   every operand is taken as fp32 and split into hi = bf16(v), lo = bf16(v - hi); a product is hi*lo + lo*hi + hi*hi with
                the lo*lo term left out, accumulated in fp32.  ctc_head_train_kernel does this for the logits (split8 of the fp32
-               product feats * mask and of W, three MFMAs: head.hip:525-533) and for both backward products (split8 of dlogit and of
-               W, respectively of x = feats * scale where kept: head.hip:761-774; the dfeats tile is multiplied by the mask on the
-               way out, head.hip:780), and ctc_head_greedy2_kernel does it for the logits (head.hip:858-869).  halo_ctc_head_train
-               and halo_ctc_head_greedy branch only on 'f32' against the rest (head.hip:971, 1038): the 'bf16' math mode runs the
+               product feats * mask and of W, three MFMAs: head.hip:433-441) and for both backward products (split8 of dlogit and of
+               W, respectively of x = feats * scale where kept: head.hip:652-665; the dfeats tile is multiplied by the mask on the
+               way out, head.hip:671), and ctc_head_greedy2_kernel does it for the logits (ctc_head_dev.h:84-96).  halo_ctc_head_train
+               and halo_ctc_head_greedy branch only on 'f32' against the rest (head.hip:794, 847): the 'bf16' math mode runs the
                SAME three-term split as 'bf16x3' in these kernels, so both modes are modelled by split='bf16x3'.
     Everything else (bias, log_softmax, lattice, dlogit, the sums over utterances) is fp32 arithmetic in the kernels and ``dtype``
     arithmetic here."""

@@ -13,7 +13,7 @@ The contract of a math mode is exact: operands of a product rounded as the table
                                         one step.  By induction over t and the layers the per-step gates still pin every output.
 
 Product model, restated from the code (line numbers: csrc/ at the commit that added this file).  rb = round-to-nearest-even to bf16
-(``(__bf16)x``: Packed<>::store lstm.hip:51, split8 lstm_persist_dev.h:147, lstm_persist2.hip:197/555, tiled_image.h);
+(``(__bf16)x``: Packed<>::store lstm.hip:51, split8 dev_util.h:20, lstm_persist2.hip:197/555, tiled_image.h);
 'bf16' = rb(a) rb(b); 'x3' = hi(a) hi(b) + hi(a) lo(b) + lo(a) hi(b), hi = rb(a), lo = rb(a - hi) (mma_chunk3 lstm.hip:104-113,
 lstm_persist.hip:120-124, gemm_bf16x3.hip:290); 'exact' = fp32 operands (v_mfma_f32_16x16x4_f32: lstm.hip:78, gemm_f32.hip).
 M = the mode's kind: f32 -> exact, bf16 -> bf16, bf16x3 -> x3.
@@ -71,7 +71,7 @@ class Case:
     fusion: bool = False           # _lib.set_lstm_fusion
     fwd_kernel: str = ''           # what lstm_chain_info must name
     bwd_kernel: str = ''
-    act: str = 'fast'              # the kernels' activation forms: 'fast' (exp2 + rcp, lstm_persist_dev.h:94-118) | 'libm' (expf / tanhf)
+    act: str = 'fast'              # the kernels' activation forms: 'fast' (exp2 + rcp, lstm_persist_dev.h:90-114) | 'libm' (expf / tanhf)
 
 
 ALL3 = ('f32', 'bf16x3', 'bf16')
@@ -194,13 +194,13 @@ def product(a, b, kind, dtype, a_trunc=False, a_exact=False):
 def _sigmoid(x, act):
     if act == 'exact':
         return torch.sigmoid(x)
-    if act == 'fast':       # fast_sigmoid, lstm_persist_dev.h:96-98
+    if act == 'fast':       # fast_sigmoid, lstm_persist_dev.h:92-94
         return 1.0 / (1.0 + torch.exp2(x * x.new_tensor(-1.4426950408889634)))
     return 1.0 / (1.0 + torch.exp(-x))         # sigmoidf_, halo_common.h:95
 
 
 def _tanh(x, act):
-    if act == 'fast':       # fast_tanh / persist2_tanh, lstm_persist_dev.h:99-111
+    if act == 'fast':       # fast_tanh / persist2_tanh, lstm_persist_dev.h:95-107
         return 1.0 - 2.0 / (1.0 + torch.exp2(x * x.new_tensor(2.8853900817779268)))
     return torch.tanh(x)
 
@@ -443,7 +443,7 @@ def first_outside(got, ref, key, bound):
     return i, got[key][i].item(), r[i].item()
 
 
-FLOOR = 1e-6       # five activations at the 2e-7 lstm_persist_dev.h:95 states (h, y, c: absolute); 1e-6 of max-abs for the gradients
+FLOOR = 1e-6       # five activations at the 2e-7 lstm_persist_dev.h:91 states (h, y, c: absolute); 1e-6 of max-abs for the gradients
 
 
 def bounds(noise, factor=8.0, floor=FLOOR):
