@@ -148,6 +148,7 @@ SIGNATURES = {
     'halo_ctc_greedy': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'halo_stream_front': (_i, [_vp] * 16 + [_i] * 8 + [_vp]),
     'halo_stream_head': (_i, [_vp] * 19 + [_i] * 6 + [_vp]),
+    'halo_stream_logits': (_i, [_vp] * 11 + [_i] * 5 + [_vp]),
     'halo_set_beam_vector_chunk': (_i, [_i]),
     'halo_logaddexp_aten': (_i, [_vp, _vp, _vp, _sz, _vp]),
     'halo_ctc_beam_workspace_bytes': (_sz, [_i] * 4),
@@ -201,6 +202,10 @@ SIGNATURES = {
     'halo_ctc_prefix_advance': (_i, [_vp, _l, _l, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_rnnt_advance': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _vp, _i, _vp, _l, _vp, _vp]),
     'halo_rnnt_lstm_cell': (_i, [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp]),
+    'halo_rnnt_stream_open': (_i, [_vp, _vp, _i, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _i, _vp, _l, _l, _vp, _l, _vp, _i, _i, _i, _vp, _i, _vp]),
+    'halo_rnnt_advance_stream': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _vp, _i, _vp, _l, _vp, _vp,
+                                      _vp, _vp]),
+    'halo_rnnt_lstm_cell_rows': (_i, [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _vp]),
     'halo_rnnt_beam_step': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_rnnt_beam_keep': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp]),

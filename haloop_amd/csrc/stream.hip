@@ -6,6 +6,9 @@
 //   halo_stream_head    one workgroup per stream: classifier -> log_softmax -> best class per step (the product as in head.hip's
 //                       ctc_head_greedy2_kernel), or the best class of log-probs the caller computed (collapse-only mode); the greedy
 //                       collapse continued from the label the previous call ended on; the LSTM state of the streams that go on.
+//   halo_stream_logits  one workgroup per stream, for the transducer head: the classifier product alone -- logits, no
+//                       softmax, zeros past the stream's steps -- or, on logits the caller computed, that zeroing alone; the same commit
+//                       of the LSTM state.
 //
 // Both are fp32, take no atomics and sum in a fixed order: a stream's results do not depend on which other streams share the launch.
 // A stream is touched by exactly one workgroup per launch, so the carry and the hypothesis are read and replaced without a hand-off
@@ -131,6 +134,14 @@ struct HeadArgs {
     int B, S, H, V, L, capacity;
 };
 
+// the LSTM's final state of this call becomes stream b's persistent state (the streams that go on; stated once for both heads)
+__device__ __forceinline__ void stream_commit_state(float *h, float *c, const float *hn, const float *cn, int L, int H, int B, int b) {
+    for (int idx = threadIdx.x; idx < L * H; idx += TNT) {
+        const long o = ((long)(idx / H) * B + b) * H + idx % H;
+        h[o] = hn[o]; c[o] = cn[o];
+    }
+}
+
 // the steps' best classes are in best_s / bv_s: continue the stream's collapse (one lane: at most MAX_STEPS dependent steps), commit the state
 __device__ __forceinline__ void head_finish(const HeadArgs &p, int b, int n, bool active, bool final, const int *best_s, const float *bv_s) {
     const int tid = threadIdx.x;
@@ -156,12 +167,7 @@ __device__ __forceinline__ void head_finish(const HeadArgs &p, int b, int n, boo
         p.last_label[b] = last; p.hyp_len[b] = len; p.score[b] = score; p.steps[b] += n;
         if (trunc) p.truncated[b] = 1;
     }
-    if (!final) {
-        for (int idx = tid; idx < p.L * p.H; idx += TNT) {
-            const long o = ((long)(idx / p.H) * p.B + b) * p.H + idx % p.H;
-            p.h[o] = p.hn[o]; p.c[o] = p.cn[o];
-        }
-    }
+    if (!final) stream_commit_state(p.h, p.c, p.hn, p.cn, p.L, p.H, p.B, b);
 }
 
 // classifier product on split-bf16 MFMA with the fragments straight from global memory, log_softmax, best class: the steps of one
@@ -235,6 +241,48 @@ __global__ __launch_bounds__(TNT) void stream_head_collapse_kernel(const HeadArg
     head_finish(p, b, n, active, final, best_s, bv_s);
 }
 
+struct LogitsArgs {
+    const float *feats;        // [B][S][H] (fused) or nullptr: f holds the caller's product
+    const float *w, *bias;     // [V][H], [V]
+    float *f;                  // [B][S][V]
+    const int *n_steps, *flags;
+    const float *hn, *cn;
+    float *h, *c;
+    int64_t *steps;            // [B] += n_steps
+    int B, S, H, V, L;
+};
+
+// FUSED: the tile product of stream_head_fused_kernel, its sums plus the bias stored as they are.  Otherwise f is the caller's: only the
+// steps past the stream's own are written (zeros).  Both commit the state.
+template <bool FUSED>
+__global__ __launch_bounds__(TNT) void stream_logits_kernel(const LogitsArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float redg[];      // [TNW][1024] when FUSED
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int S = p.S, V = p.V;
+    const int flags = p.flags[b];
+    const bool active = flags & FLAG_ACTIVE, final = flags & FLAG_FINAL;
+    const int n = active ? max(0, min(p.n_steps[b], S)) : 0;
+    if (FUSED && n > 0) {                 // (uniform over the workgroup)
+        const int r = lane & 31, kh = lane >> 5;
+        const f32x16 acc = head_logits_x3(p.feats, (long)b * S, n, p.w, V, p.H, p.H / 16, wave, r, kh);
+        head_put_acc(acc, redg, wave, r, kh);
+        __syncthreads();
+        const int tj = tid & 31;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int ti = (tid >> 5) + 16 * q;
+            const float v = head_sum_waves(redg, q);
+            if (tj < V && ti < S) p.f[((long)b * S + ti) * V + tj] = ti < n ? v + p.bias[tj] : 0.f;
+        }
+    } else {
+        for (int idx = tid + n * V; idx < S * V; idx += TNT) p.f[(long)b * S * V + idx] = 0.f;
+    }
+    if (!active) return;
+    if (tid == 0) p.steps[b] += n;
+    if (!final) stream_commit_state(p.h, p.c, p.hn, p.cn, p.L, p.H, p.B, b);
+}
+
 }  // namespace
 
 extern "C" {
@@ -283,6 +331,26 @@ int halo_stream_head(const float *feats, const float *weight, const float *bias,
     if (!halo_ctc_head_supported(S, H, V, 0) || halo_math_mode() == HALO_MATH_F32) return HALO_ENOTSUP;
     HALO_CHECK_ARG(((uintptr_t)feats % 16 == 0) && ((uintptr_t)weight % 16 == 0));
     hipLaunchKernelGGL(stream_head_fused_kernel, dim3(B), dim3(TNT), (size_t)TNW * 1024 * sizeof(float), (hipStream_t)stream, a);
+    return halo_launch_status();
+}
+
+int halo_stream_logits(const float *feats, const float *weight, const float *bias, float *f, const int *n_steps, const int *flags,
+                       const float *hn, const float *cn, float *h, float *c, int64_t *steps, int B, int S, int H, int V, int L,
+                       halo_stream_t stream) {
+    HALO_CHECK_ARG(f && n_steps && flags && hn && cn && h && c && steps);
+    HALO_CHECK_ARG(B > 0 && S > 0 && H > 0 && V > 0 && L > 0);
+    if (S > MAX_STEPS) return HALO_ENOTSUP;
+    LogitsArgs a;
+    a.feats = feats; a.w = weight; a.bias = bias; a.f = f; a.n_steps = n_steps; a.flags = flags; a.hn = hn; a.cn = cn; a.h = h; a.c = c;
+    a.steps = steps; a.B = B; a.S = S; a.H = H; a.V = V; a.L = L;
+    if (!feats) {                     // commit-only: f is the caller's product
+        hipLaunchKernelGGL(stream_logits_kernel<false>, dim3(B), dim3(TNT), 0, (hipStream_t)stream, a);
+        return halo_launch_status();
+    }
+    HALO_CHECK_ARG(weight && bias);
+    if (!halo_ctc_head_supported(S, H, V, 0) || halo_math_mode() == HALO_MATH_F32) return HALO_ENOTSUP;
+    HALO_CHECK_ARG(((uintptr_t)feats % 16 == 0) && ((uintptr_t)weight % 16 == 0));
+    hipLaunchKernelGGL(stream_logits_kernel<true>, dim3(B), dim3(TNT), (size_t)TNW * 1024 * sizeof(float), (hipStream_t)stream, a);
     return halo_launch_status();
 }
 

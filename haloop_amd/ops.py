@@ -944,6 +944,22 @@ def stream_collapse(lp, n_steps, flags, hn, cn, h, c, ali, step_scores, hyp, hyp
                                  B, S, h.shape[2], V, h.shape[0], hyp.shape[1], _stream()), 'halo_stream_head')
 
 
+def stream_logits(feats, weight, bias, f, n_steps, flags, hn, cn, h, c, steps):
+    """The transducer head of one streamed chunk (include/halo.h: halo_stream_logits): f [B,S,V] <- classifier(feats [B,S,H]) for each
+    stream's n_steps, zeros past them, no softmax; steps [B] int64 += n_steps; hn / cn committed into h / c for the streams that go on.
+    Where the fused product does not apply (``stream_head_fused``) the product comes from ``gemm`` and the launch runs commit-only."""
+    _f32c(feats, 'features'); _f32c(f, 'logits')
+    B, S, H = feats.shape
+    V = weight.shape[0]
+    if f.shape != (B, S, V) or steps.dtype != torch.int64 or steps.numel() != B:
+        raise ValueError(f'stream_logits: f must be [{B}, {S}, {V}] and steps int64 [{B}]')
+    fused = stream_head_fused(S, H, V)
+    if not fused:
+        gemm(feats.view(B * S, H), weight, True, True, B * S, V, H, out=f.view(B * S, V), bias1=bias)
+    check(lib().halo_stream_logits(ptr(feats) if fused else None, ptr(weight), ptr(bias), ptr(f), ptr(n_steps), ptr(flags), ptr(hn), ptr(cn),
+                                   ptr(h), ptr(c), ptr(steps), B, S, H, V, h.shape[0], _stream()), 'halo_stream_logits')
+
+
 def ctc_beam(em, beam, log_domain=True):
     """em [N,T,V] -> (seqs [N,beam,T] int64, lens [N,beam] int32, scores [N,beam])."""
     _f32c(em, 'emissions')
@@ -1798,12 +1814,52 @@ def rnnt_advance(f, g, g_bias, input_lengths, state, scores, tokens, frames, max
                                   ptr(wte), wte.shape[1], ptr(x_next), x_next.stride(0), ptr(live), _stream()), 'halo_rnnt_advance')
 
 
-def rnnt_lstm_cell(xh, image, b_ih, b_hh, c, h_next, h_up):
+def rnnt_lstm_cell(xh, image, b_ih, b_hh, c, h_next, h_up, row_mask=None):
     """One LSTM layer at one step: xh [rows, 2H] = x | h_prev, image: the decode image of the gate-interleaved [W_ih | W_hh]
-    (include/halo.h); c [rows, H] in place; h -> h_next and h_up (row strides kept)."""
+    (include/halo.h); c [rows, H] in place; h -> h_next and h_up (row strides kept).  ``row_mask`` int32 [rows] (halo_rnnt_lstm_cell_rows):
+    a row with 0 keeps c, has its h_prev copied to h_next and writes no h_up."""
     rows, H = c.shape
-    check(lib().halo_rnnt_lstm_cell(ptr(xh), xh.stride(0), rows, H, ptr(image), ptr(b_ih), ptr(b_hh), ptr(c), ptr(h_next), h_next.stride(0),
-                                    ptr(h_up), h_up.stride(0), _stream()), 'halo_rnnt_lstm_cell')
+    if row_mask is None:
+        check(lib().halo_rnnt_lstm_cell(ptr(xh), xh.stride(0), rows, H, ptr(image), ptr(b_ih), ptr(b_hh), ptr(c), ptr(h_next),
+                                        h_next.stride(0), ptr(h_up), h_up.stride(0), _stream()), 'halo_rnnt_lstm_cell')
+        return
+    if row_mask.dtype != torch.int32 or row_mask.numel() < rows or not row_mask.is_contiguous():
+        raise ValueError(f'rnnt_lstm_cell: row_mask must be a contiguous int32 tensor of at least {rows} words')
+    check(lib().halo_rnnt_lstm_cell_rows(ptr(xh), xh.stride(0), rows, H, ptr(image), ptr(b_ih), ptr(b_hh), ptr(c), ptr(h_next),
+                                         h_next.stride(0), ptr(h_up), h_up.stride(0), ptr(row_mask), _stream()), 'halo_rnnt_lstm_cell_rows')
+
+
+def rnnt_stream_open(n_frames, flags, state, pos, row_mask, scores, tokens, frames, xh, c, wte, live):
+    """Opens a call of the carried greedy search (include/halo.h): n_frames [B] int32 and flags [>= B] int32 or None (bit STREAM_BEGIN)
+    for the first B of the rows of state int32 [5, rows]; pos / row_mask int32 [rows]; tokens / frames int64 [rows, capacity]; xh
+    [L, rows, 2H]: the [x | h] copy the next step reads; c [L, rows, H]; live: the call's int32 words, zeroed."""
+    B, rows = n_frames.shape[0], pos.shape[0]
+    L, H = c.shape[0], c.shape[2]
+    for t, name in ((n_frames, 'n_frames'), (flags, 'flags'), (pos, 'pos'), (row_mask, 'row_mask'), (live, 'live')):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+            raise ValueError(f'rnnt_stream_open: {name} must be a contiguous int32 tensor')
+    if state.shape[1] != rows or row_mask.shape[0] != rows or scores.shape[0] != rows or tokens.shape[0] != rows or \
+            tokens.shape != frames.shape or tokens.stride(0) != frames.stride(0) or xh.shape != (L, rows, 2 * H) or c.shape[1] != rows or \
+            (flags is not None and flags.shape[0] < B) or xh.stride(2) != 1 or not c.is_contiguous():
+        raise ValueError('rnnt_stream_open: the state tensors do not fit each other')
+    check(lib().halo_rnnt_stream_open(ptr(n_frames), ptr(flags), B, rows, ptr(state), state.stride(0), ptr(pos), ptr(row_mask), ptr(scores),
+                                      ptr(tokens), ptr(frames), tokens.stride(0), tokens.shape[1], ptr(xh), xh.stride(0), xh.stride(1),
+                                      ptr(c), c.stride(0), ptr(wte), wte.shape[1], H, L, ptr(live), live.numel(), _stream()),
+          'halo_rnnt_stream_open')
+
+
+def rnnt_advance_stream(f, g, g_bias, n_frames, state, scores, tokens, frames, max_symbols, wte, x_next, live, pos, row_mask):
+    """``rnnt_advance`` over this call's chunk f [N, S, V] from pos (include/halo.h: halo_rnnt_advance_stream): a row that runs out of
+    its n_frames waits; row_mask [>= N] int32 <- whether the row emitted and goes on."""
+    N, T, V = f.shape
+    if f.stride(2) != 1 or tokens.stride(0) != frames.stride(0) or tokens.shape != frames.shape:
+        raise ValueError('rnnt_advance_stream: f must be contiguous along V; tokens and frames must share shape and row stride')
+    if wte.shape[0] < V or g.shape != (N, V) or pos.numel() < N or row_mask.numel() < N or n_frames.numel() < N:
+        raise ValueError('rnnt_advance_stream: g must be [N, V], the embedding must have a row for every symbol, pos / row_mask / n_frames N words')
+    check(lib().halo_rnnt_advance_stream(ptr(f), f.stride(0), f.stride(1), N, T, V, ptr(g), g.stride(0), ptr(g_bias), ptr(n_frames),
+                                         ptr(state), state.stride(0), ptr(scores), ptr(tokens), ptr(frames), tokens.stride(0),
+                                         tokens.shape[1], int(max_symbols), ptr(wte), wte.shape[1], ptr(x_next), x_next.stride(0),
+                                         ptr(live), ptr(pos), ptr(row_mask), _stream()), 'halo_rnnt_advance_stream')
 
 
 # ---- launches of the transducer's beam search (csrc/rnnt_beam.hip); none of these allocates ----------------------------------------

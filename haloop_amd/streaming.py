@@ -28,6 +28,10 @@ replays the push chain from one HIP graph.
 ``beam=W`` (or ``HALO_STREAM_BEAM=W``, 1 .. 16) adds n-best partials: one more launch behind the head,
 ``halo_ctc_prefix_beam_advance`` on the call's log-probs, carries a width-W CTC prefix beam per slot, so ``nbest()`` after every call
 is ``ctc.ctc_prefix_beam_search`` of the slot's log-probs so far.  The greedy path and ``last`` are unchanged by it.
+
+``StreamingTransducer`` is the same object over a ``recognizer.Transducer``: the head launch is
+``halo_stream_logits`` (the classifier product and the state commit, no softmax) and ``transducer.GreedyStream`` carries the head's
+greedy search from call to call.  The two classes share their host side, ``_ChunkedStreams``.
 """
 import os
 
@@ -42,7 +46,152 @@ _NEVER, _OPEN, _CLOSED = 0, 1, 2
 _RING = 16          # pinned host slots for the per-call flags: a slot is rewritten only after the copy that read it has run
 
 
-class StreamingRecognizer:
+class _ChunkedStreams:
+    """The host side that ``StreamingRecognizer`` and ``StreamingTransducer`` share: the slot states, the checks of a push and of a
+    finish, and the per-call flags and lengths sent through a ring of pinned host slots.  A subclass sets ``max_streams``,
+    ``chunk_frames`` and ``_dims`` = (B, Tc, S, F, ...) and then calls ``_init_host``."""
+
+    def _init_host(self, dev):
+        B, Tc, _, F = self._dims[:4]
+        self._meta = torch.zeros(2, B, device=dev, dtype=torch.int32)            # [0] flags, [1] lengths
+        self._pin = torch.zeros(_RING, 2, B, dtype=torch.int32).pin_memory()
+        self._pin_np = self._pin.numpy()
+        self._pin_events = [None] * _RING
+        self._pin_next = 0
+        self._frames = torch.zeros(B, Tc, F, device=dev, dtype=torch.float32)    # the graph's input; the frames of a finish without a tail
+        self._state = [_NEVER] * B
+
+    @staticmethod
+    def _check_geometry(name, conv, chunk_frames, max_streams, capacity):
+        if (conv.kernel_size[0], conv.stride[0], conv.padding[0]) != (5, 4, 3) or conv.dilation[0] != 1 or conv.groups != 1:
+            raise NotImplementedError(f'{name}: only the subsample geometry kernel 5, stride 4, padding 3 is streamed')
+        if chunk_frames % 4 != 0 or not 4 <= chunk_frames <= 124:
+            raise ValueError(f'{name}: chunk_frames {chunk_frames} must be a multiple of 4 in 4 .. 124')
+        if max_streams < 1 or capacity < 1:
+            raise ValueError(f'{name}: max_streams and capacity must be positive')
+
+    def _bools(self, v, default, name):
+        B = self.max_streams
+        if v is None:
+            return [default] * B
+        if torch.is_tensor(v):
+            if v.is_cuda:
+                raise ValueError(f'{type(self).__name__}: {name} is host-side (a sequence of bools or a CPU bool tensor)')
+            v = v.tolist()
+        v = [bool(e) for e in v]
+        if len(v) != B:
+            raise ValueError(f'{type(self).__name__}: {name} has {len(v)} entries for {B} slots')
+        return v
+
+    def _send_meta(self, flags, lengths):
+        """The call's flags and lengths -> the static device buffer, by an asynchronous copy from a pinned host slot."""
+        i = self._pin_next
+        self._pin_next = (i + 1) % _RING
+        if self._pin_events[i] is not None:
+            self._pin_events[i].synchronize()             # returns at once unless the device is _RING calls behind
+        else:
+            self._pin_events[i] = torch.cuda.Event()
+        self._pin_np[i, 0, :] = flags
+        self._pin_np[i, 1, :] = lengths
+        self._meta.copy_(self._pin[i], non_blocking=True)
+        self._pin_events[i].record()
+
+    def _push_args(self, frames, active, begin):
+        """Checks a push and opens the slots that begin -> (flags, lengths) of the call."""
+        name = type(self).__name__
+        B, Tc, S, F = self._dims[:4]
+        if not torch.is_tensor(frames) or frames.shape != (B, Tc, F) or frames.dtype != torch.float32 or not frames.is_cuda:
+            raise ValueError(f'{name}.push: frames must be a float32 HIP tensor [{B}, {Tc}, {F}]')
+        active, begin = self._bools(active, True, 'active'), self._bools(begin, False, 'begin')
+        flags = [0] * B
+        for b in range(B):
+            if begin[b] and not active[b]:
+                raise ValueError(f'{name}.push: slot {b} begins without being active')
+            if active[b] and not begin[b] and self._state[b] != _OPEN:
+                raise ValueError(f'{name}.push: slot {b} is closed; pass begin to start a stream in it')
+            flags[b] = (STREAM_ACTIVE if active[b] else 0) | (STREAM_BEGIN if begin[b] else 0)
+        for b in range(B):
+            if begin[b]:
+                self._state[b] = _OPEN
+        return flags, [Tc if a else 0 for a in active]
+
+    def _finish_args(self, tail, tail_lengths, rows):
+        """Checks a finish and closes its slots -> (tail, flags, lengths) of the call."""
+        name = type(self).__name__
+        B, Tc, S, F = self._dims[:4]
+        rows = [s == _OPEN for s in self._state] if rows is None else self._bools(rows, False, 'rows')
+        for b in range(B):
+            if rows[b] and self._state[b] != _OPEN:
+                raise ValueError(f'{name}.finish: slot {b} ' + ('was never begun' if self._state[b] == _NEVER else 'is closed already'))
+        if tail is None:
+            if tail_lengths is not None and any(int(t) != 0 for t in tail_lengths):
+                raise ValueError(f'{name}.finish: tail_lengths without a tail')
+            tail, lengths = self._frames, [0] * B
+        else:
+            if not torch.is_tensor(tail) or tail.dim() != 3 or tail.shape[0] != B or tail.shape[2] != F or tail.shape[1] > Tc - 1 \
+                    or tail.dtype != torch.float32 or not tail.is_cuda:
+                raise ValueError(f'{name}.finish: tail must be a float32 HIP tensor [{B}, <= {Tc - 1}, {F}]')
+            if tail_lengths is None:
+                lengths = [tail.shape[1]] * B
+            else:
+                lengths = [int(t) for t in (tail_lengths.tolist() if torch.is_tensor(tail_lengths) else tail_lengths)]
+                if len(lengths) != B or any(not 0 <= t <= tail.shape[1] for b, t in enumerate(lengths) if rows[b]):
+                    raise ValueError(f'{name}.finish: tail_lengths must give 0 .. tail.shape[1] frames for every closing slot')
+            if tail.shape[1] == 0:
+                tail = self._frames
+        for b in range(B):
+            if rows[b]:
+                self._state[b] = _CLOSED
+        return tail, [(STREAM_ACTIVE | STREAM_FINAL) if r else 0 for r in rows], [t if r else 0 for r, t in zip(rows, lengths)]
+
+    def _stamp(self):
+        """Changes whenever an LSTM weight may have changed (as ``infer.LstmCtcRecognizer._stamp``)."""
+        key = (_lib.weights_epoch(),) + tuple((p.data_ptr(), p._version) for p in lstm_param_list(self.encoder.lstm))
+        return (hash(key) & 0x7fffffffffffffff) | 1
+
+    def _lstm(self, y, S, buf):
+        B, H = self.max_streams, self._dims[6]
+        p = lstm_param_list(self.encoder.lstm)
+        _, hn, cn, _ = ops.lstm_fwd(y, p[0::4], p[1::4], p[2::4], p[3::4], h0=self._h, c0=self._c, y=buf['feats'], y_strides=(H, S * H),
+                                    y_relu=True, want_state=True, expect_backward=False, reserve=buf['reserve'],
+                                    weights_stamp=self._stamp())
+        return hn, cn
+
+    def _encode_general(self, frames, S, final, buf):
+        """The encoder side of a call on the general operators: the reset of h / c of the slots that begin, the convolution on the
+        concatenated input, the carry, the LSTM from the carried state -> (hn, cn, n [B] int32, live [B, S], act, beg, fin)."""
+        conv = self.encoder.subsample
+        B, _, _, F = self._dims[:4]
+        dev = frames.device
+        flags, length = self._meta[0], self._meta[1]
+        act, beg, fin = (flags & STREAM_ACTIVE) != 0, (flags & STREAM_BEGIN) != 0, (flags & STREAM_FINAL) != 0
+        self._h.masked_fill_(beg[None, :, None], 0.0)
+        self._c.masked_fill_(beg[None, :, None], 0.0)
+        Tc = frames.shape[1]
+        carry = self._carry.masked_fill(beg[:, None, None], 0.0)
+        fr = frames.masked_fill((torch.arange(Tc, device=dev)[None, :] >= length[:, None])[:, :, None], 0.0)
+        parts = [carry, fr]
+        if 4 * S + 1 > 3 + Tc:
+            parts.append(torch.zeros(B, 4 * S + 1 - 3 - Tc, F, device=dev, dtype=torch.float32))
+        y, _ = ops.subsample_fwd(torch.cat(parts, dim=1), conv.weight, conv.bias, NO_DROPOUT, pad=0)
+        n = torch.where(fin, (length + 1) // 4 + 1, length // 4)
+        n = torch.where(act, n, torch.zeros_like(n)).clamp(max=S).to(torch.int32)
+        live = torch.arange(S, device=dev)[None, :] < n[:, None]                                  # [B, S]
+        y = y.masked_fill(~live.t()[:, :, None], 0.0).contiguous()
+        if not final:
+            go = act & ~fin
+            self._carry.copy_(torch.where(go[:, None, None], frames[:, Tc - 3:], self._carry))
+        hn, cn = self._lstm(y, S, buf)
+        return hn, cn, n, live, act, beg, fin
+
+    def _commit_general(self, hn, cn, n, act, fin):
+        go = (act & ~fin)[None, :, None]
+        self._h.copy_(torch.where(go, hn, self._h))
+        self._c.copy_(torch.where(go, cn, self._c))
+        self._n_steps.copy_(n)
+
+
+class StreamingRecognizer(_ChunkedStreams):
     """``max_streams`` slots of streaming greedy CTC recognition over ``encoder`` (an ``rnn.Encoder``) and ``recognizer`` (a
     ``recognizer.TemporalClassifier``), both in eval mode.  Every buffer is allocated here, once.
 
@@ -70,12 +219,7 @@ class StreamingRecognizer:
         if encoder.training or recognizer.training:
             raise ValueError('StreamingRecognizer: put the encoder and the recognizer in eval mode')
         conv = encoder.subsample
-        if (conv.kernel_size[0], conv.stride[0], conv.padding[0]) != (5, 4, 3) or conv.dilation[0] != 1 or conv.groups != 1:
-            raise NotImplementedError('StreamingRecognizer: only the subsample geometry kernel 5, stride 4, padding 3 is streamed')
-        if chunk_frames % 4 != 0 or not 4 <= chunk_frames <= 124:
-            raise ValueError(f'StreamingRecognizer: chunk_frames {chunk_frames} must be a multiple of 4 in 4 .. 124')
-        if max_streams < 1 or capacity < 1:
-            raise ValueError('StreamingRecognizer: max_streams and capacity must be positive')
+        self._check_geometry('StreamingRecognizer', conv, chunk_frames, max_streams, capacity)
         self.encoder, self.recognizer = encoder, recognizer
         self.max_streams, self.chunk_frames, self.capacity = int(max_streams), int(chunk_frames), int(capacity)
         if use_graph is None:
@@ -110,107 +254,32 @@ class StreamingRecognizer:
         self._last_label = torch.full((B,), -1, device=dev, dtype=torch.int32)
         self._truncated = torch.zeros(B, device=dev, dtype=torch.bool)
         self._n_steps = torch.zeros(B, device=dev, dtype=torch.int32)
-        self._meta = torch.zeros(2, B, device=dev, dtype=torch.int32)            # [0] flags, [1] lengths
-        self._pin = torch.zeros(_RING, 2, B, dtype=torch.int32).pin_memory()
-        self._pin_np = self._pin.numpy()
-        self._pin_events = [None] * _RING
-        self._pin_next = 0
-        self._frames = torch.zeros(B, Tc, F, **f32)                              # the graph's input; the frames of a finish without a tail
+        self._init_host(dev)
         self._bufs = {}
         for s in (S, S + 1):                                                     # a push's launch shape and a finish's
             self._bufs[s] = dict(
                 y=torch.zeros(s, B, C, **f32), feats=torch.zeros(B, s, H, **f32), ali=torch.zeros(B, s, device=dev, dtype=torch.int64),
                 scores=torch.zeros(B, s, **f32), lp=torch.zeros(B, s, V, **f32), reserve=ops.lstm_reserve(s, B, C, H, L, dev))
         self._beam = PrefixBeamStream(B, V, self.beam, self.capacity, device=dev) if self.beam else None
-        self._state = [_NEVER] * B
         self._graphs = {}
         self._last = None
 
     # ---------------------------------------------------------------------------------------------------------------- host side
-    def _bools(self, v, default, name):
-        B = self.max_streams
-        if v is None:
-            return [default] * B
-        if torch.is_tensor(v):
-            if v.is_cuda:
-                raise ValueError(f'StreamingRecognizer: {name} is host-side (a sequence of bools or a CPU bool tensor)')
-            v = v.tolist()
-        v = [bool(e) for e in v]
-        if len(v) != B:
-            raise ValueError(f'StreamingRecognizer: {name} has {len(v)} entries for {B} slots')
-        return v
-
-    def _stamp(self):
-        """Changes whenever an LSTM weight may have changed (as ``infer.LstmCtcRecognizer._stamp``)."""
-        key = (_lib.weights_epoch(),) + tuple((p.data_ptr(), p._version) for p in lstm_param_list(self.encoder.lstm))
-        return (hash(key) & 0x7fffffffffffffff) | 1
-
     def _check_modes(self):
         if self.encoder.training or self.recognizer.training:
             raise ValueError('StreamingRecognizer: put the encoder and the recognizer in eval mode')
 
-    def _send_meta(self, flags, lengths):
-        """The call's flags and lengths -> the static device buffer, by an asynchronous copy from a pinned host slot."""
-        i = self._pin_next
-        self._pin_next = (i + 1) % _RING
-        if self._pin_events[i] is not None:
-            self._pin_events[i].synchronize()             # returns at once unless the device is _RING calls behind
-        else:
-            self._pin_events[i] = torch.cuda.Event()
-        self._pin_np[i, 0, :] = flags
-        self._pin_np[i, 1, :] = lengths
-        self._meta.copy_(self._pin[i], non_blocking=True)
-        self._pin_events[i].record()
-
     @torch.no_grad()
     def push(self, frames, active=None, begin=None, want_log_probs=False):
         self._check_modes()
-        B, Tc, S, F = self._dims[:4]
-        if not torch.is_tensor(frames) or frames.shape != (B, Tc, F) or frames.dtype != torch.float32 or not frames.is_cuda:
-            raise ValueError(f'StreamingRecognizer.push: frames must be a float32 HIP tensor [{B}, {Tc}, {F}]')
-        active, begin = self._bools(active, True, 'active'), self._bools(begin, False, 'begin')
-        flags = [0] * B
-        for b in range(B):
-            if begin[b] and not active[b]:
-                raise ValueError(f'StreamingRecognizer.push: slot {b} begins without being active')
-            if active[b] and not begin[b] and self._state[b] != _OPEN:
-                raise ValueError(f'StreamingRecognizer.push: slot {b} is closed; pass begin to start a stream in it')
-            flags[b] = (STREAM_ACTIVE if active[b] else 0) | (STREAM_BEGIN if begin[b] else 0)
-        for b in range(B):
-            if begin[b]:
-                self._state[b] = _OPEN
-        self._call(frames.contiguous(), S, False, want_log_probs, flags, [Tc if a else 0 for a in active])
+        flags, lengths = self._push_args(frames, active, begin)
+        self._call(frames.contiguous(), self._dims[2], False, want_log_probs, flags, lengths)
 
     @torch.no_grad()
     def finish(self, tail=None, tail_lengths=None, rows=None, want_log_probs=False):
         self._check_modes()
-        B, Tc, S, F = self._dims[:4]
-        rows = [s == _OPEN for s in self._state] if rows is None else self._bools(rows, False, 'rows')
-        for b in range(B):
-            if rows[b] and self._state[b] != _OPEN:
-                raise ValueError(f'StreamingRecognizer.finish: slot {b} ' +
-                                 ('was never begun' if self._state[b] == _NEVER else 'is closed already'))
-        if tail is None:
-            if tail_lengths is not None and any(int(t) != 0 for t in tail_lengths):
-                raise ValueError('StreamingRecognizer.finish: tail_lengths without a tail')
-            tail, lengths = self._frames, [0] * B
-        else:
-            if not torch.is_tensor(tail) or tail.dim() != 3 or tail.shape[0] != B or tail.shape[2] != F or tail.shape[1] > Tc - 1 \
-                    or tail.dtype != torch.float32 or not tail.is_cuda:
-                raise ValueError(f'StreamingRecognizer.finish: tail must be a float32 HIP tensor [{B}, <= {Tc - 1}, {F}]')
-            if tail_lengths is None:
-                lengths = [tail.shape[1]] * B
-            else:
-                lengths = [int(t) for t in (tail_lengths.tolist() if torch.is_tensor(tail_lengths) else tail_lengths)]
-                if len(lengths) != B or any(not 0 <= t <= tail.shape[1] for b, t in enumerate(lengths) if rows[b]):
-                    raise ValueError('StreamingRecognizer.finish: tail_lengths must give 0 .. tail.shape[1] frames for every closing slot')
-            if tail.shape[1] == 0:
-                tail = self._frames
-        for b in range(B):
-            if rows[b]:
-                self._state[b] = _CLOSED
-        self._call(tail.contiguous(), S + 1, True, want_log_probs,
-                   [(STREAM_ACTIVE | STREAM_FINAL) if r else 0 for r in rows], [t if r else 0 for r, t in zip(rows, lengths)])
+        tail, flags, lengths = self._finish_args(tail, tail_lengths, rows)
+        self._call(tail.contiguous(), self._dims[2] + 1, True, want_log_probs, flags, lengths)
 
     def partial(self):
         if self._beam is None:
@@ -263,14 +332,6 @@ class StreamingRecognizer:
             self._chain(self._frames, S, want_lp, buf)
         return graph
 
-    def _lstm(self, y, S, buf):
-        B, H = self.max_streams, self._dims[6]
-        p = lstm_param_list(self.encoder.lstm)
-        _, hn, cn, _ = ops.lstm_fwd(y, p[0::4], p[1::4], p[2::4], p[3::4], h0=self._h, c0=self._c, y=buf['feats'], y_strides=(H, S * H),
-                                    y_relu=True, want_state=True, expect_backward=False, reserve=buf['reserve'],
-                                    weights_stamp=self._stamp())
-        return hn, cn
-
     def _chain(self, frames, S, want_lp, buf):
         conv, cls = self.encoder.subsample, self.recognizer.classifier
         flags, length = self._meta[0], self._meta[1]
@@ -291,34 +352,16 @@ class StreamingRecognizer:
 
     def _chain_general(self, frames, S, final, buf):
         """The same call on the general operators; the merging of the collapse and the choice of the state by torch operators."""
-        conv, cls = self.encoder.subsample, self.recognizer.classifier
+        cls = self.recognizer.classifier
         B, _, _, F, C, L, H, V = self._dims
-        dev = frames.device
-        flags, length = self._meta[0], self._meta[1]
-        act, beg, fin = (flags & STREAM_ACTIVE) != 0, (flags & STREAM_BEGIN) != 0, (flags & STREAM_FINAL) != 0
-        self._h.masked_fill_(beg[None, :, None], 0.0)
-        self._c.masked_fill_(beg[None, :, None], 0.0)
+        flags = self._meta[0]
+        hn, cn, n, live, act, beg, fin = self._encode_general(frames, S, final, buf)
         self._hyp.masked_fill_(beg[:, None], 0)
         self._hyp_len.masked_fill_(beg, 0)
         self._steps.masked_fill_(beg, 0)
         self._score.masked_fill_(beg, 0.0)
         self._last_label.masked_fill_(beg, -1)
         self._truncated.masked_fill_(beg, False)
-        Tc = frames.shape[1]
-        carry = self._carry.masked_fill(beg[:, None, None], 0.0)
-        fr = frames.masked_fill((torch.arange(Tc, device=dev)[None, :] >= length[:, None])[:, :, None], 0.0)
-        parts = [carry, fr]
-        if 4 * S + 1 > 3 + Tc:
-            parts.append(torch.zeros(B, 4 * S + 1 - 3 - Tc, F, device=dev, dtype=torch.float32))
-        y, _ = ops.subsample_fwd(torch.cat(parts, dim=1), conv.weight, conv.bias, NO_DROPOUT, pad=0)
-        n = torch.where(fin, (length + 1) // 4 + 1, length // 4)
-        n = torch.where(act, n, torch.zeros_like(n)).clamp(max=S).to(torch.int32)
-        live = torch.arange(S, device=dev)[None, :] < n[:, None]                                  # [B, S]
-        y = y.masked_fill(~live.t()[:, :, None], 0.0).contiguous()
-        if not final:
-            go = act & ~fin
-            self._carry.copy_(torch.where(go[:, None, None], frames[:, Tc - 3:], self._carry))
-        hn, cn = self._lstm(y, S, buf)
         feats = buf['feats']
         logits = ops.gemm(feats.view(B * S, H), cls.weight, True, True, B * S, V, H, bias1=cls.bias)
         lp = ops.log_softmax_fwd(logits).view(B, S, V)
@@ -337,11 +380,109 @@ class StreamingRecognizer:
         for s in range(S):                                                                      # in step order
             self._score.add_(torch.where(live[:, s], scores[:, s], torch.zeros_like(self._score)))
         self._steps.add_(n.to(torch.int64))
-        go = (act & ~fin)[None, :, None]
-        self._h.copy_(torch.where(go, hn, self._h))
-        self._c.copy_(torch.where(go, cn, self._c))
-        self._n_steps.copy_(n)
+        self._commit_general(hn, cn, n, act, fin)
         buf['ali'].copy_(ali.masked_fill(~live, 0))
         buf['scores'].copy_(scores.masked_fill(~live, 0.0))
         buf['lp'].copy_(lp.masked_fill(~live[:, :, None], 0.0))
         self._advance_beam(buf['lp'], flags)
+
+
+class StreamingTransducer(_ChunkedStreams):
+    """``max_streams`` slots of streaming greedy transducer recognition over ``encoder`` (an ``rnn.Encoder``) and ``head`` (a
+    ``recognizer.Transducer``), both in eval mode.  ``push`` / ``finish`` take what ``StreamingRecognizer``'s take, with
+    the same slot states and argument checks; every buffer is allocated here, once.
+
+    A call is ``halo_stream_front``, the persistent LSTM from the carried (h, c), ``halo_stream_logits`` (the classifier product, no
+    softmax, and the commit of the LSTM state) and ``transducer.GreedyStream.advance`` on the call's logits with n_frames = n_steps:
+    the head's frame-synchronous search needs nothing beyond the current frame, so a slot's hypothesis after every call is the
+    whole-utterance greedy search of the steps it has been sent.  ``finish`` consumes the final steps, the convolution's right padding
+    included, and closes the slot, which stays readable until it begins again.  ``HALO_STREAM_FUSED=0`` runs the encoder side on the
+    general operators; the search's own path follows ``GreedyStream``'s rule (HALO_RNNT_FUSED, the math mode).
+
+    partial(): copies of (hyp [B, capacity] int64, -1 past a slot's length; hyp_len [B] int64; scores [B] fp32: the sum of the
+        log-probabilities of every move; steps [B] int64: encoder steps so far; truncated [B] bool: the slot emitted ``capacity`` symbols
+        and ignores its later steps).
+    last: (logits [B, S, V] fp32, zeros past a row's n_steps; n_steps [B] int32) of the latest call -- this object's buffers.
+
+    There is no graph replay: the number of rounds of a call depends on the data.  Unlike ``StreamingRecognizer``, a call waits for the
+    device wherever ``GreedyStream`` reads its live word (every ``transducer.SYNC_EVERY`` rounds)."""
+
+    def __init__(self, encoder, head, max_streams, chunk_frames=16, capacity=256, max_symbols_per_frame=10):
+        from .transducer import GreedyStream
+        if encoder.training or head.training:
+            raise ValueError('StreamingTransducer: put the encoder and the head in eval mode')
+        conv = encoder.subsample
+        self._check_geometry('StreamingTransducer', conv, chunk_frames, max_streams, capacity)
+        self.encoder, self.head = encoder, head
+        self.max_streams, self.chunk_frames, self.capacity = int(max_streams), int(chunk_frames), int(capacity)
+        self.fused = os.environ.get('HALO_STREAM_FUSED', '1') != '0'
+        dev = conv.weight.device
+        if dev.type != 'cuda':
+            raise _lib.HaloError('haloop_amd.streaming.StreamingTransducer runs on the HIP device only (no CPU path)')
+        _lib.lend_scratch(device=dev)
+        B, Tc, S = self.max_streams, self.chunk_frames, self.chunk_frames // 4
+        F, C = conv.in_channels, conv.out_channels
+        L, H, V = encoder.lstm.num_layers, encoder.lstm.hidden_size, head.classifier.out_features
+        if head.classifier.in_features != H:
+            raise ValueError(f'StreamingTransducer: the head takes {head.classifier.in_features} features, the encoder gives {H}')
+        self._dims = (B, Tc, S, F, C, L, H, V)
+        f32 = dict(device=dev, dtype=torch.float32)
+        self._carry = torch.zeros(B, 3, F, **f32)
+        self._h, self._c = torch.zeros(L, B, H, **f32), torch.zeros(L, B, H, **f32)
+        self._steps = torch.zeros(B, device=dev, dtype=torch.int64)
+        self._n_steps = torch.zeros(B, device=dev, dtype=torch.int32)
+        # halo_stream_front resets a CTC hypothesis of the slots that begin: small buffers of this object's own take that
+        self._ctc = (torch.zeros(B, 1, device=dev, dtype=torch.int64), torch.zeros(B, device=dev, dtype=torch.int64), torch.zeros(B, **f32),
+                     torch.zeros(B, device=dev, dtype=torch.int32), torch.zeros(B, device=dev, dtype=torch.bool))   # hyp, hyp_len, score, last_label, truncated
+        self._init_host(dev)
+        self._bufs = {}
+        for s in (S, S + 1):
+            self._bufs[s] = dict(y=torch.zeros(s, B, C, **f32), feats=torch.zeros(B, s, H, **f32), logits=torch.zeros(B, s, V, **f32),
+                                 reserve=ops.lstm_reserve(s, B, C, H, L, dev))
+        self.search = GreedyStream(head, B, self.capacity, max_symbols_per_frame)
+        self._last = None
+
+    def _check_modes(self):
+        if self.encoder.training or self.head.training:
+            raise ValueError('StreamingTransducer: put the encoder and the head in eval mode')
+
+    @torch.no_grad()
+    def push(self, frames, active=None, begin=None):
+        self._check_modes()
+        flags, lengths = self._push_args(frames, active, begin)
+        self._call(frames.contiguous(), self._dims[2], False, flags, lengths)
+
+    @torch.no_grad()
+    def finish(self, tail=None, tail_lengths=None, rows=None):
+        self._check_modes()
+        tail, flags, lengths = self._finish_args(tail, tail_lengths, rows)
+        self._call(tail.contiguous(), self._dims[2] + 1, True, flags, lengths)
+
+    def partial(self):
+        tokens, lengths, _, scores, truncated = self.search.result()
+        return tokens, lengths, scores, self._steps.clone(), truncated
+
+    @property
+    def last(self):
+        return self._last
+
+    def _call(self, frames, S, final, flags, lengths):
+        buf = self._bufs[S]
+        self._send_meta(flags, lengths)
+        dflags, length = self._meta[0], self._meta[1]
+        conv, cls = self.encoder.subsample, self.head.classifier
+        if self.fused:
+            ops.stream_front(frames, self._carry, length, dflags, conv.weight, conv.bias, buf['y'], self._n_steps, self._h, self._c,
+                             self._ctc[0], self._ctc[1], self._steps, self._ctc[2], self._ctc[3], self._ctc[4])
+            hn, cn = self._lstm(buf['y'], S, buf)
+            ops.stream_logits(buf['feats'], cls.weight, cls.bias, buf['logits'], self._n_steps, dflags, hn, cn, self._h, self._c, self._steps)
+        else:
+            B, H, V = self._dims[0], self._dims[6], self._dims[7]
+            hn, cn, n, live, act, beg, fin = self._encode_general(frames, S, final, buf)
+            logits = ops.gemm(buf['feats'].view(B * S, H), cls.weight, True, True, B * S, V, H, bias1=cls.bias).view(B, S, V)
+            buf['logits'].copy_(logits.masked_fill(~live[:, :, None], 0.0))
+            self._steps.masked_fill_(beg, 0)
+            self._steps.add_(n.to(torch.int64))
+            self._commit_general(hn, cn, n, act, fin)
+        self._last = (buf['logits'], self._n_steps)
+        self.search._advance(buf['logits'], self._n_steps, dflags, any(f & STREAM_BEGIN for f in flags))

@@ -29,6 +29,10 @@ prediction network.  The score is the sum of the log-probabilities of every move
 ``1 + num_layers + 1`` launches per emitted symbol and none per blank frame; the general path runs the same search node by node on
 ``rnn.Decoder.forward`` at T = 1 with torch's log_softmax.
 
+``GreedyStream`` is the same greedy search carried across calls: logits that arrive in chunks, every row's search entered from the
+state its previous chunk left and left into it, so a row always holds ``GreedyDecoder.decode`` of its frames so far
+(csrc/rnnt_decode.hip: the open launch, the carried advance, cells with a row mask).
+
 ``BeamDecoder`` is beam search for the same head: alignment-length synchronous decoding with exact merging ([Saon20]), n-best lists whose
 scores sum the alignment paths of a hypothesis, on ``num_layers + 3`` launches per alignment step (csrc/rnnt_beam.hip).
 """
@@ -232,6 +236,19 @@ class _HeadDecoder:
             self._images = (stamp, layers, ops.decode_image(lm.embedding.weight.detach().float().contiguous()))
         return self._images[1], self._images[2]
 
+    def _lm_step(self, N, p, layers, head_image, mask=None):
+        """The prediction network on the input rows of copy p -> g (``GreedyDecoder`` and ``GreedyStream``: both keep ``_xh`` [2, L, rows,
+        2 H], ``_c``, ``_top`` and ``_g``): every layer's cell launch reads copy p of its [x | h_prev] rows and writes h to copy 1 - p
+        (its own next h_prev) and to copy p of the layer above (that layer's x).  ``mask`` (int32 [>= N] on the device): a row with 0
+        sits the step out -- c kept, h_prev copied to copy 1 - p, its ``_top`` row untouched, so out_layer reproduces its g."""
+        lm = self.head.lm
+        H, L, w = lm.hidden_dim, lm.num_layers, lstm_param_list(lm.rnn)
+        for l in range(L):
+            h_up = self._xh[p, l + 1, :N, :H] if l + 1 < L else self._top[:N]
+            ops.rnnt_lstm_cell(self._xh[p, l, :N], layers[l], w[4 * l + 2], w[4 * l + 3], self._c[l, :N], self._xh[1 - p, l, :N, H:], h_up,
+                               row_mask=mask)
+        ops.decode_linear(self._top[:N], head_image, lm.num_classes, self._g[:N])
+
     def _check(self, features, input_lengths):
         name = type(self).__name__
         if features.dim() != 3 or features.shape[1] < 1:
@@ -297,16 +314,6 @@ class GreedyDecoder(_HeadDecoder):
                     st[4, :N] != 0)
 
     # ---- the fused path: 1 + num_layers + 1 launches per emitted symbol ------------------------------------------------------------
-    def _lm_step(self, N, p, layers, head_image):
-        """The prediction network on the input rows of copy p -> g: every layer's cell launch reads copy p of its [x | h_prev] rows and
-        writes h to copy 1 - p (its own next h_prev) and to copy p of the layer above (that layer's x)."""
-        lm = self.head.lm
-        H, L, w = lm.hidden_dim, lm.num_layers, lstm_param_list(lm.rnn)
-        for l in range(L):
-            h_up = self._xh[p, l + 1, :N, :H] if l + 1 < L else self._top[:N]
-            ops.rnnt_lstm_cell(self._xh[p, l, :N], layers[l], w[4 * l + 2], w[4 * l + 3], self._c[l, :N], self._xh[1 - p, l, :N, H:], h_up)
-        ops.decode_linear(self._top[:N], head_image, lm.num_classes, self._g[:N])
-
     def _decode_fused(self, f, il, N, cap):
         lm = self.head.lm
         layers, head_image = self._decode_images()
@@ -358,6 +365,191 @@ class GreedyDecoder(_HeadDecoder):
         st = self._state
         st[0, :N], st[1, :N], st[2, :N], st[3, :N], st[4, :N] = t.int(), u.int(), here.int(), 1, (u >= cap).int()
         self._scores[:N] = scores
+
+
+class GreedyStream(_HeadDecoder):
+    """``GreedyDecoder``'s search carried across calls: the transcription logits of ``max_rows`` rows arrive in chunks
+    and every row's search goes on where its previous chunk ended, so after every call a row holds what ``GreedyDecoder.decode`` returns
+    on the frames the row has been sent so far -- on the fused path bit for bit, scores included -- at the cost of the new frames alone.
+    The logits may be of any origin (``streaming.StreamingTransducer`` feeds its encoder's).  Every buffer is allocated here, once.
+
+    advance(f [B, S, V], n_frames=None, begin=None): B <= max_rows; f a float32 HIP tensor with a unit class stride (a slice of a wider
+        buffer is read in place); row b takes its first clamp(n_frames[b], 0, S) frames (a device int32 tensor [B]; None: S).  ``begin``
+        (host-side: a sequence of B bools or a CPU bool tensor; None: no row) starts a row from the empty hypothesis, whatever it held;
+        a row must begin before its first frames.  A row without frames, a truncated row and the rows from B on keep their state, their
+        outputs and g bit for bit.  A row that reaches ``capacity`` symbols is truncated until it begins again: its later frames are
+        ignored.  Returns views of (tokens [B, capacity] int64, lengths [B] int64, frames [B, capacity] int64 -- counted from the row's
+        begin --, scores [B] float32, truncated [B] bool) in ``GreedyDecoder.decode``'s format; the next call overwrites them.
+    result(): copies of the same five for all ``max_rows`` rows.
+    rounds: the advances of the last call.
+
+    One call is the open launch, one masked step of the prediction network if a row begins, and rounds of (advance, masked cells,
+    out_layer) until no row is live.  As in ``GreedyDecoder`` the live word is read every ``SYNC_EVERY`` rounds, so a call waits for the
+    device there, and the rounds past the last live one change nothing.  A row emits at most ``max_symbols_per_frame`` symbols per frame
+    and ``capacity`` in all and needs one more round to run out of frames: more than min(S * max_symbols_per_frame, capacity) + 1 rounds
+    raise ``HaloError``.  The general path (f32 mode, HALO_RNNT_FUSED=0, a head the fused launches do not take) carries the same search
+    on ``rnn.Decoder.forward`` at T = 1.  The path is chosen when a row begins; do not change it in the middle of a stream."""
+
+    def __init__(self, head, max_rows, capacity, max_symbols_per_frame=10):
+        self.head = head
+        self.max_rows, self.capacity, self.max_symbols = int(max_rows), int(capacity), int(max_symbols_per_frame)
+        if self.max_rows < 1 or self.capacity < 1 or self.max_symbols < 1:
+            raise ValueError('GreedyStream: need max_rows >= 1, capacity >= 1 and max_symbols_per_frame >= 1')
+        lm = head.lm
+        E, H, L, V = lm.embedding.weight.shape[1], lm.hidden_dim, lm.num_layers, lm.num_classes
+        dev = lm.embedding.weight.device
+        if dev.type != 'cuda':
+            raise _lib.HaloError('haloop_amd.transducer.GreedyStream runs on the HIP device only (no CPU path)')
+        mb = self.max_rows
+        i32 = dict(device=dev, dtype=torch.int32)
+        with torch.inference_mode(False):
+            self._state = torch.zeros(5, mb, **i32)                # t | u | here | done | truncated; t counts the stream's frames
+            self._state[3].fill_(1)
+            self._pos, self._mask = torch.zeros(mb, **i32), torch.zeros(mb, **i32)
+            self._nf, self._flags = torch.zeros(mb, **i32), torch.zeros(mb, **i32)
+            self._scores = torch.zeros(mb, device=dev, dtype=torch.float32)
+            self._tokens = torch.full((mb, self.capacity), -1, device=dev, dtype=torch.int64)
+            self._frames = torch.full((mb, self.capacity), -1, device=dev, dtype=torch.int64)
+            self._live = torch.zeros(self.capacity + 1, **i32)     # one word per advance of a call
+            self._g = torch.zeros(mb, V, device=dev, dtype=torch.float32)
+            if E == H:
+                self._xh = torch.zeros(2, L, mb, 2 * H, device=dev, dtype=torch.float32)
+                self._c = torch.zeros(L, mb, H, device=dev, dtype=torch.float32)
+                self._top = torch.zeros(mb, H, device=dev, dtype=torch.float32)
+            self._gh = torch.zeros(L, mb, H, device=dev, dtype=torch.float32)      # the general path's state
+            self._gc = torch.zeros(L, mb, H, device=dev, dtype=torch.float32)
+        self._cur = 0          # the [x | h] copy that holds every row's h: the one the next step reads.  Carried across calls.
+        self._images = None
+        self.rounds = 0
+
+    def advance(self, f, n_frames=None, begin=None):
+        mb = self.max_rows
+        V = self.head.lm.num_classes
+        if not torch.is_tensor(f) or f.dim() != 3 or not 1 <= f.shape[0] <= mb or f.shape[1] < 1 or f.shape[2] != V or f.dtype != torch.float32:
+            raise ValueError(f'GreedyStream.advance: f must be a float32 tensor [1 .. {mb}, S >= 1, {V}]')
+        B, S = f.shape[0], f.shape[1]
+        if n_frames is not None and (not torch.is_tensor(n_frames) or tuple(n_frames.shape) != (B,) or n_frames.dtype != torch.int32):
+            raise ValueError(f'GreedyStream.advance: n_frames must be an int32 tensor [{B}]')
+        if not f.is_cuda or (n_frames is not None and not n_frames.is_cuda):
+            raise _lib.HaloError('haloop_amd.transducer.GreedyStream runs on the HIP device only (no CPU path)')
+        if self.head.training:
+            raise NotImplementedError('GreedyStream is an inference path: put the head in eval mode')
+        if begin is not None:
+            if torch.is_tensor(begin):
+                if begin.is_cuda:
+                    raise ValueError('GreedyStream.advance: begin is host-side (a sequence of bools or a CPU bool tensor)')
+                begin = begin.tolist()
+            begin = [bool(e) for e in begin]
+            if len(begin) != B:
+                raise ValueError(f'GreedyStream.advance: begin has {len(begin)} entries for {B} rows')
+        with torch.no_grad():
+            any_begin = begin is not None and any(begin)
+            flags = None
+            if any_begin:
+                flags = self._flags[:B]
+                flags.copy_(torch.tensor([ops.STREAM_BEGIN if e else 0 for e in begin], dtype=torch.int32))
+            if n_frames is None:
+                nf = self._nf[:B].fill_(S)
+            else:
+                nf = n_frames.detach().contiguous()
+            return self._advance(f.detach(), nf, flags, any_begin)
+
+    def _advance(self, f, nf, flags, any_begin):
+        """f [B, S, V], nf int32 [B] and flags int32 [>= B] (or None) on the device; any_begin: whether a flag carries STREAM_BEGIN."""
+        B, S, V = f.shape
+        if f.stride(2) != 1 or f.stride(1) < V or f.stride(0) < (S - 1) * f.stride(1) + V:
+            f = f.contiguous()
+        (self._advance_fused if self.fused else self._advance_general)(f, nf, flags, any_begin)
+        st = self._state
+        return self._tokens[:B], st[1, :B].long(), self._frames[:B], self._scores[:B], st[4, :B] != 0
+
+    def result(self):
+        st = self._state
+        return self._tokens.clone(), st[1].long(), self._frames.clone(), self._scores.clone(), st[4] != 0
+
+    # ---- the fused path: per round 1 + num_layers + 1 launches over all max_rows rows, whatever B ------------------------------------
+    def _advance_fused(self, f, nf, flags, any_begin):
+        lm = self.head.lm
+        layers, head_image = self._decode_images()
+        wte, E = lm.embedding.weight, lm.embedding.weight.shape[1]
+        B, S = f.shape[0], f.shape[1]
+        mb, cap = self.max_rows, self.capacity
+        cur = self._cur
+        ops.rnnt_stream_open(nf, flags, self._state, self._pos, self._mask, self._scores, self._tokens, self._frames, self._xh[cur], self._c,
+                             wte, self._live)
+        if any_begin:
+            self._lm_step(mb, cur, layers, head_image, self._mask)
+            cur = 1 - cur
+        bound = min(S * self.max_symbols, cap) + 1
+        try:
+            for it in range(bound):
+                ops.rnnt_advance_stream(f, self._g[:B], lm.out_layer.bias, nf, self._state, self._scores, self._tokens[:B], self._frames[:B],
+                                        self.max_symbols, wte, self._xh[cur, 0, :B], self._live[it:], self._pos, self._mask)
+                if it == bound - 1 or ((it + 1) % SYNC_EVERY == 0 and int(self._live[it].item()) == 0):
+                    break
+                self._lm_step(mb, cur, layers, head_image, self._mask)
+                cur = 1 - cur
+        finally:
+            self._cur = cur
+        self.rounds = it + 1
+        if int(self._live[it].item()) != 0:
+            raise _lib.HaloError('GreedyStream: rows still live after min(S * max_symbols_per_frame, capacity) + 1 rounds')
+
+    # ---- the general path: the same carried search on rnn.Decoder.forward at T = 1, torch.where for the rows that sit out ----------
+    def _advance_general(self, f, nf, flags, any_begin):
+        lm = self.head.lm
+        dev = f.device
+        B, S, V = f.shape
+        cap = self.capacity
+        st = self._state
+        g, h, c = self._g[:B], self._gh[:, :B], self._gc[:, :B]
+        if any_begin:
+            beg = (flags[:B] & ops.STREAM_BEGIN) != 0
+            st[:, :B].masked_fill_(beg[None, :], 0)
+            self._scores[:B].masked_fill_(beg, 0.0)
+            self._tokens[:B].masked_fill_(beg[:, None], -1)
+            self._frames[:B].masked_fill_(beg[:, None], -1)
+            g0, (h0, c0) = lm.forward(torch.zeros(1, B, device=dev, dtype=torch.int64), lm.init_hidden(B))
+            g.copy_(torch.where(beg[:, None], g0, g))
+            h.copy_(torch.where(beg[None, :, None], h0, h))
+            c.copy_(torch.where(beg[None, :, None], c0, c))
+        rows, cols = torch.arange(B, device=dev), torch.arange(V, device=dev)
+        t, u, here = st[0, :B].long(), st[1, :B].long(), st[2, :B].long()
+        trunc = st[4, :B] != 0
+        L = nf.long().clamp(0, S)
+        pos = torch.zeros_like(t)
+        done = (L <= 0) | trunc
+        scores = self._scores[:B].clone()
+        g, state = g.clone(), (h.clone(), c.clone())
+        tokens, frames = self._tokens[:B], self._frames[:B]
+        self.rounds = 0
+        while not bool(done.all().item()):                      # one host read per lattice node
+            self.rounds += 1
+            live = ~done
+            fr = f[rows, pos.clamp(max=S - 1)]
+            fr = torch.where(live[:, None], fr, torch.zeros_like(fr))               # a row that sits out reads nothing of f
+            lp = torch.log_softmax(fr + g, -1)
+            top = lp.max(-1).values
+            k = torch.where(lp == top[:, None], cols, V - 1).min(-1).values        # lowest index among equal maxima
+            k = torch.where(here == self.max_symbols, torch.zeros_like(k), k)
+            scores += torch.where(live, lp[rows, k], torch.zeros_like(top))
+            blank, emit = live & (k == 0), live & (k != 0)
+            e = emit.nonzero().view(-1)
+            tokens[e, u[e]] = k[e]
+            frames[e, u[e]] = t[e]
+            step = blank.long()
+            t, pos, here, u = t + step, pos + step, torch.where(blank, torch.zeros_like(here), here + emit.long()), u + emit.long()
+            if e.numel():
+                g1, (h1, c1) = lm.forward(torch.where(emit, k, torch.zeros_like(k)).view(1, B), state)
+                g = torch.where(emit[:, None], g1, g)
+                state = (torch.where(emit[None, :, None], h1, state[0]), torch.where(emit[None, :, None], c1, state[1]))
+            trunc = trunc | (u >= cap)
+            done = done | (pos >= L) | trunc
+        st[0, :B], st[1, :B], st[2, :B], st[3, :B], st[4, :B] = t.int(), u.int(), here.int(), 1, trunc.int()
+        self._scores[:B] = scores
+        self._g[:B] = g
+        self._gh[:, :B] = state[0]
+        self._gc[:, :B] = state[1]
 
 
 BEAM_MAX = 16            # csrc/rnnt_beam.hip keeps a row's records in LDS arrays of this many entries

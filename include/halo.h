@@ -647,6 +647,13 @@ int halo_stream_head(const float *feats, const float *weight, const float *bias,
                      const int *flags, const float *hn, const float *cn, float *h, float *c, int64_t *alignments, float *step_scores,
                      int64_t *hyp, int64_t *hyp_len, int64_t *steps, float *score, int *last_label, unsigned char *truncated, int B,
                      int S, int H, int V, int L, int capacity, halo_stream_t stream);
+/* halo_stream_logits: the head launch of a streamed transducer.  f [B,S,V] = Linear(H -> V) of the first n_steps[b]
+ *   steps of feats [B,S,H], zeros past them (no softmax); steps[b] += n_steps[b]; the same commit of hn / cn into h / c as
+ *   halo_stream_head.  The fused product has halo_stream_head's conditions (HALO_ENOTSUP otherwise).  Commit-only mode: feats == NULL and
+ *   f holds the caller's product; only its steps past n_steps[b] are written. */
+int halo_stream_logits(const float *feats, const float *weight, const float *bias, float *f, const int *n_steps, const int *flags,
+                       const float *hn, const float *cn, float *h, float *c, int64_t *steps, int B, int S, int H, int V, int L,
+                       halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * 80-mel log filterbank front-end on the device (ha/data.py:136-140: torchaudio.compliance.kaldi.fbank(wav, num_mel_bins=80) with that
@@ -1090,6 +1097,33 @@ int halo_rnnt_advance(const float *f, long f_row_stride, long f_frame_stride, in
                       int *live, halo_stream_t stream);
 int halo_rnnt_lstm_cell(const float *xh, long ldx, int rows, int hidden, const void *w_image, const float *b_ih, const float *b_hh,
                         float *c, float *h_next, long ld_next, float *h_up, long ld_up, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The same greedy search carried across calls (haloop_amd/transducer.py GreedyStream): the logits arrive in chunks and
+ * a row's search goes on where the previous call left it.  The state is halo_rnnt_advance's plus pos and row_mask, int32 [rows] each.
+ * The word t counts the frames of the whole stream (frames[u] is stream-absolute); `done` means "sits out the rest of this call".
+ *   halo_rnnt_stream_open     once per call, one workgroup per row of the state (rows >= B take no part): pos = 0; done = 1 for a row
+ *                             with n_frames <= 0 or truncated, else 0; row_mask = 0.  A row whose flags (may be NULL) carry bit 1 (begin)
+ *                             is reset first: t = u = here = truncated = 0, score 0, its `capacity` slots of tokens / frames -1, h
+ *                             (xh[l][n][hidden ..], layers xh_layer_stride floats apart) and c (layers c_layer_stride apart) of every
+ *                             layer zero, xh[0][n][0 .. E) = wte[0], row_mask = 1: one masked step of the prediction network gives it g.
+ *                             live[0 .. n_live) = 0.
+ *   halo_rnnt_advance_stream  halo_rnnt_advance over this call's chunk f [N][T][V]: row n walks the frames [pos[n], clamp(n_frames[n],
+ *                             0, T)).  A row that runs out of them sets done and keeps everything else (it waits); u == capacity sets
+ *                             done and truncated, which stays until the row begins again.  pos[n] is updated; row_mask[n] = 1 for a row
+ *                             that emitted and goes on, else 0 (rows skipped as done included).
+ *   halo_rnnt_lstm_cell_rows  halo_rnnt_lstm_cell with row_mask [rows] (NULL: every row): a row with 0 keeps c, gets its h_prev
+ *                             (xh[row][hidden ..]) written to h_next, and writes no h_up. */
+int halo_rnnt_stream_open(const int *n_frames, const int *flags, int B, int rows, int *state, long state_ld, int *pos, int *row_mask,
+                          float *scores, int64_t *tokens, int64_t *frames, long tokens_ld, int capacity, float *xh, long xh_layer_stride,
+                          long ldx, float *c, long c_layer_stride, const float *wte, int E, int hidden, int layers, int *live, int n_live,
+                          halo_stream_t stream);
+int halo_rnnt_advance_stream(const float *f, long f_row_stride, long f_frame_stride, int N, int T, int V, const float *g, long ldg,
+                             const float *g_bias, const int *n_frames, int *state, long state_ld, float *scores, int64_t *tokens,
+                             int64_t *frames, long tokens_ld, int capacity, int max_symbols, const float *wte, int E, float *x_next,
+                             long ldx, int *live, int *pos, int *row_mask, halo_stream_t stream);
+int halo_rnnt_lstm_cell_rows(const float *xh, long ldx, int rows, int hidden, const void *w_image, const float *b_ih, const float *b_hh,
+                             float *c, float *h_next, long ld_next, float *h_up, long ld_up, const int *row_mask, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Beam search of the RNN transducer head (haloop_amd/transducer.py BeamDecoder; alignment-length synchronous decoding with exact merging,
