@@ -15,12 +15,14 @@
 // global -> registers, no LDS staging: every weight element is used by exactly one MFMA of the workgroup).  The four waves split K and
 // their partial tiles are summed in a fixed order through LDS (bitwise reproducible).  Arithmetic: split-bf16, three MFMAs per
 // product, fp32 accumulate (the bf16x3 mode of the library, in every math mode but exact f32, where the caller keeps the old path).
+//
+// The beam search (decode_beam.hip holds its selection) runs the same step on slots = N * W rows; its attention launch is the ANCESTORS
+// instantiation of dec_attention_pair_kernel, behind halo_decode_beam_attention below.
 #include <hip/hip_fp16.h>
 #include <type_traits>
 #include "halo_common.h"
 #include "halo_internal.h"
 #include "decode_linear.h"
-#include "decode_attn.h"
 
 namespace {
 
@@ -41,32 +43,75 @@ __global__ __launch_bounds__(128) void dec_pack_kernel(const float *__restrict__
 
 // ---- both attentions of one decode step: blockIdx.z = 0 cross-attention over the cached memory keys (key-length mask, no rotary),
 //      1 = self-attention: this step's k / v rounded to float16 and stored at cache position n_keys - 1, q rotated by that position,
-//      cached keys by theirs (from the fp16 bytes, transformer.py:341-343).  One wave per (utterance, head, kind). ----
+//      cached keys by theirs (from the fp16 bytes, transformer.py:341-343).  One wave per (row, head, kind).
+//      The greedy step has one row per utterance.  The beam search (ANCESTORS) has slots = N * W rows, slot n * W + r hypothesis r of
+//      utterance n: the cross-attention caches exist once per UTTERANCE (slot / W), and the self-attention caches are never gathered: a
+//      kept hypothesis continues its parent's history by reading position j < t = n_keys - 1 from the cache row anc[slot][j] that
+//      computed it (the per-slot ancestor table of this step), and stores position t into its own row.  With W = 1 and the identity
+//      table it is the greedy launch bit for bit: the same code.
+//      No race inside a launch: the table names positions < t only, which earlier launches stored; position t of a slot is stored by
+//      that slot's own wave into its own cache row and used by it from registers, and no slot reads position t of another slot. ----
 struct DecAttnArgs {
-    const float *a;          // [N][4C]: cross query | self q | k | v
+    const float *a;          // [rows][4C]: cross query | self q | k | v
     long a_rs;
-    int C, heads, hd;
-    const __half *mem_k, *mem_v;     // [N][heads][S][hd]
+    int C, heads, hd, W, slots;      // rows = slots = N * W (greedy: W = 1)
+    const __half *mem_k, *mem_v;     // [rows / W][heads][S][hd]: one per utterance
     int S;
-    const int *mem_len;
-    __half *time_k, *time_v;         // [N][heads][Tc][hd]
+    const int *mem_len;              // [rows / W]
+    __half *time_k, *time_v;         // [rows][heads][Tc][hd]
     int Tc, n_keys;
+    const int *anc;                  // ANCESTORS: [slots][anc_ld], the cache row that holds position j < n_keys - 1 of this slot's history
+    long anc_ld;
     const float *cs, *sn;            // rotary tables [>= n_keys][hd/2]
     float scale;
-    float *y;                        // [N][2C]: cross output | self output
+    float *y;                        // [rows][2C]: cross output | self output
     long y_rs;
 };
+
+// DPL consecutive float16 values (2, 4, 8 or 16: one lane's chunk of a cached key or value) as floats, by one or two vector loads
+template <int DPL>
+__device__ __forceinline__ void load_halfs(const __half *src, float *out) {
+    if constexpr (DPL == 2) {
+        const __half2 v = *reinterpret_cast<const __half2 *>(src);
+        out[0] = __low2float(v); out[1] = __high2float(v);
+    } else {
+        typedef unsigned uvec __attribute__((ext_vector_type(DPL == 4 ? 2 : 4)));
+#pragma unroll
+        for (int part = 0; part < (DPL == 16 ? 2 : 1); ++part) {
+            const uvec raw = *reinterpret_cast<const uvec *>(src + part * 8);
+#pragma unroll
+            for (int w = 0; w < (DPL == 4 ? 2 : 4); ++w) {
+                const unsigned u = raw[w];
+                const __half2 v = *reinterpret_cast<const __half2 *>(&u);
+                out[part * 8 + 2 * w] = __low2float(v);
+                out[part * 8 + 2 * w + 1] = __high2float(v);
+            }
+        }
+    }
+}
+
+// a lane's PPL rotary pairs of x turned by the table entries at cs / sn (the position's row, at the lane's first pair)
+template <int PPL>
+__device__ __forceinline__ void rotate_pairs(float *x, const float *cs, const float *sn) {
+#pragma unroll
+    for (int i = 0; i < PPL; ++i) {
+        const float cc = cs[i], sv = sn[i];
+        const float r0 = x[2 * i] * cc + (-x[2 * i + 1]) * sv, r1 = x[2 * i + 1] * cc + x[2 * i] * sv;
+        x[2 * i] = r0; x[2 * i + 1] = r1;
+    }
+}
 
 // Eight lanes share a key (lane = 8 * (key within the pass) + dim chunk), each holding DPL = HD / 8 dims (whole rotary pairs): a pass of
 // the wave scores eight keys (the partial dots meet by three xor shuffles) and, after the softmax, accumulates eight keys' p * v (the
 // eight key groups meet by three more) -- one vector load per lane and pass for K and one for V, nothing serial over the keys.
-// (load_halfs: decode_attn.h)
-template <int HD, int MAXK>
+template <int HD, int MAXK, bool ANCESTORS>
 __global__ __launch_bounds__(64) void dec_attention_pair_kernel(const DecAttnArgs p) {
     constexpr int DPL = HD / 8, PPL = DPL / 2, HALF = HD / 2;
     __shared__ float ps[MAXK];
     const int h = blockIdx.x, n = blockIdx.y, self = blockIdx.z, lane = threadIdx.x;
     const int c = lane & 7, jl = lane >> 3;
+    int utt = n;
+    if constexpr (ANCESTORS) utt = n / p.W;
     const float *qp = p.a + (long)n * p.a_rs + (self ? p.C : 0) + (long)h * HD;
     const int n_keys = self ? p.n_keys : p.S, Tc = self ? p.Tc : p.S;
     const int tq = n_keys - 1;
@@ -74,19 +119,12 @@ __global__ __launch_bounds__(64) void dec_attention_pair_kernel(const DecAttnArg
     float q[DPL];
 #pragma unroll
     for (int i = 0; i < DPL; ++i) q[i] = qp[c * DPL + i];
-    if (cs) {
-#pragma unroll
-        for (int i = 0; i < PPL; ++i) {
-            const float cc = cs[(long)tq * HALF + c * PPL + i], sv = sn[(long)tq * HALF + c * PPL + i];
-            const float r0 = q[2 * i] * cc + (-q[2 * i + 1]) * sv, r1 = q[2 * i + 1] * cc + q[2 * i] * sv;
-            q[2 * i] = r0; q[2 * i + 1] = r1;
-        }
-    }
+    if (cs) rotate_pairs<PPL>(q, cs + (long)tq * HALF + c * PPL, sn + (long)tq * HALF + c * PPL);
 #pragma unroll
     for (int i = 0; i < DPL; ++i) q[i] *= p.scale;
-    const long base = ((long)n * p.heads + h) * Tc * HD;
-    const __half *kb = self ? p.time_k + base : p.mem_k + base;
-    const __half *vb = self ? p.time_v + base : p.mem_v + base;
+    const long row_elems = (long)Tc * HD;                               // one (row, head) plane of a cache
+    const long base = ((long)(self ? n : utt) * p.heads + h) * row_elems;
+    const __half *kb = self ? p.time_k : p.mem_k, *vb = self ? p.time_v : p.mem_v;
     // self: this step's key / value chunk of this lane (fp32 rows, rounded to fp16 as the cache holds them); lanes of key group 0 store it
     float kf[DPL], vf[DPL];
     if (self) {
@@ -100,7 +138,18 @@ __global__ __launch_bounds__(64) void dec_attention_pair_kernel(const DecAttnArg
             }
         }
     }
-    const int klim = self ? n_keys : max(0, min(n_keys, p.mem_len ? p.mem_len[n] : n_keys));
+    const int klim = self ? n_keys : max(0, min(n_keys, p.mem_len ? p.mem_len[utt] : n_keys));
+    // the plane a key is read from: the row's own (cross: its utterance's); ANCESTORS, self, j < tq: the ancestor's row (clamped: a bad
+    // table cannot leave the caches).  Without ANCESTORS it folds to base
+    auto plane = [&](int j) {
+        if constexpr (ANCESTORS) {
+            if (!self) return base;
+            const int row = min(max(p.anc[(long)n * p.anc_ld + j], 0), p.slots - 1);
+            return ((long)row * p.heads + h) * row_elems;
+        } else {
+            return base;
+        }
+    };
     for (int j0 = 0; j0 < klim; j0 += 8) {
         const int j = j0 + jl;
         float sc = 0.f;
@@ -110,16 +159,9 @@ __global__ __launch_bounds__(64) void dec_attention_pair_kernel(const DecAttnArg
 #pragma unroll
                 for (int i = 0; i < DPL; ++i) k[i] = kf[i];
             } else {
-                load_halfs<DPL>(kb + (long)j * HD + c * DPL, k);
+                load_halfs<DPL>(kb + plane(j) + (long)j * HD + c * DPL, k);
             }
-            if (cs) {
-#pragma unroll
-                for (int i = 0; i < PPL; ++i) {
-                    const float cc = cs[(long)j * HALF + c * PPL + i], sv = sn[(long)j * HALF + c * PPL + i];
-                    const float r0 = k[2 * i] * cc + (-k[2 * i + 1]) * sv, r1 = k[2 * i + 1] * cc + k[2 * i] * sv;
-                    k[2 * i] = r0; k[2 * i + 1] = r1;
-                }
-            }
+            if (cs) rotate_pairs<PPL>(k, cs + (long)j * HALF + c * PPL, sn + (long)j * HALF + c * PPL);
 #pragma unroll
             for (int i = 0; i < DPL; ++i) sc = fmaf(q[i], k[i], sc);
         }
@@ -152,7 +194,7 @@ __global__ __launch_bounds__(64) void dec_attention_pair_kernel(const DecAttnArg
 #pragma unroll
                 for (int i = 0; i < DPL; ++i) v[i] = vf[i];
             } else {
-                load_halfs<DPL>(vb + (long)j * HD + c * DPL, v);
+                load_halfs<DPL>(vb + plane(j) + (long)j * HD + c * DPL, v);
             }
             const float pj = ps[j];
 #pragma unroll
@@ -312,6 +354,38 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const DecTokenArgs p) {
     }
 }
 
+// what both attention entry points check and launch: rows = N (greedy, beam 1) or the search's slots
+template <bool ANCESTORS>
+int dec_attention_launch(const float *a, long a_row_stride, int rows, int beam, int heads, int head_dim, const void *mem_k,
+                         const void *mem_v, int S, const int *memory_lengths, void *time_k, void *time_v, int cache_len, int n_keys,
+                         const int *ancestors, long ancestors_ld, const float *cos_table, const float *sin_table, float *y,
+                         long y_row_stride, halo_stream_t stream) {
+    HALO_CHECK_ARG(a && mem_k && mem_v && time_k && time_v && y && rows > 0 && heads > 0 && S > 0);
+    HALO_CHECK_ARG(head_dim == 16 || head_dim == 32 || head_dim == 64 || head_dim == 128);
+    HALO_CHECK_ARG(n_keys >= 1 && n_keys <= cache_len && (!cos_table) == (!sin_table));
+    const int C = heads * head_dim, maxk = n_keys > S ? n_keys : S;
+    HALO_CHECK_ARG(a_row_stride >= 4L * C && y_row_stride >= 2L * C && maxk <= 8192);
+    DecAttnArgs p;
+    p.a = a; p.a_rs = a_row_stride; p.C = C; p.heads = heads; p.hd = head_dim; p.W = beam; p.slots = rows;
+    p.mem_k = (const __half *)mem_k; p.mem_v = (const __half *)mem_v; p.S = S; p.mem_len = memory_lengths;
+    p.time_k = (__half *)time_k; p.time_v = (__half *)time_v; p.Tc = cache_len; p.n_keys = n_keys;
+    p.anc = ancestors; p.anc_ld = ancestors_ld;
+    p.cs = cos_table; p.sn = sin_table; p.scale = 1.0f / sqrtf((float)head_dim); p.y = y; p.y_rs = y_row_stride;
+    const dim3 grid((unsigned)heads, (unsigned)rows, 2);
+    hipStream_t st = (hipStream_t)stream;
+#define HALO_DEC_ATTN(HD)                                                                                                  \
+    do {                                                                                                                   \
+        if (maxk <= 1024) hipLaunchKernelGGL((dec_attention_pair_kernel<HD, 1024, ANCESTORS>), grid, dim3(64), 0, st, p);  \
+        else hipLaunchKernelGGL((dec_attention_pair_kernel<HD, 8192, ANCESTORS>), grid, dim3(64), 0, st, p);               \
+    } while (0)
+    if (head_dim == 64) HALO_DEC_ATTN(64);
+    else if (head_dim == 128) HALO_DEC_ATTN(128);
+    else if (head_dim == 32) HALO_DEC_ATTN(32);
+    else HALO_DEC_ATTN(16);
+#undef HALO_DEC_ATTN
+    return halo_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -375,29 +449,18 @@ int halo_decode_linear_pair(const float *x, const float *x_side, long ldx, int r
 int halo_decode_attention_pair(const float *a, long a_row_stride, int N, int heads, int head_dim, const void *mem_k, const void *mem_v,
                                int S, const int *memory_lengths, void *time_k, void *time_v, int cache_len, int n_keys,
                                const float *cos_table, const float *sin_table, float *y, long y_row_stride, halo_stream_t stream) {
-    HALO_CHECK_ARG(a && mem_k && mem_v && time_k && time_v && y && N > 0 && heads > 0 && S > 0);
-    HALO_CHECK_ARG(head_dim == 16 || head_dim == 32 || head_dim == 64 || head_dim == 128);
-    HALO_CHECK_ARG(n_keys >= 1 && n_keys <= cache_len && (!cos_table) == (!sin_table));
-    const int C = heads * head_dim, maxk = n_keys > S ? n_keys : S;
-    HALO_CHECK_ARG(a_row_stride >= 4L * C && y_row_stride >= 2L * C && maxk <= 8192);
-    DecAttnArgs p;
-    p.a = a; p.a_rs = a_row_stride; p.C = C; p.heads = heads; p.hd = head_dim;
-    p.mem_k = (const __half *)mem_k; p.mem_v = (const __half *)mem_v; p.S = S; p.mem_len = memory_lengths;
-    p.time_k = (__half *)time_k; p.time_v = (__half *)time_v; p.Tc = cache_len; p.n_keys = n_keys;
-    p.cs = cos_table; p.sn = sin_table; p.scale = 1.0f / sqrtf((float)head_dim); p.y = y; p.y_rs = y_row_stride;
-    const dim3 grid((unsigned)heads, (unsigned)N, 2);
-    hipStream_t st = (hipStream_t)stream;
-#define HALO_DEC_ATTN(HD)                                                                                   \
-    do {                                                                                                    \
-        if (maxk <= 1024) hipLaunchKernelGGL((dec_attention_pair_kernel<HD, 1024>), grid, dim3(64), 0, st, p); \
-        else hipLaunchKernelGGL((dec_attention_pair_kernel<HD, 8192>), grid, dim3(64), 0, st, p);           \
-    } while (0)
-    if (head_dim == 64) HALO_DEC_ATTN(64);
-    else if (head_dim == 128) HALO_DEC_ATTN(128);
-    else if (head_dim == 32) HALO_DEC_ATTN(32);
-    else HALO_DEC_ATTN(16);
-#undef HALO_DEC_ATTN
-    return halo_launch_status();
+    return dec_attention_launch<false>(a, a_row_stride, N, 1, heads, head_dim, mem_k, mem_v, S, memory_lengths, time_k, time_v, cache_len,
+                                       n_keys, nullptr, 0, cos_table, sin_table, y, y_row_stride, stream);
+}
+
+int halo_decode_beam_attention(const float *a, long a_row_stride, int slots, int beam, int heads, int head_dim, const void *mem_k,
+                               const void *mem_v, int S, const int *memory_lengths, void *time_k, void *time_v, int cache_len, int n_keys,
+                               const int *ancestors, long ancestors_ld, const float *cos_table, const float *sin_table, float *y,
+                               long y_row_stride, halo_stream_t stream) {
+    HALO_CHECK_ARG(beam >= 1 && slots % beam == 0 && slots <= 65535);
+    HALO_CHECK_ARG(n_keys <= 1 || (ancestors && ancestors_ld >= n_keys - 1));
+    return dec_attention_launch<true>(a, a_row_stride, slots, beam, heads, head_dim, mem_k, mem_v, S, memory_lengths, time_k, time_v,
+                                      cache_len, n_keys, ancestors, ancestors_ld, cos_table, sin_table, y, y_row_stride, stream);
 }
 
 int halo_decode_memory_caches(const float *kv, long row_stride, int layers, void *caches, int N, int S, int heads, int head_dim,

@@ -1,11 +1,7 @@
 // Beam search of the encoder-decoder ASR model (haloop_amd/transformer.py BeamDecoder; the definition: include/halo.h)
 // on the fused decode launches of decode.hip: a step runs the 5 launches per layer and the LayerNorm + lm_head product on slots = N * W
-// rows (slot n * W + r is hypothesis r of utterance n), with the two launches of this file in the places of dec_attention_pair_kernel and
-// dec_token_kernel:
-//   dec_beam_attention_kernel  both attentions of a step.  The cross-attention caches exist once per UTTERANCE (slot / W), not per slot.
-//                              The self-attention caches are never gathered: a kept hypothesis continues its parent's history by
-//                              reading position j < t from the cache row anc[slot][j] that computed it (the per-slot ancestor table of
-//                              this step), and stores position t into its own row.
+// rows (slot n * W + r is hypothesis r of utterance n).  The attention launch is decode.hip's dec_attention_pair_kernel with the per-slot
+// ancestor table (halo_decode_beam_attention, there); this file holds the launch in the place of dec_token_kernel:
 //   dec_beam_select_kernel     one workgroup per utterance, on the pieces of beam_common.h: the log-sum-exp of every live slot, the W
 //                              best of the W * V candidates by rank, and the new beam: scores, lengths, flags, tokens, the next step's
 //                              ancestor rows and input embeddings.
@@ -14,150 +10,11 @@
 #include <hip/hip_fp16.h>
 #include "halo_common.h"
 #include "halo_internal.h"
-#include "decode_attn.h"
 #include "beam_common.h"
 
 namespace {
 
 using namespace beam;
-
-struct BeamAttnArgs {
-    const float *a;          // [slots][4C]: cross query | self q | k | v
-    long a_rs;
-    int C, heads, hd, W, slots;
-    const __half *mem_k, *mem_v;     // [slots / W][heads][S][hd]: one per utterance
-    int S;
-    const int *mem_len;              // [slots / W]
-    __half *time_k, *time_v;         // [slots][heads][Tc][hd]
-    int Tc, n_keys;
-    const int *anc;                  // [slots][anc_ld]: the cache row that holds position j < n_keys - 1 of this slot's history
-    long anc_ld;
-    const float *cs, *sn;            // rotary tables [>= n_keys][hd/2]
-    float scale;
-    float *y;                        // [slots][2C]: cross output | self output
-    long y_rs;
-};
-
-// dec_attention_pair_kernel of decode.hip (eight lanes share a key, DPL = HD / 8 dims each; the same rotary tables, the same softmax, the
-// same order of every sum: with W = 1 and the identity table the same bits) over slots = N * W rows.
-// No race inside the launch: the table names positions < t = n_keys - 1 only, which earlier launches stored; position t of a slot is
-// stored by that slot's own wave into its own cache row and used by it from registers, and no slot reads position t of another slot.
-// So nothing needs ordering inside the launch.
-template <int HD, int MAXK>
-__global__ __launch_bounds__(64) void dec_beam_attention_kernel(const BeamAttnArgs p) {
-    constexpr int DPL = HD / 8, PPL = DPL / 2, HALF = HD / 2;
-    __shared__ float ps[MAXK];
-    const int h = blockIdx.x, n = blockIdx.y, self = blockIdx.z, lane = threadIdx.x;
-    const int c = lane & 7, jl = lane >> 3;
-    const int utt = n / p.W;
-    const float *qp = p.a + (long)n * p.a_rs + (self ? p.C : 0) + (long)h * HD;
-    const int n_keys = self ? p.n_keys : p.S, Tc = self ? p.Tc : p.S;
-    const int tq = n_keys - 1;
-    const float *cs = self ? p.cs : nullptr, *sn = p.sn;
-    float q[DPL];
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) q[i] = qp[c * DPL + i];
-    if (cs) {
-#pragma unroll
-        for (int i = 0; i < PPL; ++i) {
-            const float cc = cs[(long)tq * HALF + c * PPL + i], sv = sn[(long)tq * HALF + c * PPL + i];
-            const float r0 = q[2 * i] * cc + (-q[2 * i + 1]) * sv, r1 = q[2 * i + 1] * cc + q[2 * i] * sv;
-            q[2 * i] = r0; q[2 * i + 1] = r1;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) q[i] *= p.scale;
-    const long row_elems = (long)Tc * HD;                               // one (row, head) plane of a cache
-    const long base = ((long)(self ? n : utt) * p.heads + h) * row_elems;
-    const __half *kb = self ? p.time_k : p.mem_k, *vb = self ? p.time_v : p.mem_v;
-    // self: this step's key / value chunk of this lane (fp32 rows, rounded to fp16 as the cache holds them); lanes of key group 0 store it
-    float kf[DPL], vf[DPL];
-    if (self) {
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) {
-            const __half kh = __float2half(qp[p.C + c * DPL + i]), vh = __float2half(qp[2 * p.C + c * DPL + i]);
-            kf[i] = __half2float(kh); vf[i] = __half2float(vh);
-            if (jl == 0) {
-                p.time_k[base + (long)tq * HD + c * DPL + i] = kh;
-                p.time_v[base + (long)tq * HD + c * DPL + i] = vh;
-            }
-        }
-    }
-    const int klim = self ? n_keys : max(0, min(n_keys, p.mem_len ? p.mem_len[utt] : n_keys));
-    // the plane a key is read from: the utterance's (cross), the ancestor's row (self, j < tq; clamped: a bad table cannot leave the caches)
-    auto plane = [&](int j) {
-        if (!self) return base;
-        const int row = min(max(p.anc[(long)n * p.anc_ld + j], 0), p.slots - 1);
-        return ((long)row * p.heads + h) * row_elems;
-    };
-    for (int j0 = 0; j0 < klim; j0 += 8) {
-        const int j = j0 + jl;
-        float sc = 0.f;
-        if (j < klim) {
-            float k[DPL];
-            if (self && j == tq) {                                // this step's row: not from the store just issued
-#pragma unroll
-                for (int i = 0; i < DPL; ++i) k[i] = kf[i];
-            } else {
-                load_halfs<DPL>(kb + plane(j) + (long)j * HD + c * DPL, k);
-            }
-            if (cs) {
-#pragma unroll
-                for (int i = 0; i < PPL; ++i) {
-                    const float cc = cs[(long)j * HALF + c * PPL + i], sv = sn[(long)j * HALF + c * PPL + i];
-                    const float r0 = k[2 * i] * cc + (-k[2 * i + 1]) * sv, r1 = k[2 * i + 1] * cc + k[2 * i] * sv;
-                    k[2 * i] = r0; k[2 * i + 1] = r1;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) sc = fmaf(q[i], k[i], sc);
-        }
-        sc += __shfl_xor(sc, 1, 64);
-        sc += __shfl_xor(sc, 2, 64);
-        sc += __shfl_xor(sc, 4, 64);
-        if (c == 0 && j < klim) ps[j] = sc;
-    }
-    __syncthreads();
-    float mx = -INFINITY;
-    for (int j = lane; j < klim; j += 64) mx = fmaxf(mx, ps[j]);
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int j = lane; j < klim; j += 64) {
-        const float e = expf(ps[j] - mx);
-        ps[j] = e;
-        sum += e;
-    }
-    sum = wave_sum(sum);
-    __syncthreads();
-    const float inv = 1.0f / sum;
-    float acc[DPL];
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) acc[i] = 0.f;
-    for (int j0 = 0; j0 < klim; j0 += 8) {
-        const int j = j0 + jl;
-        if (j < klim) {
-            float v[DPL];
-            if (self && j == tq) {
-#pragma unroll
-                for (int i = 0; i < DPL; ++i) v[i] = vf[i];
-            } else {
-                load_halfs<DPL>(vb + plane(j) + (long)j * HD + c * DPL, v);
-            }
-            const float pj = ps[j];
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) acc[i] = fmaf(pj, v[i], acc[i]);
-        }
-    }
-    float *yp = p.y + (long)n * p.y_rs + (self ? p.C : 0) + (long)h * HD + c * DPL;
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) {
-        float v = acc[i];
-        v += __shfl_xor(v, 8, 64);
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        if (jl == 0) yp[i] = v * inv;
-    }
-}
 
 constexpr int BEAM_LDS_FLOATS = 8192;      // 32 KiB of dynamic LDS, under the 64 KiB a launch gets without the opt-in
 
@@ -319,37 +176,6 @@ size_t beam_select_lds(const BeamSelArgs &p) { return p.cached ? (size_t)p.W * p
 }  // namespace
 
 extern "C" {
-
-int halo_decode_beam_attention(const float *a, long a_row_stride, int slots, int beam, int heads, int head_dim, const void *mem_k,
-                               const void *mem_v, int S, const int *memory_lengths, void *time_k, void *time_v, int cache_len, int n_keys,
-                               const int *ancestors, long ancestors_ld, const float *cos_table, const float *sin_table, float *y,
-                               long y_row_stride, halo_stream_t stream) {
-    HALO_CHECK_ARG(a && mem_k && mem_v && time_k && time_v && y && slots > 0 && heads > 0 && S > 0 && beam >= 1 && slots % beam == 0);
-    HALO_CHECK_ARG(head_dim == 16 || head_dim == 32 || head_dim == 64 || head_dim == 128);
-    HALO_CHECK_ARG(n_keys >= 1 && n_keys <= cache_len && (!cos_table) == (!sin_table));
-    HALO_CHECK_ARG(n_keys == 1 || (ancestors && ancestors_ld >= n_keys - 1));
-    const int C = heads * head_dim, maxk = n_keys > S ? n_keys : S;
-    HALO_CHECK_ARG(a_row_stride >= 4L * C && y_row_stride >= 2L * C && maxk <= 8192 && slots <= 65535);
-    BeamAttnArgs p;
-    p.a = a; p.a_rs = a_row_stride; p.C = C; p.heads = heads; p.hd = head_dim; p.W = beam; p.slots = slots;
-    p.mem_k = (const __half *)mem_k; p.mem_v = (const __half *)mem_v; p.S = S; p.mem_len = memory_lengths;
-    p.time_k = (__half *)time_k; p.time_v = (__half *)time_v; p.Tc = cache_len; p.n_keys = n_keys;
-    p.anc = ancestors; p.anc_ld = ancestors_ld;
-    p.cs = cos_table; p.sn = sin_table; p.scale = 1.0f / sqrtf((float)head_dim); p.y = y; p.y_rs = y_row_stride;
-    const dim3 grid((unsigned)heads, (unsigned)slots, 2);
-    hipStream_t st = (hipStream_t)stream;
-#define HALO_BEAM_ATTN(HD)                                                                                      \
-    do {                                                                                                        \
-        if (maxk <= 1024) hipLaunchKernelGGL((dec_beam_attention_kernel<HD, 1024>), grid, dim3(64), 0, st, p);  \
-        else hipLaunchKernelGGL((dec_beam_attention_kernel<HD, 8192>), grid, dim3(64), 0, st, p);               \
-    } while (0)
-    if (head_dim == 64) HALO_BEAM_ATTN(64);
-    else if (head_dim == 128) HALO_BEAM_ATTN(128);
-    else if (head_dim == 32) HALO_BEAM_ATTN(32);
-    else HALO_BEAM_ATTN(16);
-#undef HALO_BEAM_ATTN
-    return halo_launch_status();
-}
 
 int halo_decode_beam_select(const float *logits, long ld, int N, int beam, int V, int t, int capacity, int etx, float length_bonus,
                             const float *scores_in, const int *lengths_in, const int *finished_in, const int *tokens_in,

@@ -18,6 +18,7 @@ import os
 import torch
 
 from . import _lib, lora, ops
+from ._capture import capture
 
 SYNC_EVERY = 16          # sample() reads the alive flags every this many tokens
 
@@ -184,16 +185,10 @@ class Sampler:
         key = (self._images[0], _lib.get_math_mode(), self._cfg.data_ptr())
         entry = self._graphs.get(B)
         if entry is None or entry[0] != key:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
+            def step():
                 self._fused_layers(B, layers, head)
                 self._draw(B, True)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._fused_layers(B, layers, head)
-                self._draw(B, True)
+            graph, _ = capture(step)
             entry = (key, graph, (layers, head, self._cfg))       # the graph reads the images and the settings by address
             self._graphs[B] = entry
         return entry[1]

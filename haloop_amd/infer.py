@@ -3,6 +3,7 @@ log-probs -> greedy collapse, straight on the C ABI and replayed from one HIP gr
 import torch
 
 from . import _lib, ops
+from ._capture import capture
 from .ops import NO_DROPOUT
 from .rnn import lstm_param_list
 
@@ -94,14 +95,7 @@ class LstmCtcRecognizer:
             # (a changed weight: the graph replays launches that skip the weight packing, so it is captured again)
             self._graph_stamp = stamp
             self._static = x.contiguous().clone()        # private: refilling it must not write into the caller's tensor
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._run(self._static)
-            torch.cuda.current_stream().wait_stream(side)
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self._out = self._run(self._static)
+            self._graph, self._out = capture(lambda: self._run(self._static))
         if x.data_ptr() != self._static.data_ptr():
             self._static.copy_(x)
         self._graph.replay()

@@ -1635,7 +1635,7 @@ def decode_token(logits, tokens, t, plen, etx, alive, out_len, log_probs, sum_en
                                   wte.shape[1] if wte is not None else 0, ptr(y_next), _stream()), 'halo_decode_token')
 
 
-# ---- the two launches of the attention decoder's beam search (csrc/decode_beam.hip); neither allocates -----------------------------
+# ---- the two launches of the attention decoder's beam search (csrc/decode.hip, decode_beam.hip); neither allocates ------------------
 def decode_beam_attention(a, mem_k, mem_v, memory_lengths, time_k, time_v, n_keys, ancestors, table, out):
     """decode_attention_pair over slots = N * W rows a [slots, 4C]: mem_k / mem_v [N, heads, S, hd] per utterance, time_k / time_v
     [slots, heads, Tc, hd]; position j < n_keys - 1 is read from cache row ancestors[slot, j] (int32 [slots, >= n_keys - 1])."""

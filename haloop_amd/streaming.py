@@ -38,6 +38,7 @@ import os
 import torch
 
 from . import _lib, ops
+from ._capture import capture
 from .ctc import PrefixBeamStream
 from .ops import NO_DROPOUT, STREAM_ACTIVE, STREAM_BEGIN, STREAM_FINAL
 from .rnn import lstm_param_list
@@ -322,15 +323,7 @@ class StreamingRecognizer(_ChunkedStreams):
     def _capture(self, S, want_lp, buf):
         """The push chain as one HIP graph.  The warm-up run and the capture see every slot inactive, so they change no stream."""
         self._meta.zero_()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._chain(self._frames, S, want_lp, buf)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self._chain(self._frames, S, want_lp, buf)
-        return graph
+        return capture(lambda: self._chain(self._frames, S, want_lp, buf))[0]
 
     def _chain(self, frames, S, want_lp, buf):
         conv, cls = self.encoder.subsample, self.recognizer.classifier

@@ -36,6 +36,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
+from ._capture import GraphCache
 from ._linear import (NO_SITES, DropSites, WeightImages, training_images, drop_rows, forward_images, grad_images, linear, linear_dw, linear_dx, ln_linear,
                       normed_image, rowmajor_ok, use_split)
 from .attention import LayerNorm
@@ -429,7 +430,7 @@ class Decoder(nn.Module):
         self.ln_f = LayerNorm(head_dim * heads, bias=False)
         self.lm_head = nn.Linear(head_dim * heads, vocab, bias=False)
         self._images = WeightImages()
-        self._graphs = {}                                                 # captured greedy decodes, see _decode_graph
+        self._graphs = GraphCache()                                       # captured greedy decodes, see _decode_graph
         self.dropout_stream = DropoutStream()                             # Philox (seed, offset) per training forward
         self.beam_size = int(os.environ.get('HALO_ASR_BEAM', '0'))        # decode(): 0 greedy, W >= 1 BeamDecoder's search
         self.length_bonus = 0.0                                           # of that search
@@ -520,21 +521,46 @@ class Decoder(nn.Module):
         put(self.wte.weight, dwte)
         return dmem.view(N, S, C)
 
+    def _memory_caches_general(self, mem2d, rows, S):
+        """The cross-attention caches of the operator-per-launch path [L, 2, rows, heads, S, head_dim], warmed once per decode (:324-334)."""
+        C = mem2d.shape[1]
+        heads, head_dim = self.h[0].heads, self.h[0].head_dim
+        mem_cache = torch.zeros((len(self.h), 2, rows, heads, S, head_dim), dtype=torch.float16, device=mem2d.device)
+        for l, block in enumerate(self.h):
+            mm = block.mix_memory
+            kv = linear(mm._images, mem2d, (mm.k.weight, mm.v.weight))
+            ops.kv_cache_store(kv, C, mem_cache[l, 0], mem_cache[l, 1], rows, S, heads, head_dim, 0)
+        return mem_cache
+
+    def _step_general(self, y, mem_cache, mlen, time_cache, n_keys, table):
+        """One step on the operator-per-launch path: the rows' embeddings y [rows, C] (updated in place) -> logits [rows, V], over the
+        memory caches (key lengths mlen) and the self-attention caches, which receive position n_keys - 1."""
+        C, S = y.shape[1], mem_cache.shape[4]
+        for l, block in enumerate(self.h):
+            mm, mt = block.mix_memory, block.mix_time
+            xn = ops.layernorm_fwd(y, block.ln_time.weight)
+            # both attentions read the same ln_time(x) (:476-494): one GEMM gives the cross query and the self q | k | v
+            a = linear(mt._images, xn, (mm.q.weight, mt.q.weight, mt.k.weight, mt.v.weight))      # [rows, 4C]
+            m = ops.attention_decode(a, mem_cache[l, 0], mem_cache[l, 1], S, key_lengths=mlen)
+            linear(mm._images, m, mm.proj.weight, out=y, accumulate=True)
+            # cache store (fp16) + rotary + attention over the n_keys cached positions in one launch
+            s = ops.attention_decode_step(a[:, C:2 * C], a[:, 2 * C:3 * C], a[:, 3 * C:], time_cache[l, 0], time_cache[l, 1], n_keys,
+                                          table=table)
+            linear(mt._images, s, mt.proj.weight, out=y, accumulate=True)
+            h = linear(block._images, ops.layernorm_fwd(y, block.ln_chan.weight), block.mix_chan[0].weight, gelu='erf')
+            linear(block._images, h, block.mix_chan[2].weight, out=y, accumulate=True)
+        return linear(self._images, ops.layernorm_fwd(y, self.ln_f.weight), self.lm_head.weight)
+
     @torch.no_grad()
     def _decode_core(self, mem2d, mlen, tokens_init, plen, N, S, T):
         """All launches of one batched greedy decode, host-sync free (capturable in a HIP graph).
         mem2d [N*S, C] fp32 features, mlen [N] int32, tokens_init [N, W] int64 (STX, optional prompt, ETX fill)."""
         dev = mem2d.device
-        C = mem2d.shape[1]
         L = len(self.h)
         heads, head_dim = self.h[0].heads, self.h[0].head_dim
         tokens = tokens_init.clone()
-        mem_cache = torch.zeros((L, 2, N, heads, S, head_dim), dtype=torch.float16, device=dev)
+        mem_cache = self._memory_caches_general(mem2d, N, S)
         time_cache = torch.zeros((L, 2, N, heads, T, head_dim), dtype=torch.float16, device=dev)
-        for l, block in enumerate(self.h):                                   # cross-attention caches, warmed once (:324-334)
-            mm = block.mix_memory
-            kv = linear(mm._images, mem2d, (mm.k.weight, mm.v.weight))
-            ops.kv_cache_store(kv, C, mem_cache[l, 0], mem_cache[l, 1], N, S, heads, head_dim, 0)
         table = ops.RopeTable(T, head_dim, dev)
         alive = torch.ones(N, dtype=torch.uint8, device=dev)
         out_len = torch.zeros(N, dtype=torch.int32, device=dev)
@@ -544,20 +570,7 @@ class Decoder(nn.Module):
         # compacts to the alive rows instead, which changes no alive row's result) and nothing syncs with the host
         for t in range(T):
             y = ops.embed_fwd(tokens[:, t:t + 1], self.wte.weight, None)         # [N, C]
-            for l, block in enumerate(self.h):
-                mm, mt = block.mix_memory, block.mix_time
-                xn = ops.layernorm_fwd(y, block.ln_time.weight)
-                # both attentions read the same ln_time(x) (:476-494): one GEMM gives the cross query and the self q | k | v
-                a = linear(mt._images, xn, (mm.q.weight, mt.q.weight, mt.k.weight, mt.v.weight))      # [N, 4C]
-                m = ops.attention_decode(a, mem_cache[l, 0], mem_cache[l, 1], S, key_lengths=mlen)
-                linear(mm._images, m, mm.proj.weight, out=y, accumulate=True)
-                # cache store (fp16) + rotary + attention over the t + 1 cached positions in one launch
-                s = ops.attention_decode_step(a[:, C:2 * C], a[:, 2 * C:3 * C], a[:, 3 * C:], time_cache[l, 0], time_cache[l, 1], t + 1,
-                                              table=table)
-                linear(mt._images, s, mt.proj.weight, out=y, accumulate=True)
-                h = linear(block._images, ops.layernorm_fwd(y, block.ln_chan.weight), block.mix_chan[0].weight, gelu='erf')
-                linear(block._images, h, block.mix_chan[2].weight, out=y, accumulate=True)
-            logits = linear(self._images, ops.layernorm_fwd(y, self.ln_f.weight), self.lm_head.weight)
+            logits = self._step_general(y, mem_cache, mlen, time_cache, t + 1, table)
             val, idx, negent = ops.logprob_max(logits, want_entropy=True)
             ops.greedy_update(val, idx, negent, tokens, t, plen, ETX, alive, out_len, log_probs, sum_entropies)
         return tokens, out_len, log_probs, sum_entropies
@@ -587,6 +600,41 @@ class Decoder(nn.Module):
             self._dec_images = (stamp, layers, head)
         return self._dec_images[1], self._dec_images[2]
 
+    def _memory_caches_fused(self, mem2d, N, S):
+        """The cross-attention caches of the fused path [L, 2, N, heads, S, head_dim], warmed once per decode (:324-334): the memory
+        keys / values of all layers are ONE product and one store."""
+        heads, head_dim = self.h[0].heads, self.h[0].head_dim
+        mem_cache = torch.empty((len(self.h), 2, N, heads, S, head_dim), dtype=torch.float16, device=mem2d.device)
+        kv_weights = tuple(w for block in self.h for w in (block.mix_memory.k.weight, block.mix_memory.v.weight))
+        ops.decode_memory_caches(linear(self._images, mem2d, kv_weights), mem_cache)
+        return mem_cache
+
+    @staticmethod
+    def _decode_ksplit(C):
+        """The two accumulating products of a layer (K = 2C, 4C into C features: 128 workgroups at N = 64, each streaming its weights and
+        its rows over the whole K) run as two K-slices on twice the workgroups (HALO_DECODE_KSPLIT=0: one slice, the round-4 launches):
+        _step_fused then needs the two side buffers."""
+        return os.environ.get('HALO_DECODE_KSPLIT', '1') != '0' and (2 * C) % 512 == 0
+
+    def _step_fused(self, images, y, a, att, hid, logits, sa, sb, attention):
+        """The launches of one step on the fused path, 5 per layer and the ln_f + lm_head product: the rows' embeddings y [rows, C]
+        -> logits [rows, V].  a, hid [rows, 4C]: cross query | self q | k | v and the MLP hidden rows; att [rows, 2C]: cross | self
+        attention outputs, written from a by ``attention(l)``, the step's attention launch of layer l.  With side buffers sa, sb
+        [rows, C] (K-sliced products) the residual stream is the pair (y, side): slice 0 writes y = (y + side) + its half, slice 1 its
+        half to the OTHER side buffer; the LayerNorm launches read y + side.  Every sum in a fixed order."""
+        layers, head_img = images
+        C, V = y.shape[1], logits.shape[1]
+        side = None                                                          # (y alone: the embedding of the step's token)
+        for l, block in enumerate(self.h):
+            w_qkv, w_proj, w_fc, w_fc2 = layers[l]
+            ops.decode_linear(y, w_qkv, 4 * C, a, ln_weight=block.ln_time.weight, x_side=side)      # both attentions read ln_time(x) (:476-494)
+            attention(l)
+            ops.decode_linear(att, w_proj, C, y, accumulate=True, side_in=side, side_out=sa)         # x += cross proj + self proj
+            ops.decode_linear(y, w_fc, 4 * C, hid, ln_weight=block.ln_chan.weight, gelu=True, x_side=sa)
+            ops.decode_linear(hid, w_fc2, C, y, accumulate=True, side_in=sa, side_out=sb)
+            side = sb
+        ops.decode_linear(y, head_img, V, logits, ln_weight=self.ln_f.weight, x_side=side)
+
     @torch.no_grad()
     def _decode_core_fused(self, mem2d, mlen, tokens_init, plen, N, S, T):
         """_decode_core on the fused launches: 5 per layer and step, 2 per step for the head (+ the cache warm-up)."""
@@ -595,13 +643,10 @@ class Decoder(nn.Module):
         L = len(self.h)
         heads, head_dim = self.h[0].heads, self.h[0].head_dim
         V = self.lm_head.weight.shape[0]
-        layers, head_img = self._decode_images()
+        images = self._decode_images()
         tokens = tokens_init.clone()
-        mem_cache = torch.empty((L, 2, N, heads, S, head_dim), dtype=torch.float16, device=dev)
+        mem_cache = self._memory_caches_fused(mem2d, N, S)
         time_cache = torch.zeros((L, 2, N, heads, T, head_dim), dtype=torch.float16, device=dev)
-        # cross-attention caches, warmed once (:324-334): the memory keys / values of all layers are ONE product and one store
-        kv_weights = tuple(w for block in self.h for w in (block.mix_memory.k.weight, block.mix_memory.v.weight))
-        ops.decode_memory_caches(linear(self._images, mem2d, kv_weights), mem_cache)
         table = ops.RopeTable(T, head_dim, dev)
         alive = torch.ones(2, N, dtype=torch.uint8, device=dev)             # double-buffered by step parity (halo_decode_token)
         out_len = torch.zeros(N, dtype=torch.int32, device=dev)
@@ -613,47 +658,18 @@ class Decoder(nn.Module):
         logits = torch.empty(N, V, device=dev, dtype=torch.float32)
         wte = self.wte.weight.detach()
         y = ops.embed_fwd(tokens[:, 0:1], wte, None)                         # [N, C]; later steps: written by decode_token
-        # The two accumulating products of a layer (K = 2C, 4C into C features: 128 workgroups at N = 64, each streaming its weights and
-        # its rows over the whole K) run as two K-slices on twice the workgroups: the residual stream is the pair (y, side) -- slice 0
-        # writes y = (y + side) + its half, slice 1 its half to the OTHER side buffer; the LayerNorm launches read y + side.  Every sum in
-        # a fixed order (HALO_DECODE_KSPLIT=0: one slice, the round-4 launches).
-        ksplit = os.environ.get('HALO_DECODE_KSPLIT', '1') != '0' and (2 * C) % 512 == 0
-        sa, sb = (torch.empty(N, C, device=dev, dtype=torch.float32) for _ in range(2)) if ksplit else (None, None)
+        sa, sb = (torch.empty(N, C, device=dev, dtype=torch.float32) for _ in range(2)) if self._decode_ksplit(C) else (None, None)
         for t in range(T):
-            side = None                                                      # (y alone: the embedding of the step's token)
-            for l, block in enumerate(self.h):
-                w_qkv, w_proj, w_fc, w_fc2 = layers[l]
-                ops.decode_linear(y, w_qkv, 4 * C, a, ln_weight=block.ln_time.weight, x_side=side)      # both attentions read ln_time(x) (:476-494)
-                ops.decode_attention_pair(a, mem_cache[l, 0], mem_cache[l, 1], mlen, time_cache[l, 0], time_cache[l, 1], t + 1, table, att)
-                ops.decode_linear(att, w_proj, C, y, accumulate=True, side_in=side, side_out=sa)         # x += cross proj + self proj
-                ops.decode_linear(y, w_fc, 4 * C, hid, ln_weight=block.ln_chan.weight, gelu=True, x_side=sa)
-                ops.decode_linear(hid, w_fc2, C, y, accumulate=True, side_in=sa, side_out=sb)
-                side = sb
-            ops.decode_linear(y, head_img, V, logits, ln_weight=self.ln_f.weight, x_side=side)
+            self._step_fused(images, y, a, att, hid, logits, sa, sb, lambda l: ops.decode_attention_pair(
+                a, mem_cache[l, 0], mem_cache[l, 1], mlen, time_cache[l, 0], time_cache[l, 1], t + 1, table, att))
             ops.decode_token(logits, tokens, t, plen, ETX, alive, out_len, log_probs, sum_entropies, wte, y if t + 1 < T else None)
         return tokens, out_len, log_probs, sum_entropies
 
     def _decode_graph(self, key, mem2d, mlen, tokens, plen, N, S, T):
         """One HIP graph per (shape, parameter version): ~13 launches x layers x steps become one replay."""
-        stamp = tuple((p._version, p.data_ptr()) for p in self.parameters())
-        entry = self._graphs.get(key)
-        if entry is None or entry['stamp'] != stamp:
-            core = self._decode_core_fused if self._fused_decode_ok(mem2d.shape[1]) else self._decode_core
-            static = (mem2d.clone(), mlen.clone(), tokens.clone())
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                core(*static, plen, N, S, T)                            # warm-up: weight images are built outside the capture
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                outs = core(*static, plen, N, S, T)
-            # the graph reads the cached weight images by address: keep them alive as long as the graph
-            held = [list(m._images._cache.values()) for m in self.modules() if hasattr(m, '_images')] + [getattr(self, '_dec_images', None)]
-            if len(self._graphs) >= 8:
-                self._graphs.pop(next(iter(self._graphs)))
-            entry = dict(stamp=stamp, graph=graph, static=static, outs=outs, held=held)
-            self._graphs[key] = entry
+        core = self._decode_core_fused if self._fused_decode_ok(mem2d.shape[1]) else self._decode_core
+        entry = self._graphs.entry(self, key, lambda: (mem2d.clone(), mlen.clone(), tokens.clone()),
+                                   lambda static: core(*static, plen, N, S, T))
         for dst, src in zip(entry['static'], (mem2d, mlen, tokens)):
             dst.copy_(src)
         entry['graph'].replay()
@@ -739,8 +755,8 @@ class BeamDecoder:
             B = the W best by (rank = fmaf(length_bonus, length, score) descending, position j V + k ascending), rank > -inf
 
     W = 1 with length_bonus 0 is ``Decoder.decode``'s greedy search token for token.  The fused path costs ``5 * layers + 2`` launches per
-    step for the whole batch (csrc/decode.hip's products on N * W rows, csrc/decode_beam.hip's attention through a per-slot ancestor
-    table and its selection), replayed from a captured graph unless HALO_DECODE_GRAPH=0; the general path (f32 mode, widths the fused
+    step for the whole batch (csrc/decode.hip's products and its attention through a per-slot ancestor table on N * W rows,
+    csrc/decode_beam.hip's selection), replayed from a captured graph unless HALO_DECODE_GRAPH=0; the general path (f32 mode, widths the fused
     products refuse, HALO_DECODE_FUSED=0) runs the same search on ``Decoder._decode_core``'s operators over N * W rows, the caches
     gathered physically and the candidates pruned by a stable sort.
 
@@ -772,7 +788,7 @@ class BeamDecoder:
             self._att, self._logits = torch.zeros(R * 2 * C, **f32), torch.zeros(R * V, **f32)
             self._y, self._sa, self._sb = (torch.zeros(R * C, **f32) for _ in range(3))
         self._device = dev      # of the buffers: a decoder moved since needs a new BeamDecoder
-        self._graphs = {}
+        self._graphs = GraphCache()
         self.last_logprobs = self.last_finished = self.last_ctc = None
         self._joint = None      # the joint search's buffers, allocated at its first use and again when S grows
         self._joint_S = 0
@@ -789,7 +805,7 @@ class BeamDecoder:
                                    psi=[torch.zeros(R, **f32) for _ in range(2)], par=torch.zeros(R, **i32),
                                    last=[torch.zeros(R, **i32) for _ in range(2)])
             self._joint_S = S
-            self._graphs = {k: v for k, v in self._graphs.items() if 'joint' not in k}
+            self._graphs.entries = {k: v for k, v in self._graphs.entries.items() if 'joint' not in k}
         return self._joint
 
     @property
@@ -856,11 +872,9 @@ class BeamDecoder:
         dev, C = mem2d.device, mem2d.shape[1]
         L, heads, head_dim = len(dec.h), dec.h[0].heads, dec.h[0].head_dim
         V = dec.lm_head.weight.shape[0]
-        layers, head_img = dec._decode_images()
+        images = dec._decode_images()
         R, ld = N * W, self.capacity
-        mem_cache = torch.empty((L, 2, N, heads, S, head_dim), dtype=torch.float16, device=dev)     # one per utterance, not per slot
-        kv_weights = tuple(w for block in dec.h for w in (block.mix_memory.k.weight, block.mix_memory.v.weight))
-        ops.decode_memory_caches(linear(dec._images, mem2d, kv_weights), mem_cache)
+        mem_cache = dec._memory_caches_fused(mem2d, N, S)                    # one per utterance, not per slot
         table = ops.RopeTable(cap, head_dim, dev)
         rec = [(s[:R].view(N, W), n[:R].view(N, W), f[:R].view(N, W), t[:R * ld].view(N, W, ld), a[:R * ld].view(R, ld))
                for s, n, f, t, a in self._rec]
@@ -871,9 +885,7 @@ class BeamDecoder:
         y = self._y[:R * C].view(R, C)
         wte = dec.wte.weight.detach()
         y.copy_(wte[STX].expand(R, C))                                       # later steps: written by decode_beam_select
-        # the residual stream as the pair (y, side) with K-sliced accumulating products, as in Decoder._decode_core_fused
-        ksplit = os.environ.get('HALO_DECODE_KSPLIT', '1') != '0' and (2 * C) % 512 == 0
-        sa, sb = (self._sa[:R * C].view(R, C), self._sb[:R * C].view(R, C)) if ksplit else (None, None)
+        sa, sb = (self._sa[:R * C].view(R, C), self._sb[:R * C].view(R, C)) if dec._decode_ksplit(C) else (None, None)
         if x is not None:
             jb = self._joint
             state = [b[:R * S * 2].view(R, S, 2) for b in jb['state']]
@@ -882,17 +894,8 @@ class BeamDecoder:
             ops.ctc_prefix_advance(x, mlen, ETX, state[0])                   # the empty prefix's state into slot 0 of every utterance
         for t in range(cap):
             q = t & 1
-            side = None
-            for l, block in enumerate(dec.h):
-                w_qkv, w_proj, w_fc, w_fc2 = layers[l]
-                ops.decode_linear(y, w_qkv, 4 * C, a, ln_weight=block.ln_time.weight, x_side=side)
-                ops.decode_beam_attention(a, mem_cache[l, 0], mem_cache[l, 1], mlen, time_cache[l, 0], time_cache[l, 1], t + 1, rec[q][4],
-                                          table, att)
-                ops.decode_linear(att, w_proj, C, y, accumulate=True, side_in=side, side_out=sa)
-                ops.decode_linear(y, w_fc, 4 * C, hid, ln_weight=block.ln_chan.weight, gelu=True, x_side=sa)
-                ops.decode_linear(hid, w_fc2, C, y, accumulate=True, side_in=sa, side_out=sb)
-                side = sb
-            ops.decode_linear(y, head_img, V, logits, ln_weight=dec.ln_f.weight, x_side=side)
+            dec._step_fused(images, y, a, att, hid, logits, sa, sb, lambda l: ops.decode_beam_attention(
+                a, mem_cache[l, 0], mem_cache[l, 1], mlen, time_cache[l, 0], time_cache[l, 1], t + 1, rec[q][4], table, att))
             if x is None:
                 ops.decode_beam_select(logits, t, cap, ETX, self.length_bonus, rec[q], rec[1 - q], ranks, wte, y if t + 1 < cap else None)
                 continue
@@ -908,29 +911,11 @@ class BeamDecoder:
     def _graph(self, mem2d, mlen, N, S, W, cap, x=None, c=0.0):
         """One HIP graph per (shape, width, parameter version), the sibling of ``Decoder._decode_graph``; the joint search has graphs of
         its own, with the log-probabilities copied into a static buffer."""
-        dec = self.decoder
         key = (N, S, W, cap, self.length_bonus, str(mem2d.device), _lib.get_math_mode())
         if x is not None:
             key += ('joint', c)
-        stamp = tuple((p._version, p.data_ptr()) for p in dec.parameters())
-        entry = self._graphs.get(key)
-        if entry is None or entry['stamp'] != stamp:
-            static = (mem2d.clone(), mlen.clone()) + ((x.clone(),) if x is not None else ())
-            args = (*static[:2], N, S, W, cap) + ((static[2], c) if x is not None else ())
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._core_fused(*args)                                  # warm-up: weight images are built outside the capture
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                outs = self._core_fused(*args)
-            # the graph reads the cached weight images by address: keep them alive as long as the graph
-            held = [list(m._images._cache.values()) for m in dec.modules() if hasattr(m, '_images')] + [getattr(dec, '_dec_images', None)]
-            if len(self._graphs) >= 8:
-                self._graphs.pop(next(iter(self._graphs)))
-            entry = dict(stamp=stamp, graph=graph, static=static, outs=outs, held=held)
-            self._graphs[key] = entry
+        entry = self._graphs.entry(self.decoder, key, lambda: (mem2d.clone(), mlen.clone()) + ((x.clone(),) if x is not None else ()),
+                                   lambda static: self._core_fused(*static[:2], N, S, W, cap, *((static[2], c) if x is not None else ())))
         for dst, src in zip(entry['static'], (mem2d, mlen, x)):
             dst.copy_(src)
         entry['graph'].replay()
@@ -946,12 +931,8 @@ class BeamDecoder:
         utt = torch.arange(N, device=dev).repeat_interleave(W)
         mem_r = mem2d.view(N, S, C)[utt].reshape(R * S, C)
         mlen_r = mlen[utt].contiguous()
-        mem_cache = torch.zeros((L, 2, R, heads, S, head_dim), dtype=torch.float16, device=dev)
+        mem_cache = dec._memory_caches_general(mem_r, R, S)
         time_cache = torch.zeros((L, 2, R, heads, cap, head_dim), dtype=torch.float16, device=dev)
-        for l, block in enumerate(dec.h):
-            mm = block.mix_memory
-            kv = linear(mm._images, mem_r, (mm.k.weight, mm.v.weight))
-            ops.kv_cache_store(kv, C, mem_cache[l, 0], mem_cache[l, 1], R, S, heads, head_dim, 0)
         table = ops.RopeTable(cap, head_dim, dev)
         ninf = float('-inf')
         score = torch.full((N, W), ninf, device=dev)
@@ -970,18 +951,7 @@ class BeamDecoder:
             ops.ctc_prefix_advance(x, mlen, ETX, state[0])
         for t in range(cap):
             y = ops.embed_fwd(cur, dec.wte.weight, None)
-            for l, block in enumerate(dec.h):
-                mm, mt = block.mix_memory, block.mix_time
-                xn = ops.layernorm_fwd(y, block.ln_time.weight)
-                a = linear(mt._images, xn, (mm.q.weight, mt.q.weight, mt.k.weight, mt.v.weight))
-                m = ops.attention_decode(a, mem_cache[l, 0], mem_cache[l, 1], S, key_lengths=mlen_r)
-                linear(mm._images, m, mm.proj.weight, out=y, accumulate=True)
-                s = ops.attention_decode_step(a[:, C:2 * C], a[:, 2 * C:3 * C], a[:, 3 * C:], time_cache[l, 0], time_cache[l, 1], t + 1,
-                                              table=table)
-                linear(mt._images, s, mt.proj.weight, out=y, accumulate=True)
-                h = linear(block._images, ops.layernorm_fwd(y, block.ln_chan.weight), block.mix_chan[0].weight, gelu='erf')
-                linear(block._images, h, block.mix_chan[2].weight, out=y, accumulate=True)
-            logits = linear(dec._images, ops.layernorm_fwd(y, dec.ln_f.weight), dec.lm_head.weight)
+            logits = dec._step_general(y, mem_cache, mlen_r, time_cache, t + 1, table)
             lp = torch.log_softmax(logits.float(), -1).view(N, W, V)
             present = score > ninf
             live, done = present & ~fin, present & fin
@@ -1114,7 +1084,7 @@ class AudioEncoder(nn.Module):
         self.h = nn.ModuleList([Block(head_dim=head_dim, heads=heads, p_drop=p_drop) for _ in range(layers)])
         self.ln_f = LayerNorm(head_dim * heads, bias=False)
         self.dropout_stream = DropoutStream()
-        self._graphs = {}                                                 # captured inference forwards, see _forward_graph
+        self._graphs = GraphCache()                                       # captured inference forwards, see _forward_graph
 
     def subsampled_lengths(self, input_lengths):
         return self.conv.subsampled_lengths(input_lengths)
@@ -1152,26 +1122,10 @@ class AudioEncoder(nn.Module):
         """Inference forward replayed from one HIP graph per (input shape, arithmetic mode, parameter version): the ~17 small
         launches per block are host-launch bound when issued eagerly."""
         key = (tuple(x.shape), str(x.device), _lib.get_math_mode())
-        stamp = tuple((p._version, p.data_ptr()) for p in self.parameters())
-        entry = self._graphs.get(key)
-        if entry is None or entry['stamp'] != stamp:
-            static = x.clone()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._forward_core(static)                              # warm-up: weight images are built outside the capture
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                out, _ = self._forward_core(static)
-            held = [list(m._images._cache.values()) for m in self.modules() if hasattr(m, '_images')] + [getattr(self, '_dec_images', None)]
-            if len(self._graphs) >= 8:
-                self._graphs.pop(next(iter(self._graphs)))
-            entry = dict(stamp=stamp, graph=graph, static=static, out=out, held=held)
-            self._graphs[key] = entry
+        entry = self._graphs.entry(self, key, x.clone, lambda static: self._forward_core(static)[0])
         entry['static'].copy_(x)
         entry['graph'].replay()
-        return entry['out'].clone()
+        return entry['outs'].clone()
 
     @torch.no_grad()
     def _forward_train(self, x):

@@ -1,7 +1,10 @@
-"""GPU checks of the attention decoder's beam search (haloop_amd/transformer.py BeamDecoder, csrc/decode_beam.hip):
+"""GPU checks of the attention decoder's beam search (haloop_amd/transformer.py BeamDecoder, csrc/decode.hip, csrc/decode_beam.hip;
+DESIGN.md 3.3r):
 
     halo_decode_beam_attention  with W = 1 and the identity table BITWISE halo_decode_attention_pair; with W = 3 and a random ancestor
         table within 2e-6 (that launch's own bound against its predecessors) of the existing launch on physically gathered caches;
+        at 1024 and 1025 keys (both key capacities of the kernel the two launches share) both comparisons bitwise, and
+        both launches against a float64 restatement in torch;
     halo_decode_beam_select  against a float64 restatement in torch: integers, tokens, ancestor rows and embeddings exact, scores 1e-5;
     BeamDecoder.decode in `bf16x3` against tests/asr_beam_ref.py on the rows that file says are comparable (every decision decided by
         GAP = 4e-3 or more): tokens, lengths, finished flags and counts EXACT, ranks and log-probabilities within 2e-3 (the figure of
@@ -83,6 +86,108 @@ def test_beam_attention_reads_its_history_through_the_ancestor_table(hal, hd, n_
     keep = torch.ones(Tc, dtype=torch.bool)
     keep[t] = False
     assert torch.equal(time[:, :, :, keep], before[:, :, :, keep])                  # and nothing else is written
+
+
+# ---- the MAXK dispatch both attention launches share: more than 1024 keys take the 8192-key instantiation, which no decode above reaches
+MAXK_CASES = [(1024, 4, 2),        # (S, Tc, n_keys): the last shape of the 1024 instantiation, its score row full
+              (1025, 4, 2),        # the first shape of the 8192 instantiation, taken by the cross side
+              (5, 1025, 1025)]     # the 8192 instantiation, taken by the self side
+# Largest |launch - float64| of the launches as they were before they shared one body, over the six cases and both launches, measured on
+# an MI355X: 4.195e-07 (hd = 128, 1024 memory keys, the launch through the ancestor table; fp32 scores, softmax and sums over up to
+# 1025 keys of fp16 caches).  The bound is twice that, rounded up to one significant digit; the margin is for other random draws.
+MAXK_BOUND = 9e-7
+
+
+def _attention_f64(a, mem_k, mem_v, mlen, time_k, time_v, n_keys, table):
+    """Both attentions of a step in float64 -> ([rows, 2C], this step's k and v as the cache holds them [rows, heads, hd]).  mem_* [rows,
+    heads, S, hd] and time_* [rows, heads, Tc, hd] are each row's own (gathered) caches, positions < n_keys - 1 of the latter are read."""
+    rows, heads, S, hd = mem_k.shape
+    C, t = heads * hd, n_keys - 1
+    a = a.double().cpu()
+    q_x, q_s = a[:, :C].view(rows, heads, hd), a[:, C:2 * C].view(rows, heads, hd)
+    k_t = a[:, 2 * C:3 * C].half().view(rows, heads, hd)
+    v_t = a[:, 3 * C:].half().view(rows, heads, hd)
+    scale = 1.0 / hd ** 0.5
+    # cross: key-length mask, no rotary
+    sc = torch.einsum('rhd,rhsd->rhs', q_x, mem_k.double().cpu()) * scale
+    past = torch.arange(S)[None, None, :] >= mlen.cpu().long()[:, None, None]
+    cross = torch.einsum('rhs,rhsd->rhd', sc.masked_fill(past, NINF).softmax(-1), mem_v.double().cpu())
+    # self: rotary (interleaved pairs) on q at position t and on the keys at theirs
+    cos, sin = table.cos.double().cpu(), table.sin.double().cpu()
+
+    def rot(x, pos):                                                         # x [..., hd] at positions pos (broadcast over x[..., 0])
+        x0, x1 = x[..., 0::2], x[..., 1::2]
+        return torch.stack((x0 * cos[pos] - x1 * sin[pos], x1 * cos[pos] + x0 * sin[pos]), -1).flatten(-2)
+
+    keys = torch.cat([time_k.double().cpu()[:, :, :t], k_t.double()[:, :, None]], 2)               # [rows, heads, n_keys, hd]
+    vals = torch.cat([time_v.double().cpu()[:, :, :t], v_t.double()[:, :, None]], 2)
+    sc = torch.einsum('rhd,rhjd->rhj', rot(q_s, t), rot(keys, torch.arange(n_keys))) * scale
+    own = torch.einsum('rhj,rhjd->rhd', sc.softmax(-1), vals)
+    return torch.cat([cross.reshape(rows, C), own.reshape(rows, C)], 1), k_t, v_t
+
+
+@pytest.fixture(scope='module')
+def maxk_runs(hal):
+    """Every case once: the pair launch and the W = 1 beam launch on N = 2 rows, the W = 2 beam launch with a random ancestor table on
+    one utterance and the pair launch on its gathered caches, and the float64 results of the two constructions."""
+    ops, runs = hal['ops'], {}
+
+    def run(hd, case):
+        if (hd, case) in runs:
+            return runs[hd, case]
+        S, Tc, n_keys = case
+        heads, t = 1, n_keys - 1
+        nan = lambda rows: torch.full((rows, 2 * heads * hd), float('nan'), device=DEV)
+        r = {}
+        # N = 2, W = 1
+        a, mem, time, _, _, table = _attention_inputs(ops, 2, 1, heads, hd, S, Tc, n_keys, 31 * hd + S + n_keys)
+        mlen = torch.tensor([S, S - 1], dtype=torch.int32, device=DEV)
+        ident = torch.arange(2, dtype=torch.int32)[:, None].expand(2, Tc).contiguous().to(DEV)
+        r['f64_pair'] = _attention_f64(a, mem[0], mem[1], mlen, time[0], time[1], n_keys, table)[0]
+        r['time_pair'], r['time_one'] = time.clone(), time.clone()
+        r['pair'] = ops.decode_attention_pair(a, mem[0], mem[1], mlen, r['time_pair'][0], r['time_pair'][1], n_keys, table, nan(2))
+        r['one'] = ops.decode_beam_attention(a, mem[0], mem[1], mlen, r['time_one'][0], r['time_one'][1], n_keys, ident, table, nan(2))
+        # N = 1, W = 2 through the table, and the pair launch on the physically gathered caches
+        a, mem, time, _, anc, table = _attention_inputs(ops, 1, 2, heads, hd, S, Tc, n_keys, 37 * hd + S + n_keys)
+        mlen = torch.tensor([S - 1], dtype=torch.int32, device=DEV)
+        gathered = time.gather(1, anc.long().to(DEV)[None, :, None, :, None].expand_as(time))      # slot s: position j of row anc[s, j]
+        gathered[:, :, :, t:] = time[:, :, :, t:]
+        mem_g, mlen_g = mem[:, [0, 0]].contiguous(), mlen[[0, 0]].contiguous()
+        r['f64_beam'] = _attention_f64(a, mem_g[0], mem_g[1], mlen_g, gathered[0], gathered[1], n_keys, table)[0]
+        r['time_beam'] = time.clone()
+        r['beam'] = ops.decode_beam_attention(a, mem[0], mem[1], mlen, r['time_beam'][0], r['time_beam'][1], n_keys, anc.to(DEV), table, nan(2))
+        r['time_gathered'] = gathered
+        r['gathered'] = ops.decode_attention_pair(a, mem_g[0], mem_g[1], mlen_g, gathered[0], gathered[1], n_keys, table, nan(2))
+        r['t'] = t
+        runs[hd, case] = r
+        return r
+    return run
+
+
+@pytest.mark.parametrize('hd', [16, 128])
+@pytest.mark.parametrize('case', MAXK_CASES)
+def test_both_key_capacities_width_one_is_the_pair_launch_bitwise(maxk_runs, hd, case):
+    r = maxk_runs(hd, case)
+    assert torch.equal(r['pair'], r['one']) and torch.equal(r['time_pair'], r['time_one'])
+
+
+@pytest.mark.parametrize('hd', [16, 128])
+@pytest.mark.parametrize('case', MAXK_CASES)
+def test_both_key_capacities_ancestor_table_is_the_gathered_cache_bitwise(maxk_runs, hd, case):
+    """The two sides differ in the address of a key's plane only: the same bits."""
+    r = maxk_runs(hd, case)
+    assert torch.equal(r['beam'], r['gathered'])
+    assert torch.equal(r['time_beam'][:, :, :, r['t']], r['time_gathered'][:, :, :, r['t']])
+
+
+@pytest.mark.parametrize('hd', [16, 128])
+@pytest.mark.parametrize('case', MAXK_CASES)
+def test_both_key_capacities_against_float64(maxk_runs, hd, case):
+    r = maxk_runs(hd, case)
+    dev_pair = (r['pair'].double().cpu() - r['f64_pair']).abs().max().item()
+    dev_beam = (r['beam'].double().cpu() - r['f64_beam']).abs().max().item()
+    print(f'maxk hd={hd} case={case}: |pair - f64| = {dev_pair:.3e}, |beam - f64| = {dev_beam:.3e}')
+    assert dev_pair <= MAXK_BOUND and dev_beam <= MAXK_BOUND       # (NaN fails both)
 
 
 # ---- halo_decode_beam_select ------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Beam search of the attention decoder on one MI355X: haloop_amd.transformer.BeamDecoder on its fused launches (csrc/decode.hip's
-products on N * W rows, csrc/decode_beam.hip's attention and selection, one graph replay per decode) at W = 1, 4, 8 against
+products and attention on N * W rows, csrc/decode_beam.hip's selection, one graph replay per decode) at W = 1, 4, 8 against
 Decoder.decode's greedy search on its fused launches as the yardstick and against the beam's general path (torch operators, physically
 gathered caches, stable sort), measured in the SAME process in alternating windows (the method of tools/bench_rnnt_beam.py).  The
 `transformer:32` decoder (12 layers, 8 x 64, V = 32; untrained: oracle.transformer_ref.make_decoder_params), features [64, 10, 512],
