@@ -169,8 +169,10 @@ struct GptSampleArgs {
     float *x;
 };
 
+// (-0.0 and +0.0 share a key: the kept set is defined by the float comparison >=, under which they are equal)
 __device__ __forceinline__ unsigned order_key(float f) {
     const unsigned b = __float_as_uint(f);
+    if (b == 0x80000000u) return 0x80000000u;
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
