@@ -221,6 +221,9 @@ SIGNATURES = {
     'halo_ctc_prefix_beam_advance': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_ctc_lm_beam_step': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _f, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp,
                                    _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'halo_rnnt_lm_beam_step': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _l,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                    _vp]),
     'halo_edit_distance': (_i, [_vp, _l, _vp, _i, _i, _vp, _l, _vp, _i, _i, _i, _vp, _vp, _vp]),
     'halo_nbest_risk_fwd': (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     'halo_nbest_risk_bwd': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),

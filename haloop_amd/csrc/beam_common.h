@@ -1,5 +1,5 @@
-// What the device beam searches share (csrc/rnnt_beam.hip, ctc_prefix_beam.hip, ctc_lm_beam.hip and dec_beam_select_kernel of
-// decode_beam.hip): one workgroup of BEAM_THREADS threads per row keeps a beam of at most BEAM_MAX members in LDS and takes the W best of
+// What the device beam searches share (csrc/rnnt_beam.hip, rnnt_lm_beam.hip, ctc_prefix_beam.hip, ctc_lm_beam.hip and
+// dec_beam_select_kernel of decode_beam.hip): one workgroup of BEAM_THREADS threads per row keeps a beam of at most BEAM_MAX members in LDS and takes the W best of
 // its W V candidates in W rounds, one per round: the first in the total order (score descending, candidate position ascending) behind the
 // last one taken.  No list of candidates is built; each search scans its own candidates and hands every thread's first to
 // first_in_workgroup().  The order and the merge rule are the contract of every n-best list the library returns: they are stated here,

@@ -10,6 +10,10 @@ fused path costs ``num_layers + 3`` launches per frame for the whole batch (one 
 ``out_layer`` of the transducer decoders on all N * W slots, ``halo_rnnt_beam_keep``) and reads nothing on the host between its first
 launch and its last; the general path runs the same search on ``rnn.Decoder.forward`` at T = 1 over N * W rows, pruned on the host.
 
+``TransducerFusionDecoder`` (csrc/rnnt_lm_beam.hip) fuses the same LM into the transducer head's beam search: the
+search of ``transducer.BeamDecoder`` with every candidate ranked by its transducer mass + lm_weight * log P_LM(y) + insertion_bonus *
+len(y), every hypothesis carrying the states of both the prediction network and the LM.
+
 ``lm_score`` is the teacher-forced LM log-probability of every hypothesis of an n-best list: a rescorer for any list (the transducer's
 included) and the independent check on the decoder's ``lm_scores``.
 """
@@ -17,8 +21,8 @@ import math
 
 import torch
 
-from . import _lib, ops
-from .transducer import BEAM_MAX, BeamDecoder, _HeadDecoder
+from . import _lib, functional as HF, ops
+from .transducer import BEAM_MAX, SYNC_EVERY, BeamDecoder, _HeadDecoder
 
 NEG = float('-inf')
 
@@ -224,6 +228,246 @@ class CTCFusionDecoder(_HeadDecoder):
                 lengths[n, w] = len(m['y'])
                 tokens[n, w, :len(m['y'])] = torch.tensor(m['y'], dtype=torch.int32)
         return rec.to(dev), lengths.to(dev), tokens.to(dev)
+
+
+class _Images(_HeadDecoder):
+    """The decode images and the ``fused`` rule of one network (``head.lm``), as every ``_HeadDecoder`` keeps them."""
+
+    def __init__(self, head):
+        self.head = head
+        self._images = None
+
+
+class TransducerFusionDecoder:
+    """Beam search for a ``recognizer.Transducer`` head with LM shallow fusion inside the search (csrc/rnnt_lm_beam.hip),
+    with preallocated buffers for ``max_batch`` rows, ``beam`` hypotheses per row and ``capacity`` symbols per hypothesis.  ``lm``: an
+    ``rnn.Decoder`` over the head's V classes, in eval mode, on the head's device; its hidden size and depth may differ from the
+    prediction network's.  The search is ``transducer.BeamDecoder``'s with every candidate ranked by
+
+        fma(lm_weight, log P_LM(y), s) + insertion_bonus * len(y)
+
+    s the transducer mass ``BeamDecoder`` ranks by (the definition and the tie rules are in include/halo.h); a hypothesis carries the
+    states of both networks, and a kept label steps both.  With both weights 0 it is ``BeamDecoder.decode``, token for token.  The
+    fused path runs when both networks satisfy the fused rule of the transducer decoders and costs ``Lp + Ll + 5`` launches per
+    alignment step for the whole batch (one ``halo_rnnt_lm_beam_step``; per network its cell launches, ``out_layer`` and
+    ``halo_rnnt_beam_keep``); it reads the row lengths once before its first launch and one word every ``SYNC_EVERY`` steps.  Everything
+    else takes the general path: the same search on ``rnn.Decoder.forward`` at T = 1 over N * W rows, pruned on the host."""
+
+    def __init__(self, head, lm, max_batch, capacity, beam=4, lm_weight=0.5, insertion_bonus=0.0, start_token=0):
+        self.head, self.lm = head, lm
+        self.max_batch, self.capacity, self.beam = int(max_batch), int(capacity), int(beam)
+        self.lm_weight, self.insertion_bonus, self.start_token = float(lm_weight), float(insertion_bonus), int(start_token)
+        if self.max_batch < 1 or self.capacity < 1:
+            raise ValueError('TransducerFusionDecoder: need max_batch >= 1 and capacity >= 1')
+        if self.beam < 1 or self.beam > BEAM_MAX:
+            raise ValueError(f'TransducerFusionDecoder: beam {self.beam} outside 1 .. {BEAM_MAX}')
+        if not (math.isfinite(self.lm_weight) and math.isfinite(self.insertion_bonus)):
+            raise ValueError('TransducerFusionDecoder: lm_weight and insertion_bonus must be finite')
+        V = head.lm.num_classes
+        if getattr(lm, 'num_classes', None) != V:
+            raise ValueError(f'TransducerFusionDecoder: the LM has {getattr(lm, "num_classes", None)} classes, the head {V}')
+        if self.start_token < 0 or self.start_token >= V:
+            raise ValueError(f'TransducerFusionDecoder: start_token {self.start_token} outside 0 .. {V - 1}')
+        dev = head.lm.embedding.weight.device
+        S, cap = self.max_batch * self.beam, self.capacity
+        i32 = dict(device=dev, dtype=torch.int32)
+        f32 = dict(device=dev, dtype=torch.float32)
+        self._sides = (_Images(head), _Images(_LMHead(lm)))           # the prediction network, the fusion LM
+        with torch.inference_mode(False):          # ordinary tensors: they are updated in place inside and outside inference mode
+            if dev.type == 'cuda' and lm.embedding.weight.device == dev and all(
+                    s.head.lm.embedding.weight.shape[1] == s.head.lm.hidden_dim for s in self._sides):
+                # flat buffers, viewed per call at that call's N * W slots.  The beam's records and both states exist twice (step parity).
+                self._rec = [(torch.zeros(S * 3, **f32), torch.zeros(S, **i32), torch.zeros(S * cap, **i32)) for _ in range(2)]
+                self._parent, self._last = torch.zeros(S, **i32), torch.zeros(S, **i32)
+                self._fin = (torch.zeros(S * 3, **f32), torch.zeros(S, **i32), torch.zeros(S, **i32), torch.zeros(S * cap, **i32),
+                             torch.zeros(self.max_batch, **i32))
+                self._state = []
+                for side in self._sides:
+                    H, L = side.head.lm.hidden_dim, side.head.lm.num_layers
+                    self._state.append(dict(h=torch.zeros(2 * L * S * H, **f32), c=torch.zeros(2 * L * S * H, **f32),
+                                            g=torch.zeros(2 * S * V, **f32), xh=torch.zeros(L * S * 2 * H, **f32),
+                                            top=torch.zeros(S * H, **f32)))
+                self._live = torch.zeros(64, **i32)                    # one word per alignment step; grown to T + capacity
+        self._device = dev      # of the buffers: a head moved since needs a new decoder
+        self.iterations = 0     # alignment steps of the last decode
+        self.last_parts = None  # (rnnt_scores [N, W], lm_scores [N, W]) of the last decode
+
+    @property
+    def fused(self):
+        """Whether the fused launches are in use: both networks satisfy the rule of the transducer decoders, as they are now."""
+        return not self.head.training and all(side.fused for side in self._sides)
+
+    def decode(self, features, input_lengths, capacity=None, beam=None, lm_weight=None, insertion_bonus=None):
+        """features [N, T, feat_dim], input_lengths [N] (clipped to T) -> (tokens [N, W, capacity] int64, -1 past a hypothesis's length
+        and in absent hypotheses; lengths [N, W] int64, -1: absent; scores [N, W] float32 = the rank fma(lm_weight, lm, rnnt) +
+        insertion_bonus * length, best first, -inf: absent; counts [N] int64), and ``last_parts`` = (rnnt_scores, lm_scores), both [N, W]
+        float32.  ``capacity`` / ``beam``: search with less room than the buffers hold; ``lm_weight`` / ``insertion_bonus``: this
+        call's instead of the decoder's."""
+        name, lm = 'TransducerFusionDecoder', self.lm
+        if features.dim() != 3 or features.shape[1] < 1:
+            raise ValueError(f'{name}: features must be [N, T, feat_dim] with T >= 1')
+        N, T, _ = features.shape
+        if N < 1 or N > self.max_batch:
+            raise ValueError(f'{name}: batch {N} outside 1 .. max_batch = {self.max_batch}')
+        if tuple(input_lengths.shape) != (N,):
+            raise ValueError(f'{name}: input_lengths must be [{N}]')
+        cap = self.capacity if capacity is None else int(capacity)
+        if cap < 1 or cap > self.capacity:
+            raise ValueError(f'{name}: capacity {cap} outside 1 .. {self.capacity}')
+        W = self.beam if beam is None else int(beam)
+        if W < 1 or W > self.beam:
+            raise ValueError(f'{name}: beam {W} outside 1 .. {self.beam}')
+        a = self.lm_weight if lm_weight is None else float(lm_weight)
+        b = self.insertion_bonus if insertion_bonus is None else float(insertion_bonus)
+        if not (math.isfinite(a) and math.isfinite(b)):
+            raise ValueError(f'{name}: lm_weight and insertion_bonus must be finite')
+        if lm.num_classes != self.head.lm.num_classes:
+            raise ValueError(f'{name}: the LM has {lm.num_classes} classes, the head {self.head.lm.num_classes}')
+        if self.head.training or lm.training:
+            raise NotImplementedError(f'{name} is an inference path: put the head and the LM in eval mode')
+        if not features.is_cuda or not lm.embedding.weight.is_cuda or not self.head.lm.embedding.weight.is_cuda:
+            raise _lib.HaloError(f'haloop_amd.fusion.{name} runs on the HIP device only (no CPU path)')
+        if any(x.device != self._device for x in (features, lm.embedding.weight, self.head.lm.embedding.weight)):
+            raise _lib.HaloError(f'{name}: the head, the LM and the features must be on the device the decoder was built on')
+        with torch.no_grad():
+            cl = self.head.classifier
+            f = HF.linear(features.float(), cl.weight, cl.bias).contiguous()                   # [N, T, V]
+            il = input_lengths.to(device=features.device, dtype=torch.int32).clamp(0, T).contiguous()
+            rec, seq, lengths, tokens = (self._decode_fused if self.fused else self._decode_general)(f, il, N, W, cap, a, b)
+            # the finals by (rank descending, order of completion): two stable sorts, absent hypotheses (length -1) last
+            rank = rec[:, :, 0]
+            absent = lengths < 0
+            o1 = torch.where(absent, torch.full_like(seq, 2 ** 31 - 1), seq).argsort(dim=1, stable=True)
+            key = torch.where(absent, torch.full_like(rank, float('inf')), -rank).gather(1, o1)
+            order = o1.gather(1, key.argsort(dim=1, stable=True))
+            lengths = lengths.gather(1, order).long()
+            minus = torch.full_like(rank, NEG)
+            rank, rnnt, lms = (torch.where(lengths < 0, minus, rec[:, :, x].gather(1, order)) for x in range(3))
+            self.last_parts = (rnnt, lms)
+            tokens = tokens[:, :, :cap].gather(1, order[:, :, None].expand(N, W, cap)).long()
+            past = torch.arange(cap, device=tokens.device)[None, None, :] >= lengths[:, :, None]
+            return tokens.masked_fill(past, -1), lengths, rank, (lengths >= 0).sum(1)
+
+    # ---- the fused path: Lp + Ll + 5 launches per alignment step ----------------------------------------------------------------------
+    def _decode_fused(self, f, il, N, W, cap, a, b):
+        nets = [side.head.lm for side in self._sides]
+        images = [side._decode_images() for side in self._sides]
+        V = nets[0].num_classes
+        R, ld = N * W, self.capacity
+        frames = int(il.max().item())                          # the one host read before the first launch
+        steps = frames + cap if frames else 1                  # a hypothesis at step i has t + u = i, t < L, u <= cap
+        if self._live.numel() < steps:
+            self._live = torch.zeros(steps, device=self._live.device, dtype=torch.int32)
+        live = self._live[:steps]
+        live.zero_()
+        rec = [(r[:R * 3].view(N, W, 3), u[:R].view(N, W), t[:R * ld].view(N, W, ld)) for r, u, t in self._rec]
+        parent, last = self._parent[:R].view(N, W), self._last[:R].view(N, W)
+        fr, fq, fl, ft, fn = self._fin
+        fin = (fr[:R * 3].view(N, W, 3), fq[:R].view(N, W), fl[:R].view(N, W), ft[:R * ld].view(N, W, ld), fn[:N])
+        h, c, g, xh, top = [], [], [], [], []
+        for net, buf, first in zip(nets, self._state, (0, self.start_token)):
+            H, L = net.hidden_dim, net.num_layers
+            h.append(buf['h'][:2 * L * R * H].view(2, L, R, H)); c.append(buf['c'][:2 * L * R * H].view(2, L, R, H))
+            g.append(buf['g'][:2 * R * V].view(2, R, V))
+            xh.append(buf['xh'][:L * R * 2 * H].view(L, R, 2 * H)); top.append(buf['top'][:R * H].view(R, H))
+            xh[-1].zero_(); c[-1][0].zero_()
+            xh[-1][0, :, :H] = net.embedding.weight[first]     # the zero prefix of training / the LM's start token, in every slot
+        cells = lambda x, q: BeamDecoder._cells(self._sides[x], xh[x], c[x][q], h[x][q], top[x], g[x][q], *images[x])
+        cells(0, 0); cells(1, 0)
+        for i in range(steps):
+            q = i & 1
+            ops.rnnt_lm_beam_step(f, g[0][q], nets[0].out_layer.bias, g[1][q], nets[1].out_layer.bias, il, i, cap, a, b, rec[q], rec[1 - q],
+                                  parent, last, fin, nets[0].embedding.weight, h[0][q], c[0][q], xh[0], c[0][1 - q],
+                                  nets[1].embedding.weight, h[1][q], c[1][q], xh[1], c[1][1 - q], live[i:])
+            if i == steps - 1 or ((i + 1) % SYNC_EVERY == 0 and int(live[i].item()) == 0):
+                break
+            for x in range(2):
+                cells(x, 1 - q)
+                ops.rnnt_beam_keep(parent, last, h[x][q], c[x][q], g[x][q], h[x][1 - q], c[x][1 - q], g[x][1 - q])
+        self.iterations = i + 1
+        if int(live[i].item()) != 0:
+            raise _lib.HaloError('TransducerFusionDecoder: rows still live after max(L) + capacity alignment steps')
+        return fin[0].clone(), fin[1].clone(), fin[2].clone(), fin[3].clone()
+
+    # ---- the general path: the same search on rnn.Decoder.forward at T = 1 over N * W rows, pruned on the host ---------------------------
+    def _decode_general(self, f, il, N, W, cap, a, b):
+        pn, lm = self.head.lm, self.lm
+        dev, T, V = f.device, f.shape[1], f.shape[2]
+        R = N * W
+        Ls = il.tolist()
+        g, state = pn.forward(torch.zeros(1, R, device=dev, dtype=torch.int64), pn.init_hidden(R))
+        lg, lstate = lm.forward(torch.full((1, R), self.start_token, device=dev, dtype=torch.int64), lm.init_hidden(R))
+        beams = [[((), 0.0, 0.0)] if Ls[n] > 0 else [] for n in range(N)]     # (y, s, lm); hypothesis j of row n lives in slot n W + j
+        finals = [[((), 0.0, 0.0, 0.0)] if Ls[n] == 0 else [] for n in range(N)]           # (y, rank, s, lm)
+        slot_row = torch.arange(R, device=dev) // W
+        f64 = lambda x: torch.tensor(x, dtype=torch.float64)
+        self.iterations = 0
+        for i in range(T + cap):
+            if not any(beams):
+                break
+            self.iterations += 1
+            t = torch.zeros(R, dtype=torch.int64)
+            for n, B in enumerate(beams):
+                for j, (y, _, _) in enumerate(B):
+                    t[n * W + j] = i - len(y)
+            jp = torch.log_softmax(f[slot_row, t.to(dev)] + g, -1).double().cpu()      # the host reads of the alignment step
+            lp = torch.log_softmax(lg, -1).double().cpu()
+            src, tok = torch.arange(R), torch.zeros(R, dtype=torch.int64)
+            for n, B in enumerate(beams):
+                if not B:
+                    continue
+                where = {y: j for j, (y, _, _) in enumerate(B)}
+                blank = [s + float(jp[n * W + j, 0]) for j, (_, s, _) in enumerate(B)]
+                labels = [s + jp[n * W + j, 1:] for j, (_, s, _) in enumerate(B)]
+                lms = [m + lp[n * W + j, 1:] for j, (_, _, m) in enumerate(B)]
+                gone = [torch.zeros(V - 1, dtype=torch.bool) for _ in B]
+                complete = [i - len(y) + 1 == Ls[n] for y, _, _ in B]
+                for sidx, (y, _, _) in enumerate(B):         # the extension of y[:-1] by y[-1] merges into y's blank extension (mass only)
+                    j = where.get(y[:-1]) if y and not complete[sidx] else None
+                    if j is not None:
+                        blank[sidx] = float(torch.logaddexp(f64(blank[sidx]), labels[j][y[-1] - 1]))
+                        gone[j][y[-1] - 1] = True
+                cand, vals = [], []                          # (parent, token, s', lm') in candidate order, and their ranks
+                for j, (y, _, m) in enumerate(B):
+                    rank = blank[j] + a * m + b * len(y)
+                    if complete[j]:
+                        finals[n].append((y, rank, blank[j], m))
+                    else:
+                        cand.append((j, 0, blank[j], m)); vals.append(f64([rank]))
+                for j, (y, _, m) in enumerate(B):
+                    if len(y) < cap:
+                        ks = (~gone[j]).nonzero().view(-1)
+                        cand += [(j, int(k) + 1, float(labels[j][k]), float(lms[j][k])) for k in ks]
+                        vals.append(labels[j][ks] + a * lms[j][ks] + b * (len(y) + 1))
+                new = []
+                if cand:
+                    vals = torch.cat(vals)
+                    for x in torch.sort(-vals, stable=True).indices[:W].tolist():
+                        j, k, s, m = cand[x]
+                        src[n * W + len(new)], tok[n * W + len(new)] = n * W + j, k
+                        new.append((B[j][0] + ((k,) if k else ()), s, m))
+                beams[n] = new
+            if not any(beams):
+                break
+            src, tok = src.to(dev), tok.to(dev)
+            emit = tok != 0
+            g, state = g[src], (state[0][:, src].contiguous(), state[1][:, src].contiguous())
+            g1, (h1, c1) = pn.forward(tok.view(1, R), state)
+            g = torch.where(emit[:, None], g1, g)
+            state = (torch.where(emit[None, :, None], h1, state[0]), torch.where(emit[None, :, None], c1, state[1]))
+            lg, lstate = lg[src], (lstate[0][:, src].contiguous(), lstate[1][:, src].contiguous())
+            g1, (h1, c1) = lm.forward(tok.view(1, R), lstate)
+            lg = torch.where(emit[:, None], g1, lg)
+            lstate = (torch.where(emit[None, :, None], h1, lstate[0]), torch.where(emit[None, :, None], c1, lstate[1]))
+        rec = torch.full((N, W, 3), NEG, dtype=torch.float32)
+        seq, lengths = torch.zeros(N, W, dtype=torch.int32), torch.full((N, W), -1, dtype=torch.int32)
+        tokens = torch.zeros(N, W, cap, dtype=torch.int32)
+        for n, fin in enumerate(finals):
+            best = sorted(range(len(fin)), key=lambda x: (-fin[x][1], x))[:W]
+            for w, x in enumerate(best):
+                rec[n, w], seq[n, w], lengths[n, w] = torch.tensor(fin[x][1:]), w, len(fin[x][0])
+                tokens[n, w, :len(fin[x][0])] = torch.tensor(fin[x][0], dtype=torch.int32)
+        return rec.to(dev), seq.to(dev), lengths.to(dev), tokens.to(dev)
 
 
 def lm_score(lm, tokens, lengths, start_token=0):

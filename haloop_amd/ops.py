@@ -1928,6 +1928,40 @@ def ctc_lm_beam_step(emissions, emission_lengths, frame, capacity, lm_weight, in
           'halo_ctc_lm_beam_step')
 
 
+# ---- the per-step launch of transducer beam search with LM shallow fusion (csrc/rnnt_lm_beam.hip); it does not allocate ----------------
+def rnnt_lm_beam_step(f, g, g_bias, lg, lg_bias, input_lengths, step, capacity, lm_weight, insertion_bonus, rec_in, rec_out, parent, last,
+                      finals, wte, h_in, c_in, xh, c_out, lm_wte, lm_h_in, lm_c_in, lm_xh, lm_c_out, live):
+    """One alignment step of every row (include/halo.h): f [N, T, V]; g / lg [N * W, V] the prediction network's / the LM's logits (biases
+    apart); rec_in / rec_out = (rec [N, W, 3] fp32 = s | lm | rank, u [N, W] int32, tokens [N, W, >= capacity] int32); parent / last
+    [N, W] int32; finals = (rec [N, W, 3] = rank | s | lm, seq, lengths [N, W], tokens [N, W, >= capacity], n [N]); per network h_in /
+    c_in / c_out [layers, N * W, H] and xh [layers, N * W, 2 H] with its own layers and H, all contiguous; live: one int32 word."""
+    N, T, V = f.shape
+    W = parent.shape[1]
+    slots = N * W
+    tensors = (g, lg, *rec_in, *rec_out, parent, last, *finals, h_in, c_in, xh, c_out, lm_h_in, lm_c_in, lm_xh, lm_c_out, input_lengths)
+    if f.dtype != torch.float32 or f.stride(2) != 1 or not all(t.is_contiguous() for t in tensors):
+        raise ValueError('rnnt_lm_beam_step: f must be fp32 and contiguous along V and every other tensor contiguous')
+    if g.shape != (slots, V) or lg.shape != (slots, V) or input_lengths.shape != (N,) or input_lengths.dtype != torch.int32:
+        raise ValueError('rnnt_lm_beam_step: g and lg must be [N * W, V], input_lengths [N] int32')
+    for name, e, h, c, x, co in (('prediction network', wte, h_in, c_in, xh, c_out), ('LM', lm_wte, lm_h_in, lm_c_in, lm_xh, lm_c_out)):
+        if h.dim() != 3 or h.shape[1] != slots or e.shape != (e.shape[0], h.shape[2]) or e.shape[0] < V or not e.is_contiguous():
+            raise ValueError(f'rnnt_lm_beam_step: the {name}\'s state must be [layers, N * W, H] and its embedding [>= V, H]')
+        if x.shape != (h.shape[0], slots, 2 * h.shape[2]) or c.shape != h.shape or co.shape != h.shape:
+            raise ValueError(f'rnnt_lm_beam_step: the {name}\'s xh must be [layers, N * W, 2 H], c_in and c_out as h_in')
+    ld = rec_in[2].shape[2]
+    if any(t.shape != (N, W, 3) for t in (rec_in[0], rec_out[0], finals[0])) \
+            or any(t.shape != (N, W) for t in (rec_in[1], rec_out[1], parent, last, finals[1], finals[2])) \
+            or any(t.shape != (N, W, ld) for t in (rec_in[2], rec_out[2], finals[3])) or finals[4].shape != (N,) or ld < capacity:
+        raise ValueError('rnnt_lm_beam_step: records and finals must be [N, W, 3] / [N, W] with tokens [N, W, ld >= capacity]')
+    check(lib().halo_rnnt_lm_beam_step(ptr(f), f.stride(0), f.stride(1), N, T, V, ptr(g), g.stride(0), ptr(g_bias), ptr(lg), lg.stride(0),
+                                       ptr(lg_bias), ptr(input_lengths), int(step), W, int(capacity), float(lm_weight),
+                                       float(insertion_bonus), ptr(rec_in[0]), ptr(rec_in[1]), ptr(rec_in[2]), ptr(rec_out[0]),
+                                       ptr(rec_out[1]), ptr(rec_out[2]), ld, ptr(parent), ptr(last), ptr(finals[0]), ptr(finals[1]),
+                                       ptr(finals[2]), ptr(finals[3]), ptr(finals[4]), ptr(wte), h_in.shape[2], h_in.shape[0], ptr(h_in),
+                                       ptr(c_in), ptr(xh), ptr(c_out), ptr(lm_wte), lm_h_in.shape[2], lm_h_in.shape[0], ptr(lm_h_in),
+                                       ptr(lm_c_in), ptr(lm_xh), ptr(lm_c_out), ptr(live), _stream()), 'halo_rnnt_lm_beam_step')
+
+
 # ---- channels-last conv front-end (ha/conv.py) -------------------------------------------------------------
 def conv_out_length(T, ks, stride, pad):
     return (T + 2 * pad - ks) // stride + 1

@@ -6,7 +6,7 @@ import torch.nn as nn
 
 from . import _lib, functional as HF, ops, wer
 from .ctc import ctc_prefix_beam_search, ctc_reduce_mean, ctc_viterbi
-from .fusion import CTCFusionDecoder
+from .fusion import CTCFusionDecoder, TransducerFusionDecoder
 from .rnn import Decoder, DropoutStream
 from .star import star_ctc_forward_score
 from .transducer import BeamDecoder, GreedyDecoder, nbest_risk, transducer_align, transducer_forward_score, transducer_loss
@@ -206,7 +206,12 @@ class Transducer(nn.Module):
 
     ``mwer_beam`` (HALO_RNNT_MWER when the head is built; a caller may set the attribute): 0, the default, leaves ``forward`` as it is;
     W >= 1 makes ``forward`` of a head in training mode return ``mwer_forward(..., beam_size=W)``, minimum-word-error-rate fine-tuning
-    on the n-best lists of the beam search."""
+    on the n-best lists of the beam search.
+
+    ``set_fusion_lm(lm, lm_weight, insertion_bonus)`` fuses an ``rnn.Decoder`` language model into the search of ``decode`` at a width
+    W >= 1 (``fusion.TransducerFusionDecoder``); ``set_fusion_lm(None)`` takes it out again.  (``self.lm`` is the
+    prediction network, hence the name.)  The fusion LM is no submodule of the head: ``state_dict()``, ``parameters()``, ``to()`` and
+    ``train()`` do not see it."""
 
     def __init__(self, feat_dim=1024, vocab_size=256):
         super().__init__()
@@ -218,6 +223,19 @@ class Transducer(nn.Module):
         self.beam_size = int(os.environ.get('HALO_RNNT_BEAM', '0'))
         self.mwer_beam = int(os.environ.get('HALO_RNNT_MWER', '0'))
         self.last_nbest = None
+        self.last_parts = None
+        self._fusion = None    # None, or a dict (not a module: the fusion LM stays out of this head's parameters and state_dict)
+
+    def set_fusion_lm(self, lm, lm_weight=0.5, insertion_bonus=0.0):
+        """Fuse ``lm`` (an ``rnn.Decoder`` over this head's classes, in eval mode, on the device; the caller moves it) into
+        ``decode(beam_size=W >= 1)``: candidates rank by their transducer mass + lm_weight * log P_LM + insertion_bonus * length,
+        ``last_nbest`` holds the fused lists and ``last_parts`` their (rnnt_scores, lm_scores).  ``set_fusion_lm(None)`` restores the
+        unfused search.  Greedy decoding, ``mwer_forward`` and ``align`` do not use the LM."""
+        if lm is None:
+            self._fusion, self.last_parts = None, None
+            return
+        TransducerFusionDecoder(self, lm, 1, 1, 1, lm_weight, insertion_bonus)      # the argument checks, now and not at the first decode
+        self._fusion = {'lm': lm, 'lm_weight': float(lm_weight), 'insertion_bonus': float(insertion_bonus), 'decoder': None}
 
     def decode(self, features, input_lengths, condtarget_lengths=None, prompt=None, beam_size=None):
         """The ``Decodable`` call (ha/recognizer.py:12-34, as ha/loop.py:295-303 makes it): greedy transducer search with room for
@@ -259,7 +277,19 @@ class Transducer(nn.Module):
         third value is [None] * N); ``last_nbest`` = (tokens [N, W, capacity], lengths [N, W], scores [N, W], counts [N])."""
         if width < 0:
             raise ValueError(f'Transducer.decode: beam_size {width} is negative')
-        self.last_nbest = self._beam_decoder_for(features, N, capacity, width).decode(features, input_lengths, capacity, width)
+        fusion = getattr(self, '_fusion', None)
+        if fusion is None:
+            self.last_nbest = self._beam_decoder_for(features, N, capacity, width).decode(features, input_lengths, capacity, width)
+        else:
+            if width > ops.BEAM_MAX:
+                raise ValueError(f'Transducer.decode: beam_size {width} outside 1 .. {ops.BEAM_MAX}')
+            dec = fusion['decoder']
+            if dec is None or dec.max_batch < N or dec.capacity < capacity or dec.beam < width or dec._device != features.device:
+                dec = TransducerFusionDecoder(self, fusion['lm'], max(N, dec.max_batch if dec else 0),
+                                              max(capacity, dec.capacity if dec else 0), max(width, dec.beam if dec else 0))
+                fusion['decoder'] = dec
+            self.last_nbest = dec.decode(features, input_lengths, capacity, width, fusion['lm_weight'], fusion['insertion_bonus'])
+            self.last_parts = dec.last_parts
         tokens, lengths, scores, _ = self.last_nbest
         lens = lengths[:, 0].tolist()                           # every row returns at least one hypothesis
         hypotheses = torch.nested.nested_tensor([tokens[i, 0, :n] for i, n in enumerate(lens)])

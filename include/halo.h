@@ -1357,6 +1357,60 @@ int halo_ctc_lm_beam_step(const float *emissions, long stride_t, long stride_n, 
                           const float *c_in, float *xh, float *c_out, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Beam search of the RNN transducer head with shallow fusion of an LSTM language model (haloop_amd/fusion.py TransducerFusionDecoder;
+ * csrc/rnnt_lm_beam.hip) as a launch sequence: per alignment step one halo_rnnt_lm_beam_step, then for each of the two
+ * networks (the prediction network, Lp layers; the fusion LM, Ll layers) one halo_rnnt_lstm_cell per layer, one halo_decode_linear and
+ * one halo_rnnt_beam_keep on all N * beam slots: Lp + Ll + 5 launches.  Slot n * beam + r is hypothesis r of row n.  The beam's records
+ * and both states (h and c [layers][N * beam][hidden], logits [N * beam][ld]) exist twice, by step parity; a step reads one copy and
+ * writes the other.
+ *   Definition, per row, with F = f[n], L = clamp(input_lengths[n], 0, T), W = beam, cap = capacity, a = lm_weight, b =
+ *   insertion_bonus.  A member is (y, s, lm, g, pstate, lp, lstate): y the token sequence, s the transducer mass of
+ *   halo_rnnt_beam_step, lm the LM's log-probability of y, g the prediction network's logits after the zero prefix and then y, pstate
+ *   its state behind g, lp = log_softmax(lg + lg_bias) over all V classes of the fusion LM after it consumed the start token and then
+ *   y, lstate the LM's state behind lp.
+ *       B = [((), s = 0, lm = 0, g / pstate after one prediction-network step on token 0 from the zero state,
+ *             lp / lstate after one LM step on the start token from the zero state)];  finals = []
+ *       if L == 0: finals = [((), rank 0, s 0, lm 0)]
+ *       for i in 0 .. L + cap - 1, while B is not empty:
+ *         t_j = i - len(y_j);  q_j = log_softmax(F[t_j] + g_j)
+ *         candidates, in this order:
+ *           for j in beam order: blank (y_j, s' = s_j + q_j[0], lm' = lm_j); if t_j + 1 == L it is complete: appended to finals, no
+ *               candidate
+ *           for j in beam order, if len(y_j) < cap, for k = 1 .. V-1: (y_j + [k], s' = s_j + q_j[k], lm' = lm_j + lp_j[k])
+ *         equal token sequences merge into the earliest (masses by logaddexp; the earliest keeps its own lm'), exactly
+ *           halo_rnnt_beam_step's merge
+ *         rank(candidate) = fma(a, lm', s') + b * len(y')
+ *         B = the W best by (rank descending, candidate position ascending: blank of j at j, j extended by k at W + j V + k); a kept
+ *           blank keeps its parent's g, pstate, lp, lstate; a kept label takes one step of BOTH networks on k from its parent's states
+ *       result: the W best finals by (rank descending, order of completion), kept as halo_rnnt_beam_step keeps its running W best: a
+ *         later one displaces the worst kept (lowest rank, the latest among equals) only with a strictly higher rank.
+ *   Everything else is halo_rnnt_beam_step's: the log-sum-exp order, hypotheses at the capacity take no label, frames at or past L are
+ *   never read, the tie rules.  With a = b = 0 this is halo_rnnt_beam_step, token for token.
+ *   halo_rnnt_lm_beam_step  alignment step `step` of every row, one workgroup of 256 threads per row.  rec [N][beam][3] fp32 = s | lm |
+ *                           rank, u [N][beam] (symbols emitted; -1: no hypothesis), tokens [N][beam][tokens_ld]; at step 0 the input
+ *                           records are not read and the finals are reset.  g [N * beam][ldg] / lg [N * beam][ldlg]: the logits of the
+ *                           prediction network / the LM of every slot without their biases (g_bias, lg_bias [V]; may be NULL).  Outputs:
+ *                           the new beam's records in the order taken, parent (-1: no hypothesis) and last (0: a blank extension);
+ *                           the finals fin_rec [N][beam][3] = rank | s | lm (-inf: none), fin_seq, fin_lengths (-1: none), fin_tokens,
+ *                           fin_n as halo_rnnt_beam_step's; the gather of halo_rnnt_beam_step once per network: xh / lm_xh
+ *                           [layers][N * beam][2 hidden] of every new slot = wte[last] | h_in of its parent, c_out = c_in of its
+ *                           parent, each with its own embedding, hidden size and depth.  *live += 1 for every row whose new beam is not
+ *                           empty.  lp_j[k] = (lg[slot j][k] + lg_bias[k]) - lse_j, both log-sum-exps summed in one fixed order.
+ *                           LDS rule: the row's beam * V joint logits and beam * V LM logits are both kept in LDS when 2 * beam * V
+ *                           <= 14336 floats (56 KiB of dynamic LDS, what a launch gets without the opt-in) and both recomputed from L2
+ *                           by the same operations otherwise: the same bits.  fp32, no float atomics, bit-reproducible.
+ *                           Limits: 2 <= V <= 8192, 1 <= beam <= 16, hidden % 4 == 0 and lm_hidden % 4 == 0, 1 <= capacity <=
+ *                           tokens_ld; both embeddings hold a row for every class. */
+int halo_rnnt_lm_beam_step(const float *f, long f_row_stride, long f_frame_stride, int N, int T, int V, const float *g, long ldg,
+                           const float *g_bias, const float *lg, long ldlg, const float *lg_bias, const int *input_lengths, int step,
+                           int beam, int capacity, float lm_weight, float insertion_bonus, const float *rec_in, const int *u_in,
+                           const int *tokens_in, float *rec_out, int *u_out, int *tokens_out, long tokens_ld, int *parent, int *last,
+                           float *fin_rec, int *fin_seq, int *fin_lengths, int *fin_tokens, int *fin_n, const float *wte, int hidden,
+                           int layers, const float *h_in, const float *c_in, float *xh, float *c_out, const float *lm_wte, int lm_hidden,
+                           int lm_layers, const float *lm_h_in, const float *lm_c_in, float *lm_xh, float *lm_c_out, int *live,
+                           halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Backward operators of the GPT / transformer training step (the autograd graph of ha/attention.py:205-232 as
  * `hal` runs it, ha/attention_loop.py:196-215: loss.backward()).
  *   halo_attention_bwd         gradient of halo_attention_fwd: dq, dk, dv (same row layouts as q, k, v; written, not
