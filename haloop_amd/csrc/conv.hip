@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void dwconv1d_cl_bwd_dw_kernel(const float *__
 extern "C" {
 
 int halo_im2col_cl(const float *x, float *col, int N, int T, int Cin, int ks, int stride, int pad, halo_stream_t stream) {
-    HALO_CHECK_ARG(x && col && N > 0 && T > 0 && Cin > 0 && ks > 0 && stride > 0 && pad >= 0);
+    HALO_CHECK_ARG(x && col && N > 0 && T > 0 && Cin > 0 && ks > 0 && stride > 0 && pad >= 0 && T + 2 * pad >= ks);
     const int To = (T + 2 * pad - ks) / stride + 1;
     HALO_CHECK_ARG(To > 0);
     const long n = (long)N * To * Cin * ks;
@@ -120,7 +120,7 @@ int halo_im2col_cl(const float *x, float *col, int N, int T, int Cin, int ks, in
 }
 
 int halo_col2im_cl(const float *dcol, float *dx, int N, int T, int Cin, int ks, int stride, int pad, halo_stream_t stream) {
-    HALO_CHECK_ARG(dcol && dx && N > 0 && T > 0 && Cin > 0 && ks > 0 && stride > 0 && pad >= 0);
+    HALO_CHECK_ARG(dcol && dx && N > 0 && T > 0 && Cin > 0 && ks > 0 && stride > 0 && pad >= 0 && T + 2 * pad >= ks);
     const int To = (T + 2 * pad - ks) / stride + 1;
     HALO_CHECK_ARG(To > 0);
     const long n = (long)N * T * Cin;
@@ -131,7 +131,7 @@ int halo_col2im_cl(const float *dcol, float *dx, int N, int T, int Cin, int ks, 
 
 int halo_dwconv1d_cl(const float *x, const float *weight, const float *bias, float *y, int N, int T, int C, int ks, int stride,
                      int pad, halo_stream_t stream) {
-    HALO_CHECK_ARG(x && weight && y && N > 0 && T > 0 && C > 0 && ks > 0 && stride > 0 && pad >= 0);
+    HALO_CHECK_ARG(x && weight && y && N > 0 && T > 0 && C > 0 && ks > 0 && stride > 0 && pad >= 0 && T + 2 * pad >= ks);
     const int To = (T + 2 * pad - ks) / stride + 1;
     HALO_CHECK_ARG(To > 0);
     const long n = (long)N * To * C;
@@ -149,7 +149,7 @@ size_t halo_dwconv1d_cl_bwd_workspace_bytes(int C, int ks) {
 
 int halo_dwconv1d_cl_bwd(const float *dy, const float *x, const float *weight, float *dx, float *dweight, float *dbias,
                          void *workspace, int N, int T, int C, int ks, int stride, int pad, halo_stream_t stream) {
-    HALO_CHECK_ARG(dy && x && weight && dweight && workspace && N > 0 && T > 0 && C > 0 && ks > 0 && ks <= 8 && stride > 0 && pad >= 0);
+    HALO_CHECK_ARG(dy && x && weight && dweight && workspace && N > 0 && T > 0 && C > 0 && ks > 0 && ks <= 8 && stride > 0 && pad >= 0 && T + 2 * pad >= ks);
     const int To = (T + 2 * pad - ks) / stride + 1;
     HALO_CHECK_ARG(To > 0);
     hipStream_t st = (hipStream_t)stream;

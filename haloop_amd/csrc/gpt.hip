@@ -65,11 +65,13 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float *__restr
     for (int c = threadIdx.x; c < V4; c += 256) {
         const f32x4 v = *reinterpret_cast<const f32x4 *>(row + 4 * c);
         const float vm = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+        if (vm == -INFINITY) continue;                   // nothing to add; with m still -inf, -inf - m would be NaN (lse_merge guards the same case)
         if (vm > m) { s *= __expf(m - vm); m = vm; }
         s += (__expf(v[0] - m) + __expf(v[1] - m)) + (__expf(v[2] - m) + __expf(v[3] - m));
     }
     for (int c = 4 * V4 + threadIdx.x; c < V; c += 256) {
         const float v = row[c];
+        if (v == -INFINITY) continue;
         if (v > m) { s *= __expf(m - v); m = v; }
         s += __expf(v - m);
     }

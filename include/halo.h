@@ -810,7 +810,9 @@ int halo_topk_f32(const float *values, int rows, int n, int k, float *out_values
  *   halo_layernorm_fwd        F.layer_norm(x, (C,), weight, bias|NULL, eps)  :29  (also StableEmbedding's norm :61)
  *   halo_attention_causal_fwd F.scaled_dot_product_attention(q,k,v,is_causal=True) on the packed c_attn
  *                             output qkv [B,T,3C] (q|k|v, heads side by side) -> y [B,T,C]  :113-123,90
- *   halo_cross_entropy_fwd    F.cross_entropy(logits, targets, ignore_index, reduction='none')  :231
+ *   halo_cross_entropy_fwd    F.cross_entropy(logits, targets, ignore_index, reduction='none')  :231; every target must be
+ *                             ignore_index or inside [0, V): the row is read at the target unchecked.  -inf logits are
+ *                             fine as long as one logit of the row is finite
  * Linear layers, tanh-GELU and the residual adds are halo_gemm_f32 / halo_gemm_split epilogues.
  * halo_attention_causal_fwd is halo_attention_fwd on the packed qkv rows; head_dim in {16, 32, 64} (GPT-2 small: 64). */
 int halo_embed_fwd(const int64_t *ids, const float *wte, const float *wpe, float *x, int n_tokens, int T, int C,
@@ -1485,7 +1487,8 @@ int halo_add_rows_bcast(float *x, const float *p, int rows, int T, int C, halo_s
  *   halo_im2col_cl    the unfold of nn.Conv1d(input_dim, hidden_dim, 3, stride, padding=1) :29; the conv itself is a
  *                     GEMM of col [N*T', Cin*ks] with weight [Cout, Cin*ks] + bias + HALO_GEMM_GELU_ERF (:46)
  *   halo_dwconv1d_cl  DWConv1d.depthwise (groups = channels) :15-18; .pointwise :19 is a GEMM over the rows
- * x [N, T, C] -> [N, T', C] with T' = (T + 2*pad - ks)/stride + 1; no length masking (the reference has none). */
+ * x [N, T, C] -> [N, T', C] with T' = (T + 2*pad - ks)/stride + 1; no length masking (the reference has none).  A window wider
+ * than the padded input (T + 2*pad < ks) is HALO_EINVAL in all four launches, whatever the stride (nn.Conv1d refuses it too). */
 int halo_im2col_cl(const float *x, float *col, int N, int T, int Cin, int ks, int stride, int pad,
                    halo_stream_t stream);
 /* gradient of the unfold (the fold): dx [N,T,Cin] from dcol [N*T', Cin*ks]; with it a dense Conv1d whose input is an activation
