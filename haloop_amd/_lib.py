@@ -209,6 +209,10 @@ SIGNATURES = {
     'halo_rnnt_beam_step': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_rnnt_beam_keep': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp]),
+    'halo_rnnt_beam_step_stream': (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'halo_rnnt_beam_stream_open': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _l, _i, _i, _vp, _i, _vp]),
     'halo_rnnt_joint_fwd': (_i, [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_rnnt_joint_bwd': (_i, [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _vp, _l, _l, _vp]),
     'halo_ctc_viterbi_workspace_bytes': (_sz, [_i, _i, _i]),

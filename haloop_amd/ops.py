@@ -1900,6 +1900,59 @@ def rnnt_beam_keep(parent, last, h_in, c_in, g_in, h_out, c_out, g_out):
                                     ptr(h_out), ptr(c_out), ptr(g_out), _stream()), 'halo_rnnt_beam_keep')
 
 
+def rnnt_beam_stream_open(f, n_frames, flags, ring, stream_state, rec, finals, zero_state, h, c, g, live):
+    """Opens a call of the carried beam search (include/halo.h): f [B, S, V] with unit class stride, n_frames [B] int32 and flags [>= B]
+    int32 or None (bits STREAM_BEGIN, STREAM_FINAL) for the first B of the rows of ring [rows, ring_frames, V] and stream_state int32
+    [4, rows]; rec = (scores, u [rows, W], ...) and h / c [layers, rows * W, H], g [rows * W, V] of the copy the next step reads;
+    finals as ``rnnt_beam_step``'s; zero_state = (h0, c0 [layers, H], g0 [V]); live: the call's int32 words, zeroed."""
+    B, S, V = f.shape
+    rows, W = rec[0].shape
+    layers, slots, H = h.shape
+    tensors = (n_frames, ring, stream_state, rec[0], rec[1], *finals, *zero_state, h, c, g, live) + (() if flags is None else (flags,))
+    if f.stride(2) != 1 or not all(t.is_contiguous() for t in tensors):
+        raise ValueError('rnnt_beam_stream_open: f must be contiguous along V and every other tensor contiguous')
+    if ring.shape[0] != rows or ring.shape[2] != V or ring.shape[1] < S or stream_state.shape != (4, rows) or slots != rows * W \
+            or n_frames.shape != (B,) or B > rows or (flags is not None and flags.shape[0] < B) or c.shape != h.shape \
+            or g.shape != (slots, V) or zero_state[0].shape != (layers, H) or zero_state[1].shape != (layers, H) \
+            or zero_state[2].shape != (V,) or any(t.shape != (rows, W) for t in (rec[1], finals[0], finals[1], finals[2])) \
+            or finals[4].shape != (rows,):
+        raise ValueError('rnnt_beam_stream_open: the tensors do not fit each other')
+    if any(t.dtype != torch.int32 for t in (n_frames, stream_state, live) + (() if flags is None else (flags,))):
+        raise ValueError('rnnt_beam_stream_open: n_frames, flags, stream_state and live must be int32')
+    check(lib().halo_rnnt_beam_stream_open(ptr(f), f.stride(0), f.stride(1), B, S, V, ptr(n_frames), ptr(flags), rows, ptr(ring),
+                                           ring.shape[1], ptr(stream_state), stream_state.stride(0), W, ptr(rec[0]), ptr(rec[1]),
+                                           ptr(finals[0]), ptr(finals[1]), ptr(finals[2]), ptr(finals[4]), ptr(zero_state[0]),
+                                           ptr(zero_state[1]), ptr(zero_state[2]), ptr(h), ptr(c), ptr(g), g.stride(0), H, layers,
+                                           ptr(live), live.numel(), _stream()), 'halo_rnnt_beam_stream_open')
+
+
+def rnnt_beam_step_stream(ring, g, g_bias, stream_state, capacity, rec_in, rec_out, parent, last, finals, wte, h_in, c_in, xh, c_out, live):
+    """One round of the carried beam search for every row (include/halo.h): ``rnnt_beam_step`` with the frames read from ring [rows,
+    ring_frames, V] and the step, the frames received and the final / closed flags from stream_state int32 [4, rows]; a row that
+    cannot execute its step does an identity round."""
+    rows, ring_frames, V = ring.shape
+    W = parent.shape[1]
+    layers, slots, H = h_in.shape
+    tensors = (ring, g, stream_state, *rec_in, *rec_out, parent, last, *finals, h_in, c_in, xh, c_out)
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError('rnnt_beam_step_stream: every tensor must be contiguous')
+    if slots != rows * W or g.shape != (slots, V) or wte.shape != (wte.shape[0], H) or wte.shape[0] < V or not wte.is_contiguous() \
+            or stream_state.shape != (4, rows) or stream_state.dtype != torch.int32:
+        raise ValueError('rnnt_beam_step_stream: g must be [rows * W, V], the state [layers, rows * W, H], the embedding [>= V, H] and '
+                         'stream_state int32 [4, rows]')
+    if xh.shape != (layers, slots, 2 * H) or c_in.shape != h_in.shape or c_out.shape != h_in.shape:
+        raise ValueError('rnnt_beam_step_stream: xh must be [layers, rows * W, 2 H], c_in and c_out as h_in')
+    ld = rec_in[2].shape[2]
+    if any(t.shape != (rows, W) for t in (rec_in[0], rec_in[1], rec_out[0], rec_out[1], parent, last, finals[0], finals[1], finals[2])) \
+            or any(t.shape != (rows, W, ld) for t in (rec_in[2], rec_out[2], finals[3])) or finals[4].shape != (rows,):
+        raise ValueError('rnnt_beam_step_stream: records and finals must be [rows, W] with tokens [rows, W, ld]')
+    check(lib().halo_rnnt_beam_step_stream(ptr(ring), ring_frames, rows, V, ptr(g), g.stride(0), ptr(g_bias), ptr(stream_state),
+                                           stream_state.stride(0), W, int(capacity), ptr(rec_in[0]), ptr(rec_in[1]), ptr(rec_in[2]),
+                                           ptr(rec_out[0]), ptr(rec_out[1]), ptr(rec_out[2]), ld, ptr(parent), ptr(last), ptr(finals[0]),
+                                           ptr(finals[1]), ptr(finals[2]), ptr(finals[3]), ptr(finals[4]), ptr(wte), H, layers, ptr(h_in),
+                                           ptr(c_in), ptr(xh), ptr(c_out), ptr(live), _stream()), 'halo_rnnt_beam_step_stream')
+
+
 # ---- the per-frame launch of CTC prefix beam search with LM shallow fusion (csrc/ctc_lm_beam.hip); it does not allocate ---------------
 def ctc_lm_beam_step(emissions, emission_lengths, frame, capacity, lm_weight, insertion_bonus, g, g_bias, rec_in, rec_out, parent, last, wte,
                      h_in, c_in, xh, c_out):

@@ -397,11 +397,15 @@ class StreamingTransducer(_ChunkedStreams):
         and ignores its later steps).
     last: (logits [B, S, V] fp32, zeros past a row's n_steps; n_steps [B] int32) of the latest call -- this object's buffers.
 
+    ``beam=W`` (None reads HALO_STREAM_RNNT_BEAM, 0 .. 16, default 0: this object as described, launch for launch) puts a
+    ``transducer.BeamStream`` in place of the greedy search: ``push`` marks no slot final, ``finish`` marks its rows
+    final, ``partial()`` returns the best hypothesis with ``truncated`` all False, and ``nbest()`` the n-best lists.
+
     There is no graph replay: the number of rounds of a call depends on the data.  Unlike ``StreamingRecognizer``, a call waits for the
     device wherever ``GreedyStream`` reads its live word (every ``transducer.SYNC_EVERY`` rounds)."""
 
-    def __init__(self, encoder, head, max_streams, chunk_frames=16, capacity=256, max_symbols_per_frame=10):
-        from .transducer import GreedyStream
+    def __init__(self, encoder, head, max_streams, chunk_frames=16, capacity=256, max_symbols_per_frame=10, beam=None):
+        from .transducer import BEAM_MAX, BeamStream, GreedyStream
         if encoder.training or head.training:
             raise ValueError('StreamingTransducer: put the encoder and the head in eval mode')
         conv = encoder.subsample
@@ -432,7 +436,15 @@ class StreamingTransducer(_ChunkedStreams):
         for s in (S, S + 1):
             self._bufs[s] = dict(y=torch.zeros(s, B, C, **f32), feats=torch.zeros(B, s, H, **f32), logits=torch.zeros(B, s, V, **f32),
                                  reserve=ops.lstm_reserve(s, B, C, H, L, dev))
-        self.search = GreedyStream(head, B, self.capacity, max_symbols_per_frame)
+        if beam is None:
+            beam = os.environ.get('HALO_STREAM_RNNT_BEAM', '0')
+        self.beam = int(beam)
+        if self.beam < 0 or self.beam > BEAM_MAX:
+            raise ValueError(f'StreamingTransducer: beam {self.beam} outside 0 .. {BEAM_MAX}')
+        if self.beam:
+            self.search = BeamStream(head, B, self.capacity, self.beam, max_chunk=S + 1)
+        else:
+            self.search = GreedyStream(head, B, self.capacity, max_symbols_per_frame)
         self._last = None
 
     def _check_modes(self):
@@ -452,8 +464,19 @@ class StreamingTransducer(_ChunkedStreams):
         self._call(tail.contiguous(), self._dims[2] + 1, True, flags, lengths)
 
     def partial(self):
+        if self.beam:
+            tokens, lengths, scores, counts = self.search.nbest()
+            none = counts == 0                                           # a slot that never began: the empty hypothesis, as greedy
+            return (tokens[:, 0], lengths[:, 0].clamp(min=0), scores[:, 0].masked_fill(none, 0.0), self._steps.clone(),
+                    torch.zeros_like(none))
         tokens, lengths, _, scores, truncated = self.search.result()
         return tokens, lengths, scores, self._steps.clone(), truncated
+
+    def nbest(self):
+        """``transducer.BeamStream.nbest`` of every slot (beam >= 1): a closed slot's finals, an open slot's stalled beam."""
+        if not self.beam:
+            raise ValueError('StreamingTransducer.nbest: built without a beam (beam=W or HALO_STREAM_RNNT_BEAM)')
+        return self.search.nbest()
 
     @property
     def last(self):

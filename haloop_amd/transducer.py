@@ -35,6 +35,10 @@ state its previous chunk left and left into it, so a row always holds ``GreedyDe
 
 ``BeamDecoder`` is beam search for the same head: alignment-length synchronous decoding with exact merging ([Saon20]), n-best lists whose
 scores sum the alignment paths of a hypothesis, on ``num_layers + 3`` launches per alignment step (csrc/rnnt_beam.hip).
+
+``BeamStream`` is that beam search carried across calls: a row executes an alignment step only when every frame the step reads has
+arrived and no blank extension could be complete, so after its final call a row holds ``BeamDecoder.decode`` of its whole utterance
+(csrc/rnnt_beam.hip: the open launch and the carried instantiation of the step).
 """
 import os
 
@@ -44,6 +48,7 @@ from . import _lib, functional as HF, ops
 from .rnn import lstm_param_list
 
 SYNC_EVERY = 16          # GreedyDecoder.decode reads the live-row counter every this many advances
+STREAM_BEAM_SYNC_EVERY = 4   # BeamStream.advance: after its first S rounds a call reads the live word every this many rounds
 
 
 class _Transducer(torch.autograd.Function):
@@ -555,6 +560,60 @@ class GreedyStream(_HeadDecoder):
 BEAM_MAX = 16            # csrc/rnnt_beam.hip keeps a row's records in LDS arrays of this many entries
 
 
+def _prune_row(beam, finals, lp, i, L, W, cap):
+    """Alignment step i of one row on the host (the general paths of ``BeamDecoder`` and ``BeamStream``): beam = [(tokens tuple, score)],
+    lp [len(beam), V] float64 = the log-probabilities of its hypotheses at their frames, L the row's length.  Complete blank extensions
+    are appended to ``finals`` -> (the new beam, [(parent j, token k; 0: blank)] of its members)."""
+    V = lp.shape[1]
+    where = {y: j for j, (y, _) in enumerate(beam)}
+    blank, labels, gone = [], [], []
+    for j, (y, s) in enumerate(beam):
+        blank.append(s + float(lp[j, 0]))
+        labels.append(s + lp[j, 1:])
+        gone.append(torch.zeros(V - 1, dtype=torch.bool))
+    complete = [i - len(y) + 1 == L for y, _ in beam]
+    for sidx, (y, _) in enumerate(beam):                  # the extension of y[:-1] by y[-1] merges into y's blank extension
+        j = where.get(y[:-1]) if y and not complete[sidx] else None
+        if j is not None:
+            a, b = torch.tensor(blank[sidx], dtype=torch.float64), labels[j][y[-1] - 1]
+            blank[sidx] = float(torch.logaddexp(a, b))
+            gone[j][y[-1] - 1] = True
+    cand, vals = [], []                                  # (parent, token) in candidate order, and their scores
+    for j, (y, _) in enumerate(beam):
+        if complete[j]:
+            finals.append((y, blank[j]))
+        else:
+            cand.append((j, 0)); vals.append(torch.tensor([blank[j]], dtype=torch.float64))
+    for j, (y, _) in enumerate(beam):
+        if len(y) < cap:
+            ks = (~gone[j]).nonzero().view(-1)
+            cand += [(j, int(k) + 1) for k in ks]
+            vals.append(labels[j][ks])
+    new, picks = [], []
+    if cand:
+        vals = torch.cat(vals)
+        for a in torch.sort(-vals, stable=True).indices[:W].tolist():
+            j, k = cand[a]
+            picks.append((j, k))
+            new.append((beam[j][0] + ((k,) if k else ()), float(vals[a])))
+    return new, picks
+
+
+def _ranked_finals(scores, seq, lengths, tokens, cap):
+    """The finals of a beam search (scores, order of completion, lengths [N, W], -1: absent; tokens [N, W, >= cap]) by (score descending,
+    order of completion), absent ones last, in ``BeamDecoder.decode``'s format: two stable sorts."""
+    N, W = lengths.shape
+    absent = lengths < 0
+    o1 = torch.where(absent, torch.full_like(seq, 2 ** 31 - 1), seq).argsort(dim=1, stable=True)
+    key = torch.where(absent, torch.full_like(scores, float('inf')), -scores).gather(1, o1)
+    order = o1.gather(1, key.argsort(dim=1, stable=True))
+    lengths = lengths.gather(1, order).long()
+    scores = torch.where(lengths < 0, torch.full_like(scores, float('-inf')), scores.gather(1, order))
+    tokens = tokens[:, :, :cap].gather(1, order[:, :, None].expand(N, W, cap)).long()
+    past = torch.arange(cap, device=tokens.device)[None, None, :] >= lengths[:, :, None]
+    return tokens.masked_fill(past, -1), lengths, scores, (lengths >= 0).sum(1)
+
+
 class BeamDecoder(_HeadDecoder):
     """Beam search for a ``recognizer.Transducer`` head: alignment-length synchronous decoding with exact merging ([Saon20] Saon,
     Tueske, Audhkhasi, ICASSP 2020), with preallocated buffers for ``max_batch`` rows, ``beam`` hypotheses per row and
@@ -617,17 +676,7 @@ class BeamDecoder(_HeadDecoder):
             cl = self.head.classifier
             f = HF.linear(features.float(), cl.weight, cl.bias).contiguous()                   # [N, T, V]
             il = input_lengths.to(device=features.device, dtype=torch.int32).clamp(0, T).contiguous()
-            scores, seq, lengths, tokens = (self._decode_fused if self.fused else self._decode_general)(f, il, N, W, cap)
-            # the finals by (score descending, order of completion): two stable sorts, absent hypotheses (length -1) last
-            absent = lengths < 0
-            o1 = torch.where(absent, torch.full_like(seq, 2 ** 31 - 1), seq).argsort(dim=1, stable=True)
-            key = torch.where(absent, torch.full_like(scores, float('inf')), -scores).gather(1, o1)
-            order = o1.gather(1, key.argsort(dim=1, stable=True))
-            lengths = lengths.gather(1, order).long()
-            scores = torch.where(lengths < 0, torch.full_like(scores, float('-inf')), scores.gather(1, order))
-            tokens = tokens[:, :, :cap].gather(1, order[:, :, None].expand(N, W, cap)).long()
-            past = torch.arange(cap, device=tokens.device)[None, None, :] >= lengths[:, :, None]
-            return tokens.masked_fill(past, -1), lengths, scores, (lengths >= 0).sum(1)
+            return _ranked_finals(*(self._decode_fused if self.fused else self._decode_general)(f, il, N, W, cap), cap)
 
     # ---- the fused path: num_layers + 3 launches per alignment step --------------------------------------------------------------------
     def _cells(self, xh, c, h_out, top, g_out, layers, head_image):
@@ -696,38 +745,9 @@ class BeamDecoder(_HeadDecoder):
             for n, B in enumerate(beams):
                 if not B:
                     continue
-                where = {y: j for j, (y, _) in enumerate(B)}
-                blank, labels, gone = [], [], []
-                for j, (y, s) in enumerate(B):
-                    blank.append(s + float(lp[n * W + j, 0]))
-                    labels.append(s + lp[n * W + j, 1:])
-                    gone.append(torch.zeros(V - 1, dtype=torch.bool))
-                complete = [i - len(y) + 1 == Ls[n] for y, _ in B]
-                for sidx, (y, _) in enumerate(B):            # the extension of y[:-1] by y[-1] merges into y's blank extension
-                    j = where.get(y[:-1]) if y and not complete[sidx] else None
-                    if j is not None:
-                        a, b = torch.tensor(blank[sidx], dtype=torch.float64), labels[j][y[-1] - 1]
-                        blank[sidx] = float(torch.logaddexp(a, b))
-                        gone[j][y[-1] - 1] = True
-                cand, vals = [], []                          # (parent, token) in candidate order, and their scores
-                for j, (y, _) in enumerate(B):
-                    if complete[j]:
-                        finals[n].append((y, blank[j]))
-                    else:
-                        cand.append((j, 0)); vals.append(torch.tensor([blank[j]], dtype=torch.float64))
-                for j, (y, _) in enumerate(B):
-                    if len(y) < cap:
-                        ks = (~gone[j]).nonzero().view(-1)
-                        cand += [(j, int(k) + 1) for k in ks]
-                        vals.append(labels[j][ks])
-                new = []
-                if cand:
-                    vals = torch.cat(vals)
-                    for a in torch.sort(-vals, stable=True).indices[:W].tolist():
-                        j, k = cand[a]
-                        src[n * W + len(new)], tok[n * W + len(new)] = n * W + j, k
-                        new.append((B[j][0] + ((k,) if k else ()), float(vals[a])))
-                beams[n] = new
+                beams[n], picks = _prune_row(B, finals[n], lp[n * W:n * W + len(B)], i, Ls[n], W, cap)
+                for r, (j, k) in enumerate(picks):
+                    src[n * W + r], tok[n * W + r] = n * W + j, k
             if not any(beams):
                 break
             src, tok = src.to(dev), tok.to(dev)
@@ -745,3 +765,246 @@ class BeamDecoder(_HeadDecoder):
                 scores[n, w], seq[n, w], lengths[n, w] = fin[a][1], w, len(fin[a][0])
                 tokens[n, w, :len(fin[a][0])] = torch.tensor(fin[a][0], dtype=torch.int32)
         return scores.to(dev), seq.to(dev), lengths.to(dev), tokens.to(dev)
+
+
+class BeamStream(_HeadDecoder):
+    """``BeamDecoder``'s search carried across calls: the transcription logits of ``max_rows`` rows arrive in chunks,
+    every row's beam stays in device memory between the calls, and after the call that marks a row final its n-best list is what
+    ``BeamDecoder.decode`` returns on the row's whole utterance -- on the fused path bit for bit, scores included -- at the cost of the
+    new frames alone.  The search is alignment-length synchronous: at step i hypothesis j stands at frame t_j = i - len(y_j), and a step
+    depends on the row's length L only through t_j < L and t_j + 1 == L.  With R frames received a row that is not final executes step
+    i iff max_j t_j + 1 < R: then every frame it reads has arrived and both tests come out as for any L > R.  Otherwise it stalls and
+    keeps its beam; a final row runs on with L = R until its beam is empty.  Hypotheses with more symbols stand at earlier frames, so
+    the rows keep their latest ``capacity + max_chunk + 1`` logit frames in a ring, which holds every frame a step can read.
+
+    advance(f [B, S, V], n_frames=None, begin=None, final=None): ``GreedyStream.advance``'s arguments, S <= max_chunk, and ``final``
+        (host-side like ``begin``): no frames follow this call's for the row.  A row must begin before its first frames; a row that is
+        final (or never began) is closed until it begins again, and frames sent to it change nothing, as for the rows from B on.
+        Returns nothing: ``nbest()`` reads the rows out.
+    nbest(): (tokens [max_rows, W, capacity] int64, lengths [max_rows, W] int64, scores [max_rows, W] fp32, counts [max_rows] int64)
+        in ``BeamDecoder.decode``'s format: a closed row's finals, ordered as ``BeamDecoder.decode`` orders them; an open row's
+        stalled beam in slot order, which the selection leaves score-descending.
+    rounds: the rounds of the last call.
+
+    One call is the open launch, then rounds of (step, ``num_layers`` cells, out_layer, keep) over all max_rows * W slots until no row
+    is live.  Records and state are double-buffered by the round's parity for all rows alike, so a row that cannot execute its step
+    does an identity round, and the parity is carried across calls.  A round is always completed: the next call needs the kept slots'
+    state.  The live word is read after S rounds and then every ``sync_every`` rounds (``STREAM_BEAM_SYNC_EVERY``; DESIGN.md 3.3aa
+    has the measured cadences); the rounds past the last live one are identity rounds and change no result.  A call needs at most S + capacity + 2 rounds; more raise ``HaloError``.  The general path (f32 mode, HALO_RNNT_FUSED=0, a
+    head the fused launches do not take) carries the same search on ``rnn.Decoder.forward`` at T = 1, pruned on the host.  The path is
+    chosen when a row begins; do not change it in the middle of a stream."""
+
+    _cells = BeamDecoder._cells
+
+    def __init__(self, head, max_rows, capacity, beam=4, max_chunk=64):
+        self.head = head
+        self.max_rows, self.capacity, self.beam, self.max_chunk = int(max_rows), int(capacity), int(beam), int(max_chunk)
+        if self.max_rows < 1 or self.capacity < 1 or self.max_chunk < 1:
+            raise ValueError('BeamStream: need max_rows >= 1, capacity >= 1 and max_chunk >= 1')
+        if self.beam < 1 or self.beam > BEAM_MAX:
+            raise ValueError(f'BeamStream: beam {self.beam} outside 1 .. {BEAM_MAX}')
+        lm = head.lm
+        E, H, L, V = lm.embedding.weight.shape[1], lm.hidden_dim, lm.num_layers, lm.num_classes
+        dev = lm.embedding.weight.device
+        if dev.type != 'cuda':
+            raise _lib.HaloError('haloop_amd.transducer.BeamStream runs on the HIP device only (no CPU path)')
+        mb, W, cap = self.max_rows, self.beam, self.capacity
+        R = mb * W
+        i32 = dict(device=dev, dtype=torch.int32)
+        f32 = dict(device=dev, dtype=torch.float32)
+        with torch.inference_mode(False):
+            self._ring = torch.zeros(mb, cap + self.max_chunk + 1, V, **f32)
+            self._meta = torch.zeros(4, mb, **i32)                 # step | frames received | final | closed, one word per row
+            self._meta[3].fill_(1)
+            self._nf, self._flags = torch.zeros(mb, **i32), torch.zeros(mb, **i32)
+            self._live = torch.zeros(self.max_chunk + cap + 2, **i32)            # one word per round of a call
+            if E == H:
+                self._rec = [(torch.full((mb, W), float('-inf'), **f32), torch.full((mb, W), -1, **i32), torch.zeros(mb, W, cap, **i32))
+                             for _ in range(2)]
+                self._parent, self._last = torch.zeros(mb, W, **i32), torch.zeros(mb, W, **i32)
+                self._fin = (torch.full((mb, W), float('-inf'), **f32), torch.zeros(mb, W, **i32), torch.full((mb, W), -1, **i32),
+                             torch.zeros(mb, W, cap, **i32), torch.zeros(mb, **i32))
+                self._h, self._c = torch.zeros(2, L, R, H, **f32), torch.zeros(2, L, R, H, **f32)
+                self._g = torch.zeros(2, R, V, **f32)
+                self._xh, self._top = torch.zeros(L, R, 2 * H, **f32), torch.zeros(R, H, **f32)
+                # the prediction network after the zero prefix, one row: computed with the cell launches whenever a weight changes
+                self._zero = (torch.zeros(L, H, **f32), torch.zeros(L, H, **f32), torch.zeros(V, **f32))
+                self._zxh, self._ztop = torch.zeros(L, 1, 2 * H, **f32), torch.zeros(1, H, **f32)
+            self._gg = torch.zeros(R, V, **f32)                    # the general path's state
+            self._gh, self._gc = torch.zeros(L, R, H, **f32), torch.zeros(L, R, H, **f32)
+        self._rows = [dict(beam=[], finals=[], step=0, R=0, final=False, closed=True) for _ in range(mb)]     # the general path's records
+        self._general = False  # which path holds the streams
+        self._cur = 0          # the copy of records and state that the next round reads.  Carried across calls.
+        self._images = None
+        self._zero_stamp = None
+        self.sync_every = STREAM_BEAM_SYNC_EVERY
+        self.rounds = 0
+
+    def advance(self, f, n_frames=None, begin=None, final=None):
+        mb = self.max_rows
+        V = self.head.lm.num_classes
+        if not torch.is_tensor(f) or f.dim() != 3 or not 1 <= f.shape[0] <= mb or not 1 <= f.shape[1] <= self.max_chunk \
+                or f.shape[2] != V or f.dtype != torch.float32:
+            raise ValueError(f'BeamStream.advance: f must be a float32 tensor [1 .. {mb}, 1 .. {self.max_chunk}, {V}]')
+        B, S = f.shape[0], f.shape[1]
+        if n_frames is not None and (not torch.is_tensor(n_frames) or tuple(n_frames.shape) != (B,) or n_frames.dtype != torch.int32):
+            raise ValueError(f'BeamStream.advance: n_frames must be an int32 tensor [{B}]')
+        if not f.is_cuda or (n_frames is not None and not n_frames.is_cuda):
+            raise _lib.HaloError('haloop_amd.transducer.BeamStream runs on the HIP device only (no CPU path)')
+        if self.head.training:
+            raise NotImplementedError('BeamStream is an inference path: put the head in eval mode')
+        marks = []
+        for name, mark in (('begin', begin), ('final', final)):
+            if mark is not None:
+                if torch.is_tensor(mark):
+                    if mark.is_cuda:
+                        raise ValueError(f'BeamStream.advance: {name} is host-side (a sequence of bools or a CPU bool tensor)')
+                    mark = mark.tolist()
+                mark = [bool(e) for e in mark]
+                if len(mark) != B:
+                    raise ValueError(f'BeamStream.advance: {name} has {len(mark)} entries for {B} rows')
+            marks.append(mark)
+        begin, final = marks
+        with torch.no_grad():
+            any_begin = begin is not None and any(begin)
+            flags = None
+            if any_begin or (final is not None and any(final)):
+                flags = self._flags[:B]
+                flags.copy_(torch.tensor([(ops.STREAM_BEGIN if begin and begin[b] else 0) | (ops.STREAM_FINAL if final and final[b] else 0)
+                                          for b in range(B)], dtype=torch.int32))
+            if n_frames is None:
+                nf = self._nf[:B].fill_(S)
+            else:
+                nf = n_frames.detach().contiguous()
+            self._advance(f.detach(), nf, flags, any_begin)
+
+    def _advance(self, f, nf, flags, any_begin):
+        """f [B, S, V], nf int32 [B] and flags int32 [>= B] (or None; bits STREAM_BEGIN and STREAM_FINAL) on the device; any_begin:
+        whether a flag carries STREAM_BEGIN."""
+        B, S, V = f.shape
+        if f.stride(2) != 1 or f.stride(1) < V or f.stride(0) < (S - 1) * f.stride(1) + V:
+            f = f.contiguous()
+        if any_begin:
+            self._general = not self.fused
+        (self._advance_general if self._general else self._advance_fused)(f, nf, flags)
+
+    # ---- the fused path: per round num_layers + 3 launches over all max_rows * W slots, whatever B ---------------------------------
+    def _zero_state(self, layers, head_image):
+        """(h0, c0, g0) of the prediction network after the zero prefix of training, with the launches ``BeamDecoder`` computes it with."""
+        stamp = self._stamp()
+        if self._zero_stamp != stamp:
+            h0, c0, g0 = self._zero
+            H = self.head.lm.hidden_dim
+            self._zxh.zero_(); c0.zero_()
+            self._zxh[0, :, :H] = self.head.lm.embedding.weight[0]
+            self._cells(self._zxh, c0[:, None], h0[:, None], self._ztop, g0[None], layers, head_image)
+            self._zero_stamp = stamp
+        return self._zero
+
+    def _advance_fused(self, f, nf, flags):
+        lm = self.head.lm
+        layers, head_image = self._decode_images()
+        zero = self._zero_state(layers, head_image)
+        wte, cap = lm.embedding.weight, self.capacity
+        S = f.shape[1]
+        rec, h, c, g, xh, top, fin = self._rec, self._h, self._c, self._g, self._xh, self._top, self._fin
+        q = self._cur
+        ops.rnnt_beam_stream_open(f, nf, flags, self._ring, self._meta, rec[q], fin, zero, h[q], c[q], g[q], self._live)
+        bound = S + cap + 2
+        try:
+            for it in range(bound):
+                ops.rnnt_beam_step_stream(self._ring, g[q], lm.out_layer.bias, self._meta, cap, rec[q], rec[1 - q], self._parent, self._last,
+                                          fin, wte, h[q], c[q], xh, c[1 - q], self._live[it:])
+                self._cells(xh, c[1 - q], h[1 - q], top, g[1 - q], layers, head_image)
+                ops.rnnt_beam_keep(self._parent, self._last, h[q], c[q], g[q], h[1 - q], c[1 - q], g[1 - q])
+                q = 1 - q
+                # a row sent S frames needs S rounds: the first read comes after them, the next every ``sync_every`` rounds
+                if it == bound - 1 or (it + 1 >= S and (it + 1 - S) % self.sync_every == 0 and int(self._live[it].item()) == 0):
+                    break
+        finally:
+            self._cur = q
+        self.rounds = it + 1
+        if int(self._live[it].item()) != 0:
+            raise _lib.HaloError('BeamStream: rows still live after S + capacity + 2 rounds')
+
+    # ---- the general path: the same carried search on rnn.Decoder.forward at T = 1 over max_rows * W rows, pruned on the host --------
+    def _advance_general(self, f, nf, flags):
+        lm = self.head.lm
+        dev = f.device
+        B, S, V = f.shape
+        mb, W, cap, ring = self.max_rows, self.beam, self.capacity, self._ring.shape[1]
+        R = mb * W
+        counts = nf.clamp(0, S).tolist()
+        marks = [0] * B if flags is None else flags[:B].tolist()
+        g, state = self._gg, (self._gh, self._gc)
+        if any(m & ops.STREAM_BEGIN for m in marks):                    # the zero prefix of training
+            g0, (h0, c0) = lm.forward(torch.zeros(1, 1, device=dev, dtype=torch.int64), lm.init_hidden(1))
+        for n in range(B):
+            r = self._rows[n]
+            if marks[n] & ops.STREAM_BEGIN:
+                g[n * W], state[0][:, n * W], state[1][:, n * W] = g0[0], h0[:, 0], c0[:, 0]
+                r.update(beam=[((), 0.0)], finals=[], step=0, R=0, final=False, closed=False)
+            elif r['closed'] or r['final']:
+                continue
+            if counts[n]:
+                self._ring[n, (r['R'] + torch.arange(counts[n], device=dev)) % ring] = f[n, :counts[n]]
+            r['R'] += counts[n]
+            if marks[n] & ops.STREAM_FINAL:
+                r['final'] = True
+                if r['R'] == 0:
+                    r.update(beam=[], finals=[((), 0.0)], closed=True)
+        slot_row = torch.arange(R, device=dev) // W
+        self.rounds = 0
+        while True:
+            runs = [n for n, r in enumerate(self._rows) if not r['closed'] and r['beam'] and
+                    (r['final'] or r['step'] - min(len(y) for y, _ in r['beam']) + 1 < r['R'])]
+            if not runs:
+                break
+            self.rounds += 1
+            if self.rounds > S + cap + 2:
+                raise _lib.HaloError('BeamStream: rows still live after S + capacity + 2 rounds')
+            t = torch.zeros(R, dtype=torch.int64)
+            for n in runs:
+                for j, (y, _) in enumerate(self._rows[n]['beam']):
+                    t[n * W + j] = (self._rows[n]['step'] - len(y)) % ring
+            lp = torch.log_softmax(self._ring[slot_row, t.to(dev)] + g, -1).double().cpu()      # one host read per round
+            src, tok = torch.arange(R), torch.zeros(R, dtype=torch.int64)
+            for n in runs:
+                r = self._rows[n]
+                beam, i = r['beam'], r['step']
+                new, picks = _prune_row(beam, r['finals'], lp[n * W:n * W + len(beam)], i, r['R'] if r['final'] else r['R'] + 1, W, cap)
+                for w, (j, k) in enumerate(picks):
+                    src[n * W + w], tok[n * W + w] = n * W + j, k
+                r['beam'], r['step'] = new, i + 1
+                if not new and r['final']:
+                    r['closed'] = True
+            src, tok = src.to(dev), tok.to(dev)
+            g, state = g[src], (state[0][:, src].contiguous(), state[1][:, src].contiguous())
+            g1, (h1, c1) = lm.forward(tok.view(1, R), state)
+            emit = tok != 0
+            g = torch.where(emit[:, None], g1, g)
+            state = (torch.where(emit[None, :, None], h1, state[0]), torch.where(emit[None, :, None], c1, state[1]))
+        self._gg.copy_(g); self._gh.copy_(state[0]); self._gc.copy_(state[1])
+
+    def nbest(self):
+        mb, W, cap = self.max_rows, self.beam, self.capacity
+        with torch.no_grad():
+            if self._general:
+                tokens = torch.full((mb, W, cap), -1, dtype=torch.int64)
+                lengths, scores = torch.full((mb, W), -1, dtype=torch.int64), torch.full((mb, W), float('-inf'), dtype=torch.float32)
+                for n, r in enumerate(self._rows):
+                    fin = r['finals']
+                    hyps = [fin[a] for a in sorted(range(len(fin)), key=lambda a: (-fin[a][1], a))[:W]] if r['closed'] else r['beam']
+                    for w, (y, s) in enumerate(hyps):
+                        lengths[n, w], scores[n, w] = len(y), s
+                        tokens[n, w, :len(y)] = torch.tensor(y, dtype=torch.int64)
+                dev = self._ring.device
+                return tokens.to(dev), lengths.to(dev), scores.to(dev), (lengths >= 0).sum(1).to(dev)
+            ft, fl, fs, fc = _ranked_finals(self._fin[0], self._fin[1], self._fin[2], self._fin[3], cap)
+            sc, u, tok = self._rec[self._cur]
+            bl = u.long()
+            bt = tok.long().masked_fill(torch.arange(cap, device=tok.device)[None, None, :] >= bl[:, :, None], -1)
+            bs = torch.where(bl < 0, torch.full_like(sc, float('-inf')), sc)
+            closed = self._meta[3] != 0
+            return (torch.where(closed[:, None, None], ft, bt), torch.where(closed[:, None], fl, bl), torch.where(closed[:, None], fs, bs),
+                    torch.where(closed, fc, (bl >= 0).sum(1)))

@@ -1160,6 +1160,41 @@ int halo_rnnt_beam_keep(int slots, int beam, int V, int hidden, int layers, cons
                         const float *c_in, const float *g_in, long ldg, float *h_out, float *c_out, float *g_out, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same beam search carried across calls (haloop_amd/transducer.py BeamStream): the logits arrive in chunks, the beam
+ * stays in device memory, and after the final call a row's finals are halo_rnnt_beam_step's over the whole utterance, bit for bit.  Every
+ * row has four words in stream_state int32 [4][state_ld]: its alignment step, the frames received R, final (no more frames follow) and
+ * closed (its search is over, or it never began), and a ring [rows][ring_frames][V] of its latest logit frames, frame t at t % ring_frames.
+ * A call is one halo_rnnt_beam_stream_open, then rounds of (halo_rnnt_beam_step_stream, the cells and halo_decode_linear on all rows *
+ * beam slots, halo_rnnt_beam_keep) until a round leaves its live word 0.  Records and state exist twice and every round crosses to the
+ * other copy for every row; the caller carries the parity across calls.
+ *   halo_rnnt_beam_stream_open  one workgroup per row of the state; rows >= B take no part.  live[0 .. n_live) = 0.  A row whose flags
+ *                               (may be NULL) carry bit 1 (begin) is reset first: step = R = final = closed = 0, the empty hypothesis with
+ *                               score 0 in slot 0 of scores / u (the copy the next step reads), no finals, and h0 / c0 [layers][hidden] and
+ *                               g0 [V] (the prediction network after the zero prefix) in slot 0 of h, c [layers][rows * beam][hidden] and
+ *                               g.  A row that is closed or final and does not begin is left as it is.  Otherwise the row's first
+ *                               clamp(n_frames, 0, S) frames of f [B][S][V] go to the ring at R % ring_frames and R grows; bit 2 (final)
+ *                               sets final, and with R == 0 the finals become the empty hypothesis with score 0 and the row is closed.
+ *   halo_rnnt_beam_step_stream  halo_rnnt_beam_step with the step, R and the flags read from the row's words.  A row executes its step
+ *                               iff it is not closed, its beam is not empty, and it is final (then L = R) or every hypothesis stands
+ *                               at a frame t_j with t_j + 1 < R (then no blank extension is complete and no frame >= R is read);
+ *                               it then adds 1 to its step, sets closed when a final row's new beam is empty, and *live += 1 iff its
+ *                               next step is executable by the same rule.  Every other row does an identity round: records and tokens
+ *                               cross to the other copy unchanged, parent[r] = r for a present slot and -1 otherwise, last = 0, the
+ *                               gather is from the slot itself, so halo_rnnt_beam_keep carries h, c and g across.  ring_frames >=
+ *                               capacity + S + 1 holds every frame a step can read after calls of at most S frames. */
+int halo_rnnt_beam_step_stream(const float *ring, int ring_frames, int rows, int V, const float *g, long ldg, const float *g_bias,
+                               int *stream_state, long state_ld, int beam, int capacity, const float *scores_in, const int *u_in,
+                               const int *tokens_in, float *scores_out, int *u_out, int *tokens_out, long tokens_ld, int *parent,
+                               int *last, float *fin_scores, int *fin_seq, int *fin_lengths, int *fin_tokens, int *fin_n,
+                               const float *wte, int hidden, int layers, const float *h_in, const float *c_in, float *xh, float *c_out,
+                               int *live, halo_stream_t stream);
+int halo_rnnt_beam_stream_open(const float *f, long f_row_stride, long f_frame_stride, int B, int S, int V, const int *n_frames,
+                               const int *flags, int rows, float *ring, int ring_frames, int *stream_state, long state_ld, int beam,
+                               float *scores, int *u, float *fin_scores, int *fin_seq, int *fin_lengths, int *fin_n, const float *h0,
+                               const float *c0, const float *g0, float *h, float *c, float *g, long ldg, int hidden, int layers,
+                               int *live, int n_live, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The RNN transducer's training loss over the additive joint z[n, t, u, k] = f[n, t, k] + g[n, u, k] (haloop_amd/transducer.py
  * transducer_loss; the quantity of ha/recognizer.py:121-126, rnnt_loss(..., fused_log_softmax=True)) without a tensor of N T U1 V elements:
  * halo_rnnt_joint_fwd, then halo_transducer_fwd / halo_transducer_bwd on lp2 as a joint with K = 2 and targets of ones, then
