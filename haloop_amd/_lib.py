@@ -199,6 +199,9 @@ SIGNATURES = {
     'halo_ctc_prefix_scores': (_i, [_vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _l, _vp]),
     'halo_decode_beam_select_joint': (_i, [_vp, _l, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp, _vp, _vp, _l, _l, _vp, _i, _i, _vp, _vp]),
+    'halo_decode_beam_select_lm': (_i, [_vp, _l, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp,
+                                        _vp, _vp]),
     'halo_ctc_prefix_advance': (_i, [_vp, _l, _l, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_rnnt_advance': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _vp, _i, _vp, _l, _vp, _vp]),
     'halo_rnnt_lstm_cell': (_i, [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp]),

@@ -113,6 +113,7 @@ __device__ __forceinline__ void child_rows(Tok *out, const Tok *in, long ld, int
 // ---- the gather of the LSTM state for the cell launches that follow a selection (halo_rnnt_lstm_cell): slot r of the row's W takes the
 // cell inputs [wte[k[r]] | h of slot src[r]] and c of slot src[r], for every layer: 2 layers + 1 rows of H floats per slot, all of the
 // row's copies spread over the threads, four loads in flight per thread before their stores.  `first` is the row's first slot.
+// ZERO_ABSENT: a slot with src[r] < 0 (it steps nothing) has its rows zeroed instead, so that the cells read nothing unwritten.
 struct StateGather {
     const float *wte;          // [V][H] the embedding
     const float *h_in, *c_in;  // [layers][slots][H] the state read
@@ -120,6 +121,7 @@ struct StateGather {
     int H, layers;
 };
 
+template <bool ZERO_ABSENT = false>
 __device__ __forceinline__ void gather_state(const StateGather &g, long first, int W, const int *src, const int *k) {
     const int H4 = g.H / 4, per = 2 * g.layers + 1, total = W * per * H4;
     const long slots = (long)gridDim.x * W;
@@ -133,14 +135,16 @@ __device__ __forceinline__ void gather_state(const StateGather &g, long first, i
             dst[e] = nullptr;
             if (idx >= total) continue;
             const int r = idx / (per * H4), q = idx / H4 % per, x = idx % H4, par = src[r];
+            const bool zero = ZERO_ABSENT && par < 0;
+            if (zero) v[e] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (q < g.layers) {                                         // h of layer q -> the h half of its [x | h] row
-                v[e] = reinterpret_cast<const f32x4 *>(g.h_in + ((long)q * slots + first + par) * g.H)[x];
+                if (!zero) v[e] = reinterpret_cast<const f32x4 *>(g.h_in + ((long)q * slots + first + par) * g.H)[x];
                 dst[e] = reinterpret_cast<f32x4 *>(g.xh + ((long)q * slots + first + r) * 2 * g.H) + H4 + x;
             } else if (q < 2 * g.layers) {                              // c of layer q - layers
-                v[e] = reinterpret_cast<const f32x4 *>(g.c_in + ((long)(q - g.layers) * slots + first + par) * g.H)[x];
+                if (!zero) v[e] = reinterpret_cast<const f32x4 *>(g.c_in + ((long)(q - g.layers) * slots + first + par) * g.H)[x];
                 dst[e] = reinterpret_cast<f32x4 *>(g.c_out + ((long)(q - g.layers) * slots + first + r) * g.H) + x;
             } else {                                                    // the new token's embedding -> layer 0's x half
-                v[e] = reinterpret_cast<const f32x4 *>(g.wte + (long)k[r] * g.H)[x];
+                if (!zero) v[e] = reinterpret_cast<const f32x4 *>(g.wte + (long)k[r] * g.H)[x];
                 dst[e] = reinterpret_cast<f32x4 *>(g.xh + (first + r) * 2 * g.H) + x;
             }
         }

@@ -14,6 +14,10 @@ launch and its last; the general path runs the same search on ``rnn.Decoder.forw
 search of ``transducer.BeamDecoder`` with every candidate ranked by its transducer mass + lm_weight * log P_LM(y) + insertion_bonus *
 len(y), every hypothesis carrying the states of both the prediction network and the LM.
 
+``AttentionFusionDecoder`` (csrc/decode_beam.hip) fuses the LM into the attention decoder's beam search
+(``transformer.BeamDecoder``, with or without the CTC prefix scores): every candidate is ranked by fmaf(lm_weight, log P_LM, rank).  The
+search is label-synchronous, so no ``keep`` launch is needed: ``Ll + 1`` launches a step on top of the decoder's.
+
 ``lm_score`` is the teacher-forced LM log-probability of every hypothesis of an n-best list: a rescorer for any list (the transducer's
 included) and the independent check on the decoder's ``lm_scores``.
 """
@@ -468,6 +472,139 @@ class TransducerFusionDecoder:
                 rec[n, w], seq[n, w], lengths[n, w] = torch.tensor(fin[x][1:]), w, len(fin[x][0])
                 tokens[n, w, :len(fin[x][0])] = torch.tensor(fin[x][0], dtype=torch.int32)
         return rec.to(dev), seq.to(dev), lengths.to(dev), tokens.to(dev)
+
+
+class _LMSide:
+    """The LM side of ``AttentionFusionDecoder``, as ``transformer.BeamDecoder``'s cores drive it: the slots' lm (two copies by step
+    parity), the LSTM state (likewise), the cells' input rows and the LM's logits, for ``slots`` = max_batch * beam rows; ``weight``,
+    ``start_token`` and ``eos`` are those of the running call."""
+
+    def __init__(self, lm, slots, etx):
+        self.lm, self.etx = lm, etx
+        self.images = _Images(_LMHead(lm))
+        self.weight, self.start_token, self.eos = 0.0, 0, None
+        wte = lm.embedding.weight
+        dev, E, H, L, V = wte.device, wte.shape[1], lm.hidden_dim, lm.num_layers, lm.num_classes
+        i32, f32 = dict(device=dev, dtype=torch.int32), dict(device=dev, dtype=torch.float32)
+        self._buf = None
+        with torch.inference_mode(False):          # ordinary tensors: they are updated in place inside and outside inference mode
+            if E == H and dev.type == 'cuda':      # flat buffers, viewed per call at that call's N * W slots
+                self._buf = dict(lm=[torch.zeros(slots, **f32) for _ in range(2)], par=torch.zeros(slots, **i32), last=torch.zeros(slots, **i32),
+                                 h=torch.zeros(2 * L * slots * H, **f32), c=torch.zeros(2 * L * slots * H, **f32),
+                                 g=torch.zeros(slots * V, **f32), xh=torch.zeros(L * slots * 2 * H, **f32), top=torch.zeros(slots * H, **f32))
+
+    @property
+    def fused(self):
+        return self._buf is not None and self.images.fused
+
+    def key(self):
+        """What a captured search depends on besides the shapes: the LM's parameters as they are now, and the call's three settings."""
+        return self.images._stamp() + (self.weight, self.start_token, self.eos)
+
+    def start(self, N, W):
+        """The views of this search's N * W slots; the LM after the start token, in every slot."""
+        lm, b = self.lm, self._buf
+        H, L, V, R = lm.hidden_dim, lm.num_layers, lm.num_classes, N * W
+        self._lm = [x[:R].view(N, W) for x in b['lm']]
+        self._par, self._last = b['par'][:R].view(N, W), b['last'][:R].view(N, W)
+        self._h, self._c = b['h'][:2 * L * R * H].view(2, L, R, H), b['c'][:2 * L * R * H].view(2, L, R, H)
+        self._g, self._xh, self._top = b['g'][:R * V].view(R, V), b['xh'][:L * R * 2 * H].view(L, R, 2 * H), b['top'][:R * H].view(R, H)
+        self._xh.zero_(); self._c[0].zero_()
+        self._xh[0, :, :H] = lm.embedding.weight[self.start_token]
+        self._cells(0)
+
+    def _cells(self, q):
+        BeamDecoder._cells(self.images, self._xh, self._c[q], self._h[q], self._top, self._g, *self.images._decode_images())
+
+    def select(self, logits, t, cap, length_bonus, rec_in, rec_out, ranks, wte, y_next, par=None, last=None, c=0.0, psi_cand=None, psi_in=None,
+               psi_out=None):
+        """Step t's selection with the LM in the rank; the gather for the next LM step unless this is the last."""
+        q, lm = t & 1, self.lm
+        more = t + 1 < cap
+        ops.decode_beam_select_lm(logits, t, cap, self.etx, length_bonus, self._g, lm.out_layer.bias, self._lm[q], self._lm[1 - q], self.weight,
+                                  self.eos, rec_in, rec_out, ranks, self._par if par is None else par, self._last if last is None else last,
+                                  lm.embedding.weight if more else None, self._h[q] if more else None, self._c[q] if more else None,
+                                  self._xh if more else None, self._c[1 - q] if more else None, wte, y_next, c, psi_cand, psi_in, psi_out)
+
+    def step(self, t, cap):
+        """The LM's cell launches and out_layer on the rows the selection of step t gathered (the last step: nobody reads them)."""
+        if t + 1 < cap:
+            self._cells(1 - (t & 1))
+
+    def scores(self, cap):
+        return self._lm[cap & 1]
+
+
+class AttentionFusionDecoder:
+    """Beam search for a ``transformer.Decoder`` with LM shallow fusion inside the search (csrc/decode_beam.hip; the
+    definition: include/halo.h), on ``transformer.BeamDecoder``'s buffers and launch sequence.  ``lm``: an ``rnn.Decoder`` over the
+    decoder's V classes, in eval mode, on the decoder's device.  Every slot carries the LM's log-probability ``lm`` of its tokens and the
+    LSTM state after ``start_token`` and those tokens; a candidate's rank is
+
+        fmaf(lm_weight, lmc, base)
+
+    ``base`` the rank of ``BeamDecoder`` (attention-only, or the mix with the CTC prefix score), lmc = lm + log P_LM(k) for a label k, lm +
+    log P_LM(lm_eos) for ETX (``lm_eos=None``: closing costs nothing), lm for a finished slot.  With ``lm_weight`` 0 it is
+    ``BeamDecoder.decode``.  The fused path runs when the decoder's fused decode applies and the LM passes the fused rule of the
+    transducer decoders: per step the decoder's launches, ``halo_decode_beam_select_lm``, then ``Ll`` cell launches and one ``out_layer``
+    launch for the next step -- ``5 * layers + Ll + 3`` launches (``+ 6`` with CTC), replayed from one captured graph per decode
+    unless HALO_DECODE_GRAPH=0.  Everything else (f32 mode, an LM the fused cells refuse, HALO_DECODE_FUSED=0) takes the general path:
+    the same search on ``Decoder._step_general`` and ``rnn.Decoder.forward`` at T = 1 over N * W rows."""
+
+    def __init__(self, decoder, lm, max_batch, capacity, beam=4, lm_weight=0.5, length_bonus=0.0, start_token=0, lm_eos=None):
+        V = decoder.lm_head.weight.shape[0]
+        self.lm_weight, self.start_token, self.lm_eos = _fusion_settings('AttentionFusionDecoder', lm, V, lm_weight, start_token, lm_eos)
+        from .transformer import ETX, BeamDecoder as AttentionBeamDecoder     # (transformer imports this module through recognizer)
+        self._beam = AttentionBeamDecoder(decoder, max_batch, capacity, beam, length_bonus)      # its buffers, cores and graphs
+        self.lm = lm
+        self._side = _LMSide(lm, self.max_batch * self.beam, ETX)
+        self.last_parts = None  # (attention [N, W], lm_scores [N, W]) of the last decode
+
+    def __getattr__(self, name):
+        """decoder, max_batch, capacity, beam, length_bonus, last_logprobs, last_finished, last_ctc: the search's own."""
+        if name == '_beam':
+            raise AttributeError(name)
+        return getattr(self._beam, name)
+
+    @property
+    def fused(self):
+        """Whether the fused launches are in use: the decoder's rule and the LM's, as they are now."""
+        return self._beam.fused and self._side.fused
+
+    def decode(self, features, input_lengths, capacity=None, beam=None, ctc_log_probs=None, ctc_weight=0.0, lm_weight=None):
+        """``BeamDecoder.decode`` with the LM in every rank: the same n-best format, scores = the fused rank; ``last_logprobs``,
+        ``last_finished`` and ``last_ctc`` as there, and ``last_parts`` = (attention [N, W] = logprob + length_bonus * length, lm_scores
+        [N, W]), -inf where absent.  ``lm_weight``: this call's instead of the decoder's."""
+        name, lm, dec = 'AttentionFusionDecoder', self.lm, self.decoder
+        a, _, _ = _fusion_settings(name, lm, dec.lm_head.weight.shape[0], self.lm_weight if lm_weight is None else lm_weight,
+                                   self.start_token, self.lm_eos)
+        if lm.training or dec.training:
+            raise NotImplementedError(f'{name} is an inference path: put the decoder and the LM in eval mode')
+        if not features.is_cuda or not lm.embedding.weight.is_cuda or not dec.wte.weight.is_cuda:
+            raise _lib.HaloError(f'haloop_amd.fusion.{name} runs on the HIP device only (no CPU path)')
+        if any(x.device != self._beam._device for x in (features, lm.embedding.weight, dec.wte.weight)):
+            raise _lib.HaloError(f'{name}: the decoder, the LM and the features must be on the device the decoder was built on')
+        side = self._side
+        side.weight, side.start_token, side.eos = a, self.start_token, self.lm_eos
+        if self.fused:
+            side.images._decode_images()           # built (or rebuilt after an update) before any capture
+        out = self._beam._search(features, input_lengths, capacity, beam, ctc_log_probs, ctc_weight, side)
+        lengths = out[1]
+        attention = self.last_logprobs + self.length_bonus * lengths.clamp(min=0).float()
+        self.last_parts = (torch.where(lengths < 0, torch.full_like(attention, NEG), attention), self._last_lm)
+        return out
+
+
+def _fusion_settings(name, lm, V, lm_weight, start_token, lm_eos):
+    """The checks of an LM and its settings against a decoder of V classes -> (lm_weight, start_token, lm_eos) as numbers."""
+    if getattr(lm, 'num_classes', None) != V:
+        raise ValueError(f'{name}: the LM has {getattr(lm, "num_classes", None)} classes, the decoder {V}')
+    a, start, eos = float(lm_weight), int(start_token), None if lm_eos is None else int(lm_eos)
+    if not math.isfinite(a):
+        raise ValueError(f'{name}: lm_weight must be finite')
+    if start < 0 or start >= V or (eos is not None and (eos < 0 or eos >= V)):
+        raise ValueError(f'{name}: start_token {start} / lm_eos {eos} outside 0 .. {V - 1}')
+    return a, start, eos
 
 
 def lm_score(lm, tokens, lengths, start_token=0):

@@ -2,6 +2,7 @@
 current HIP stream and allocates its outputs/workspaces with torch (device memory plumbing only).
 """
 import ctypes as C
+import math
 from collections import namedtuple
 
 import torch
@@ -1752,6 +1753,56 @@ def decode_beam_select_joint(logits, t, capacity, etx, length_bonus, ctc_weight,
                                               ptr(parents_out), ptr(last_out), beam_in[3].shape[2], beam_in[4].shape[1], ptr(wte),
                                               wte.shape[0] if wte is not None else 0, wte.shape[1] if wte is not None else 0, ptr(y_next),
                                               _stream()), 'halo_decode_beam_select_joint')
+
+
+# ---- the selection with LM shallow fusion (csrc/decode_beam.hip); it does not allocate -----------------------------------
+DECODE_BEAM_LM_LDS_FLOATS = 14336    # HALO_DECODE_BEAM_LM_LDS_FLOATS (include/halo.h): both tables stay in LDS while 2 W V <= this
+
+
+def decode_beam_select_lm(logits, t, capacity, etx, length_bonus, lm_logits, lm_bias, lm_in, lm_out, lm_weight, lm_eos, beam_in, beam_out,
+                          ranks_out, parents_out, last_out, lm_wte=None, h_in=None, c_in=None, lm_xh=None, c_out=None, wte=None, y_next=None,
+                          ctc_weight=0.0, psi_cand=None, psi_in=None, psi_out=None):
+    """decode_beam_select (psi_cand None) or decode_beam_select_joint with rank = fmaf(lm_weight, lmc, rank) (include/halo.h): lm_logits
+    [N * W, V] the LM's logits without their bias, lm_bias [V] or None, lm_in / lm_out [N, W] float32 (two copies), lm_eos -1 .. V-1 or
+    None.  With lm_xh (None: the last step) the next LM step's cell inputs are gathered: h_in, c_in, c_out [Ll, N * W, H], lm_xh
+    [Ll, N * W, 2 H], lm_wte [V, H], all contiguous float32."""
+    name = 'decode_beam_select_lm'
+    N, W, V = _check_beam_select(name, logits, beam_in, beam_out, ranks_out, wte, y_next)
+    if lm_logits.shape != (N * W, V) or lm_logits.dtype != torch.float32 or lm_logits.stride(1) != 1:
+        raise ValueError(f'{name}: lm_logits must be float32 [N * W, V] with unit class stride')
+    if lm_bias is not None and (lm_bias.shape != (V,) or lm_bias.dtype != torch.float32 or not lm_bias.is_contiguous()):
+        raise ValueError(f'{name}: lm_bias must be a contiguous float32 [V]')
+    _prefix_records(name, N, W, (parents_out, last_out), (lm_in, lm_out))
+    eos = -1 if lm_eos is None else int(lm_eos)
+    if not math.isfinite(float(lm_weight)) or eos < -1 or eos >= V:
+        raise ValueError(f'{name}: lm_weight must be finite and lm_eos in -1 .. {V - 1}')
+    if psi_cand is not None:
+        if psi_cand.shape != (N * W, V) or psi_cand.dtype != torch.float32 or psi_cand.stride(1) != 1:
+            raise ValueError(f'{name}: psi_cand must be float32 [N * W, V] with unit class stride')
+        _prefix_records(name, N, W, (), (psi_in, psi_out))
+        if not 0.0 <= float(ctc_weight) <= 1.0:
+            raise ValueError(f'{name}: ctc_weight {ctc_weight} outside [0, 1]')
+    elif psi_in is not None or psi_out is not None:
+        raise ValueError(f'{name}: psi_in / psi_out come with psi_cand')
+    H = Ll = 0
+    if lm_xh is not None:
+        if any(x is None for x in (lm_wte, h_in, c_in, c_out)):
+            raise ValueError(f'{name}: lm_xh comes with lm_wte, h_in, c_in and c_out')
+        Ll, H = h_in.shape[0], h_in.shape[2]
+        for x, shape in ((h_in, (Ll, N * W, H)), (c_in, (Ll, N * W, H)), (c_out, (Ll, N * W, H)), (lm_xh, (Ll, N * W, 2 * H)), (lm_wte, (V, H))):
+            if tuple(x.shape) != shape or x.dtype != torch.float32 or not x.is_contiguous():
+                raise ValueError(f'{name}: the LM state must be contiguous float32 h_in, c_in, c_out [Ll, N * W, H], lm_xh [Ll, N * W, 2 H] and '
+                                 'lm_wte [V, H]')
+    else:
+        lm_wte = h_in = c_in = c_out = None
+    check(lib().halo_decode_beam_select_lm(ptr(logits), logits.stride(0), N, W, V, int(t), int(capacity), int(etx), float(length_bonus),
+                                           float(ctc_weight), ptr(psi_cand), psi_cand.stride(0) if psi_cand is not None else 0, ptr(psi_in),
+                                           ptr(psi_out), ptr(lm_logits), lm_logits.stride(0), ptr(lm_bias), ptr(lm_in), ptr(lm_out),
+                                           float(lm_weight), eos, *(ptr(x) for x in beam_in), ptr(beam_out[0]), ptr(ranks_out),
+                                           *(ptr(x) for x in beam_out[1:]), ptr(parents_out), ptr(last_out), beam_in[3].shape[2],
+                                           beam_in[4].shape[1], ptr(wte), wte.shape[0] if wte is not None else 0,
+                                           wte.shape[1] if wte is not None else 0, ptr(y_next), ptr(lm_wte), H, Ll, ptr(h_in), ptr(c_in),
+                                           ptr(lm_xh), ptr(c_out), _stream()), 'halo_decode_beam_select_lm')
 
 
 # ---- fused launches of a GPT sampling step (csrc/gpt_decode.hip); none of these allocates: they run inside a captured step ----------

@@ -435,6 +435,7 @@ class Decoder(nn.Module):
         self.beam_size = int(os.environ.get('HALO_ASR_BEAM', '0'))        # decode(): 0 greedy, W >= 1 BeamDecoder's search
         self.length_bonus = 0.0                                           # of that search
         self._beams = {}                                                  # its BeamDecoder, built at the first beam decode
+        self.last_parts = None                                            # (attention, lm_scores) of a beam decode after set_fusion_lm
 
     def forward(self, features, targets, input_lengths=None, target_lengths=None, star_penalty=None, measure_entropy=False,
                 drop_labels=None, reduction='mean'):
@@ -675,18 +676,40 @@ class Decoder(nn.Module):
         entry['graph'].replay()
         return tuple(o.clone() for o in entry['outs'])
 
+    def set_fusion_lm(self, lm, lm_weight=0.5, start_token=0, lm_eos=None):
+        """Shallow fusion for ``decode(..., beam_size=W)``: ``lm``, an ``rnn.Decoder`` over this decoder's classes, scores every candidate
+        inside the search (``fusion.AttentionFusionDecoder``), and ``last_parts`` = (attention, lm_scores) is kept with
+        ``last_nbest``.  The LM is not a submodule: the state dict and the parameters are unchanged.  ``set_fusion_lm(None)``: the plain
+        search again.  Greedy decoding does not use it."""
+        self._beams.pop('fusion', None)
+        if lm is None:
+            self._beams.pop('lm', None)
+            return
+        from .fusion import _fusion_settings
+        a, start, eos = _fusion_settings('Decoder.set_fusion_lm', lm, self.lm_head.weight.shape[0], lm_weight, start_token, lm_eos)
+        self._beams['lm'] = dict(lm=lm, lm_weight=a, start_token=start, lm_eos=eos)        # (in the dict: not registered as a submodule)
+
     @torch.no_grad()
-    def _decode_beam(self, features, input_lengths, T, W, ctc_log_probs=None, ctc_weight=0.0):
+    def _decode_beam(self, features, input_lengths, T, W, ctc_log_probs=None, ctc_weight=0.0, fusion=True):
         """Beam search at width W with room for T steps (the greedy decode's step count): each row's best hypothesis in the greedy
-        decode's five-value form, the lists in ``last_nbest``.  With ``ctc_log_probs`` and a weight: the joint search."""
+        decode's five-value form, the lists in ``last_nbest``.  With ``ctc_log_probs`` and a weight: the joint search.  With an LM set
+        by ``set_fusion_lm`` (and ``fusion``): the search with the LM, ``last_parts`` kept."""
         N = features.shape[0]
-        bd = self._beams.get('decoder')
+        which = 'fusion' if fusion and 'lm' in self._beams else 'decoder'
+        bd = self._beams.get(which)
         if bd is None or bd.max_batch < N or bd.capacity < T or bd.beam < W or bd._device != self.wte.weight.device \
                 or bd.length_bonus != float(self.length_bonus):
-            bd = BeamDecoder(self, max(N, bd.max_batch if bd else 0), max(T, bd.capacity if bd else 0), max(W, bd.beam if bd else 0),
-                             self.length_bonus)
-            self._beams['decoder'] = bd
+            sizes = (max(N, bd.max_batch if bd else 0), max(T, bd.capacity if bd else 0), max(W, bd.beam if bd else 0))
+            if which == 'fusion':
+                from .fusion import AttentionFusionDecoder
+                f = self._beams['lm']
+                bd = AttentionFusionDecoder(self, f['lm'], *sizes, f['lm_weight'], self.length_bonus, f['start_token'], f['lm_eos'])
+            else:
+                bd = BeamDecoder(self, *sizes, self.length_bonus)
+            self._beams[which] = bd
+        self._beams['used'] = which
         self.last_nbest = bd.decode(features, input_lengths, capacity=T, beam=W, ctc_log_probs=ctc_log_probs, ctc_weight=ctc_weight)
+        self.last_parts = bd.last_parts if which == 'fusion' else None
         tokens, lengths, _, _ = self.last_nbest
         # greedy's output_lengths count the steps a row was alive: its tokens and, where it closed, the ETX; greedy's outputs are
         # tokens[1:output_lengths] (sic: a row that never closed loses its last token, ha/transformer.py:197) -- kept, so W = 1 is greedy
@@ -697,11 +720,11 @@ class Decoder(nn.Module):
         return outputs, out_len.to(input_lengths.dtype), [None] * N, bd.last_logprobs[:, 0].clone(), nan
 
     @torch.no_grad()
-    def decode(self, features, input_lengths, target_lengths, prompt=None, beam_size=None):
+    def decode(self, features, input_lengths, target_lengths, prompt=None, beam_size=None, fusion=True):
         """Perform batched greedy decoding (ha/transformer.py:124-199).  ``beam_size`` W >= 1 (default: the attribute ``beam_size``, read
         from HALO_ASR_BEAM when the module is built; 0: greedy): ``BeamDecoder``'s search at width W with the attribute ``length_bonus``
         and the greedy decode's step count; returns each row's best hypothesis (its plain log-probability, NaN for the entropy sum) and
-        keeps the lists as ``last_nbest``."""
+        keeps the lists as ``last_nbest``.  After ``set_fusion_lm`` the search ranks with the LM (``fusion=False``: without it)."""
         _require_inference(self, features)
         width = self.beam_size if beam_size is None else int(beam_size)
         if width < 0:
@@ -709,7 +732,7 @@ class Decoder(nn.Module):
         if width:
             if prompt is not None:
                 raise NotImplementedError('Decoder.decode(beam_size >= 1): prompts are not built')
-            return self._decode_beam(features, input_lengths, int(target_lengths.max().item()) + 1, width)
+            return self._decode_beam(features, input_lengths, int(target_lengths.max().item()) + 1, width, fusion=fusion)
         dev = features.device
         N, S, C = features.shape
         T = int(target_lengths.max().item()) + 1
@@ -763,7 +786,10 @@ class BeamDecoder:
     Joint CTC/attention decoding (the definition: include/halo.h): ``decode(..., ctc_log_probs, ctc_weight=c)`` with c > 0
     ranks every candidate by ``(1 - c) * rank + c * psi``, psi the CTC prefix score of the extended token sequence (for ETX and for a
     finished slot: the full CTC log-probability of the hypothesis).  Three more launches a step (csrc/ctc_prefix_score.hip's scores, the
-    joint selection, the state advance): ``5 * layers + 4``; the general path takes scores and advance from the same launches."""
+    joint selection, the state advance): ``5 * layers + 4``; the general path takes scores and advance from the same launches.
+
+    LM shallow fusion: ``fusion.AttentionFusionDecoder`` runs these cores with an LM side, which puts
+    ``halo_decode_beam_select_lm`` in the place of the selection and the LM's cell launches behind it."""
 
     def __init__(self, decoder, max_batch, capacity, beam=4, length_bonus=0.0):
         self.decoder = decoder
@@ -789,7 +815,7 @@ class BeamDecoder:
             self._y, self._sa, self._sb = (torch.zeros(R * C, **f32) for _ in range(3))
         self._device = dev      # of the buffers: a decoder moved since needs a new BeamDecoder
         self._graphs = GraphCache()
-        self.last_logprobs = self.last_finished = self.last_ctc = None
+        self.last_logprobs = self.last_finished = self.last_ctc = self._last_lm = None
         self._joint = None      # the joint search's buffers, allocated at its first use and again when S grows
         self._joint_S = 0
 
@@ -820,6 +846,11 @@ class BeamDecoder:
         ``capacity`` / ``beam``: search with less room than the buffers hold (default: all of it).
         ``ctc_log_probs`` [N, S, V] float32 (the CTC head's, V the decoder's) with ``ctc_weight`` in (0, 1]: the joint search; scores
         hold the joint rank, ``last_ctc`` [N, W] each hypothesis's psi (-inf: absent).  Without them the attention-only launches run."""
+        return self._search(features, input_lengths, capacity, beam, ctc_log_probs, ctc_weight)
+
+    @torch.no_grad()
+    def _search(self, features, input_lengths, capacity, beam, ctc_log_probs, ctc_weight, side=None):
+        """``decode``; ``side``: the LM side of ``fusion.AttentionFusionDecoder``, whose scores are kept as ``_last_lm``."""
         dec = self.decoder
         _require_inference(dec, features)
         if dec.wte.weight.device != self._device or features.device != self._device:
@@ -849,15 +880,16 @@ class BeamDecoder:
             dev = features.device
             mlen = input_lengths.to(device=dev, dtype=torch.int32).contiguous()
             mem2d = features.reshape(N * S, C).float().contiguous()
-            if not self.fused:
-                outs = self._core_general(mem2d, mlen, N, S, W, cap, x, c)
+            if not (self.fused and (side is None or side.fused)):
+                outs = self._core_general(mem2d, mlen, N, S, W, cap, x, c, side)
             elif os.environ.get('HALO_DECODE_GRAPH', '1') != '0':
-                outs = self._graph(mem2d, mlen, N, S, W, cap, x, c)
+                outs = self._graph(mem2d, mlen, N, S, W, cap, x, c, side)
             else:
-                outs = tuple(t.clone() for t in self._core_fused(mem2d, mlen, N, S, W, cap, x, c))
+                outs = tuple(t.clone() for t in self._core_fused(mem2d, mlen, N, S, W, cap, x, c, side))
             scores, lengths, fin, tokens, ranks = outs[:5]
             self.last_ctc = outs[5] if x is not None else None
             absent = ~(scores > float('-inf'))
+            self._last_lm = torch.where(absent, torch.full_like(scores, float('-inf')), outs[-1]) if side is not None else None
             lengths = torch.where(absent, torch.full_like(lengths, -1), lengths).long()
             past = torch.arange(cap, device=dev)[None, None, :] >= lengths[:, :, None]
             self.last_logprobs = scores
@@ -865,9 +897,10 @@ class BeamDecoder:
             return tokens[:, :, :cap].long().masked_fill(past, -1), lengths, ranks, (~absent).sum(1)
 
     # ---- the fused path: 5 * layers + 2 launches per step --------------------------------------------------------------------------
-    def _core_fused(self, mem2d, mlen, N, S, W, cap, x=None, c=0.0):
+    def _core_fused(self, mem2d, mlen, N, S, W, cap, x=None, c=0.0, side=None):
         """All launches of one search, host-sync free (capturable); returns views of the final beam's records (the joint search, x
-        given: and of the slots' psi)."""
+        given: and of the slots' psi; with the LM ``side``: and of the slots' lm).  The LM side adds its selection in the place of the
+        other two and, behind it, the LM's cell and out_layer launches for the next step: one linear chain on the one stream."""
         dec = self.decoder
         dev, C = mem2d.device, mem2d.shape[1]
         L, heads, head_dim = len(dec.h), dec.h[0].heads, dec.h[0].head_dim
@@ -892,37 +925,54 @@ class BeamDecoder:
             psi_cand, par = jb['cand'][:R * V].view(R, V), jb['par'][:R].view(N, W)
             psi, last = [b[:R].view(N, W) for b in jb['psi']], [b[:R].view(N, W) for b in jb['last']]
             ops.ctc_prefix_advance(x, mlen, ETX, state[0])                   # the empty prefix's state into slot 0 of every utterance
+        if side is not None:
+            side.start(N, W)                                                 # the LM after its start token, in every slot
         for t in range(cap):
             q = t & 1
+            y_next = y if t + 1 < cap else None
             dec._step_fused(images, y, a, att, hid, logits, sa, sb, lambda l: ops.decode_beam_attention(
                 a, mem_cache[l, 0], mem_cache[l, 1], mlen, time_cache[l, 0], time_cache[l, 1], t + 1, rec[q][4], table, att))
             if x is None:
-                ops.decode_beam_select(logits, t, cap, ETX, self.length_bonus, rec[q], rec[1 - q], ranks, wte, y if t + 1 < cap else None)
+                if side is None:
+                    ops.decode_beam_select(logits, t, cap, ETX, self.length_bonus, rec[q], rec[1 - q], ranks, wte, y_next)
+                else:
+                    side.select(logits, t, cap, self.length_bonus, rec[q], rec[1 - q], ranks, wte, y_next)
+                    side.step(t, cap)
                 continue
             s_in, n_in, f_in = rec[q][:3]
             ops.ctc_prefix_scores(x, mlen, state[q], t, ETX, psi_cand, last[q], n_in, s_in, f_in)
-            ops.decode_beam_select_joint(logits, t, cap, ETX, self.length_bonus, c, psi_cand, psi[q], psi[1 - q], rec[q], rec[1 - q], ranks,
-                                         par, last[1 - q], wte, y if t + 1 < cap else None)
+            if side is None:
+                ops.decode_beam_select_joint(logits, t, cap, ETX, self.length_bonus, c, psi_cand, psi[q], psi[1 - q], rec[q], rec[1 - q],
+                                             ranks, par, last[1 - q], wte, y_next)
+            else:
+                side.select(logits, t, cap, self.length_bonus, rec[q], rec[1 - q], ranks, wte, y_next, par, last[1 - q], c, psi_cand, psi[q],
+                            psi[1 - q])
             if t + 1 < cap:                                                  # (the last beam's states are read by nobody)
                 ops.ctc_prefix_advance(x, mlen, ETX, state[1 - q], state[q], par, last[1 - q], rec[1 - q][1], last[q])
+            if side is not None:
+                side.step(t, cap)
         s, n, f, tok, _ = rec[cap & 1]
-        return (s, n, f, tok, ranks) if x is None else (s, n, f, tok, ranks, psi[cap & 1])
+        outs = (s, n, f, tok, ranks) if x is None else (s, n, f, tok, ranks, psi[cap & 1])
+        return outs if side is None else outs + (side.scores(cap),)
 
-    def _graph(self, mem2d, mlen, N, S, W, cap, x=None, c=0.0):
+    def _graph(self, mem2d, mlen, N, S, W, cap, x=None, c=0.0, side=None):
         """One HIP graph per (shape, width, parameter version), the sibling of ``Decoder._decode_graph``; the joint search has graphs of
-        its own, with the log-probabilities copied into a static buffer."""
+        its own, with the log-probabilities copied into a static buffer, and so has the search with an LM side (keyed by the LM's
+        parameter stamp, its weight, start token and end class; its decode images are built before the capture)."""
         key = (N, S, W, cap, self.length_bonus, str(mem2d.device), _lib.get_math_mode())
         if x is not None:
             key += ('joint', c)
+        if side is not None:
+            key += ('lm', side.key())
         entry = self._graphs.entry(self.decoder, key, lambda: (mem2d.clone(), mlen.clone()) + ((x.clone(),) if x is not None else ()),
-                                   lambda static: self._core_fused(*static[:2], N, S, W, cap, *((static[2], c) if x is not None else ())))
+                                   lambda static: self._core_fused(*static[:2], N, S, W, cap, static[2] if x is not None else None, c, side))
         for dst, src in zip(entry['static'], (mem2d, mlen, x)):
             dst.copy_(src)
         entry['graph'].replay()
         return tuple(o.clone() for o in entry['outs'])
 
     # ---- the general path: the same search on Decoder._decode_core's operators over N * W rows ---------------------------------------
-    def _core_general(self, mem2d, mlen, N, S, W, cap, x=None, c=0.0):
+    def _core_general(self, mem2d, mlen, N, S, W, cap, x=None, c=0.0, side=None):
         dec = self.decoder
         dev, C = mem2d.device, mem2d.shape[1]
         L, heads, head_dim = len(dec.h), dec.h[0].heads, dec.h[0].head_dim
@@ -949,6 +999,10 @@ class BeamDecoder:
             psi_cand, psi = torch.empty(R, V, device=dev), torch.full((N, W), ninf, device=dev)
             last = torch.zeros(N, W, dtype=torch.int32, device=dev)
             ops.ctc_prefix_advance(x, mlen, ETX, state[0])
+        if side is not None:   # the LM side: rnn.Decoder.forward at T = 1 over the R rows, the states gathered by index_select
+            lm, lm_w, lm_eos = side.lm, side.weight, side.eos
+            lg, lstate = lm.forward(torch.full((1, R), side.start_token, dtype=torch.long, device=dev), lm.init_hidden(R))
+            lms = torch.zeros(N, W, device=dev)                                               # (finite in absent slots: they rank -inf anyway)
         for t in range(cap):
             y = ops.embed_fwd(cur, dec.wte.weight, None)
             logits = dec._step_general(y, mem_cache, mlen_r, time_cache, t + 1, table)
@@ -964,6 +1018,12 @@ class BeamDecoder:
                 pc = psi_cand.view(N, W, V).clone()
                 pc[:, :, ETX] = torch.where(done, psi, pc[:, :, ETX])                         # a finished slot carries its psi
                 rk = (1.0 - c) * rk + c * pc
+            if side is not None:
+                llp = torch.log_softmax(lg.float(), -1).view(N, W, V)
+                lmc = lms[:, :, None] + llp
+                lmc[:, :, ETX] = lms + llp[:, :, lm_eos] if lm_eos is not None else lms       # closing: the LM's end class, or nothing
+                lmc[:, :, ETX] = torch.where(done, lms, lmc[:, :, ETX])
+                rk = rk + lm_w * lmc
             rk = torch.where(rk.isnan(), torch.full_like(rk, ninf), rk)
             top, idx = rk.view(N, W * V).sort(dim=1, descending=True, stable=True)             # equal ranks: position ascending
             top, idx = top[:, :W], idx[:, :W]
@@ -988,9 +1048,16 @@ class BeamDecoder:
                     ops.ctc_prefix_advance(x, mlen, ETX, state[1 - (t & 1)], state[t & 1], torch.where(taken, par, -1).int(), new_last,
                                            length.int(), last)
                 last = new_last
-        if x is not None:
-            return score, length.int(), fin.int(), tokens.int(), rank, psi
-        return score, length.int(), fin.int(), tokens.int(), rank
+            if side is not None:
+                lms = torch.where(taken, lmc.view(N, W * V).gather(1, idx), torch.zeros_like(top))
+                if t + 1 < cap:                                                               # a slot that took a label: from its parent's state
+                    step = grow.view(-1)
+                    lg, lstate = lg.index_select(0, src), tuple(z.index_select(1, src).contiguous() for z in lstate)
+                    g1, (h1, c1) = lm.forward(torch.where(step, k.view(-1), torch.zeros_like(src)).view(1, R), lstate)
+                    lg = torch.where(step[:, None], g1, lg)
+                    lstate = (torch.where(step[None, :, None], h1, lstate[0]), torch.where(step[None, :, None], c1, lstate[1]))
+        outs = (score, length.int(), fin.int(), tokens.int(), rank) + ((psi,) if x is not None else ())
+        return outs if side is None else outs + (lms,)
 
 
 class CTCAttentionDecoder(nn.Module):
@@ -1020,7 +1087,8 @@ class CTCAttentionDecoder(nn.Module):
         ``joint=True`` (default: the attribute ``joint``, read from HALO_ASR_JOINT=1 when the module is built; off): the one-pass joint
         search instead (``BeamDecoder.decode`` with the head's log-probabilities) -- every candidate extension is ranked
         by (1 - c) * rank + c * its CTC prefix score while the search runs; ``last_nbest`` / ``last_parts`` as above, in the search's
-        order.  It needs a beam and c > 0 (``joint=True`` without them: ValueError)."""
+        order.  It needs a beam and c > 0 (``joint=True`` without them: ValueError).  An LM set by ``decoder.set_fusion_lm`` takes part
+        in the joint search alone (``last_parts`` = (attention, ctc, lm) then); greedy decoding and the re-ranking route do not use it."""
         width = self.decoder.beam_size if beam_size is None else int(beam_size)
         c = float(ctc_weight)
         if joint and (width < 1 or not c > 0.0):
@@ -1033,12 +1101,15 @@ class CTCAttentionDecoder(nn.Module):
                 lp =self.recognizer.log_probs(features).float()                             # [N, S, V]
                 out = self.decoder._decode_beam(features, input_lengths, int(target_lengths.max().item()) + 1, width,
                                                 ctc_log_probs=lp, ctc_weight=c)
-                bd = self.decoder._beams['decoder']
+                bd = self.decoder._beams[self.decoder._beams['used']]
                 self.last_nbest = self.decoder.last_nbest
                 lengths = self.last_nbest[1]
-                self.last_parts = (bd.last_logprobs + float(self.decoder.length_bonus) * lengths.clamp(min=0).float(), bd.last_ctc)
+                if self.decoder.last_parts is not None:                                     # set_fusion_lm: (attention, ctc, lm)
+                    self.last_parts = (self.decoder.last_parts[0], bd.last_ctc, self.decoder.last_parts[1])
+                else:
+                    self.last_parts = (bd.last_logprobs + float(self.decoder.length_bonus) * lengths.clamp(min=0).float(), bd.last_ctc)
             return out
-        out = self.decoder.decode(features, input_lengths, target_lengths, prompt=prompt, beam_size=beam_size)
+        out = self.decoder.decode(features, input_lengths, target_lengths, prompt=prompt, beam_size=beam_size, fusion=False)
         if not width:
             return out
         self.last_nbest = self.decoder.last_nbest

@@ -1030,6 +1030,46 @@ int halo_ctc_prefix_advance(const float *log_probs, long batch_stride, long fram
                             const int *last_tokens_new, const int *lengths_new, const int *last_tokens_prev, halo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LM shallow fusion inside the attention decoder's beam search (fusion.AttentionFusionDecoder): the search of
+ * halo_decode_beam_select / _joint with every candidate also scored by an LSTM language model (rnn.Decoder).  The library's own definition,
+ * per utterance, W slots, `capacity` steps, exactly the search above with these additions:
+ *
+ *   Every slot also carries lm, the LM's log-probability of its tokens, and the LSTM state behind lp = log_softmax(lg + lg_bias) over all
+ *   V classes, after the LM consumed start_token and then the slot's tokens.  Before step 0 slot 0 holds lm = 0 and the state after
+ *   start_token.
+ *   lmc(j, k), the LM score of candidate (j, k): lm_j + lp_j[k] for a label k != ETX; for k == ETX lm_j + lp_j[lm_eos] when lm_eos >= 0
+ *   and lm_j when lm_eos < 0 (closing costs nothing); lm_j for a finished slot's one candidate.
+ *   rank = fmaf(lm_weight, lmc, base), base the rank of the launches above: fmaf(length_bonus, length, score), or the (1 - c) * . + c * psi
+ *   mix when psi_cand is given.  The order, the tie rule (rank descending, position j V + k ascending) and the treatment of -inf / NaN
+ *   are unchanged.  A taken candidate's lmc becomes its slot's lm.
+ *   A slot that took a label steps the LM from its PARENT's state with that label as input; a finished or empty slot's LM state is never
+ *   read again.  lm_weight = 0 gives the tokens, lengths, flags and counts of the launches above, scores and ranks comparing equal.
+ *
+ *   halo_decode_beam_select_lm  the same kernel body as halo_decode_beam_select / _joint (a further instantiation; psi_cand, psi_in and
+ *                            psi_out all NULL: the attention-only rank, ctc_weight ignored).  lg [N * beam][ldlg] the LM's logits of every
+ *                            slot without their bias, lg_bias [V] (may be NULL); lm_in / lm_out [N][beam] (two copies; lm_in is not read
+ *                            at t == 0; -inf in an empty slot); lm_weight finite; lm_eos in -1 .. V-1.  parents_out / last_out as the
+ *                            joint launch writes them.  After the selection the launch gathers the next LM step's cell inputs
+ *                            (halo_rnnt_lstm_cell): for a slot r that took a label k from parent p, lm_xh[0][r][:H] = lm_wte[k],
+ *                            lm_xh[l][r][H:] = h_in[l][p] and c_out[l][r] = c_in[l][p] for every layer l; for every other slot zeros in
+ *                            those places (the x halves of the layers above 0 are the cells' own).  h_in, c_in, c_out
+ *                            [lm_layers][N * beam][lm_hidden], lm_xh [lm_layers][N * beam][2 lm_hidden], lm_wte [V][lm_hidden], 16-byte
+ *                            aligned, lm_hidden % 4 == 0; the state exists twice by step parity (h_in != lm_xh, c_in != c_out), and
+ *                            nothing a workgroup writes is read by another in the launch.  lm_xh == NULL (the last step): no gather.
+ *                            Both tables of an utterance (beam V decoder logits, beam V LM logits) stay in LDS when 2 beam V <=
+ *                            HALO_DECODE_BEAM_LM_LDS_FLOATS and are both recomputed from L2 by the same operations otherwise: the same
+ *                            bits.  fp32 in every arithmetic mode, no float atomics, every sum in one order. */
+#define HALO_DECODE_BEAM_LM_LDS_FLOATS 14336
+int halo_decode_beam_select_lm(const float *logits, long ld, int N, int beam, int V, int t, int capacity, int etx, float length_bonus,
+                               float ctc_weight, const float *psi_cand, long psi_ld, const float *psi_in, float *psi_out, const float *lg,
+                               long ldlg, const float *lg_bias, const float *lm_in, float *lm_out, float lm_weight, int lm_eos,
+                               const float *scores_in, const int *lengths_in, const int *finished_in, const int *tokens_in,
+                               const int *ancestors_in, float *scores_out, float *ranks_out, int *lengths_out, int *finished_out,
+                               int *tokens_out, int *ancestors_out, int *parents_out, int *last_out, long tokens_ld, long ancestors_ld,
+                               const float *wte, int vocab, int C, float *y_next, const float *lm_wte, int lm_hidden, int lm_layers,
+                               const float *h_in, const float *c_in, float *lm_xh, float *c_out, halo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused launches of one batched GPT sampling step (haloop_amd/generation.py; the T == 1 case of ha/attention.py:253-321 under a KV
  * cache): 5 launches per layer (LayerNorm + c_attn | cache store + attention | c_proj, accumulate | LayerNorm + c_fc + tanh-GELU |
  * mlp.c_proj, accumulate) and 2 per token (LayerNorm + lm_head | the draw), over the decode images of halo_decode_image.  Every per-step
