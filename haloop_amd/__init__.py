@@ -10,4 +10,4 @@ or eager fallback.
 from . import _lib  # noqa: F401
 
 __all__ = ['rnn', 'recognizer', 'ctc', 'beam', 'attention', 'score', 'transformer', 'conv', 'symbol_tape', 'functional', 'ops',
-           'train', 'dp', 'infer', 'grad_norm', 'wer', 'fusion']
+           'train', 'dp', 'infer', 'grad_norm', 'wer', 'fusion', 'biasing']

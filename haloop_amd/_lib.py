@@ -226,6 +226,10 @@ SIGNATURES = {
     'halo_ctc_prefix_beam': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'halo_ctc_prefix_beam_state_bytes': (_sz, [_i, _i, _i]),
     'halo_ctc_prefix_beam_advance': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'halo_ctc_prefix_beam_biased': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    'halo_ctc_prefix_beam_biased_state_bytes': (_sz, [_i, _i, _i]),
+    'halo_ctc_prefix_beam_advance_biased': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp,
+                                                 _vp, _vp]),
     'halo_ctc_lm_beam_step': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _f, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp,
                                    _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'halo_rnnt_lm_beam_step': (_i, [_vp, _l, _l, _i, _i, _i, _vp, _l, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _l,

@@ -7,6 +7,7 @@ launch (csrc/viterbi.hip).
 ``ctc_prefix_beam_search`` is CTC prefix beam search with exact merging, n-best lists from CTC emissions in the format of
 ``transducer.BeamDecoder.decode``: the whole batch in one launch (csrc/ctc_prefix_beam.hip).  ``PrefixBeamStream`` is
 the same search over emissions that arrive in chunks, its beam carried in device memory between calls.
+Both take a ``biasing.ContextGraph`` as ``context``: phrase boosts inside the same launch.
 ``haloop_amd.beam`` stays the reference's unmerged ha/beam.py."""
 import torch
 
@@ -72,7 +73,16 @@ def ctc_viterbi(emissions, targets, emission_lengths, target_lengths):
     return (scores, ali, starts[:, :0], ends[:, :0]) if S == 0 else (scores, ali, starts, ends)
 
 
-def ctc_prefix_beam_search(emissions, emission_lengths=None, beam=4, capacity=None):
+def _check_context(context, V, name):
+    """``context`` must be a ``biasing.ContextGraph`` over V classes."""
+    from .biasing import ContextGraph
+    if not isinstance(context, ContextGraph):
+        raise ValueError(f'{name}: context must be a haloop_amd.biasing.ContextGraph')
+    if context.vocab_size != V:
+        raise ValueError(f'{name}: the context was compiled for {context.vocab_size} classes, the search has {V}')
+
+
+def ctc_prefix_beam_search(emissions, emission_lengths=None, beam=4, capacity=None, context=None, return_parts=False):
     """CTC prefix beam search with exact merging ([Hannun14], Graves' prefix search; csrc/ctc_prefix_beam.hip), the whole
     batch in one launch: emissions [T, N, V] log-probabilities with class 0 the blank (a strided view with a unit class stride is read in
     place, so the head's ``log_probs.permute(1, 0, 2)`` costs no copy; they are not normalised here), emission_lengths [N] (None: T;
@@ -89,7 +99,13 @@ def ctc_prefix_beam_search(emissions, emission_lengths=None, beam=4, capacity=No
     merged into it, and the W best by (score descending, candidate position ascending) are kept: the definition and the tie rules are in
     include/halo.h.  The empty hypothesis is an ordinary member of the list; a row of no frames returns it alone, score 0.  Without
     pruning a score is ``-functional.ctc_loss(reduction='none')`` of its hypothesis, with pruning a lower bound.  Frames at or past a
-    row's length are never read.  Not differentiable: the inputs are detached."""
+    row's length are never read.  Not differentiable: the inputs are detached.
+
+    ``context`` (a ``biasing.ContextGraph`` over V classes) biases the search towards its phrases inside the same one
+    launch: a member also carries the state of the phrase automaton and the boost it holds, candidates rank by CTC mass + boost, and
+    ``scores`` is that rank.  ``return_parts=True`` appends (boosts [N, W] float32, 0 where absent; states [N, W] int64, -1 where
+    absent): ``scores - boosts`` is the CTC mass, ``scores - context.held.to(device)[states]`` settles the matches left open.  Without a
+    context the parts are zeros and the root state."""
     if emissions.dim() != 3 or emissions.shape[0] < 1 or emissions.shape[1] < 1 or emissions.shape[2] < 2:
         raise ValueError(f'ctc_prefix_beam_search: emissions must be [T >= 1, N >= 1, V >= 2], got {tuple(emissions.shape)}')
     T, N, _ = emissions.shape
@@ -101,13 +117,22 @@ def ctc_prefix_beam_search(emissions, emission_lengths=None, beam=4, capacity=No
         raise ValueError(f'ctc_prefix_beam_search: capacity {cap} outside 1 .. T = {T}')
     if emission_lengths is not None and tuple(emission_lengths.shape) != (N,):
         raise ValueError(f'ctc_prefix_beam_search: emission_lengths must be [{N}]')
+    if context is not None:
+        _check_context(context, emissions.shape[2], 'ctc_prefix_beam_search')
     if not emissions.is_cuda:
         raise _lib.HaloError('haloop_amd.ctc.ctc_prefix_beam_search runs on the HIP device only (no CPU path)')
     em = emissions.detach().float()
     if em.stride(-1) != 1:
         em = em.contiguous()
     il = None if emission_lengths is None else emission_lengths.detach().to(em.device)
-    return ops.ctc_prefix_beam(em, il, W, cap)
+    if context is not None:
+        out = ops.ctc_prefix_beam_biased(em, il, W, cap, context.to(em.device))
+        return out if return_parts else out[:4]
+    out = ops.ctc_prefix_beam(em, il, W, cap)
+    if return_parts:
+        present = out[1] >= 0
+        return out + (torch.zeros_like(out[2]), present.to(torch.int64) - 1)
+    return out
 
 
 class PrefixBeamStream:
@@ -124,9 +149,12 @@ class PrefixBeamStream:
         lengths [N, W], scores [N, W], counts [N]) in ``ctc_prefix_beam_search``'s format as views of this object's buffers: the next
         call overwrites them.  A row that never began holds no hypothesis (counts 0).
     nbest(): copies of the same four.
+    ``context`` (a ``biasing.ContextGraph`` over ``vocab_size`` classes, kept by this object): the biased search of
+        ``ctc_prefix_beam_search(context=...)``, still one launch per ``advance``; ``scores`` is then CTC mass + boost, and the buffers
+        ``boosts`` [N, W] float32 and ``states`` [N, W] int64 are written with the other four.  parts(): copies of those two.
     Not differentiable: the inputs are detached."""
 
-    def __init__(self, max_rows, vocab_size, beam=4, capacity=256, device='cuda'):
+    def __init__(self, max_rows, vocab_size, beam=4, capacity=256, device='cuda', context=None):
         N, V, W, cap = int(max_rows), int(vocab_size), int(beam), int(capacity)
         if N < 1 or V < 2:
             raise ValueError(f'PrefixBeamStream: max_rows {N} and vocab_size {V} must be at least 1 and 2')
@@ -134,10 +162,12 @@ class PrefixBeamStream:
             raise ValueError(f'PrefixBeamStream: beam {W} outside 1 .. {ops.BEAM_MAX}')
         if cap < 1 or cap > ops.PREFIX_BEAM_MAX_CAPACITY:
             raise ValueError(f'PrefixBeamStream: capacity {cap} outside 1 .. {ops.PREFIX_BEAM_MAX_CAPACITY}')
+        if context is not None:
+            _check_context(context, V, 'PrefixBeamStream')
         dev = torch.device(device)
         if dev.type != 'cuda':
             raise _lib.HaloError('haloop_amd.ctc.PrefixBeamStream runs on the HIP device only (no CPU path)')
-        nbytes = ops.ctc_prefix_beam_state_bytes(V, W, cap)
+        nbytes = (ops.ctc_prefix_beam_state_bytes if context is None else ops.ctc_prefix_beam_biased_state_bytes)(V, W, cap)
         if nbytes == 0:
             raise ValueError(f'PrefixBeamStream: vocab_size {V} is more than the search takes')
         self.max_rows, self.vocab_size, self.beam, self.capacity = N, V, W, cap
@@ -146,6 +176,11 @@ class PrefixBeamStream:
         self.lengths = torch.full((N, W), -1, device=dev, dtype=torch.int64)
         self.scores = torch.full((N, W), float('-inf'), device=dev, dtype=torch.float32)
         self.counts = torch.zeros(N, device=dev, dtype=torch.int64)
+        self.context = context
+        if context is not None:
+            self._tables = context.to(self.state.device)
+            self.boosts = torch.zeros(N, W, device=dev, dtype=torch.float32)
+            self.states = torch.full((N, W), -1, device=dev, dtype=torch.int64)
 
     def advance(self, emissions, n_frames=None, begin=None):
         N, V = self.max_rows, self.vocab_size
@@ -161,11 +196,25 @@ class PrefixBeamStream:
             em = em.contiguous()
         nf = None if n_frames is None else n_frames.detach().clamp(0, em.shape[0]).to(torch.int32).contiguous()
         flags = None if begin is None else (begin.detach() != 0).to(torch.int32).mul_(ops.STREAM_BEGIN)
-        ops.ctc_prefix_beam_advance(em, nf, flags, self.beam, self.capacity, self.state, self.tokens, self.lengths, self.scores, self.counts)
+        self._launch(em, nf, flags)
         return self.tokens, self.lengths, self.scores, self.counts
+
+    def _launch(self, em, nf, flags):
+        """The one launch of a call: em [T, N, V] float32 with a unit class stride, nf and flags int32 [N] on the device or None."""
+        if self.context is None:
+            ops.ctc_prefix_beam_advance(em, nf, flags, self.beam, self.capacity, self.state, self.tokens, self.lengths, self.scores,
+                                        self.counts)
+        else:
+            ops.ctc_prefix_beam_advance_biased(em, nf, flags, self.beam, self.capacity, self.state, self.tokens, self.lengths, self.scores,
+                                               self.counts, self._tables, self.boosts, self.states)
 
     def nbest(self):
         return self.tokens.clone(), self.lengths.clone(), self.scores.clone(), self.counts.clone()
+
+    def parts(self):
+        if self.context is None:
+            raise ValueError('PrefixBeamStream.parts: constructed without a context')
+        return self.boosts.clone(), self.states.clone()
 
 
 def ctc_reduce_mean(losses, target_lengths):

@@ -1526,6 +1526,74 @@ def ctc_prefix_beam_advance(emissions, n_frames, flags, beam, capacity, state, t
           'halo_ctc_prefix_beam_advance')
 
 
+def _context_tables(context, V, name):
+    """(columns [V] int32, next [S, A + 1] int32, gain [S, A + 1] f32) of a phrase automaton on the device (include/halo.h)."""
+    columns, nxt, gain = context
+    for t, dt, what in ((columns, torch.int32, 'columns'), (nxt, torch.int32, 'next'), (gain, torch.float32, 'gain')):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f'{name}: the context\'s {what} must be a contiguous {dt} HIP tensor')
+    if columns.shape != (V,) or nxt.dim() != 2 or nxt.shape[0] < 1 or nxt.shape[1] < 1 or gain.shape != nxt.shape:
+        raise ValueError(f'{name}: the context\'s tables must be columns [{V}] and next, gain [states, columns + 1]')
+    return columns, nxt, gain
+
+
+def ctc_prefix_beam_biased(emissions, emission_lengths, beam, capacity, context):
+    """``ctc_prefix_beam`` with a phrase automaton inside the launch (include/halo.h: halo_ctc_prefix_beam_biased): context = (columns,
+    next, gain) on the device -> (tokens, lengths, scores = CTC mass + boost, counts, boosts [N, beam] f32, states [N, beam] int64)."""
+    if emissions.dtype != torch.float32 or emissions.dim() != 3 or emissions.stride(-1) != 1 or not emissions.is_cuda:
+        raise ValueError('ctc_prefix_beam_biased: emissions must be a float32 HIP tensor of three dimensions with unit class stride')
+    T, N, V = emissions.shape
+    il = None if emission_lengths is None else _i64c(emission_lengths, 'emission_lengths')
+    if il is not None and il.shape != (N,):
+        raise ValueError(f'ctc_prefix_beam_biased: emission_lengths must be [{N}]')
+    columns, nxt, gain = _context_tables(context, V, 'ctc_prefix_beam_biased')
+    dev = emissions.device
+    tokens = torch.empty(N, beam, capacity, device=dev, dtype=torch.int64)
+    lengths = torch.empty(N, beam, device=dev, dtype=torch.int64)
+    scores = torch.empty(N, beam, device=dev, dtype=torch.float32)
+    counts = torch.empty(N, device=dev, dtype=torch.int64)
+    boosts = torch.empty(N, beam, device=dev, dtype=torch.float32)
+    states = torch.empty(N, beam, device=dev, dtype=torch.int64)
+    nbytes = lib().halo_ctc_prefix_beam_workspace_bytes(N, T, V, beam, capacity)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    check(lib().halo_ctc_prefix_beam_biased(ptr(emissions), emissions.stride(0), emissions.stride(1), T, N, V, ptr(il), beam, capacity,
+                                            ptr(ws), ptr(tokens), ptr(lengths), ptr(scores), ptr(counts), ptr(columns), ptr(nxt), ptr(gain),
+                                            nxt.shape[0], nxt.shape[1], ptr(boosts), ptr(states), _stream()), 'halo_ctc_prefix_beam_biased')
+    return tokens, lengths, scores, counts, boosts, states
+
+
+def ctc_prefix_beam_biased_state_bytes(V, beam, capacity):
+    """Bytes of one row of the biased carried search's state; 0 for a shape the search does not take (include/halo.h)."""
+    return int(lib().halo_ctc_prefix_beam_biased_state_bytes(V, beam, capacity))
+
+
+def ctc_prefix_beam_advance_biased(emissions, n_frames, flags, beam, capacity, state, tokens, lengths, scores, counts, context, boosts,
+                                   states):
+    """``ctc_prefix_beam_advance`` with a phrase automaton inside the launch (include/halo.h: halo_ctc_prefix_beam_advance_biased):
+    state [N, ctc_prefix_beam_biased_state_bytes(V, beam, capacity)] uint8, context = (columns, next, gain) on the device, boosts
+    [N, beam] f32 and states [N, beam] int64 written in place with the other four.  Nothing is allocated."""
+    if emissions.dtype != torch.float32 or emissions.dim() != 3 or emissions.stride(-1) != 1 or not emissions.is_cuda:
+        raise ValueError('ctc_prefix_beam_advance_biased: emissions must be a float32 HIP tensor of three dimensions with unit class stride')
+    T, N, V = emissions.shape
+    nbytes = ctc_prefix_beam_biased_state_bytes(V, beam, capacity)
+    if nbytes == 0:
+        raise ValueError(f'ctc_prefix_beam_advance_biased: V {V}, beam {beam}, capacity {capacity} outside what the search takes')
+    columns, nxt, gain = _context_tables(context, V, 'ctc_prefix_beam_advance_biased')
+    for t, dt, name in ((n_frames, torch.int32, 'n_frames'), (flags, torch.int32, 'flags')):
+        if t is not None and (t.dtype != dt or t.shape != (N,) or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError(f'ctc_prefix_beam_advance_biased: {name} must be a contiguous {dt} HIP tensor [{N}]')
+    for t, dt, shape, name in ((state, torch.uint8, (N, nbytes), 'state'), (tokens, torch.int64, (N, beam, capacity), 'tokens'),
+                               (lengths, torch.int64, (N, beam), 'lengths'), (scores, torch.float32, (N, beam), 'scores'),
+                               (counts, torch.int64, (N,), 'counts'), (boosts, torch.float32, (N, beam), 'boosts'),
+                               (states, torch.int64, (N, beam), 'states')):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f'ctc_prefix_beam_advance_biased: {name} must be a contiguous {dt} HIP tensor {list(shape)}')
+    check(lib().halo_ctc_prefix_beam_advance_biased(ptr(emissions), emissions.stride(0), emissions.stride(1), T, N, V, ptr(n_frames),
+                                                    ptr(flags), beam, capacity, ptr(state), ptr(tokens), ptr(lengths), ptr(scores),
+                                                    ptr(counts), ptr(columns), ptr(nxt), ptr(gain), nxt.shape[0], nxt.shape[1], ptr(boosts),
+                                                    ptr(states), _stream()), 'halo_ctc_prefix_beam_advance_biased')
+
+
 # ---- edit distance and the risk of an n-best list (csrc/edit_distance.hip) -----------------------------------------------------------
 EDIT_DISTANCE_MAX_LEN = 1024     # HALO_EDIT_DISTANCE_MAX_LEN (include/halo.h)
 

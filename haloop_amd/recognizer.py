@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, functional as HF, ops, wer
-from .ctc import ctc_prefix_beam_search, ctc_reduce_mean, ctc_viterbi
+from .ctc import _check_context, ctc_prefix_beam_search, ctc_reduce_mean, ctc_viterbi
 from .fusion import CTCFusionDecoder, TransducerFusionDecoder
 from .rnn import Decoder, DropoutStream
 from .star import star_ctc_forward_score
@@ -25,7 +25,10 @@ class TemporalClassifier(nn.Module):
 
     ``set_lm(lm, lm_weight, insertion_bonus)`` fuses an ``rnn.Decoder`` language model into the search of ``decode`` at a width
     W >= 1 (``fusion.CTCFusionDecoder``); ``set_lm(None)`` takes it out again.  The LM is no submodule of the head:
-    ``state_dict()``, ``parameters()``, ``to()`` and ``train()`` do not see it."""
+    ``state_dict()``, ``parameters()``, ``to()`` and ``train()`` do not see it.
+
+    ``set_context(graph)`` biases the search of ``decode`` at a width W >= 1 towards the phrases of a ``biasing.ContextGraph`` inside its
+    one launch; ``set_context(None)`` takes it out again.  Like the LM it is no submodule."""
 
     def __init__(self, feat_dim=1024, vocab_size=256):
         super().__init__()
@@ -37,6 +40,7 @@ class TemporalClassifier(nn.Module):
         self.last_nbest = None
         self.last_parts = None
         self._fusion = None    # None, or a dict (not a module: the LM stays out of this head's parameters and state_dict)
+        self._context = None   # None, or a biasing.ContextGraph
 
     def set_lm(self, lm, lm_weight=0.5, insertion_bonus=0.0):
         """Fuse ``lm`` (an ``rnn.Decoder`` over this head's classes, in eval mode, on the device; the caller moves it) into
@@ -51,6 +55,18 @@ class TemporalClassifier(nn.Module):
             raise ValueError(f'TemporalClassifier.set_lm: the LM has {getattr(lm, "num_classes", None)} classes, the head {V}')
         CTCFusionDecoder(lm, 1, 1, 1, lm_weight, insertion_bonus)      # the argument checks, now and not at the first decode
         self._fusion = {'lm': lm, 'lm_weight': float(lm_weight), 'insertion_bonus': float(insertion_bonus), 'decoder': None}
+
+    def set_context(self, graph):
+        """Bias ``decode(beam_size=W >= 1)`` towards the phrases of ``graph`` (a ``biasing.ContextGraph`` over this head's classes):
+        candidates rank by their CTC mass + the boost of the phrase they are spelling, ``last_nbest`` holds the biased lists and
+        ``last_parts`` their (ctc_scores, boosts).  ``set_context(None)`` restores the unbiased search.  Greedy decoding, ``mwer_forward``
+        and ``align`` do not use the context.  A head with both an LM and a context refuses ``decode(beam_size >= 1)``: biasing inside
+        the fused search is not built."""
+        if graph is None:
+            self._context, self.last_parts = None, None
+            return
+        _check_context(graph, self.classifier.out_features, 'TemporalClassifier.set_context')
+        self._context = graph
 
     def log_probs(self, features):
         if not features.is_cuda:
@@ -81,10 +97,17 @@ class TemporalClassifier(nn.Module):
         if self.training:
             raise NotImplementedError('TemporalClassifier.decode(beam_size >= 1) is an inference path: put the head in eval mode')
         N = features.shape[0]
-        fusion = getattr(self, '_fusion', None)
+        fusion, context = getattr(self, '_fusion', None), getattr(self, '_context', None)
+        if fusion is not None and context is not None:
+            raise NotImplementedError('TemporalClassifier.decode: contextual biasing inside the LM-fused search (fusion.CTCFusionDecoder) '
+                                      'is not built: take out the LM (set_lm(None)) or the context (set_context(None))')
         with torch.no_grad():
             logits = self.log_probs(features)
-            if fusion is None:
+            if context is not None:
+                *nbest, boosts, _ = ctc_prefix_beam_search(logits.permute(1, 0, 2), input_lengths, width, context=context, return_parts=True)
+                self.last_nbest = tuple(nbest)
+                self.last_parts = (torch.where(nbest[1] >= 0, nbest[2] - boosts, nbest[2]), boosts)     # (-inf stays -inf where absent)
+            elif fusion is None:
                 self.last_nbest = ctc_prefix_beam_search(logits.permute(1, 0, 2), input_lengths, width)
             else:
                 if width > ops.BEAM_MAX:

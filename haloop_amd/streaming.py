@@ -27,7 +27,8 @@ replays the push chain from one HIP graph.
 
 ``beam=W`` (or ``HALO_STREAM_BEAM=W``, 1 .. 16) adds n-best partials: one more launch behind the head,
 ``halo_ctc_prefix_beam_advance`` on the call's log-probs, carries a width-W CTC prefix beam per slot, so ``nbest()`` after every call
-is ``ctc.ctc_prefix_beam_search`` of the slot's log-probs so far.  The greedy path and ``last`` are unchanged by it.
+is ``ctc.ctc_prefix_beam_search`` of the slot's log-probs so far.  The greedy path and ``last`` are unchanged by it.  ``context=graph``
+(a ``biasing.ContextGraph``) makes that launch ``halo_ctc_prefix_beam_advance_biased``: phrase boosts inside the search.
 
 ``StreamingTransducer`` is the same object over a ``recognizer.Transducer``: the head launch is
 ``halo_stream_logits`` (the classifier product and the state commit, no softmax) and ``transducer.GreedyStream`` carries the head's
@@ -214,9 +215,12 @@ class StreamingRecognizer(_ChunkedStreams):
 
     Neither call reads from the device or waits for it (the flags travel through a ring of pinned host slots; a slot is waited for
     only if the device is a whole ring of calls behind).  ``use_graph``: None reads HALO_STREAM_GRAPH (default off).
-    ``beam``: None reads HALO_STREAM_BEAM (0 .. 16, default 0: the greedy object, launch for launch)."""
+    ``beam``: None reads HALO_STREAM_BEAM (0 .. 16, default 0: the greedy object, launch for launch).
+    ``context`` (a ``biasing.ContextGraph`` over the recognizer's classes; needs a beam, else ValueError): the beam's
+    launch is the biased one, eager and under graph replay; ``nbest()`` / ``partial()`` then score by CTC mass + boost, and
+    nbest_parts() returns copies of (boosts [B, W] fp32, states [B, W] int64).  The greedy path and ``last`` are unchanged by it."""
 
-    def __init__(self, encoder, recognizer, max_streams, chunk_frames=16, capacity=256, use_graph=None, beam=None):
+    def __init__(self, encoder, recognizer, max_streams, chunk_frames=16, capacity=256, use_graph=None, beam=None, context=None):
         if encoder.training or recognizer.training:
             raise ValueError('StreamingRecognizer: put the encoder and the recognizer in eval mode')
         conv = encoder.subsample
@@ -261,7 +265,9 @@ class StreamingRecognizer(_ChunkedStreams):
             self._bufs[s] = dict(
                 y=torch.zeros(s, B, C, **f32), feats=torch.zeros(B, s, H, **f32), ali=torch.zeros(B, s, device=dev, dtype=torch.int64),
                 scores=torch.zeros(B, s, **f32), lp=torch.zeros(B, s, V, **f32), reserve=ops.lstm_reserve(s, B, C, H, L, dev))
-        self._beam = PrefixBeamStream(B, V, self.beam, self.capacity, device=dev) if self.beam else None
+        if context is not None and not self.beam:
+            raise ValueError('StreamingRecognizer: a context biases the beam search: give a beam of 1 .. 16 with it')
+        self._beam = PrefixBeamStream(B, V, self.beam, self.capacity, device=dev, context=context) if self.beam else None
         self._graphs = {}
         self._last = None
 
@@ -294,6 +300,11 @@ class StreamingRecognizer(_ChunkedStreams):
         if self._beam is None:
             raise ValueError('StreamingRecognizer.nbest: constructed without a beam (beam=0)')
         return self._beam.nbest()
+
+    def nbest_parts(self):
+        if self._beam is None or self._beam.context is None:
+            raise ValueError('StreamingRecognizer.nbest_parts: constructed without a context')
+        return self._beam.parts()
 
     @property
     def last(self):
@@ -340,8 +351,7 @@ class StreamingRecognizer(_ChunkedStreams):
         """The beam's launch on the call's log-probs [B, S, V], read in place as [S, B, V]: slot b takes its n_steps[b] steps."""
         bm = self._beam
         if bm is not None:
-            ops.ctc_prefix_beam_advance(lp.permute(1, 0, 2), self._n_steps, flags, bm.beam, bm.capacity, bm.state, bm.tokens, bm.lengths,
-                                        bm.scores, bm.counts)
+            bm._launch(lp.permute(1, 0, 2), self._n_steps, flags)
 
     def _chain_general(self, frames, S, final, buf):
         """The same call on the general operators; the merging of the collapse and the choice of the state by torch operators."""

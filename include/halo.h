@@ -1389,6 +1389,49 @@ int halo_ctc_prefix_beam_advance(const float *emissions, long stride_t, long str
                                  const int *flags, int beam, int capacity, void *state, int64_t *tokens, int64_t *lengths, float *scores,
                                  int64_t *counts, halo_stream_t stream);
 
+/* Contextual biasing ("hotwords") inside both searches (haloop_amd/biasing.py ContextGraph, csrc/ctc_prefix_beam.hip with BIASED set;
+ * DESIGN.md 3.3ac): a phrase list compiled on the host into an automaton over token ids; a hypothesis that is spelling a phrase holds a
+ * bonus per matched token, gives it back when the match breaks and keeps it when the phrase completes.  Still one launch, no host read.
+ *   The automaton.  Phrases are non-empty token sequences over 1 .. V-1, duplicates dropped.  Their trie has the root as state 0, d(s)
+ *   the depth of s and final(s) where a phrase ends.  fail(s) is the Aho-Corasick failure link: the state of the longest proper suffix
+ *   of s's path that is a trie path.  goto(s, k) is the trie child of s by k if there is one, else the child by k of the first state on
+ *   s's failure chain that has one, else the root.  Dictionary (output) links are not followed: a phrase is credited only along the
+ *   active path, so a phrase that ends inside a longer match earns nothing by itself.
+ *       fa(s)   = the depth of the deepest final proper ancestor of s in the trie, 0 if there is none
+ *       held(s) = 0 if final(s), else bonus * (d(s) - fa(s))            what a hypothesis in s loses if its match breaks
+ *       gain(s, k) = bonus * (d(s') - fa(s')) - held(s),  s' = goto(s, k)
+ *   bonus is one finite number and may be negative.  A hypothesis y_1 .. y_n has state c_0 = 0, c_i = goto(c_{i-1}, y_i) and boost
+ *   z_0 = 0, z_i = z_{i-1} + gain(c_{i-1}, y_i), one fp32 addition per token, left to right.
+ *   Device form.  ctx_columns [V] int32: 0 for a token in no phrase, else its column 1 .. A.  ctx_next [ctx_states][ctx_width] int32 and
+ *   ctx_gain [ctx_states][ctx_width] fp32 with ctx_width = A + 1: entry (s, columns[k]) is goto(s, k) and gain(s, k), gains computed in
+ *   float64 and rounded once; column 0 is "any other token": next 0, gain -held(s).  No phrases: one state, one column.  Limits:
+ *   1 <= ctx_states <= HALO_CONTEXT_MAX_STATES, ctx_width >= 1, ctx_states * ctx_width < 2^31.  The tables are read, never written; every
+ *   column, state and next entry read from memory is clamped into its table before it indexes one.
+ *   The search is halo_ctc_prefix_beam's with these changes.  A member carries (c, z) besides pb / pnb; the empty prefix has c = 0,
+ *   z = 0.  A stay candidate keeps its member's (c, z) and ranks by logaddexp(pb', pnb') + z.  The extension of j by k has
+ *   col = columns[k], c' = next[c_j][col], z' = z_j + gain[c_j][col], pnb' = its CTC mass as above, and ranks by pnb' + z'.  The merge
+ *   is unchanged and on CTC mass alone: members that spell the same prefix took the same gains in the same order, so the stay
+ *   candidate's (c, z) are the merged extension's.  The W best are taken by (rank descending, candidate position ascending); a candidate
+ *   whose CTC mass is -inf is never taken, whatever its boost.  pb / pnb stay CTC masses throughout.
+ *   halo_ctc_prefix_beam_biased   halo_ctc_prefix_beam's arguments, workspace rule and outputs, with scores [N][beam] = the rank, CTC
+ *                          mass + boost, and boosts [N][beam] fp32 (the boost in that score, 0 where absent: scores - boosts is the CTC
+ *                          mass) and states [N][beam] int64 (the automaton state, -1 where absent).  A caller that wants broken
+ *                          matches settled at the end of an utterance subtracts held(state) itself.
+ *   halo_ctc_prefix_beam_advance_biased  halo_ctc_prefix_beam_advance with the same extra arguments; state
+ *                          [N][halo_ctc_prefix_beam_biased_state_bytes(V, beam, capacity)]: halo_ctc_prefix_beam_state_bytes + 128, every
+ *                          member's c and z behind the records (zeros are an empty beam here too).  A row with no frames and no begin
+ *                          keeps its rows of boosts and states as well.  A stream keeps one automaton from its begin on. */
+#define HALO_CONTEXT_MAX_STATES 65535
+int halo_ctc_prefix_beam_biased(const float *emissions, long stride_t, long stride_n, int T, int N, int V, const int64_t *emission_lengths,
+                                int beam, int capacity, void *workspace, int64_t *tokens, int64_t *lengths, float *scores, int64_t *counts,
+                                const int *ctx_columns, const int *ctx_next, const float *ctx_gain, int ctx_states, int ctx_width,
+                                float *boosts, int64_t *states, halo_stream_t stream);
+size_t halo_ctc_prefix_beam_biased_state_bytes(int V, int beam, int capacity);
+int halo_ctc_prefix_beam_advance_biased(const float *emissions, long stride_t, long stride_n, int T, int N, int V, const int *n_frames,
+                                        const int *flags, int beam, int capacity, void *state, int64_t *tokens, int64_t *lengths,
+                                        float *scores, int64_t *counts, const int *ctx_columns, const int *ctx_next, const float *ctx_gain,
+                                        int ctx_states, int ctx_width, float *boosts, int64_t *states, halo_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * CTC prefix beam search with shallow fusion of an LSTM language model (haloop_amd/fusion.py CTCFusionDecoder; csrc/ctc_lm_beam.hip,
  * DESIGN.md 3.3q) as a launch sequence: per frame one halo_ctc_lm_beam_step, one halo_rnnt_lstm_cell per LSTM layer and one
