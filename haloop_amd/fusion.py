@@ -25,21 +25,10 @@ import math
 
 import torch
 
-from . import _lib, functional as HF, ops
-from .transducer import BEAM_MAX, SYNC_EVERY, BeamDecoder, _HeadDecoder
+from . import _lib, _slots, functional as HF, ops
+from .transducer import BEAM_MAX, SYNC_EVERY, _ranked_finals
 
 NEG = float('-inf')
-
-
-class _LMHead:
-    """What ``_HeadDecoder`` reads of a head (its prediction network and its mode), for a bare language model."""
-
-    def __init__(self, lm):
-        self.lm = lm
-
-    @property
-    def training(self):
-        return self.lm.training
 
 
 def _lae(a, b):
@@ -47,43 +36,41 @@ def _lae(a, b):
     return m if m == NEG else m + math.log1p(math.exp(-abs(a - b)))
 
 
-class CTCFusionDecoder(_HeadDecoder):
+class CTCFusionDecoder:
     """CTC prefix beam search with LM shallow fusion, with preallocated buffers for ``max_batch`` rows, ``beam`` members per row and
     ``capacity`` symbols per hypothesis.  ``lm``: an ``rnn.Decoder`` over the emissions' V classes, in eval mode, on the device of the
     emissions.  It shares the decode images and the ``fused`` rule of the transducer decoders (bf16x3 / bf16 modes, E == H, H % 512 == 0,
     HALO_RNNT_FUSED != 0); everything else takes the general path."""
 
-    _cells = BeamDecoder._cells
-
     def __init__(self, lm, max_batch, capacity, beam=4, lm_weight=0.5, insertion_bonus=0.0, start_token=0):
-        self.head = _LMHead(lm)
+        self.lm, self._net = lm, _slots.Network(lm)
         self.max_batch, self.capacity, self.beam = int(max_batch), int(capacity), int(beam)
-        self.lm_weight, self.insertion_bonus, self.start_token = float(lm_weight), float(insertion_bonus), int(start_token)
-        if self.max_batch < 1 or self.capacity < 1:
-            raise ValueError('CTCFusionDecoder: need max_batch >= 1 and capacity >= 1')
-        if self.beam < 1 or self.beam > BEAM_MAX:
-            raise ValueError(f'CTCFusionDecoder: beam {self.beam} outside 1 .. {BEAM_MAX}')
-        if not (math.isfinite(self.lm_weight) and math.isfinite(self.insertion_bonus)):
-            raise ValueError('CTCFusionDecoder: lm_weight and insertion_bonus must be finite')
-        E, H, L, V = lm.embedding.weight.shape[1], lm.hidden_dim, lm.num_layers, lm.num_classes
-        if self.start_token < 0 or self.start_token >= V:
-            raise ValueError(f'CTCFusionDecoder: start_token {self.start_token} outside 0 .. {V - 1}')
+        _slots.check_sizes('CTCFusionDecoder', self, BEAM_MAX)
+        self.lm_weight, self.start_token, _, self.insertion_bonus = _fusion_settings('CTCFusionDecoder', lm, lm.num_classes, lm_weight,
+                                                                                     start_token, None, insertion_bonus)
         dev = lm.embedding.weight.device
         S, cap = self.max_batch * self.beam, self.capacity
         i32 = dict(device=dev, dtype=torch.int32)
         f32 = dict(device=dev, dtype=torch.float32)
+        self._lstm = _slots.SlotState(self._net, S)               # the LM's state in every slot
         with torch.inference_mode(False):          # ordinary tensors: they are updated in place inside and outside inference mode
-            if E == H and dev.type == 'cuda':
-                # flat buffers, viewed per call at that call's N * W slots.  The beam's records and the state exist twice (frame parity).
+            if self._lstm.allocated:
+                # flat buffers, viewed per call at that call's N * W slots.  The beam's records exist twice (frame parity), like the state.
                 self._rec = [(torch.zeros(S * 4, **f32), torch.zeros(S * 4, **i32), torch.zeros(S * cap, **i32)) for _ in range(2)]
                 self._parent, self._last = torch.zeros(S, **i32), torch.zeros(S, **i32)
-                self._h, self._c = torch.zeros(2 * L * S * H, **f32), torch.zeros(2 * L * S * H, **f32)
-                self._g = torch.zeros(2 * S * V, **f32)
-                self._xh, self._top = torch.zeros(L * S * 2 * H, **f32), torch.zeros(S * H, **f32)
         self._device = dev      # of the buffers: an LM moved since needs a new decoder
-        self._images = None
         self.iterations = 0     # frames of the last decode
         self.last_parts = None  # (ctc_scores [N, W], lm_scores [N, W]) of the last decode
+
+    @property
+    def head(self):
+        """A compatibility alias for callers of the former ``head`` attribute, which read the LM as ``head.lm``: the decoder itself."""
+        return self
+
+    @property
+    def fused(self):
+        """Whether the fused launches are in use (decided from the LM, the math mode and HALO_RNNT_FUSED as they are now)."""
+        return not self.lm.training and self._net.fused
 
     def decode(self, emissions, emission_lengths=None, capacity=None, beam=None, lm_weight=None, insertion_bonus=None):
         """emissions [T, N, V] log-probabilities, class 0 the blank (a strided view with a unit class stride is read in place),
@@ -91,7 +78,7 @@ class CTCFusionDecoder(_HeadDecoder):
         hypotheses; lengths [N, W] int64, -1: absent; scores [N, W] float32 = ctc + lm_weight * lm + insertion_bonus * length, best first,
         -inf: absent; counts [N] int64), and ``last_parts`` = (ctc_scores, lm_scores), both [N, W] float32.  ``capacity`` / ``beam``:
         search with less room than the buffers hold; ``lm_weight`` / ``insertion_bonus``: this call's instead of the decoder's."""
-        lm = self.head.lm
+        lm = self.lm
         if emissions.dim() != 3 or emissions.shape[0] < 1 or emissions.shape[1] < 1:
             raise ValueError(f'CTCFusionDecoder: emissions must be [T >= 1, N >= 1, V], got {tuple(emissions.shape)}')
         T, N, V = emissions.shape
@@ -99,16 +86,9 @@ class CTCFusionDecoder(_HeadDecoder):
             raise ValueError(f'CTCFusionDecoder: the LM has {lm.num_classes} classes, the emissions {V}')
         if N > self.max_batch:
             raise ValueError(f'CTCFusionDecoder: batch {N} outside 1 .. max_batch = {self.max_batch}')
-        cap = self.capacity if capacity is None else int(capacity)
-        if cap < 1 or cap > self.capacity:
-            raise ValueError(f'CTCFusionDecoder: capacity {cap} outside 1 .. {self.capacity}')
-        W = self.beam if beam is None else int(beam)
-        if W < 1 or W > self.beam:
-            raise ValueError(f'CTCFusionDecoder: beam {W} outside 1 .. {self.beam}')
-        a = self.lm_weight if lm_weight is None else float(lm_weight)
-        b = self.insertion_bonus if insertion_bonus is None else float(insertion_bonus)
-        if not (math.isfinite(a) and math.isfinite(b)):
-            raise ValueError('CTCFusionDecoder: lm_weight and insertion_bonus must be finite')
+        cap, W = _slots.room('CTCFusionDecoder', self, capacity, beam)
+        a, _, _, b = _fusion_settings('CTCFusionDecoder', lm, V, self.lm_weight if lm_weight is None else lm_weight, self.start_token, None,
+                                      self.insertion_bonus if insertion_bonus is None else insertion_bonus)
         if emission_lengths is not None and tuple(emission_lengths.shape) != (N,):
             raise ValueError(f'CTCFusionDecoder: emission_lengths must be [{N}]')
         if lm.training:
@@ -131,38 +111,30 @@ class CTCFusionDecoder(_HeadDecoder):
             minus = torch.full_like(rec[:, :, 0], NEG)
             ctc_scores = torch.where(absent, minus, torch.logaddexp(rec[:, :, 0], rec[:, :, 1]))
             self.last_parts = (ctc_scores, torch.where(absent, minus, rec[:, :, 2]))
-            past = torch.arange(cap, device=tokens.device)[None, None, :] >= lengths[:, :, None]
-            return tokens.long().masked_fill(past, -1), lengths, torch.where(absent, minus, rec[:, :, 3]), (~absent).sum(1)
+            return _slots.mask_tokens(tokens, lengths), lengths, torch.where(absent, minus, rec[:, :, 3]), (~absent).sum(1)
 
     # ---- the fused path: num_layers + 3 launches per frame ---------------------------------------------------------------------------
     def _decode_fused(self, e, il, N, W, cap, a, b):
-        lm = self.head.lm
-        layers, head_image = self._decode_images()
-        wte, H, L, V = lm.embedding.weight, lm.hidden_dim, lm.num_layers, lm.num_classes
+        st = self._lstm.view(N, W)
         R, ld = N * W, self.capacity
         frames = max(1, int(il.max().item()))                  # the one host read, before the first launch
         rec = [(f[:R * 4].view(N, W, 4), m[:R * 4].view(N, W, 4), t[:R * ld].view(N, W, ld)) for f, m, t in self._rec]
         parent, last = self._parent[:R].view(N, W), self._last[:R].view(N, W)
-        h, c = self._h[:2 * L * R * H].view(2, L, R, H), self._c[:2 * L * R * H].view(2, L, R, H)
-        g = self._g[:2 * R * V].view(2, R, V)
-        xh, top = self._xh[:L * R * 2 * H].view(L, R, 2 * H), self._top[:R * H].view(R, H)
-        xh.zero_(); c[0].zero_()
-        xh[0, :, :H] = wte[self.start_token]                   # the LM after the start token, in every slot
-        self._cells(xh, c[0], h[0], top, g[0], layers, head_image)
+        st.start(self.start_token)                             # the LM after the start token, in every slot
         for t in range(frames):
             q = t & 1
-            ops.ctc_lm_beam_step(e, il, t, cap, a, b, g[q], lm.out_layer.bias, rec[q], rec[1 - q], parent, last, wte, h[q], c[q], xh, c[1 - q])
+            ops.ctc_lm_beam_step(e, il, t, cap, a, b, st.g[q], st.bias, rec[q], rec[1 - q], parent, last, *st.gather(q))
             if t == frames - 1:
                 break                                          # the last frame's members need no LM step: lm is in their records
-            self._cells(xh, c[1 - q], h[1 - q], top, g[1 - q], layers, head_image)
-            ops.rnnt_beam_keep(parent, last, h[q], c[q], g[q], h[1 - q], c[1 - q], g[1 - q])
+            st.cells(1 - q)
+            st.keep(parent, last, q)
         self.iterations = frames
         out = rec[frames & 1]
         return out[0].clone(), out[1][:, :, 0].clone(), out[2][:, :, :cap].clone()
 
     # ---- the general path: the same search on rnn.Decoder.forward at T = 1 over N * W rows, pruned on the host ---------------------------
     def _decode_general(self, e, il, N, W, cap, a, b):
-        lm = self.head.lm
+        lm = self.lm
         dev, V = e.device, e.shape[2]
         R = N * W
         Ls = il.tolist()
@@ -218,11 +190,7 @@ class CTCFusionDecoder(_HeadDecoder):
             if t == frames - 1:
                 break
             src, tok = src.to(dev), tok.to(dev)
-            g, state = g[src], (state[0][:, src].contiguous(), state[1][:, src].contiguous())
-            g1, (h1, c1) = lm.forward(tok.view(1, R), state)
-            emit = tok != 0
-            g = torch.where(emit[:, None], g1, g)
-            state = (torch.where(emit[None, :, None], h1, state[0]), torch.where(emit[None, :, None], c1, state[1]))
+            g, state = _slots.step_general(lm, g, state, src, tok, tok != 0)
         rec = torch.full((N, W, 4), NEG, dtype=torch.float32)
         lengths = torch.full((N, W), -1, dtype=torch.int32)
         tokens = torch.zeros(N, W, cap, dtype=torch.int32)
@@ -232,14 +200,6 @@ class CTCFusionDecoder(_HeadDecoder):
                 lengths[n, w] = len(m['y'])
                 tokens[n, w, :len(m['y'])] = torch.tensor(m['y'], dtype=torch.int32)
         return rec.to(dev), lengths.to(dev), tokens.to(dev)
-
-
-class _Images(_HeadDecoder):
-    """The decode images and the ``fused`` rule of one network (``head.lm``), as every ``_HeadDecoder`` keeps them."""
-
-    def __init__(self, head):
-        self.head = head
-        self._images = None
 
 
 class TransducerFusionDecoder:
@@ -260,37 +220,22 @@ class TransducerFusionDecoder:
     def __init__(self, head, lm, max_batch, capacity, beam=4, lm_weight=0.5, insertion_bonus=0.0, start_token=0):
         self.head, self.lm = head, lm
         self.max_batch, self.capacity, self.beam = int(max_batch), int(capacity), int(beam)
-        self.lm_weight, self.insertion_bonus, self.start_token = float(lm_weight), float(insertion_bonus), int(start_token)
-        if self.max_batch < 1 or self.capacity < 1:
-            raise ValueError('TransducerFusionDecoder: need max_batch >= 1 and capacity >= 1')
-        if self.beam < 1 or self.beam > BEAM_MAX:
-            raise ValueError(f'TransducerFusionDecoder: beam {self.beam} outside 1 .. {BEAM_MAX}')
-        if not (math.isfinite(self.lm_weight) and math.isfinite(self.insertion_bonus)):
-            raise ValueError('TransducerFusionDecoder: lm_weight and insertion_bonus must be finite')
-        V = head.lm.num_classes
-        if getattr(lm, 'num_classes', None) != V:
-            raise ValueError(f'TransducerFusionDecoder: the LM has {getattr(lm, "num_classes", None)} classes, the head {V}')
-        if self.start_token < 0 or self.start_token >= V:
-            raise ValueError(f'TransducerFusionDecoder: start_token {self.start_token} outside 0 .. {V - 1}')
+        _slots.check_sizes('TransducerFusionDecoder', self, BEAM_MAX)
+        self.lm_weight, self.start_token, _, self.insertion_bonus = _fusion_settings('TransducerFusionDecoder', lm, head.lm.num_classes,
+                                                                                     lm_weight, start_token, None, insertion_bonus)
         dev = head.lm.embedding.weight.device
         S, cap = self.max_batch * self.beam, self.capacity
         i32 = dict(device=dev, dtype=torch.int32)
         f32 = dict(device=dev, dtype=torch.float32)
-        self._sides = (_Images(head), _Images(_LMHead(lm)))           # the prediction network, the fusion LM
+        # the states of the prediction network and of the fusion LM in every slot
+        self._lstms = tuple(_slots.SlotState(_slots.Network(net), S) for net in (head.lm, lm))
         with torch.inference_mode(False):          # ordinary tensors: they are updated in place inside and outside inference mode
-            if dev.type == 'cuda' and lm.embedding.weight.device == dev and all(
-                    s.head.lm.embedding.weight.shape[1] == s.head.lm.hidden_dim for s in self._sides):
-                # flat buffers, viewed per call at that call's N * W slots.  The beam's records and both states exist twice (step parity).
+            if lm.embedding.weight.device == dev and all(st.allocated for st in self._lstms):
+                # flat buffers, viewed per call at that call's N * W slots.  The beam's records exist twice (step parity), like the states.
                 self._rec = [(torch.zeros(S * 3, **f32), torch.zeros(S, **i32), torch.zeros(S * cap, **i32)) for _ in range(2)]
                 self._parent, self._last = torch.zeros(S, **i32), torch.zeros(S, **i32)
                 self._fin = (torch.zeros(S * 3, **f32), torch.zeros(S, **i32), torch.zeros(S, **i32), torch.zeros(S * cap, **i32),
                              torch.zeros(self.max_batch, **i32))
-                self._state = []
-                for side in self._sides:
-                    H, L = side.head.lm.hidden_dim, side.head.lm.num_layers
-                    self._state.append(dict(h=torch.zeros(2 * L * S * H, **f32), c=torch.zeros(2 * L * S * H, **f32),
-                                            g=torch.zeros(2 * S * V, **f32), xh=torch.zeros(L * S * 2 * H, **f32),
-                                            top=torch.zeros(S * H, **f32)))
                 self._live = torch.zeros(64, **i32)                    # one word per alignment step; grown to T + capacity
         self._device = dev      # of the buffers: a head moved since needs a new decoder
         self.iterations = 0     # alignment steps of the last decode
@@ -299,7 +244,7 @@ class TransducerFusionDecoder:
     @property
     def fused(self):
         """Whether the fused launches are in use: both networks satisfy the rule of the transducer decoders, as they are now."""
-        return not self.head.training and all(side.fused for side in self._sides)
+        return not (self.head.training or self.lm.training) and all(st.network.fused for st in self._lstms)
 
     def decode(self, features, input_lengths, capacity=None, beam=None, lm_weight=None, insertion_bonus=None):
         """features [N, T, feat_dim], input_lengths [N] (clipped to T) -> (tokens [N, W, capacity] int64, -1 past a hypothesis's length
@@ -315,18 +260,9 @@ class TransducerFusionDecoder:
             raise ValueError(f'{name}: batch {N} outside 1 .. max_batch = {self.max_batch}')
         if tuple(input_lengths.shape) != (N,):
             raise ValueError(f'{name}: input_lengths must be [{N}]')
-        cap = self.capacity if capacity is None else int(capacity)
-        if cap < 1 or cap > self.capacity:
-            raise ValueError(f'{name}: capacity {cap} outside 1 .. {self.capacity}')
-        W = self.beam if beam is None else int(beam)
-        if W < 1 or W > self.beam:
-            raise ValueError(f'{name}: beam {W} outside 1 .. {self.beam}')
-        a = self.lm_weight if lm_weight is None else float(lm_weight)
-        b = self.insertion_bonus if insertion_bonus is None else float(insertion_bonus)
-        if not (math.isfinite(a) and math.isfinite(b)):
-            raise ValueError(f'{name}: lm_weight and insertion_bonus must be finite')
-        if lm.num_classes != self.head.lm.num_classes:
-            raise ValueError(f'{name}: the LM has {lm.num_classes} classes, the head {self.head.lm.num_classes}')
+        cap, W = _slots.room(name, self, capacity, beam)
+        a, _, _, b = _fusion_settings(name, lm, self.head.lm.num_classes, self.lm_weight if lm_weight is None else lm_weight,
+                                      self.start_token, None, self.insertion_bonus if insertion_bonus is None else insertion_bonus)
         if self.head.training or lm.training:
             raise NotImplementedError(f'{name} is an inference path: put the head and the LM in eval mode')
         if not features.is_cuda or not lm.embedding.weight.is_cuda or not self.head.lm.embedding.weight.is_cuda:
@@ -337,26 +273,16 @@ class TransducerFusionDecoder:
             cl = self.head.classifier
             f = HF.linear(features.float(), cl.weight, cl.bias).contiguous()                   # [N, T, V]
             il = input_lengths.to(device=features.device, dtype=torch.int32).clamp(0, T).contiguous()
-            rec, seq, lengths, tokens = (self._decode_fused if self.fused else self._decode_general)(f, il, N, W, cap, a, b)
-            # the finals by (rank descending, order of completion): two stable sorts, absent hypotheses (length -1) last
-            rank = rec[:, :, 0]
-            absent = lengths < 0
-            o1 = torch.where(absent, torch.full_like(seq, 2 ** 31 - 1), seq).argsort(dim=1, stable=True)
-            key = torch.where(absent, torch.full_like(rank, float('inf')), -rank).gather(1, o1)
-            order = o1.gather(1, key.argsort(dim=1, stable=True))
-            lengths = lengths.gather(1, order).long()
-            minus = torch.full_like(rank, NEG)
-            rank, rnnt, lms = (torch.where(lengths < 0, minus, rec[:, :, x].gather(1, order)) for x in range(3))
+            # the finals by (rank descending, order of completion), their records rank | s | lm along
+            finals = (self._decode_fused if self.fused else self._decode_general)(f, il, N, W, cap, a, b)
+            tokens, lengths, rec, counts = _ranked_finals(*finals, cap)
+            rank, rnnt, lms = (x.contiguous() for x in rec.unbind(2))
             self.last_parts = (rnnt, lms)
-            tokens = tokens[:, :, :cap].gather(1, order[:, :, None].expand(N, W, cap)).long()
-            past = torch.arange(cap, device=tokens.device)[None, None, :] >= lengths[:, :, None]
-            return tokens.masked_fill(past, -1), lengths, rank, (lengths >= 0).sum(1)
+            return tokens, lengths, rank, counts
 
     # ---- the fused path: Lp + Ll + 5 launches per alignment step ----------------------------------------------------------------------
     def _decode_fused(self, f, il, N, W, cap, a, b):
-        nets = [side.head.lm for side in self._sides]
-        images = [side._decode_images() for side in self._sides]
-        V = nets[0].num_classes
+        pn, lm = (st.view(N, W) for st in self._lstms)
         R, ld = N * W, self.capacity
         frames = int(il.max().item())                          # the one host read before the first launch
         steps = frames + cap if frames else 1                  # a hypothesis at step i has t + u = i, t < L, u <= cap
@@ -368,26 +294,17 @@ class TransducerFusionDecoder:
         parent, last = self._parent[:R].view(N, W), self._last[:R].view(N, W)
         fr, fq, fl, ft, fn = self._fin
         fin = (fr[:R * 3].view(N, W, 3), fq[:R].view(N, W), fl[:R].view(N, W), ft[:R * ld].view(N, W, ld), fn[:N])
-        h, c, g, xh, top = [], [], [], [], []
-        for net, buf, first in zip(nets, self._state, (0, self.start_token)):
-            H, L = net.hidden_dim, net.num_layers
-            h.append(buf['h'][:2 * L * R * H].view(2, L, R, H)); c.append(buf['c'][:2 * L * R * H].view(2, L, R, H))
-            g.append(buf['g'][:2 * R * V].view(2, R, V))
-            xh.append(buf['xh'][:L * R * 2 * H].view(L, R, 2 * H)); top.append(buf['top'][:R * H].view(R, H))
-            xh[-1].zero_(); c[-1][0].zero_()
-            xh[-1][0, :, :H] = net.embedding.weight[first]     # the zero prefix of training / the LM's start token, in every slot
-        cells = lambda x, q: BeamDecoder._cells(self._sides[x], xh[x], c[x][q], h[x][q], top[x], g[x][q], *images[x])
-        cells(0, 0); cells(1, 0)
+        pn.start(0)                                            # the zero prefix of training, in every slot
+        lm.start(self.start_token)                             # the LM after its start token
         for i in range(steps):
             q = i & 1
-            ops.rnnt_lm_beam_step(f, g[0][q], nets[0].out_layer.bias, g[1][q], nets[1].out_layer.bias, il, i, cap, a, b, rec[q], rec[1 - q],
-                                  parent, last, fin, nets[0].embedding.weight, h[0][q], c[0][q], xh[0], c[0][1 - q],
-                                  nets[1].embedding.weight, h[1][q], c[1][q], xh[1], c[1][1 - q], live[i:])
+            ops.rnnt_lm_beam_step(f, pn.g[q], pn.bias, lm.g[q], lm.bias, il, i, cap, a, b, rec[q], rec[1 - q], parent, last, fin,
+                                  *pn.gather(q), *lm.gather(q), live[i:])
             if i == steps - 1 or ((i + 1) % SYNC_EVERY == 0 and int(live[i].item()) == 0):
                 break
-            for x in range(2):
-                cells(x, 1 - q)
-                ops.rnnt_beam_keep(parent, last, h[x][q], c[x][q], g[x][q], h[x][1 - q], c[x][1 - q], g[x][1 - q])
+            for st in (pn, lm):
+                st.cells(1 - q)
+                st.keep(parent, last, q)
         self.iterations = i + 1
         if int(live[i].item()) != 0:
             raise _lib.HaloError('TransducerFusionDecoder: rows still live after max(L) + capacity alignment steps')
@@ -454,15 +371,8 @@ class TransducerFusionDecoder:
             if not any(beams):
                 break
             src, tok = src.to(dev), tok.to(dev)
-            emit = tok != 0
-            g, state = g[src], (state[0][:, src].contiguous(), state[1][:, src].contiguous())
-            g1, (h1, c1) = pn.forward(tok.view(1, R), state)
-            g = torch.where(emit[:, None], g1, g)
-            state = (torch.where(emit[None, :, None], h1, state[0]), torch.where(emit[None, :, None], c1, state[1]))
-            lg, lstate = lg[src], (lstate[0][:, src].contiguous(), lstate[1][:, src].contiguous())
-            g1, (h1, c1) = lm.forward(tok.view(1, R), lstate)
-            lg = torch.where(emit[:, None], g1, lg)
-            lstate = (torch.where(emit[None, :, None], h1, lstate[0]), torch.where(emit[None, :, None], c1, lstate[1]))
+            g, state = _slots.step_general(pn, g, state, src, tok, tok != 0)
+            lg, lstate = _slots.step_general(lm, lg, lstate, src, tok, tok != 0)
         rec = torch.full((N, W, 3), NEG, dtype=torch.float32)
         seq, lengths = torch.zeros(N, W, dtype=torch.int32), torch.full((N, W), -1, dtype=torch.int32)
         tokens = torch.zeros(N, W, cap, dtype=torch.int32)
@@ -476,60 +386,47 @@ class TransducerFusionDecoder:
 
 class _LMSide:
     """The LM side of ``AttentionFusionDecoder``, as ``transformer.BeamDecoder``'s cores drive it: the slots' lm (two copies by step
-    parity), the LSTM state (likewise), the cells' input rows and the LM's logits, for ``slots`` = max_batch * beam rows; ``weight``,
-    ``start_token`` and ``eos`` are those of the running call."""
+    parity) and the LM's state in every slot (``state``: one copy of the logits, the search is label-synchronous), for ``slots`` =
+    max_batch * beam rows; ``weight``, ``start_token`` and ``eos`` are those of the running call."""
 
     def __init__(self, lm, slots, etx):
         self.lm, self.etx = lm, etx
-        self.images = _Images(_LMHead(lm))
+        self.state = _slots.SlotState(_slots.Network(lm), slots, copies=1)
         self.weight, self.start_token, self.eos = 0.0, 0, None
-        wte = lm.embedding.weight
-        dev, E, H, L, V = wte.device, wte.shape[1], lm.hidden_dim, lm.num_layers, lm.num_classes
-        i32, f32 = dict(device=dev, dtype=torch.int32), dict(device=dev, dtype=torch.float32)
+        dev = lm.embedding.weight.device
         self._buf = None
         with torch.inference_mode(False):          # ordinary tensors: they are updated in place inside and outside inference mode
-            if E == H and dev.type == 'cuda':      # flat buffers, viewed per call at that call's N * W slots
-                self._buf = dict(lm=[torch.zeros(slots, **f32) for _ in range(2)], par=torch.zeros(slots, **i32), last=torch.zeros(slots, **i32),
-                                 h=torch.zeros(2 * L * slots * H, **f32), c=torch.zeros(2 * L * slots * H, **f32),
-                                 g=torch.zeros(slots * V, **f32), xh=torch.zeros(L * slots * 2 * H, **f32), top=torch.zeros(slots * H, **f32))
+            if self.state.allocated:               # flat buffers, viewed per call at that call's N * W slots
+                self._buf = ([torch.zeros(slots, device=dev, dtype=torch.float32) for _ in range(2)],
+                             torch.zeros(slots, device=dev, dtype=torch.int32), torch.zeros(slots, device=dev, dtype=torch.int32))
 
     @property
     def fused(self):
-        return self._buf is not None and self.images.fused
+        return self.state.allocated and not self.lm.training and self.state.network.fused
 
     def key(self):
         """What a captured search depends on besides the shapes: the LM's parameters as they are now, and the call's three settings."""
-        return self.images._stamp() + (self.weight, self.start_token, self.eos)
+        return self.state.network.stamp() + (self.weight, self.start_token, self.eos)
 
     def start(self, N, W):
         """The views of this search's N * W slots; the LM after the start token, in every slot."""
-        lm, b = self.lm, self._buf
-        H, L, V, R = lm.hidden_dim, lm.num_layers, lm.num_classes, N * W
-        self._lm = [x[:R].view(N, W) for x in b['lm']]
-        self._par, self._last = b['par'][:R].view(N, W), b['last'][:R].view(N, W)
-        self._h, self._c = b['h'][:2 * L * R * H].view(2, L, R, H), b['c'][:2 * L * R * H].view(2, L, R, H)
-        self._g, self._xh, self._top = b['g'][:R * V].view(R, V), b['xh'][:L * R * 2 * H].view(L, R, 2 * H), b['top'][:R * H].view(R, H)
-        self._xh.zero_(); self._c[0].zero_()
-        self._xh[0, :, :H] = lm.embedding.weight[self.start_token]
-        self._cells(0)
-
-    def _cells(self, q):
-        BeamDecoder._cells(self.images, self._xh, self._c[q], self._h[q], self._top, self._g, *self.images._decode_images())
+        lm, par, last = self._buf
+        self._lm = [x[:N * W].view(N, W) for x in lm]
+        self._par, self._last = par[:N * W].view(N, W), last[:N * W].view(N, W)
+        self.state.view(N, W).start(self.start_token)
 
     def select(self, logits, t, cap, length_bonus, rec_in, rec_out, ranks, wte, y_next, par=None, last=None, c=0.0, psi_cand=None, psi_in=None,
                psi_out=None):
         """Step t's selection with the LM in the rank; the gather for the next LM step unless this is the last."""
-        q, lm = t & 1, self.lm
-        more = t + 1 < cap
-        ops.decode_beam_select_lm(logits, t, cap, self.etx, length_bonus, self._g, lm.out_layer.bias, self._lm[q], self._lm[1 - q], self.weight,
+        q, st = t & 1, self.state
+        ops.decode_beam_select_lm(logits, t, cap, self.etx, length_bonus, st.g[q], st.bias, self._lm[q], self._lm[1 - q], self.weight,
                                   self.eos, rec_in, rec_out, ranks, self._par if par is None else par, self._last if last is None else last,
-                                  lm.embedding.weight if more else None, self._h[q] if more else None, self._c[q] if more else None,
-                                  self._xh if more else None, self._c[1 - q] if more else None, wte, y_next, c, psi_cand, psi_in, psi_out)
+                                  *(st.gather(q) if t + 1 < cap else (None,) * 5), wte, y_next, c, psi_cand, psi_in, psi_out)
 
     def step(self, t, cap):
         """The LM's cell launches and out_layer on the rows the selection of step t gathered (the last step: nobody reads them)."""
         if t + 1 < cap:
-            self._cells(1 - (t & 1))
+            self.state.cells(1 - (t & 1))
 
     def scores(self, cap):
         return self._lm[cap & 1]
@@ -553,7 +450,7 @@ class AttentionFusionDecoder:
 
     def __init__(self, decoder, lm, max_batch, capacity, beam=4, lm_weight=0.5, length_bonus=0.0, start_token=0, lm_eos=None):
         V = decoder.lm_head.weight.shape[0]
-        self.lm_weight, self.start_token, self.lm_eos = _fusion_settings('AttentionFusionDecoder', lm, V, lm_weight, start_token, lm_eos)
+        self.lm_weight, self.start_token, self.lm_eos, _ = _fusion_settings('AttentionFusionDecoder', lm, V, lm_weight, start_token, lm_eos)
         from .transformer import ETX, BeamDecoder as AttentionBeamDecoder     # (transformer imports this module through recognizer)
         self._beam = AttentionBeamDecoder(decoder, max_batch, capacity, beam, length_bonus)      # its buffers, cores and graphs
         self.lm = lm
@@ -576,8 +473,8 @@ class AttentionFusionDecoder:
         ``last_finished`` and ``last_ctc`` as there, and ``last_parts`` = (attention [N, W] = logprob + length_bonus * length, lm_scores
         [N, W]), -inf where absent.  ``lm_weight``: this call's instead of the decoder's."""
         name, lm, dec = 'AttentionFusionDecoder', self.lm, self.decoder
-        a, _, _ = _fusion_settings(name, lm, dec.lm_head.weight.shape[0], self.lm_weight if lm_weight is None else lm_weight,
-                                   self.start_token, self.lm_eos)
+        a = _fusion_settings(name, lm, dec.lm_head.weight.shape[0], self.lm_weight if lm_weight is None else lm_weight, self.start_token,
+                             self.lm_eos)[0]
         if lm.training or dec.training:
             raise NotImplementedError(f'{name} is an inference path: put the decoder and the LM in eval mode')
         if not features.is_cuda or not lm.embedding.weight.is_cuda or not dec.wte.weight.is_cuda:
@@ -587,7 +484,7 @@ class AttentionFusionDecoder:
         side = self._side
         side.weight, side.start_token, side.eos = a, self.start_token, self.lm_eos
         if self.fused:
-            side.images._decode_images()           # built (or rebuilt after an update) before any capture
+            side.state.network.images()            # built (or rebuilt after an update) before any capture
         out = self._beam._search(features, input_lengths, capacity, beam, ctc_log_probs, ctc_weight, side)
         lengths = out[1]
         attention = self.last_logprobs + self.length_bonus * lengths.clamp(min=0).float()
@@ -595,16 +492,17 @@ class AttentionFusionDecoder:
         return out
 
 
-def _fusion_settings(name, lm, V, lm_weight, start_token, lm_eos):
-    """The checks of an LM and its settings against a decoder of V classes -> (lm_weight, start_token, lm_eos) as numbers."""
+def _fusion_settings(name, lm, V, lm_weight, start_token, lm_eos=None, insertion_bonus=0.0):
+    """The checks of an LM and its settings against a decoder of V classes -> (lm_weight, start_token, lm_eos, insertion_bonus) as
+    numbers."""
     if getattr(lm, 'num_classes', None) != V:
         raise ValueError(f'{name}: the LM has {getattr(lm, "num_classes", None)} classes, the decoder {V}')
-    a, start, eos = float(lm_weight), int(start_token), None if lm_eos is None else int(lm_eos)
-    if not math.isfinite(a):
-        raise ValueError(f'{name}: lm_weight must be finite')
+    a, b, start, eos = float(lm_weight), float(insertion_bonus), int(start_token), None if lm_eos is None else int(lm_eos)
+    if not (math.isfinite(a) and math.isfinite(b)):
+        raise ValueError(f'{name}: lm_weight and insertion_bonus must be finite')
     if start < 0 or start >= V or (eos is not None and (eos < 0 or eos >= V)):
         raise ValueError(f'{name}: start_token {start} / lm_eos {eos} outside 0 .. {V - 1}')
-    return a, start, eos
+    return a, start, eos, b
 
 
 def lm_score(lm, tokens, lengths, start_token=0):

@@ -1856,11 +1856,9 @@ def decode_beam_select_lm(logits, t, capacity, etx, length_bonus, lm_logits, lm_
     if lm_xh is not None:
         if any(x is None for x in (lm_wte, h_in, c_in, c_out)):
             raise ValueError(f'{name}: lm_xh comes with lm_wte, h_in, c_in and c_out')
-        Ll, H = h_in.shape[0], h_in.shape[2]
-        for x, shape in ((h_in, (Ll, N * W, H)), (c_in, (Ll, N * W, H)), (c_out, (Ll, N * W, H)), (lm_xh, (Ll, N * W, 2 * H)), (lm_wte, (V, H))):
-            if tuple(x.shape) != shape or x.dtype != torch.float32 or not x.is_contiguous():
-                raise ValueError(f'{name}: the LM state must be contiguous float32 h_in, c_in, c_out [Ll, N * W, H], lm_xh [Ll, N * W, 2 H] and '
-                                 'lm_wte [V, H]')
+        Ll, H = _check_slot_state(name, 'LM', V, N * W, lm_wte, h_in, c_in, lm_xh, c_out)
+        if lm_wte.shape[0] != V:
+            raise ValueError(f'{name}: lm_wte must be [V, H]')
     else:
         lm_wte = h_in = c_in = c_out = None
     check(lib().halo_decode_beam_select_lm(ptr(logits), logits.stride(0), N, W, V, int(t), int(capacity), int(etx), float(length_bonus),
@@ -1982,20 +1980,30 @@ def rnnt_advance_stream(f, g, g_bias, n_frames, state, scores, tokens, frames, m
 
 
 # ---- launches of the transducer's beam search (csrc/rnnt_beam.hip); none of these allocates ----------------------------------------
+def _check_slot_state(name, who, V, slots, wte, h_in, c_in, xh, c_out):
+    """The gather arguments of a beam step for one network (``who``): h_in / c_in / c_out [layers, slots, H], xh [layers, slots, 2 H] and
+    the embedding [>= V, H], all contiguous float32 -> (layers, H)."""
+    layers, H = (h_in.shape[0], h_in.shape[2]) if h_in.dim() == 3 else (0, 0)
+    state = (layers, slots, H)
+    if h_in.shape != state or c_in.shape != state or c_out.shape != state or xh.shape != (layers, slots, 2 * H) \
+            or wte.shape != (wte.shape[0], H) or wte.shape[0] < V or not all(x.dtype == torch.float32 and x.is_contiguous()
+                                                                             for x in (wte, h_in, c_in, xh, c_out)):
+        raise ValueError(f'{name}: of the {who}, h_in, c_in and c_out must be contiguous float32 [layers, {slots}, H], xh [layers, {slots}, '
+                         f'2 H] and the embedding [>= {V}, H]')
+    return layers, H
+
+
 def rnnt_beam_step(f, g, g_bias, input_lengths, step, capacity, rec_in, rec_out, parent, last, finals, wte, h_in, c_in, xh, c_out, live):
     """One alignment step of every row (include/halo.h): f [N, T, V]; g [N * W, V] (bias apart); rec_in / rec_out = (scores [N, W] fp32,
     u [N, W] int32, tokens [N, W, >= capacity] int32); parent / last [N, W] int32; finals = (scores, seq, lengths [N, W], tokens
     [N, W, >= capacity], n [N]); h_in / c_in / c_out [layers, N * W, H], xh [layers, N * W, 2 H], all contiguous; live: one int32 word."""
     N, T, V = f.shape
     W = parent.shape[1]
-    layers, slots, H = h_in.shape
-    tensors = (g, *rec_in, *rec_out, parent, last, *finals, h_in, c_in, xh, c_out)
-    if f.stride(2) != 1 or not all(t.is_contiguous() for t in tensors):
+    layers, H = _check_slot_state('rnnt_beam_step', 'prediction network', V, N * W, wte, h_in, c_in, xh, c_out)
+    if f.stride(2) != 1 or not all(t.is_contiguous() for t in (g, *rec_in, *rec_out, parent, last, *finals)):
         raise ValueError('rnnt_beam_step: f must be contiguous along V and every other tensor contiguous')
-    if slots != N * W or g.shape != (slots, V) or wte.shape != (wte.shape[0], H) or wte.shape[0] < V or not wte.is_contiguous():
-        raise ValueError('rnnt_beam_step: g must be [N * W, V], the state [layers, N * W, H] and the embedding [>= V, H]')
-    if xh.shape != (layers, slots, 2 * H) or c_in.shape != h_in.shape or c_out.shape != h_in.shape:
-        raise ValueError('rnnt_beam_step: xh must be [layers, N * W, 2 H], c_in and c_out as h_in')
+    if g.shape != (N * W, V):
+        raise ValueError('rnnt_beam_step: g must be [N * W, V]')
     ld = rec_in[2].shape[2]
     if any(t.shape != (N, W) for t in (rec_in[0], rec_in[1], rec_out[0], rec_out[1], parent, last, finals[0], finals[1], finals[2])) \
             or any(t.shape != (N, W, ld) for t in (rec_in[2], rec_out[2], finals[3])) or finals[4].shape != (N,):
@@ -2051,16 +2059,11 @@ def rnnt_beam_step_stream(ring, g, g_bias, stream_state, capacity, rec_in, rec_o
     cannot execute its step does an identity round."""
     rows, ring_frames, V = ring.shape
     W = parent.shape[1]
-    layers, slots, H = h_in.shape
-    tensors = (ring, g, stream_state, *rec_in, *rec_out, parent, last, *finals, h_in, c_in, xh, c_out)
-    if not all(t.is_contiguous() for t in tensors):
+    layers, H = _check_slot_state('rnnt_beam_step_stream', 'prediction network', V, rows * W, wte, h_in, c_in, xh, c_out)
+    if not all(t.is_contiguous() for t in (ring, g, stream_state, *rec_in, *rec_out, parent, last, *finals)):
         raise ValueError('rnnt_beam_step_stream: every tensor must be contiguous')
-    if slots != rows * W or g.shape != (slots, V) or wte.shape != (wte.shape[0], H) or wte.shape[0] < V or not wte.is_contiguous() \
-            or stream_state.shape != (4, rows) or stream_state.dtype != torch.int32:
-        raise ValueError('rnnt_beam_step_stream: g must be [rows * W, V], the state [layers, rows * W, H], the embedding [>= V, H] and '
-                         'stream_state int32 [4, rows]')
-    if xh.shape != (layers, slots, 2 * H) or c_in.shape != h_in.shape or c_out.shape != h_in.shape:
-        raise ValueError('rnnt_beam_step_stream: xh must be [layers, rows * W, 2 H], c_in and c_out as h_in')
+    if g.shape != (rows * W, V) or stream_state.shape != (4, rows) or stream_state.dtype != torch.int32:
+        raise ValueError('rnnt_beam_step_stream: g must be [rows * W, V] and stream_state int32 [4, rows]')
     ld = rec_in[2].shape[2]
     if any(t.shape != (rows, W) for t in (rec_in[0], rec_in[1], rec_out[0], rec_out[1], parent, last, finals[0], finals[1], finals[2])) \
             or any(t.shape != (rows, W, ld) for t in (rec_in[2], rec_out[2], finals[3])) or finals[4].shape != (rows,):
@@ -2080,14 +2083,12 @@ def ctc_lm_beam_step(emissions, emission_lengths, frame, capacity, lm_weight, in
     last [N, W] int32; h_in / c_in / c_out [layers, N * W, H], xh [layers, N * W, 2 H], all contiguous."""
     T, N, V = emissions.shape
     W = parent.shape[1]
-    layers, slots, H = h_in.shape
-    tensors = (g, *rec_in, *rec_out, parent, last, h_in, c_in, xh, c_out, emission_lengths)
+    layers, H = _check_slot_state('ctc_lm_beam_step', 'LM', V, N * W, wte, h_in, c_in, xh, c_out)
+    tensors = (g, *rec_in, *rec_out, parent, last, emission_lengths)
     if emissions.dtype != torch.float32 or emissions.stride(2) != 1 or not all(t.is_contiguous() for t in tensors):
         raise ValueError('ctc_lm_beam_step: emissions must be fp32 with unit class stride and every other tensor contiguous')
-    if slots != N * W or g.shape != (slots, V) or wte.shape != (wte.shape[0], H) or wte.shape[0] < V or not wte.is_contiguous():
-        raise ValueError('ctc_lm_beam_step: g must be [N * W, V], the state [layers, N * W, H] and the embedding [>= V, H]')
-    if xh.shape != (layers, slots, 2 * H) or c_in.shape != h_in.shape or c_out.shape != h_in.shape:
-        raise ValueError('ctc_lm_beam_step: xh must be [layers, N * W, 2 H], c_in and c_out as h_in')
+    if g.shape != (N * W, V):
+        raise ValueError('ctc_lm_beam_step: g must be [N * W, V]')
     ld = rec_in[2].shape[2]
     if any(t.shape != (N, W, 4) for t in (rec_in[0], rec_in[1], rec_out[0], rec_out[1])) or last.shape != (N, W) \
             or any(t.shape != (N, W, ld) for t in (rec_in[2], rec_out[2])) or emission_lengths.shape != (N,) \
@@ -2110,16 +2111,13 @@ def rnnt_lm_beam_step(f, g, g_bias, lg, lg_bias, input_lengths, step, capacity, 
     N, T, V = f.shape
     W = parent.shape[1]
     slots = N * W
-    tensors = (g, lg, *rec_in, *rec_out, parent, last, *finals, h_in, c_in, xh, c_out, lm_h_in, lm_c_in, lm_xh, lm_c_out, input_lengths)
+    tensors = (g, lg, *rec_in, *rec_out, parent, last, *finals, input_lengths)
     if f.dtype != torch.float32 or f.stride(2) != 1 or not all(t.is_contiguous() for t in tensors):
         raise ValueError('rnnt_lm_beam_step: f must be fp32 and contiguous along V and every other tensor contiguous')
     if g.shape != (slots, V) or lg.shape != (slots, V) or input_lengths.shape != (N,) or input_lengths.dtype != torch.int32:
         raise ValueError('rnnt_lm_beam_step: g and lg must be [N * W, V], input_lengths [N] int32')
-    for name, e, h, c, x, co in (('prediction network', wte, h_in, c_in, xh, c_out), ('LM', lm_wte, lm_h_in, lm_c_in, lm_xh, lm_c_out)):
-        if h.dim() != 3 or h.shape[1] != slots or e.shape != (e.shape[0], h.shape[2]) or e.shape[0] < V or not e.is_contiguous():
-            raise ValueError(f'rnnt_lm_beam_step: the {name}\'s state must be [layers, N * W, H] and its embedding [>= V, H]')
-        if x.shape != (h.shape[0], slots, 2 * h.shape[2]) or c.shape != h.shape or co.shape != h.shape:
-            raise ValueError(f'rnnt_lm_beam_step: the {name}\'s xh must be [layers, N * W, 2 H], c_in and c_out as h_in')
+    _check_slot_state('rnnt_lm_beam_step', 'prediction network', V, slots, wte, h_in, c_in, xh, c_out)
+    _check_slot_state('rnnt_lm_beam_step', 'LM', V, slots, lm_wte, lm_h_in, lm_c_in, lm_xh, lm_c_out)
     ld = rec_in[2].shape[2]
     if any(t.shape != (N, W, 3) for t in (rec_in[0], rec_out[0], finals[0])) \
             or any(t.shape != (N, W) for t in (rec_in[1], rec_out[1], parent, last, finals[1], finals[2])) \

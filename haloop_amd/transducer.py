@@ -40,11 +40,9 @@ scores sum the alignment paths of a hypothesis, on ``num_layers + 3`` launches p
 arrived and no blank extension could be complete, so after its final call a row holds ``BeamDecoder.decode`` of its whole utterance
 (csrc/rnnt_beam.hip: the open launch and the carried instantiation of the step).
 """
-import os
-
 import torch
 
-from . import _lib, functional as HF, ops
+from . import _lib, _slots, functional as HF, ops
 from .rnn import lstm_param_list
 
 SYNC_EVERY = 16          # GreedyDecoder.decode reads the live-row counter every this many advances
@@ -204,42 +202,14 @@ def nbest_risk(losses, errors):
     return _NbestRisk.apply(losses, errors.to(device=losses.device, dtype=torch.int32).contiguous())
 
 
-def _fused_default():
-    """HALO_RNNT_FUSED=0: the general path even where the fused launches apply (the measured pair: DESIGN.md 3.3j)."""
-    return os.environ.get('HALO_RNNT_FUSED', '1') != '0'
-
-
 class _HeadDecoder:
-    """What the decoders of a ``recognizer.Transducer`` head share: when the fused launches apply, and the decode images of the
-    prediction network (``self.head``; ``self._images`` = None or (stamp, per-layer gate images, out_layer image))."""
+    """What the decoders of a ``recognizer.Transducer`` head (``self.head``) share; ``self._net``: its prediction network as the fused
+    launches read it (``_slots.Network``: the decode images and the network's part of the fused rule)."""
 
     @property
     def fused(self):
         """Whether the fused launches are in use (decided from the head, the math mode and HALO_RNNT_FUSED as they are now)."""
-        lm = self.head.lm
-        E, H = lm.embedding.weight.shape[1], lm.hidden_dim
-        if not _fused_default() or _lib.get_math_mode() == 'f32' or self.head.training or E != H or H % 512 != 0:
-            return False
-        return lm.num_classes <= 8192 and ops.decode_linear_supported(H, False) and ops.decode_linear_supported(2 * H, False)
-
-    def _stamp(self):
-        return tuple((p._version, p.data_ptr()) for p in self.head.lm.parameters()) + (_lib.weights_epoch(),)
-
-    @torch.no_grad()
-    def _decode_images(self):
-        """Decode images of every layer's [W_ih | W_hh], rows permuted so that feature tile j holds the four gates of hidden units
-        4 j .. 4 j + 3 (row 16 j + 4 q + i <- row q H + 4 j + i), and of the tied embedding; rebuilt when a parameter changes."""
-        stamp = self._stamp()
-        if self._images is None or self._images[0] != stamp:
-            lm = self.head.lm
-            H, p = lm.hidden_dim, lstm_param_list(lm.rnn)
-            layers = []
-            for l in range(lm.num_layers):
-                w = torch.cat([p[4 * l].detach().float(), p[4 * l + 1].detach().float()], 1)           # [4H, 2H]
-                w = w.view(4, H // 4, 4, 2 * H).permute(1, 0, 2, 3).reshape(4 * H, 2 * H).contiguous()
-                layers.append(ops.decode_image(w))
-            self._images = (stamp, layers, ops.decode_image(lm.embedding.weight.detach().float().contiguous()))
-        return self._images[1], self._images[2]
+        return not self.head.training and self._net.fused
 
     def _lm_step(self, N, p, layers, head_image, mask=None):
         """The prediction network on the input rows of copy p -> g (``GreedyDecoder`` and ``GreedyStream``: both keep ``_xh`` [2, L, rows,
@@ -275,7 +245,7 @@ class GreedyDecoder(_HeadDecoder):
     not meet; it bounds an untrained one)."""
 
     def __init__(self, head, max_batch, capacity, max_symbols_per_frame=10):
-        self.head = head
+        self.head, self._net = head, _slots.Network(head.lm)
         self.max_batch, self.capacity, self.max_symbols = int(max_batch), int(capacity), int(max_symbols_per_frame)
         if self.max_batch < 1 or self.capacity < 1 or self.max_symbols < 1:
             raise ValueError('GreedyDecoder: need max_batch >= 1, capacity >= 1 and max_symbols_per_frame >= 1')
@@ -295,7 +265,6 @@ class GreedyDecoder(_HeadDecoder):
                 self._c = torch.zeros(L, mb, H, device=dev, dtype=torch.float32)
                 self._top = torch.zeros(mb, H, device=dev, dtype=torch.float32)
                 self._g = torch.zeros(mb, V, device=dev, dtype=torch.float32)
-        self._images = None    # (stamp, per-layer gate images, out_layer image)
         self.iterations = 0    # of the last decode: advances (fused path) or lattice nodes visited in lockstep (general path)
 
     def decode(self, features, input_lengths, capacity=None):
@@ -321,7 +290,7 @@ class GreedyDecoder(_HeadDecoder):
     # ---- the fused path: 1 + num_layers + 1 launches per emitted symbol ------------------------------------------------------------
     def _decode_fused(self, f, il, N, cap):
         lm = self.head.lm
-        layers, head_image = self._decode_images()
+        layers, head_image = self._net.images()
         wte, E = lm.embedding.weight, lm.embedding.weight.shape[1]
         self._xh.zero_(); self._c.zero_(); self._live.zero_()
         self._xh[0, 0, :N, :E] = wte[0]                       # the zero prefix of training (recognizer.py:107)
@@ -396,7 +365,7 @@ class GreedyStream(_HeadDecoder):
     on ``rnn.Decoder.forward`` at T = 1.  The path is chosen when a row begins; do not change it in the middle of a stream."""
 
     def __init__(self, head, max_rows, capacity, max_symbols_per_frame=10):
-        self.head = head
+        self.head, self._net = head, _slots.Network(head.lm)
         self.max_rows, self.capacity, self.max_symbols = int(max_rows), int(capacity), int(max_symbols_per_frame)
         if self.max_rows < 1 or self.capacity < 1 or self.max_symbols < 1:
             raise ValueError('GreedyStream: need max_rows >= 1, capacity >= 1 and max_symbols_per_frame >= 1')
@@ -424,7 +393,6 @@ class GreedyStream(_HeadDecoder):
             self._gh = torch.zeros(L, mb, H, device=dev, dtype=torch.float32)      # the general path's state
             self._gc = torch.zeros(L, mb, H, device=dev, dtype=torch.float32)
         self._cur = 0          # the [x | h] copy that holds every row's h: the one the next step reads.  Carried across calls.
-        self._images = None
         self.rounds = 0
 
     def advance(self, f, n_frames=None, begin=None):
@@ -475,7 +443,7 @@ class GreedyStream(_HeadDecoder):
     # ---- the fused path: per round 1 + num_layers + 1 launches over all max_rows rows, whatever B ------------------------------------
     def _advance_fused(self, f, nf, flags, any_begin):
         lm = self.head.lm
-        layers, head_image = self._decode_images()
+        layers, head_image = self._net.images()
         wte, E = lm.embedding.weight, lm.embedding.weight.shape[1]
         B, S = f.shape[0], f.shape[1]
         mb, cap = self.max_rows, self.capacity
@@ -600,18 +568,19 @@ def _prune_row(beam, finals, lp, i, L, W, cap):
 
 
 def _ranked_finals(scores, seq, lengths, tokens, cap):
-    """The finals of a beam search (scores, order of completion, lengths [N, W], -1: absent; tokens [N, W, >= cap]) by (score descending,
-    order of completion), absent ones last, in ``BeamDecoder.decode``'s format: two stable sorts."""
+    """The finals of a beam search (scores [N, W], or records [N, W, K] whose column 0 ranks; order of completion, lengths [N, W], -1:
+    absent; tokens [N, W, >= cap]) by (score descending, order of completion), absent ones last, in ``BeamDecoder.decode``'s format
+    (the scores in their own shape, -inf where absent): two stable sorts."""
     N, W = lengths.shape
+    cols = scores.reshape(N, W, -1)
     absent = lengths < 0
     o1 = torch.where(absent, torch.full_like(seq, 2 ** 31 - 1), seq).argsort(dim=1, stable=True)
-    key = torch.where(absent, torch.full_like(scores, float('inf')), -scores).gather(1, o1)
+    key = torch.where(absent, torch.full_like(cols[:, :, 0], float('inf')), -cols[:, :, 0]).gather(1, o1)
     order = o1.gather(1, key.argsort(dim=1, stable=True))
     lengths = lengths.gather(1, order).long()
-    scores = torch.where(lengths < 0, torch.full_like(scores, float('-inf')), scores.gather(1, order))
-    tokens = tokens[:, :, :cap].gather(1, order[:, :, None].expand(N, W, cap)).long()
-    past = torch.arange(cap, device=tokens.device)[None, None, :] >= lengths[:, :, None]
-    return tokens.masked_fill(past, -1), lengths, scores, (lengths >= 0).sum(1)
+    cols = torch.where(lengths[:, :, None] < 0, torch.full_like(cols, float('-inf')), cols.gather(1, order[:, :, None].expand_as(cols)))
+    tokens = tokens[:, :, :cap].gather(1, order[:, :, None].expand(N, W, cap))
+    return _slots.mask_tokens(tokens, lengths), lengths, cols.view(scores.shape), (lengths >= 0).sum(1)
 
 
 class BeamDecoder(_HeadDecoder):
@@ -633,31 +602,23 @@ class BeamDecoder(_HeadDecoder):
     torch operators, the candidates pruned on the host."""
 
     def __init__(self, head, max_batch, capacity, beam=4):
-        self.head = head
+        self.head, self._net = head, _slots.Network(head.lm)
         self.max_batch, self.capacity, self.beam = int(max_batch), int(capacity), int(beam)
-        if self.max_batch < 1 or self.capacity < 1:
-            raise ValueError('BeamDecoder: need max_batch >= 1 and capacity >= 1')
-        if self.beam < 1 or self.beam > BEAM_MAX:
-            raise ValueError(f'BeamDecoder: beam {self.beam} outside 1 .. {BEAM_MAX}')
-        lm = head.lm
-        E, H, L, V = lm.embedding.weight.shape[1], lm.hidden_dim, lm.num_layers, lm.num_classes
-        dev = lm.embedding.weight.device
+        _slots.check_sizes('BeamDecoder', self, BEAM_MAX)
+        dev = head.lm.embedding.weight.device
         S, cap = self.max_batch * self.beam, self.capacity
         i32 = dict(device=dev, dtype=torch.int32)
         f32 = dict(device=dev, dtype=torch.float32)
+        self._lstm = _slots.SlotState(self._net, S)               # the prediction network's state in every slot
         with torch.inference_mode(False):          # ordinary tensors: they are updated in place inside and outside inference mode
-            if E == H:
-                # flat buffers, viewed per call at that call's N * W slots.  The beam's records and the state exist twice (step parity).
+            if self._lstm.allocated:
+                # flat buffers, viewed per call at that call's N * W slots.  The beam's records exist twice (step parity), like the state.
                 self._rec = [(torch.zeros(S, **f32), torch.zeros(S, **i32), torch.zeros(S * cap, **i32)) for _ in range(2)]
                 self._parent, self._last = torch.zeros(S, **i32), torch.zeros(S, **i32)
                 self._fin = (torch.zeros(S, **f32), torch.zeros(S, **i32), torch.zeros(S, **i32), torch.zeros(S * cap, **i32),
                              torch.zeros(self.max_batch, **i32))
-                self._h, self._c = torch.zeros(2 * L * S * H, **f32), torch.zeros(2 * L * S * H, **f32)
-                self._g = torch.zeros(2 * S * V, **f32)
-                self._xh, self._top = torch.zeros(L * S * 2 * H, **f32), torch.zeros(S * H, **f32)
                 self._live = torch.zeros(64, **i32)                  # one word per alignment step; grown to T + capacity
         self._device = dev      # of the buffers: a head moved since needs a new decoder
-        self._images = None
         self.iterations = 0    # alignment steps of the last decode
 
     def decode(self, features, input_lengths, capacity=None, beam=None):
@@ -665,12 +626,7 @@ class BeamDecoder(_HeadDecoder):
         and in absent hypotheses; lengths [N, W] int64, -1: absent; scores [N, W] float32, best first, -inf: absent; counts [N] int64).
         ``capacity`` / ``beam``: search with less room than the buffers hold (default: all of it)."""
         self._check(features, input_lengths)
-        cap = self.capacity if capacity is None else int(capacity)
-        if cap < 1 or cap > self.capacity:
-            raise ValueError(f'BeamDecoder: capacity {cap} outside 1 .. {self.capacity}')
-        W = self.beam if beam is None else int(beam)
-        if W < 1 or W > BEAM_MAX or W > self.beam:
-            raise ValueError(f'BeamDecoder: beam {W} outside 1 .. {min(BEAM_MAX, self.beam)}')
+        cap, W = _slots.room('BeamDecoder', self, capacity, beam)
         with torch.no_grad():
             N, T, _ = features.shape
             cl = self.head.classifier
@@ -679,20 +635,8 @@ class BeamDecoder(_HeadDecoder):
             return _ranked_finals(*(self._decode_fused if self.fused else self._decode_general)(f, il, N, W, cap), cap)
 
     # ---- the fused path: num_layers + 3 launches per alignment step --------------------------------------------------------------------
-    def _cells(self, xh, c, h_out, top, g_out, layers, head_image):
-        """The prediction network on the [x | h_prev] rows of every slot: c [L, R, H] in place, h -> h_out [L, R, H] (and the x half of
-        the layer above / ``top``), out_layer -> g_out."""
-        lm = self.head.lm
-        H, L, w = lm.hidden_dim, lm.num_layers, lstm_param_list(lm.rnn)
-        for l in range(L):
-            h_up = xh[l + 1, :, :H] if l + 1 < L else top
-            ops.rnnt_lstm_cell(xh[l], layers[l], w[4 * l + 2], w[4 * l + 3], c[l], h_out[l], h_up)
-        ops.decode_linear(top, head_image, lm.num_classes, g_out)
-
     def _decode_fused(self, f, il, N, W, cap):
-        lm = self.head.lm
-        layers, head_image = self._decode_images()
-        wte, H, L, V = lm.embedding.weight, lm.hidden_dim, lm.num_layers, lm.num_classes
+        st = self._lstm.view(N, W)
         R, ld, steps = N * W, self.capacity, f.shape[1] + cap
         if self._live.numel() < steps:
             self._live = torch.zeros(steps, device=self._live.device, dtype=torch.int32)
@@ -702,20 +646,14 @@ class BeamDecoder(_HeadDecoder):
         parent, last = self._parent[:R].view(N, W), self._last[:R].view(N, W)
         fs, fq, fl, ft, fn = self._fin
         fin = (fs[:R].view(N, W), fq[:R].view(N, W), fl[:R].view(N, W), ft[:R * ld].view(N, W, ld), fn[:N])
-        h, c = self._h[:2 * L * R * H].view(2, L, R, H), self._c[:2 * L * R * H].view(2, L, R, H)
-        g = self._g[:2 * R * V].view(2, R, V)
-        xh, top = self._xh[:L * R * 2 * H].view(L, R, 2 * H), self._top[:R * H].view(R, H)
-        xh.zero_(); c[0].zero_()
-        xh[0, :, :H] = wte[0]                                  # the zero prefix of training (recognizer.py:107), in every slot
-        self._cells(xh, c[0], h[0], top, g[0], layers, head_image)
+        st.start(0)                                            # the zero prefix of training (recognizer.py:107), in every slot
         for i in range(steps):                                 # a hypothesis at step i has t + u = i, t < L, u <= cap: none after L + cap
             q = i & 1
-            ops.rnnt_beam_step(f, g[q], lm.out_layer.bias, il, i, cap, rec[q], rec[1 - q], parent, last, fin, wte, h[q], c[q], xh, c[1 - q],
-                               live[i:])
+            ops.rnnt_beam_step(f, st.g[q], st.bias, il, i, cap, rec[q], rec[1 - q], parent, last, fin, *st.gather(q), live[i:])
             if i == steps - 1 or ((i + 1) % SYNC_EVERY == 0 and int(live[i].item()) == 0):
                 break
-            self._cells(xh, c[1 - q], h[1 - q], top, g[1 - q], layers, head_image)
-            ops.rnnt_beam_keep(parent, last, h[q], c[q], g[q], h[1 - q], c[1 - q], g[1 - q])
+            st.cells(1 - q)
+            st.keep(parent, last, q)
         self.iterations = i + 1
         if int(live[i].item()) != 0:
             raise _lib.HaloError('BeamDecoder: rows still live after T + capacity alignment steps')
@@ -751,11 +689,7 @@ class BeamDecoder(_HeadDecoder):
             if not any(beams):
                 break
             src, tok = src.to(dev), tok.to(dev)
-            g, state = g[src], (state[0][:, src].contiguous(), state[1][:, src].contiguous())
-            g1, (h1, c1) = lm.forward(tok.view(1, R), state)
-            emit = tok != 0
-            g = torch.where(emit[:, None], g1, g)
-            state = (torch.where(emit[None, :, None], h1, state[0]), torch.where(emit[None, :, None], c1, state[1]))
+            g, state = _slots.step_general(lm, g, state, src, tok, tok != 0)
         scores = torch.full((N, W), float('-inf'), dtype=torch.float32)
         seq, lengths = torch.zeros(N, W, dtype=torch.int32), torch.full((N, W), -1, dtype=torch.int32)
         tokens = torch.zeros(N, W, cap, dtype=torch.int32)
@@ -794,22 +728,22 @@ class BeamStream(_HeadDecoder):
     head the fused launches do not take) carries the same search on ``rnn.Decoder.forward`` at T = 1, pruned on the host.  The path is
     chosen when a row begins; do not change it in the middle of a stream."""
 
-    _cells = BeamDecoder._cells
-
     def __init__(self, head, max_rows, capacity, beam=4, max_chunk=64):
-        self.head = head
+        self.head, self._net = head, _slots.Network(head.lm)
         self.max_rows, self.capacity, self.beam, self.max_chunk = int(max_rows), int(capacity), int(beam), int(max_chunk)
         if self.max_rows < 1 or self.capacity < 1 or self.max_chunk < 1:
             raise ValueError('BeamStream: need max_rows >= 1, capacity >= 1 and max_chunk >= 1')
         if self.beam < 1 or self.beam > BEAM_MAX:
             raise ValueError(f'BeamStream: beam {self.beam} outside 1 .. {BEAM_MAX}')
         lm = head.lm
-        E, H, L, V = lm.embedding.weight.shape[1], lm.hidden_dim, lm.num_layers, lm.num_classes
+        H, L, V = lm.hidden_dim, lm.num_layers, lm.num_classes
         dev = lm.embedding.weight.device
         if dev.type != 'cuda':
             raise _lib.HaloError('haloop_amd.transducer.BeamStream runs on the HIP device only (no CPU path)')
         mb, W, cap = self.max_rows, self.beam, self.capacity
         R = mb * W
+        self._lstm = _slots.SlotState(self._net, R)               # the prediction network's state in every slot
+        self._zero = _slots.SlotState(self._net, 1)                # and after the zero prefix, on one slot: what a beginning row starts from
         i32 = dict(device=dev, dtype=torch.int32)
         f32 = dict(device=dev, dtype=torch.float32)
         with torch.inference_mode(False):
@@ -818,25 +752,17 @@ class BeamStream(_HeadDecoder):
             self._meta[3].fill_(1)
             self._nf, self._flags = torch.zeros(mb, **i32), torch.zeros(mb, **i32)
             self._live = torch.zeros(self.max_chunk + cap + 2, **i32)            # one word per round of a call
-            if E == H:
+            if self._lstm.allocated:
                 self._rec = [(torch.full((mb, W), float('-inf'), **f32), torch.full((mb, W), -1, **i32), torch.zeros(mb, W, cap, **i32))
                              for _ in range(2)]
                 self._parent, self._last = torch.zeros(mb, W, **i32), torch.zeros(mb, W, **i32)
                 self._fin = (torch.full((mb, W), float('-inf'), **f32), torch.zeros(mb, W, **i32), torch.full((mb, W), -1, **i32),
                              torch.zeros(mb, W, cap, **i32), torch.zeros(mb, **i32))
-                self._h, self._c = torch.zeros(2, L, R, H, **f32), torch.zeros(2, L, R, H, **f32)
-                self._g = torch.zeros(2, R, V, **f32)
-                self._xh, self._top = torch.zeros(L, R, 2 * H, **f32), torch.zeros(R, H, **f32)
-                # the prediction network after the zero prefix, one row: computed with the cell launches whenever a weight changes
-                self._zero = (torch.zeros(L, H, **f32), torch.zeros(L, H, **f32), torch.zeros(V, **f32))
-                self._zxh, self._ztop = torch.zeros(L, 1, 2 * H, **f32), torch.zeros(1, H, **f32)
             self._gg = torch.zeros(R, V, **f32)                    # the general path's state
             self._gh, self._gc = torch.zeros(L, R, H, **f32), torch.zeros(L, R, H, **f32)
         self._rows = [dict(beam=[], finals=[], step=0, R=0, final=False, closed=True) for _ in range(mb)]     # the general path's records
         self._general = False  # which path holds the streams
         self._cur = 0          # the copy of records and state that the next round reads.  Carried across calls.
-        self._images = None
-        self._zero_stamp = None
         self.sync_every = STREAM_BEAM_SYNC_EVERY
         self.rounds = 0
 
@@ -889,34 +815,22 @@ class BeamStream(_HeadDecoder):
         (self._advance_general if self._general else self._advance_fused)(f, nf, flags)
 
     # ---- the fused path: per round num_layers + 3 launches over all max_rows * W slots, whatever B ---------------------------------
-    def _zero_state(self, layers, head_image):
-        """(h0, c0, g0) of the prediction network after the zero prefix of training, with the launches ``BeamDecoder`` computes it with."""
-        stamp = self._stamp()
-        if self._zero_stamp != stamp:
-            h0, c0, g0 = self._zero
-            H = self.head.lm.hidden_dim
-            self._zxh.zero_(); c0.zero_()
-            self._zxh[0, :, :H] = self.head.lm.embedding.weight[0]
-            self._cells(self._zxh, c0[:, None], h0[:, None], self._ztop, g0[None], layers, head_image)
-            self._zero_stamp = stamp
-        return self._zero
-
     def _advance_fused(self, f, nf, flags):
-        lm = self.head.lm
-        layers, head_image = self._decode_images()
-        zero = self._zero_state(layers, head_image)
-        wte, cap = lm.embedding.weight, self.capacity
-        S = f.shape[1]
-        rec, h, c, g, xh, top, fin = self._rec, self._h, self._c, self._g, self._xh, self._top, self._fin
+        st, zero = self._lstm.view(self.max_rows, self.beam), self._zero
+        if zero.built is not st.built:             # the stamp moved: a weight changed.  The launches ``BeamDecoder`` starts with
+            zero.view(1, 1).start(0)
+        cap, S = self.capacity, f.shape[1]
+        rec, fin = self._rec, self._fin
         q = self._cur
-        ops.rnnt_beam_stream_open(f, nf, flags, self._ring, self._meta, rec[q], fin, zero, h[q], c[q], g[q], self._live)
+        ops.rnnt_beam_stream_open(f, nf, flags, self._ring, self._meta, rec[q], fin, (zero.h[0, :, 0], zero.c[0, :, 0], zero.g[0][0]),
+                                  st.h[q], st.c[q], st.g[q], self._live)
         bound = S + cap + 2
         try:
             for it in range(bound):
-                ops.rnnt_beam_step_stream(self._ring, g[q], lm.out_layer.bias, self._meta, cap, rec[q], rec[1 - q], self._parent, self._last,
-                                          fin, wte, h[q], c[q], xh, c[1 - q], self._live[it:])
-                self._cells(xh, c[1 - q], h[1 - q], top, g[1 - q], layers, head_image)
-                ops.rnnt_beam_keep(self._parent, self._last, h[q], c[q], g[q], h[1 - q], c[1 - q], g[1 - q])
+                ops.rnnt_beam_step_stream(self._ring, st.g[q], st.bias, self._meta, cap, rec[q], rec[1 - q], self._parent, self._last, fin,
+                                          *st.gather(q), self._live[it:])
+                st.cells(1 - q)
+                st.keep(self._parent, self._last, q)
                 q = 1 - q
                 # a row sent S frames needs S rounds: the first read comes after them, the next every ``sync_every`` rounds
                 if it == bound - 1 or (it + 1 >= S and (it + 1 - S) % self.sync_every == 0 and int(self._live[it].item()) == 0):
@@ -979,11 +893,7 @@ class BeamStream(_HeadDecoder):
                 if not new and r['final']:
                     r['closed'] = True
             src, tok = src.to(dev), tok.to(dev)
-            g, state = g[src], (state[0][:, src].contiguous(), state[1][:, src].contiguous())
-            g1, (h1, c1) = lm.forward(tok.view(1, R), state)
-            emit = tok != 0
-            g = torch.where(emit[:, None], g1, g)
-            state = (torch.where(emit[None, :, None], h1, state[0]), torch.where(emit[None, :, None], c1, state[1]))
+            g, state = _slots.step_general(lm, g, state, src, tok, tok != 0)
         self._gg.copy_(g); self._gh.copy_(state[0]); self._gc.copy_(state[1])
 
     def nbest(self):
@@ -1003,7 +913,7 @@ class BeamStream(_HeadDecoder):
             ft, fl, fs, fc = _ranked_finals(self._fin[0], self._fin[1], self._fin[2], self._fin[3], cap)
             sc, u, tok = self._rec[self._cur]
             bl = u.long()
-            bt = tok.long().masked_fill(torch.arange(cap, device=tok.device)[None, None, :] >= bl[:, :, None], -1)
+            bt = _slots.mask_tokens(tok, bl)
             bs = torch.where(bl < 0, torch.full_like(sc, float('-inf')), sc)
             closed = self._meta[3] != 0
             return (torch.where(closed[:, None, None], ft, bt), torch.where(closed[:, None], fl, bl), torch.where(closed[:, None], fs, bs),

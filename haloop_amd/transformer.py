@@ -35,7 +35,7 @@ from collections import namedtuple
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, _slots, ops
 from ._capture import GraphCache
 from ._linear import (NO_SITES, DropSites, WeightImages, training_images, drop_rows, forward_images, grad_images, linear, linear_dw, linear_dx, ln_linear,
                       normed_image, rowmajor_ok, use_split)
@@ -686,7 +686,7 @@ class Decoder(nn.Module):
             self._beams.pop('lm', None)
             return
         from .fusion import _fusion_settings
-        a, start, eos = _fusion_settings('Decoder.set_fusion_lm', lm, self.lm_head.weight.shape[0], lm_weight, start_token, lm_eos)
+        a, start, eos, _ = _fusion_settings('Decoder.set_fusion_lm', lm, self.lm_head.weight.shape[0], lm_weight, start_token, lm_eos)
         self._beams['lm'] = dict(lm=lm, lm_weight=a, start_token=start, lm_eos=eos)        # (in the dict: not registered as a submodule)
 
     @torch.no_grad()
@@ -794,10 +794,7 @@ class BeamDecoder:
     def __init__(self, decoder, max_batch, capacity, beam=4, length_bonus=0.0):
         self.decoder = decoder
         self.max_batch, self.capacity, self.beam, self.length_bonus = int(max_batch), int(capacity), int(beam), float(length_bonus)
-        if self.max_batch < 1 or self.capacity < 1:
-            raise ValueError('BeamDecoder: need max_batch >= 1 and capacity >= 1')
-        if self.beam < 1 or self.beam > BEAM_MAX:
-            raise ValueError(f'BeamDecoder: beam {self.beam} outside 1 .. {BEAM_MAX}')
+        _slots.check_sizes('BeamDecoder', self, BEAM_MAX)
         wte = decoder.wte.weight
         dev, C, V, L = wte.device, wte.shape[1], decoder.lm_head.weight.shape[0], len(decoder.h)
         R, cap = self.max_batch * self.beam, self.capacity
@@ -855,12 +852,7 @@ class BeamDecoder:
         _require_inference(dec, features)
         if dec.wte.weight.device != self._device or features.device != self._device:
             raise ValueError('BeamDecoder: the decoder or the features are not on the device of the buffers')
-        cap = self.capacity if capacity is None else int(capacity)
-        if cap < 1 or cap > self.capacity:
-            raise ValueError(f'BeamDecoder: capacity {cap} outside 1 .. {self.capacity}')
-        W = self.beam if beam is None else int(beam)
-        if W < 1 or W > self.beam:
-            raise ValueError(f'BeamDecoder: beam {W} outside 1 .. {self.beam}')
+        cap, W = _slots.room('BeamDecoder', self, capacity, beam)
         N, S, C = features.shape
         if N < 1 or N > self.max_batch:
             raise ValueError(f'BeamDecoder: {N} utterances outside 1 .. {self.max_batch}')
@@ -891,10 +883,9 @@ class BeamDecoder:
             absent = ~(scores > float('-inf'))
             self._last_lm = torch.where(absent, torch.full_like(scores, float('-inf')), outs[-1]) if side is not None else None
             lengths = torch.where(absent, torch.full_like(lengths, -1), lengths).long()
-            past = torch.arange(cap, device=dev)[None, None, :] >= lengths[:, :, None]
             self.last_logprobs = scores
             self.last_finished = (fin != 0) & ~absent
-            return tokens[:, :, :cap].long().masked_fill(past, -1), lengths, ranks, (~absent).sum(1)
+            return _slots.mask_tokens(tokens[:, :, :cap], lengths), lengths, ranks, (~absent).sum(1)
 
     # ---- the fused path: 5 * layers + 2 launches per step --------------------------------------------------------------------------
     def _core_fused(self, mem2d, mlen, N, S, W, cap, x=None, c=0.0, side=None):
@@ -1052,10 +1043,7 @@ class BeamDecoder:
                 lms = torch.where(taken, lmc.view(N, W * V).gather(1, idx), torch.zeros_like(top))
                 if t + 1 < cap:                                                               # a slot that took a label: from its parent's state
                     step = grow.view(-1)
-                    lg, lstate = lg.index_select(0, src), tuple(z.index_select(1, src).contiguous() for z in lstate)
-                    g1, (h1, c1) = lm.forward(torch.where(step, k.view(-1), torch.zeros_like(src)).view(1, R), lstate)
-                    lg = torch.where(step[:, None], g1, lg)
-                    lstate = (torch.where(step[None, :, None], h1, lstate[0]), torch.where(step[None, :, None], c1, lstate[1]))
+                    lg, lstate = _slots.step_general(lm, lg, lstate, src, torch.where(step, k.view(-1), torch.zeros_like(src)), step)
         outs = (score, length.int(), fin.int(), tokens.int(), rank) + ((psi,) if x is not None else ())
         return outs if side is None else outs + (lms,)
 

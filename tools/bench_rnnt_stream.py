@@ -141,7 +141,7 @@ for V in (int(v) for v in args.vocabs.split(',')):
             r['symbols_per_push_mean'] = float(st.partial()[1].float().mean()) / n_push
         if 'round' in LEGS:                                                          # one round's launches alone: no row is live
             gs, lm = st.search, head.lm
-            layers, head_image = gs._decode_images()
+            layers, head_image = gs._net.images()
             nf = torch.zeros(B, dtype=torch.int32).cuda()
             f = logits_all[:, :S].contiguous()
             gs._live.zero_()
